@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the block-quantised linear path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -22,9 +22,14 @@ N GPUs: "scaling": "strong".  `--shard tokens` times independent replicas instea
 `--workload quantizers` (BASELINE config 5): the memory-bound fake-quantisers (block_fp, block_minifloat,
 block_log) at the Llama-7B activation / weight shapes, GB/s at 8 B per element against the HBM roofline.
 
-After the timed region the step's output is checked against the oracle (64 sampled rows x all columns of y; the
-activation quantiser's exponents and mantissas over the whole 4096 x 4096 tensor, bit for bit): exit code 1 on
-mismatch.  Prints ONE JSON line on rank 0.
+A plain run does only what the headline figure needs: set-up, the clock ramp and W warm-up steps, K timed steps, the
+outputs of the last timed step if `--dump-outputs DIR` is given (DIR/y.npy: DUMP_ROWS seeded rows x all columns of y,
+float32), and the JSON line.  `--full` adds everything else, after the timed steps: the literal no-ramp pass, the
+event-timed pass behind `roofline`, the kernel alone back to back and its measured ceiling, the weight-packing cost,
+config 5, the outlier-channel variant, config 3, the CPU baselines and, for N > 1, the replica and quantised-gather
+figures; and the oracle check of the step's output (64 sampled rows x all columns of y; the activation quantiser's
+exponents and mantissas over the whole 4096 x 4096 tensor, bit for bit): exit code 1 on mismatch.
+Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
 
@@ -48,6 +53,7 @@ CFG = dict(name="block_fp", is_ptq=True, bypass=False,
            data_in_width=6, data_in_exponent_width=8, data_in_exponent_bias=127, data_in_block_size=[1, 16],
            weight_width=6, weight_exponent_width=8, weight_exponent_bias=127, weight_block_size=[1, 16],
            bias_width=6, bias_exponent_width=8, bias_exponent_bias=127, bias_block_size=[16])
+DUMP_ROWS, DUMP_SEED = 2048, 0     # --dump-outputs: the rows of y written (32 MiB), a fixed seeded choice
 INT8_DENSE_PEAK_TFLOPS = 5000.0   # MI355X_MICROARCH.md: I8 MFMA = 2x the ~2.5 PF dense bf16 rate
 HBM_PEAK_GBS = 8000.0             # HBM3E spec; ~6300 achievable by a copy (MI355X_MICROARCH.md)
 
@@ -58,6 +64,27 @@ def make_inputs(torch, device, rank):
     w = torch.randn(N, K, generator=g(2)) * 0.02
     b = torch.randn(N, generator=g(3)) * 0.02
     return x.to(device), w.to(device), b.to(device)
+
+
+def dump_rows():
+    """the rows of y that --dump-outputs writes: DUMP_ROWS of the M, chosen once by a seeded generator, ascending"""
+    import numpy as np
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(M, size=DUMP_ROWS, replace=False))
+
+
+def dump_capture(torch, y_all):
+    """Right behind the timed steps, on the device: the dumped rows of the y the last step left.  `y_all` is [P, M, N / P]
+    (the rank-major buffer the sharded step hands on; P = 1 otherwise), so the rows come back as [DUMP_ROWS, N]."""
+    pick = torch.from_numpy(dump_rows()).to(y_all.device)
+    return y_all.index_select(1, pick).permute(1, 0, 2).reshape(DUMP_ROWS, -1)
+
+
+def dump_write(out_dir, arrays):
+    """DIR/<name>.npy, float32, for each captured array (after everything else: the copies to the host are not timed)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
 
 
 def cpu_baseline(torch):
@@ -471,6 +498,12 @@ def main():
     ap.add_argument("--workload", choices=["gemm", "quantizers"], default="gemm")
     ap.add_argument("--clock-ramp-ms", type=float, default=60.0,
                     help="un-timed launches of the step for this long before the warm-up steps (GPU clock ramp; 0 = off)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, every other figure and check as well: the no-ramp pass, the event-timed "
+                         "roofline, back-to-back launches and the measured ceiling, weight packing, config 5, the outlier-channel "
+                         "variant, config 3, replicas / quantised gather (N > 1), the oracle check and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; y: a fixed seeded sample of its rows)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-verify", action="store_true", help="skip the oracle check of the timed step's output")
     ap.add_argument("--no-config5", action="store_true", help="leave the fake-quantiser summary (BASELINE config 5) out of the line")
@@ -482,6 +515,8 @@ def main():
                     help="exponent alignment of the packed operands: whole rows (row-scale int8 GEMM); the 256-value-group "
                          "flavour was removed in round 5")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "gemm":
+        ap.error("--dump-outputs writes the gemm workload's step output; --workload quantizers has none to write")
 
     # stdout carries the ONE JSON line and nothing else: whatever native libraries print there (RCCL's "Librccl path" banner
     # arrives at process exit, behind the JSON line) goes to stderr instead
@@ -550,14 +585,14 @@ def main():
                 # rank-major [P, M, N/P]: what the sharded module hands on (sharded.ShardedRows); the next mi355q Linear's
                 # quantiser reads the P row segments where they lie, so y [M, N] is never re-assembled
                 dist.all_gather_into_tensor(gathered.view(world * M, n_out), y)
-        return step, x, w, b, y
+        return step, x, w, b, y, (gathered if shard_w else y[None])
 
-    step, x, w, b, y = build(sharded, 0 if sharded or world == 1 else rank)
+    step, x, w, b, y, y_all = build(sharded, 0 if sharded or world == 1 else rank)
     ops.gemm_timing(False)
-    # the literal protocol first -- W warm-up steps, K timed steps, straight from the idle GPU (the clocks are still rising:
-    # reported as `no_ramp`); then the clock ramp and the steady-state figure the line's `value` carries
+    # --full: the literal protocol first -- W warm-up steps, K timed steps, straight from the idle GPU (the clocks are still
+    # rising: reported as `no_ramp`); then, in every run, the clock ramp and the steady-state figure the line's `value` carries
     no_ramp = None
-    if args.clock_ramp_ms > 0:
+    if args.full and args.clock_ramp_ms > 0:
         dt0 = timed(torch, dist, world, device, step, args.steps, args.warmup)
         no_ramp = (dt0, None)
     clock_ramp(torch, step, args.clock_ramp_ms)
@@ -565,21 +600,23 @@ def main():
         step()
     torch.cuda.synchronize()
     # Two passes of exactly K steps each, both bracketed as `timed` brackets them.  Pass 1 is the step as a caller runs it:
-    # `value` and `ms_per_step`.  Pass 2 has the library record a HIP event pair around every launch of the dominant kernel on
-    # the launch stream: `roofline.avg_launch_ms`.  One pass for both overstates the step: two event records per step are two
-    # more packets in the queue between dependent kernels (measured: +5-6 us per 90-us step, reported as
+    # `value` and `ms_per_step`.  Pass 2 (--full) has the library record a HIP event pair around every launch of the dominant
+    # kernel on the launch stream: `roofline.avg_launch_ms`.  One pass for both overstates the step: two event records per step
+    # are two more packets in the queue between dependent kernels (measured: +5-6 us per 90-us step, reported as
     # `ms_per_step_with_events`).
     dt = timed(torch, dist, world, device, step, args.steps, 0)
-    cap = verify_capture(torch, ops, x, w, b, y) if (rank == 0 and not args.no_verify) else None
-    ops.gemm_timing(True)
-    dt_events = timed(torch, dist, world, device, step, args.steps, 0)
-    ops.gemm_timing(False)
-    n_timed, gemm_avg_ms, gemm_min_ms = ops.gemm_timing_read()
+    dumped = {"y": dump_capture(torch, y_all)} if (rank == 0 and args.dump_outputs) else None
+    cap = verify_capture(torch, ops, x, w, b, y) if (args.full and rank == 0 and not args.no_verify) else None
+    if args.full:
+        ops.gemm_timing(True)
+        dt_events = timed(torch, dist, world, device, step, args.steps, 0)
+        ops.gemm_timing(False)
+        n_timed, gemm_avg_ms, gemm_min_ms = ops.gemm_timing_read()
     # ... and the dominant kernel alone, K launches back to back on the operands of the last step, no events: launch to
     # launch, i.e. its duration plus one dispatch gap -- what the event pair (and the profiler's per-dispatch signals) add to
     # a kernel's measured duration shows against this figure
     b2b_ms, ceiling = None, {}
-    if not sharded and rows_mode:
+    if args.full and not sharded and rows_mode:
         xa_last = quantize_x(x, xw, 8, 127)
         _, wm_b, we_b = ops.block_fp_quantize(w, ww, 8, 127, [1, 16], False, want_fake=False, want_packed=True, fast_zero_blocks=True)
         wa_b, bq_b = ops.bfp_align_rows(wm_b, we_b, ww - 1, 127), ops.block_fp_quantize(b, CFG["bias_width"], 8, 127, [16], False)
@@ -592,7 +629,7 @@ def main():
     value = flops_job * args.steps / dt / 1e12
 
     replicas = None
-    if sharded:                                               # the independent-replica number next to it
+    if args.full and sharded:                                 # the independent-replica number next to it
         step_r, *_ = build(False, rank)
         dt_r = timed(torch, dist, world, device, step_r, args.steps, args.warmup)
         replicas = {"value": round(2.0 * M * N * K * world * args.steps / dt_r / 1e12, 2), "unit": "TFLOP/s", "scaling": "weak",
@@ -600,7 +637,7 @@ def main():
                     "what": "each rank its own 4096 rows against replicated packed weights, no collective"}
 
     qgather = None
-    if sharded and N % (32 * world) == 0 and N == K:
+    if args.full and sharded and N % (32 * world) == 0 and N == K:
         # the same layer as one link of a CHAIN of sharded layers under gather = "quantised" (sharded.py): the x operand
         # arrives as the previous layer's gathered tiled-bf16 segments; this rank multiplies on the bf16 tile GEMM, quantises its
         # own output slice with the next layer's quantiser and the ranks all-gather THAT (2 bytes per value).  Reported beside the
@@ -627,11 +664,10 @@ def main():
 
     failed = False
     if rank == 0:
-        achieved = flops_kernel / (gemm_avg_ms * 1e-3) / 1e12
         # (the dominant kernel: the 256 x 256 tile GEMM of mi355q_gemm_v9.hip with its exception add-back -- round 4; MI355Q_V9_FIX=0
         #  puts the round-2 kernel bfp_gemm_v8<1, 8, 2, false> back)
         kname = "mi355q::bfp_gemm_v8<1, 8, 2, false>" if os.environ.get("MI355Q_V9_FIX") == "0" else "mi355q::bfp_gemm_v9<1, false, false>"
-        traffic, tsrc = committed_traffic(kname) if rows_mode and not sharded else (None, None)
+        traffic, tsrc = committed_traffic(kname) if args.full and rows_mode and not sharded else (None, None)
         ms_step = dt / args.steps * 1e3
         out = {
             "metric": "quantised-GEMM TFLOP/s (4096^2, block=16, W6A6 BFP)",
@@ -648,26 +684,28 @@ def main():
                        "arithmetic": "int8 mantissa x int8 mantissa -> int32 (MFMA), fp32 row/block scaling, fp32 y",
                        "M_per_gpu": M, "N": N, "N_per_gpu": n_out, "K": K, "shard": args.shard if world > 1 else "none",
                        "align": args.align, "gemm_variant": ops.set_gemm_variant(args.variant)},
-            "roofline": {"bound": "mfma", "kernel": kname.replace("mi355q::", "") + " (row-scale int8 tile GEMM)",
-                         "achieved": round(achieved, 2), "peak": INT8_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / INT8_DENSE_PEAK_TFLOPS, 4),
-                         "step_frac": round(value / world / INT8_DENSE_PEAK_TFLOPS, 4),
-                         "step_frac_note": "the whole step (activation quantiser + GEMM + launch gaps) per GPU against the same peak",
-                         "traffic": traffic,
-                         "traffic_source": (f"committed profile profiles/{tsrc}: rocprofv3 --pmc FETCH_SIZE x 2 + WRITE_SIZE per launch, "
-                                            "separate passes over tools/cdriver/step_driver (same step through the C ABI); not "
-                                            "measured by this run") if traffic else None,
-                         "avg_launch_ms": round(gemm_avg_ms, 4), "min_launch_ms": round(gemm_min_ms, 4), "launches_timed": n_timed,
-                         "measured": f"second pass of {args.steps} steps with a HIP event pair on every launch of this kernel (library, launch "
-                                     "stream; since round 6 the pair is attached to the kernel's own dispatch -- hipExtLaunchKernelGGL start / stop "
-                                     "events: kernel start to kernel end -- instead of two marker records around it, which also timed the command "
-                                     "processor's way from marker to dispatch to marker: 69-71 us on the same boxes); `value` is the first pass, "
-                                     "without events",
-                         "ms_per_step_with_events": round(dt_events / args.steps * 1e3, 4),
-                         "back_to_back_launch_ms": None if b2b_ms is None else round(b2b_ms, 4),
-                         "back_to_back_note": "the same kernel alone, launch to launch without events (duration + one dispatch gap)"},
         }
-        prof_us, prof_calls, prof_src = committed_profile_launch_us(kname) if rows_mode and not sharded else (None, None, None)
+        if args.full:
+            achieved = flops_kernel / (gemm_avg_ms * 1e-3) / 1e12
+            out["roofline"] = {"bound": "mfma", "kernel": kname.replace("mi355q::", "") + " (row-scale int8 tile GEMM)",
+                               "achieved": round(achieved, 2), "peak": INT8_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s",
+                               "frac": round(achieved / INT8_DENSE_PEAK_TFLOPS, 4),
+                               "step_frac": round(value / world / INT8_DENSE_PEAK_TFLOPS, 4),
+                               "step_frac_note": "the whole step (activation quantiser + GEMM + launch gaps) per GPU against the same peak",
+                               "traffic": traffic,
+                               "traffic_source": (f"committed profile profiles/{tsrc}: rocprofv3 --pmc FETCH_SIZE x 2 + WRITE_SIZE per launch, "
+                                                  "separate passes over tools/cdriver/step_driver (same step through the C ABI); not "
+                                                  "measured by this run") if traffic else None,
+                               "avg_launch_ms": round(gemm_avg_ms, 4), "min_launch_ms": round(gemm_min_ms, 4), "launches_timed": n_timed,
+                               "measured": f"second pass of {args.steps} steps with a HIP event pair on every launch of this kernel (library, launch "
+                                           "stream; since round 6 the pair is attached to the kernel's own dispatch -- hipExtLaunchKernelGGL start / stop "
+                                           "events: kernel start to kernel end -- instead of two marker records around it, which also timed the command "
+                                           "processor's way from marker to dispatch to marker: 69-71 us on the same boxes); `value` is the first pass, "
+                                           "without events",
+                               "ms_per_step_with_events": round(dt_events / args.steps * 1e3, 4),
+                               "back_to_back_launch_ms": None if b2b_ms is None else round(b2b_ms, 4),
+                               "back_to_back_note": "the same kernel alone, launch to launch without events (duration + one dispatch gap)"}
+        prof_us, prof_calls, prof_src = committed_profile_launch_us(kname) if args.full and rows_mode and not sharded else (None, None, None)
         if prof_us:
             out["roofline"]["committed_profile"] = {
                 "avg_launch_us": round(prof_us, 2), "launches": prof_calls, "frac": round(2.0 * M * n_out * K / (prof_us * 1e-6) / 1e12 / INT8_DENSE_PEAK_TFLOPS, 4),
@@ -694,7 +732,7 @@ def main():
             out["quantised_gather"] = qgather
         if replicas:
             out["replicas"] = replicas
-        if rows_mode:
+        if args.full and rows_mode:
             # the one-off cost the steady-state step leaves out (reported separately): quantise + pack + row-align
             # this rank's weights and quantise its bias, as the first PTQ forward / pack_now() does; second of two runs
             ww = CFG["weight_width"]
@@ -713,14 +751,14 @@ def main():
         # (the GPU-side objects first, the host-side ones -- oracle check, CPU baselines: tens of seconds of all-core host work --
         #  last: the first GPU case measured right behind them ran 4-5x slow on this round's boxes, r5m / r5p / r5r, although neither
         #  an idle GPU nor busy host threads alone reproduce it, tools/dbg/host_after_cpu.py)
-        if world == 1 and not args.no_config5:
+        if args.full and world == 1 and not args.no_config5:
             out["config5"] = config5_summary(torch, ops, args, device, False)
-        if world == 1 and not args.no_robustness:
+        if args.full and world == 1 and not args.no_robustness:
             try:
                 out["robustness"] = robustness_summary(torch, ops, device)
             except Exception as e:                                   # noqa: BLE001  (reported, never raised: the headline stands)
                 out["robustness"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if world == 1 and not args.no_config3:
+        if args.full and world == 1 and not args.no_config3:
             out["config3"] = config3_summary(torch)
         if cap is not None:
             out["verify"] = verify_check(cap)
@@ -729,10 +767,12 @@ def main():
         rob = out.get("robustness", {})
         if isinstance(rob.get("verify"), dict) and not rob["verify"].get("ok", True):
             failed = True
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(torch)
             if "config5" in out:
                 out["config5"]["cpu_baseline"] = cpu_baseline_config5(torch)
+        if dumped:
+            dump_write(args.dump_outputs, dumped)
         result_out.write(json.dumps(out) + "\n")
         result_out.flush()
     if world > 1 or force_dist:
