@@ -4,6 +4,8 @@
 //
 //     a = h + m + l,   h = bf16(a), m = bf16(a - h), l = bf16(a - h - m)        (both differences exact in fp32: 24 significand bits
 //                                                                               in three parts of 8)
+//     (|a| >= 0x7F7F8000 rounds to inf in bf16: h is then a TRUNCATED to bf16, so that a - h -- the low 16 bits -- stays finite
+//      and a finite input never yields a NaN part; inf / NaN inputs still give non-finite parts, as F.linear gives)
 //     x . w^T = sum over the SIX part pairs of weight >= 2^-18:  (m,m) (l,h) (h,l) (m,h) (h,m) (h,h)   -- the three dropped pairs
 //               (m,l) (l,m) (l,l) weigh <= 2^-26 of a product, below the rounding of the fp32 accumulation itself
 //
@@ -25,6 +27,14 @@
 #include "mi355q_quant_dev.h"
 
 namespace mi355q {
+
+// bf16 RNE of both values, except where that overflows a finite value to inf: there the value truncated to bf16
+__device__ __forceinline__ unsigned split_part_bf16(float a0, float a1) {
+    unsigned pk = pack_bf16(a0, a1);
+    if ((pk & 0x7FFFu) == 0x7F80u && __builtin_isfinite(a0)) pk = (pk & 0xFFFF0000u) | (__float_as_uint(a0) >> 16);
+    if ((pk & 0x7FFF0000u) == 0x7F800000u && __builtin_isfinite(a1)) pk = (pk & 0xFFFFu) | (__float_as_uint(a1) & 0xFFFF0000u);
+    return pk;
+}
 
 // part index (0 = h, 1 = m, 2 = l) of each of the six column segments: ROLE 0 = left operand, 1 = right operand
 template <int ROLE>
@@ -49,7 +59,7 @@ __global__ __launch_bounds__(256) void fp32_split_tile_kernel(const float* __res
             float a0 = v[e], a1 = v[e + 1];
 #pragma unroll
             for (int s = 0; s < 3; ++s) {
-                const unsigned pk = pack_bf16(a0, a1);
+                const unsigned pk = split_part_bf16(a0, a1);
                 part[s][e >> 1] = pk;
                 a0 -= __uint_as_float(pk << 16);                  // (exact: the part shares a's leading bits)
                 a1 -= __uint_as_float(pk & 0xFFFF0000u);

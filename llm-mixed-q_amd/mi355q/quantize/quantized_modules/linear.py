@@ -925,7 +925,8 @@ def gated_mlp(x, gate, up, down, norm=None, residual=None):
         return None
     with torch.no_grad():
         pair = gate.__dict__.get("_gated_pair")
-        key = (id(up), gate.weight._version, up.weight._version, gate._packed[0].tiled.data_ptr(), up._packed[0].tiled.data_ptr())
+        key = (id(up), gate.weight._version, up.weight._version, gate._packed[0].tiled.data_ptr(), up._packed[0].tiled.data_ptr(),
+               None if gate.bias is None else gate.bias._version, None if up.bias is None else up.bias._version)
         if pair is None or pair[0] != key:
             w_gu = ops.interleave_gate_up(gate._packed[0], up._packed[0])
             b_gu = None

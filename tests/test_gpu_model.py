@@ -166,12 +166,95 @@ def _check_fixture(tag, knobs, forwards=1, loss_tol=2e-5):
         assert lin._packed is not None, "K % 128 == 0 layer did not take the int8 path"
 
 
+# the switches BASELINE config 3 runs with (tools/config3_full_depth.quant_config("resident") and its model.mi355q_lm_head;
+# tests/test_oracle_compare.py keeps the two equal): every_knob's five, the residual in the stores, the gated / relu MLP epilogues,
+# the mixed contraction, rotary on load in the attention pass, the attention pass writing o_proj's quantised operand, the
+# split-bf16 lm_head
+CONFIG3_KNOBS = dict(mi355q_fused_attention=True, mi355q_grouped_linear=True, mi355q_fused_activation=True, mi355q_fused_norm=True,
+                     mi355q_token_major_output=True, mi355q_fused_residual=True, mi355q_fused_gate_up=True, mi355q_mixed="auto",
+                     mi355q_fused_rotary=True, mi355q_fused_attention_output=True)
+CONFIG3_LM_HEAD = "split"
+
+
+def _config3_knobs(knobs):
+    return dict(CONFIG3_KNOBS, **({"mi355q_weight_storage": "hybrid"} if knobs == "config3_hybrid" else {}))
+
+
+def _route_census():
+    """wraps the ops entry points of config 3's fused paths; returns (counts, restore).  `residual` is read from the bound
+    arguments, so that it counts whether it was passed by keyword or by position"""
+    import inspect
+    from mi355q import ops
+    counts = dict(gated=0, relu=0, attention=0, attention_consumer=0, attention_rope=0, residual=0, mixed=0)
+    names = ("bfp_gemm_aligned_gated", "bfp_gemm_aligned_relu", "bfp_attention", "bfp_gemm_aligned", "bf16_gemm_tiled", "bfp_gemm_mixed")
+    real = {n: getattr(ops, n) for n in names}
+    sig = {n: inspect.signature(f) for n, f in real.items()}
+
+    def wrap(name):
+        def f(*a, **k):
+            arg = sig[name].bind(*a, **k).arguments
+            if name == "bfp_gemm_aligned_gated":
+                counts["gated"] += 1
+            elif name == "bfp_gemm_aligned_relu":
+                counts["relu"] += 1
+            elif name == "bfp_attention":
+                counts["attention"] += 1
+                counts["attention_consumer"] += arg.get("consumer") is not None
+                counts["attention_rope"] += arg.get("rope") is not None
+            elif name == "bfp_gemm_mixed":
+                counts["mixed"] += 1
+            counts["residual"] += arg.get("residual") is not None
+            return real[name](*a, **k)
+        return f
+
+    for n in names:
+        setattr(ops, n, wrap(n))
+
+    def restore():
+        for n, f in real.items():
+            setattr(ops, n, f)
+    return counts, restore
+
+
+def _assert_config3_routes(what, family, counts, io, hooked, reached):
+    """prints the route census and the Linears whose hooks fired on the last forward, and asserts both against what the
+    first MI355X run of the config-3 cases recorded (hooked / reached: family -> sorted names / paths with a count > 0)"""
+    fired = sorted(io)
+    print(f"{what} route census, last forward: {counts}; hooks fired: {fired}")
+    if hooked.get(family) is not None:
+        assert fired == hooked[family], (fired, hooked[family])
+    if reached.get(family) is not None:
+        assert sorted(k for k, v in counts.items() if v) == reached[family], (counts, reached[family])
+
+
 _G5W = _json.loads((_GOLDEN / "models_wide.json").read_text())
 
 
-@pytest.mark.parametrize("knobs", ["plain", "every_knob"])
+@pytest.mark.parametrize("knobs", ["plain", "every_knob", "config3"])
 @pytest.mark.parametrize("tag", sorted(_G5W))
 def test_reference_model_fixture_at_real_widths(tag, knobs):
+    _fixture_at_real_widths(tag, knobs)
+
+
+@pytest.mark.parametrize("tag", sorted(t for t in _G5W if _G5W[t]["family"] == "llama"))
+def test_reference_model_fixture_at_real_widths_config3_hybrid(tag):
+    """config 3's switches with mi355q_weight_storage = "hybrid" (the layers on the per-block route packed at width + 0.5 bits,
+    expanded per forward)"""
+    _fixture_at_real_widths(tag, "config3_hybrid")
+
+
+# which Linears' forward hooks still fire under config 3 at these widths (2 x 128 tokens): the others run inside fused launches
+# (grouped q / k / v and gate / up, the residual in o_proj's / down_proj's / fc2's stores) and are held to the oracle by
+# tests/test_gpu_fused_oracle.py
+# -- none at 2 x 128 tokens, so the teacher-forced per-Linear check has nothing left to hold here
+_CONFIG3_HOOKED = {"opt": [], "llama": []}
+# which of config 3's fused paths the last forward took (count > 0), per family, as the first MI355X run found them: the gated
+# epilogue (Llama) and the relu one (OPT) with down_proj / fc2 on the per-block route, rotary on load, the residual in the stores;
+# NOT the attention consumer (2 x 128 tokens: batch 2) and not the mixed contraction (no layer's rows miss every window)
+_CONFIG3_REACHED = {"opt": ["attention", "relu", "residual"], "llama": ["attention", "attention_rope", "gated", "residual"]}
+
+
+def _fixture_at_real_widths(tag, knobs):
     """2 decoder layers at OPT-1.3B width (2048 / 8192, 32 heads of 64) and Llama-7B width (4096 / 11008, 32 heads of 128),
     2 x 128 tokens: the reference's own logits and loss (tools/gen_golden_models.py --wide; the weights are a seeded recipe in
     the fixture).  At these widths every Linear takes the 256 x 256-tile int8 GEMM with its exception lists and the heads
@@ -183,6 +266,9 @@ def test_reference_model_fixture_at_real_widths(tag, knobs):
     sd, _, ids, ref_logits, ref_loss, m = NM.load_wide_fixture(_G5W, data, tag)
     kn = {} if knobs == "plain" else dict(mi355q_grouped_linear=True, mi355q_fused_norm=True, mi355q_fused_activation=True,
                                           mi355q_fused_attention=True, mi355q_token_major_output=True)
+    c3 = knobs.startswith("config3")
+    if c3:
+        kn = _config3_knobs(knobs)
     if m["family"] == "opt":
         cfg = H.TinyOPTConfig(vocab_size=m["vocab_size"], hidden_size=m["hidden_size"], ffn_dim=m["ffn_dim"],
                               num_layers=m["num_layers"], num_heads=m["num_heads"], max_positions=m["max_positions"])
@@ -193,9 +279,15 @@ def test_reference_model_fixture_at_real_widths(tag, knobs):
                                 rms_eps=m["rms_eps"])
         model = H.TinyLlamaForCausalLM(cfg, H.expand_llama_quant_config(_with_knob(m["quant_config"], **kn), cfg.num_layers))
     model.load_reference_state_dict(sd).to("cuda:0").eval()
+    if c3:
+        model.mi355q_lm_head = CONFIG3_LM_HEAD
     taps, io = {}, {}
-    model.layers[0].self_attn.register_forward_hook(lambda mod, i, o: taps.__setitem__("attn0", o.detach()))
-    if knobs == "plain":                                     # (every Linear's input and output as the forward saw them)
+    if c3:                                                   # (fused residual: the block returns residual + attention)
+        model.layers[0].self_attn.register_forward_hook(
+            lambda mod, i, k, o: taps.update(attn0=o.detach(), res0=k.get("residual")), with_kwargs=True)
+    else:
+        model.layers[0].self_attn.register_forward_hook(lambda mod, i, o: taps.__setitem__("attn0", o.detach()))
+    if knobs == "plain" or c3:                               # (every Linear's input and output as the forward saw them)
         from mi355q.quantize import get_quantized_cls
         lin_cls = get_quantized_cls("linear", m["quant_config"]["default"])
         for name, mod in model.named_modules():
@@ -203,15 +295,28 @@ def test_reference_model_fixture_at_real_widths(tag, knobs):
                 mod.register_forward_hook(lambda mod, i, o, name=name: io.__setitem__(name, (i[0].detach().clone(), o.detach().clone())))
     t = torch.from_numpy(ids).to("cuda:0")
     with torch.no_grad():
-        for _ in range(2):                                   # (the second forward runs on the packed weights)
-            logits, loss = model(t, labels=t)
+        for f in range(2):                                   # (the second forward runs on the packed weights)
+            if c3 and f == 1:
+                io.clear()
+                counts, restore = _route_census()
+            try:
+                logits, loss = model(t, labels=t)
+            finally:
+                if c3 and f == 1:
+                    restore()
     lin = model.layers[0].fc2 if m["family"] == "opt" else model.layers[0].down_proj
     assert lin._packed is not None and lin._align_mode == "rows", "the row-aligned int8 GEMM was not taken"
+    if c3:
+        _assert_config3_routes(f"{tag} [{knobs}]", m["family"], counts, io, _CONFIG3_HOOKED, _CONFIG3_REACHED)
     # (1) the first layer's attention output (q / k / v projections at K = hidden, rotary, both products, softmax, the
     #     output projection): tight -- nothing upstream of it amplifies a last-bit difference
     ref_attn = data[tag + "/attn0"]
     a = taps["attn0"].reshape(ids.shape[0], ids.shape[1], -1)[:, :, :128].cpu().numpy()
     ea = float(np.abs(a - ref_attn).max() / np.abs(ref_attn).max())
+    if c3:                                                   # out - x: the attn0 bound plus the rounding of the add, 2^-23 max|x|
+        x0 = taps["res0"].reshape(ids.shape[0], ids.shape[1], -1)[:, :, :128].cpu().numpy()
+        a = a - x0
+        ea = max(0.0, float(np.abs(a - ref_attn).max()) - 2.0 ** -23 * float(np.abs(x0).max())) / float(np.abs(ref_attn).max())
     # (2) logits and loss.  Downstream every fp32 value passes W6 quantisers (relative step 2^-5 of its block's maximum): two
     #     implementations whose Linear outputs differ in the last bit (summation order) round a handful of the ~10^6
     #     activations per tensor to different neighbours, and a moved value moves the roundings behind it -- the numpy oracle
@@ -237,17 +342,40 @@ def test_reference_model_fixture_at_real_widths(tag, knobs):
         e = float(np.abs(yout.cpu().numpy().reshape(want.shape) - want).max() / np.abs(want).max())
         worst = max(worst, e)
         assert e < 4e-6, (name, e)
-    if io:
+    if io and not c3:
         print(f"{tag}: {len(io)} Linear layers teacher-forced against the oracle, worst relative error {worst:.2e}")
         assert len(io) == (6 if m["family"] == "opt" else 7) * m["num_layers"]
+    if c3:
+        print(f"{tag} [{knobs}]: {len(io)} Linear layers teacher-forced against the oracle, worst relative error {worst:.2e}")
 
 
 _G5W2 = _json.loads((_GOLDEN / "models_wide2.json").read_text())
 
 
-@pytest.mark.parametrize("knobs", ["plain", "every_knob"])
+@pytest.mark.parametrize("knobs", ["plain", "every_knob", "config3"])
 @pytest.mark.parametrize("tag", sorted(_G5W2))
 def test_reference_model_fixture_wide2(tag, knobs):
+    _fixture_wide2(tag, knobs)
+
+
+@pytest.mark.parametrize("tag", sorted(t for t in _G5W2 if _G5W2[t]["family"] == "llama"))
+def test_reference_model_fixture_wide2_config3_hybrid(tag):
+    """config 3's switches with mi355q_weight_storage = hybrid"""
+    _fixture_wide2(tag, "config3_hybrid")
+
+
+# as _CONFIG3_HOOKED / _CONFIG3_REACHED, for the wide2 fixtures (keyed by tag: the T = 2048 cases run batch 1, so the attention
+# pass can write o_proj's / out_proj's operand there)
+# (first MI355X run: the Llama T = 2048 case reaches the attention consumer; OPT's out_proj is not on the per-block route in either
+#  OPT case, so no OPT fixture reaches it -- held by tests/test_gpu_fused_oracle.py instead; no case reaches the mixed contraction)
+_CONFIG3_HOOKED_W2 = {"llama7b_width_w6a6_t2048": [], "opt1p3b_width_w6a6_t2048": [],
+                      "opt1p3b_width_w4a4_mixed": ["layers.0.self_attn.k_proj", "layers.0.self_attn.q_proj", "layers.0.self_attn.v_proj"]}
+_CONFIG3_REACHED_W2 = {"llama7b_width_w6a6_t2048": ["attention", "attention_consumer", "attention_rope", "gated", "residual"],
+                       "opt1p3b_width_w6a6_t2048": ["attention", "relu", "residual"],
+                       "opt1p3b_width_w4a4_mixed": ["attention", "relu", "residual"]}
+
+
+def _fixture_wide2(tag, knobs):
     """tools/gen_golden_models.py --wide2, the reference's own numbers for (1) OPT-1.3B width under W4A4 with MIXED per-layer
     widths (BASELINE config 4's kind: experiments/emnlp/configs/search/opt_1.3b_sst2.toml:24-37) and (2), (3) one T = 2048 case
     per family at OPT-1.3B / Llama-7B width (the one-pass attention kernel at its full length against reference-produced
@@ -263,6 +391,9 @@ def test_reference_model_fixture_wide2(tag, knobs):
                                           mi355q_fused_attention=True, mi355q_token_major_output=True)
     if knobs == "plain" and sampled:
         kn = dict(mi355q_fused_attention=True)       # (the stepped attention at T = 2048 needs [32, 2048, 2048] tensors: one-pass only)
+    c3 = knobs.startswith("config3")
+    if c3:
+        kn = _config3_knobs(knobs)
     if m["family"] == "opt":
         cfg = H.TinyOPTConfig(vocab_size=m["vocab_size"], hidden_size=m["hidden_size"], ffn_dim=m["ffn_dim"],
                               num_layers=m["num_layers"], num_heads=m["num_heads"], max_positions=m["max_positions"])
@@ -273,21 +404,45 @@ def test_reference_model_fixture_wide2(tag, knobs):
                                 rms_eps=m["rms_eps"])
         model = H.TinyLlamaForCausalLM(cfg, H.expand_llama_quant_config(_with_knob(m["quant_config"], **kn), cfg.num_layers))
     model.load_reference_state_dict(sd).to("cuda:0").eval()
-    taps = {}
-    model.layers[0].self_attn.register_forward_hook(lambda mod, i, o: taps.__setitem__("attn0", o.detach()))
+    taps, io = {}, {}
+    if c3:
+        model.mi355q_lm_head = CONFIG3_LM_HEAD
+        model.layers[0].self_attn.register_forward_hook(
+            lambda mod, i, k, o: taps.update(attn0=o.detach(), res0=k.get("residual")), with_kwargs=True)
+        from mi355q.quantize import get_quantized_cls
+        lin_cls = get_quantized_cls("linear", m["quant_config"]["default"])
+        for name, mod in model.named_modules():
+            if isinstance(mod, lin_cls) and name.startswith("layers."):
+                mod.register_forward_hook(lambda mod, i, o, name=name: io.__setitem__(name, True))
+    else:
+        model.layers[0].self_attn.register_forward_hook(lambda mod, i, o: taps.__setitem__("attn0", o.detach()))
     t = torch.from_numpy(ids).to("cuda:0")
     with torch.no_grad():
-        for _ in range(2):
-            logits, loss = model(t, labels=t)
+        for f in range(2):
+            if c3 and f == 1:
+                io.clear()
+                counts, restore = _route_census()
+            try:
+                logits, loss = model(t, labels=t)
+            finally:
+                if c3 and f == 1:
+                    restore()
+    if c3:
+        _assert_config3_routes(f"{tag} [{knobs}]", tag, counts, io, _CONFIG3_HOOKED_W2, _CONFIG3_REACHED_W2)
     a = taps["attn0"].reshape(ids.shape[0], ids.shape[1], -1)[:, :, :128].cpu().numpy()
+    x0 = taps["res0"].reshape(ids.shape[0], ids.shape[1], -1)[:, :, :128].cpu().numpy() if c3 else None
     lg = logits.cpu().numpy()
     if sampled:
         rows = data[tag + "/rows"]
         ref_attn, ref_logits = data[tag + "/attn0_rows"], data[tag + "/logits_rows"]
         a, lg = a[0, rows], lg[0, rows]
+        x0 = None if x0 is None else x0[0, rows]
     else:
         ref_attn, ref_logits = data[tag + "/attn0"], data[tag + "/logits"]
     ea = float(np.abs(a - ref_attn).max() / np.abs(ref_attn).max())
+    if c3:                                                   # out - x: the attn0 bound plus the rounding of the add, 2^-23 max|x|
+        a = a - x0
+        ea = max(0.0, float(np.abs(a - ref_attn).max()) - 2.0 ** -23 * float(np.abs(x0).max())) / float(np.abs(ref_attn).max())
     d = np.abs(lg - ref_logits)
     scale = float(np.abs(ref_logits).max())
     dl = abs(float(loss) - ref_loss)
@@ -527,8 +682,15 @@ def test_tiny_llama_loss_parity_other_block_arithmetics(arith, products):
 # ---- trained weights: perplexity as eval/eval_lm.py computes it, on a model that is not noise ------------------------------
 _TRAINED = _json.loads((_GOLDEN / "trained.json").read_text()) if (_GOLDEN / "trained.json").exists() else {}
 
+# the fused paths the last config-3 forward took (count > 0), per fixture and widths
+# (first MI355X run: Llama W6A6 reaches the attention consumer in 2 of its 4 layers -- the o_proj layers on the per-block route --,
+#  Llama W4A4 and OPT in none; hidden 128 has no gated / relu epilogue; no mixed contraction)
+_CONFIG3_REACHED_TRAINED = {"llama_trained/w6a6": ["attention", "attention_consumer", "attention_rope", "residual"],
+                            "llama_trained/w4a4": ["attention", "attention_rope", "residual"],
+                            "opt_trained/w6a6": ["attention", "residual"], "opt_trained/w4a4": ["attention", "residual"]}
 
-@pytest.mark.parametrize("knobs", ["plain", "every_knob"])
+
+@pytest.mark.parametrize("knobs", ["plain", "every_knob", "config3"])
 @pytest.mark.parametrize("name", ["w6a6", "w4a4"])
 @pytest.mark.parametrize("tag", sorted(_TRAINED))
 def test_perplexity_on_trained_weights(tag, name, knobs):
@@ -550,6 +712,8 @@ def test_perplexity_on_trained_weights(tag, name, knobs):
     sd = {k[len(pre):]: data[k].astype(np.float32) for k in data.files if k.startswith(pre)}
     kn = {} if knobs == "plain" else dict(mi355q_grouped_linear=True, mi355q_fused_norm=True, mi355q_fused_activation=True,
                                           mi355q_fused_attention=True, mi355q_token_major_output=True)
+    if knobs == "config3":
+        kn = CONFIG3_KNOBS
     if m["family"] == "opt":
         cfg = H.TinyOPTConfig(vocab_size=m["vocab_size"], hidden_size=m["hidden_size"], ffn_dim=m["ffn_dim"], num_layers=m["num_layers"],
                               num_heads=m["num_heads"], max_positions=m["max_positions"])
@@ -559,14 +723,27 @@ def test_perplexity_on_trained_weights(tag, name, knobs):
                                 num_layers=m["num_layers"], num_heads=m["num_heads"], max_positions=m["max_positions"], rms_eps=m["rms_eps"])
         model = H.TinyLlamaForCausalLM(cfg, H.expand_llama_quant_config(_with_knob(ev["quant_config"], **kn), cfg.num_layers))
     model.load_reference_state_dict(sd).to("cuda:0").eval()
+    if knobs == "config3":
+        model.mi355q_lm_head = CONFIG3_LM_HEAD
     chunks = torch.from_numpy(data["input_ids"])
     ref_chunks = data[f"{tag}/{name}/chunk_losses"]
     losses = []
     with torch.no_grad():
         model(chunks[0][None].to("cuda:0"))        # (the first forward quantises and packs the weights; the knobs act from the second on)
         for c in chunks:
-            _, loss = model(c[None].to("cuda:0"), labels=c[None].to("cuda:0"))
+            if knobs == "config3" and len(losses) == len(chunks) - 1:
+                counts, restore = _route_census()  # (the last forward: which of config 3's fused paths ran)
+            try:
+                _, loss = model(c[None].to("cuda:0"), labels=c[None].to("cuda:0"))
+            finally:
+                if knobs == "config3" and len(losses) == len(chunks) - 1:
+                    restore()
             losses.append(float(loss))
+    if knobs == "config3":
+        # route census (hidden 128: no gated / relu MLP epilogue, which needs in_features >= 256)
+        assert counts["gated"] == counts["relu"] == 0
+        assert counts["attention"] == m["num_layers"] and counts["attention_rope"] == (m["num_layers"] if m["family"] == "llama" else 0)
+        _assert_config3_routes(f"{tag} {name} [config3]", f"{tag}/{name}", counts, {}, {}, _CONFIG3_REACHED_TRAINED)
     res = H.eval_lm_perplexity(model, [c[None] for c in chunks], device="cuda:0")       # (the harness's eval_lm loop: same number)
     ppl = math.exp(sum(losses) / len(losses))
     assert abs(res["perplexity"] - ppl) < 1e-9 * ppl and res["num_samples"] == 16 and res["seq_len"] == 512
