@@ -54,7 +54,7 @@
 extern "C" {
 #endif
 
-#define MI355Q_ABI_VERSION 24
+#define MI355Q_ABI_VERSION 25
 #define MI355Q_WORKSPACE_BYTES 16384
 
 /* negative error codes (positive values are hipError_t) */
@@ -209,6 +209,30 @@ size_t mi355q_bfp_packed_bytes(int64_t rows, int64_t K, int32_t width);
 int mi355q_bfp_pack_bits(const int8_t* mant, uint8_t* packed, int64_t rows, int64_t K, int32_t width, void* stream);
 int mi355q_bfp_expand(const uint8_t* packed, const uint8_t* codes, void* out_tiled, int64_t rows, int64_t K, int32_t width,
                       int32_t mode, int32_t exp_offset, const uint8_t* row_exp, uint8_t* exp_out, void* stream);
+
+/* ---- small-batch product on the at-rest form (ABI 25; mi355q_gemv.hip) -------------------------------------------
+ * replaces: quantized_modules/linear.py:59-76 (F.linear(x_q, W_q, b_q)) for 1 <= M <= 16 rows of x -- token-by-token generation,
+ *           a search trial on a few prompts, a classification head -- on weights kept as mi355q_bfp_pack_bits writes them.
+ * The contraction of mi355q_bfp_gemm with the weight side read straight from `packed` + `codes`: no expanded operand is written
+ * and no scratch is used (the product is bound by the weight stream: width + 0.5 bits per value are read once).
+ *   x_tiled  the activations as TILED bf16 VALUES, what mi355q_block_fp_quantize_bf16_tiled writes for x fp32 [M, K]
+ *            (mi355q_bfp_tiled_bytes(M, 2 K) bytes; a block_fp value of width <= 9 is exact in bf16 and a product of two exact
+ *            in fp32).  The values carry x's exponents, so x_mbits / x_exp_bias are only range-checked.
+ *   packed   [N, K * width / 8], width = w_mbits + 1 in 2 .. 8;  codes uint8 [N, K / 16];
+ *   row_exp  NULL: the per-block flavour, a code is its block's biased exponent;
+ *            [N]:  the row flavour, a block's biased exponent is row_exp[n] + code, code 0xFF marks an exception block whose
+ *                  exponent and mantissas are taken from `list` (the bucketed list of "ROW-aligned operands" below, `list_cap`
+ *                  entries per bucket, 0 = 120; required with row_exp) and added back exactly; an operand whose list[0] != 0
+ *                  (rows that did not fit their bucket) is not a row-flavour operand;
+ *   bias     (nullable) fp32 [N];  y fp32 [M, ldy], ldy >= N;  N need not be a multiple of 16.
+ * One workgroup per 16 weight rows, K split over its waves, partial sums added in a fixed order: reproducible, no atomics.
+ * MI355Q_E_BADARG: null pointer, M < 0, a width outside 2 .. 8, ldy < N;  MI355Q_E_UNSUPPORTED: M > 16 or K % 64 != 0;
+ * MI355Q_E_ALIGN: x_tiled / packed not 16-byte, codes not 8-byte, y / bias / list not 4-byte aligned;  M == 0 or N == 0: 0,
+ * nothing launched.  Fast when K % 128 == 0 (16-byte aligned rows); other K % 64 == 0 are correct. */
+int mi355q_bfp_gemm_packed_small(const uint16_t* x_tiled, const uint8_t* packed, const uint8_t* codes, const uint8_t* row_exp,
+                                 const int32_t* list, int32_t list_cap, const float* bias, float* y, int64_t M, int64_t N,
+                                 int64_t K, int64_t ldy, int32_t x_mbits, int32_t x_exp_bias, int32_t w_mbits,
+                                 int32_t w_exp_bias, void* stream);
 
 /* values that are already quantised (exact in bf16), fp32 [rows, K] -> the same tiled bf16 (a cast; K % 32 == 0) */
 int mi355q_bf16_tile(const float* x, uint16_t* y_tiled, int64_t rows, int64_t K, void* stream);

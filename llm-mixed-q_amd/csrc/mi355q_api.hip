@@ -11,6 +11,7 @@
 #include <mutex>
 
 #include "mi355q_internal.h"
+#include "mi355q_gemv.h"
 #include "mi355q_align_row.h"
 
 using namespace mi355q;
@@ -222,6 +223,28 @@ int mi355q_bfp_expand(const uint8_t* packed, const uint8_t* codes, void* out_til
     if (reinterpret_cast<uintptr_t>(packed) % 2 || reinterpret_cast<uintptr_t>(out_tiled) % 16) return MI355Q_E_ALIGN;
     return launch_bfp_expand(mode, reinterpret_cast<const uint16_t*>(packed), codes, out_tiled, rows, K, width, exp_offset,
                              static_cast<hipStream_t>(stream), row_exp, exp_out);
+}
+
+int mi355q_bfp_gemm_packed_small(const uint16_t* x_tiled, const uint8_t* packed, const uint8_t* codes, const uint8_t* row_exp,
+                                 const int32_t* list, int32_t list_cap, const float* bias, float* y, int64_t M, int64_t N,
+                                 int64_t K, int64_t ldy, int32_t x_mbits, int32_t x_exp_bias, int32_t w_mbits,
+                                 int32_t w_exp_bias, void* stream) {
+    if (M < 0 || N < 0 || K < 0 || x_mbits < 1 || x_mbits > 7 || w_mbits < 1 || w_mbits > 7) return MI355Q_E_BADARG;
+    if (x_exp_bias < 0 || w_exp_bias < 0 || list_cap < 0 || list_cap > MI355Q_ROW_BUCKET_CAP_MAX) return MI355Q_E_BADARG;
+    if (M == 0 || N == 0) return 0;
+    if (!x_tiled || !packed || !codes || !y || (row_exp != nullptr && list == nullptr)) return MI355Q_E_BADARG;
+    if (ldy < N) return MI355Q_E_BADARG;
+    if (M > 16 || K == 0 || K % 64 != 0) return MI355Q_E_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(x_tiled) % 16 || reinterpret_cast<uintptr_t>(packed) % 16 || reinterpret_cast<uintptr_t>(codes) % 8 ||
+        reinterpret_cast<uintptr_t>(y) % 4 || reinterpret_cast<uintptr_t>(bias) % 4 || reinterpret_cast<uintptr_t>(list) % 4)
+        return MI355Q_E_ALIGN;
+    PackedSmallArgs a;
+    a.x_tiled = reinterpret_cast<const uint8_t*>(x_tiled);
+    a.packed = packed; a.codes = codes; a.row_exp = row_exp;
+    a.list = row_exp ? list : nullptr; a.list_cap = list_cap;
+    a.bias = bias; a.y = y; a.M = M; a.N = N; a.K = K; a.ldy = ldy;
+    a.width = w_mbits + 1; a.w_off = w_exp_bias + w_mbits;
+    return launch_bfp_gemm_packed_small(a, static_cast<hipStream_t>(stream));
 }
 
 int mi355q_bf16_tile(const float* x, uint16_t* y_tiled, int64_t rows, int64_t K, void* stream) {

@@ -414,6 +414,52 @@ def pack_block_exponent_weights(wm: torch.Tensor, we: torch.Tensor, width: int, 
     return PackedWeights(bfp_pack_bits(wm, width), we.contiguous().view(rows, K // 16), rows, K, width, exp_bias)
 
 
+SMALL_M_MAX = 16                 # rows of x the small-batch product on packed weights takes (mi355q_bfp_gemm_packed_small)
+_SMALL_M_CALLS = [0]
+
+
+def small_m_calls(reset: bool = False) -> int:
+    """launches of the small-batch product on packed weights so far (tests: was the route really taken?)"""
+    n = _SMALL_M_CALLS[0]
+    if reset:
+        _SMALL_M_CALLS[0] = 0
+    return n
+
+
+def bfp_linear_packed_small(x: torch.Tensor, pw: PackedWeights, x_width: int, x_exponent_width: int, x_exponent_bias,
+                            bias=None, out: torch.Tensor = None, pre=None) -> torch.Tensor:
+    """y [M, N] = block_fp(x) . W^T (+ bias) for 1 <= M <= SMALL_M_MAX rows of fp32 x [M, K], with W read straight from its at-rest
+    form `pw` (either flavour): no expanded operand, no scratch (csrc/mi355q_gemv.hip).  x goes through the existing tiled bf16
+    quantiser (`pre` as there); `out` may be a column slice view of a wider row-major buffer (its stride(0) becomes ldy).  No host
+    synchronisation: safe under HIP graph capture."""
+    _require_device(x, "bfp_linear_packed_small")
+    assert x.ndim == 2 and x.shape[1] == pw.K and pw.packed.device == x.device
+    M, K, N = x.shape[0], pw.K, pw.rows
+    if M > SMALL_M_MAX:
+        raise ValueError(f"mi355q.bfp_linear_packed_small: {M} rows (at most {SMALL_M_MAX}); larger batches take the tile GEMMs")
+    given = out is not None
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.shape == (M, N) and (N == 0 or out.stride(1) == 1) and out.device == x.device
+    if M == 0 or N == 0:
+        return out
+    xt = block_fp_quantize_bf16_tiled(x.contiguous(), x_width, x_exponent_width, x_exponent_bias, pre=pre)
+    ldy = out.stride(0) if M > 1 else max(N, out.stride(0))
+    xb = _default_bias(x_exponent_bias)
+    xb = 2 ** (int(x_exponent_width) - 1) - 1 if xb == BIAS_DEFAULT else xb
+    row = pw.row_scale_flavour
+    lib = _lib.load_library()
+    with _on_device(x.device):
+        rc = lib.mi355q_bfp_gemm_packed_small(_ptr(xt), _ptr(pw.packed), _ptr(pw.codes), _ptr(pw.rowexp) if row else 0,
+                                              _ptr(pw.sparse) if row else 0, 0, _ptr(bias), _ptr(out), M, N, K, ldy,
+                                              int(x_width) - 1, int(xb), pw.width - 1, pw.exp_bias, _stream_ptr(x.device))
+    _lib.check(rc, "mi355q_bfp_gemm_packed_small")
+    _SMALL_M_CALLS[0] += 1
+    if given:
+        _wrote_into(out)
+    return out
+
+
 def bf16_tile(x: torch.Tensor) -> torch.Tensor:
     """already-quantised fp32 values [rows, K] -> tiled bf16 (a cast into the tile order; exact for widths <= 9)"""
     _require_device(x, "bf16_tile")

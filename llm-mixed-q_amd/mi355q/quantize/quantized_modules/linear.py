@@ -126,6 +126,8 @@ class _LinearBase(nn.Linear):
         #       lie outside their rows' exponent window in a large share of the rows -- split in_features into two classes of block
         #       columns and run ONE launch of the mixed contraction (ops.bfp_gemm_mixed: class 0 on the int8 MFMA, class 1 on the
         #       bf16 MFMA) instead of the whole layer on the bf16 flavour (round 6)
+        #   mi355q_small_m = "off" (default) / "packed": forward() of at most ops.SMALL_M_MAX rows on a layer that keeps packed
+        #       weights runs the small-batch product that reads them in place (`_small_m_takes`)
         self._mixed = None           # dict(classes, wa0, w1): the column split and the weights' two operands
         self._w_packed = None
         self._pending_flavour = None
@@ -512,6 +514,8 @@ class _LinearBase(nn.Linear):
                 if plan is not None and self._mx_w is not None and self._mx_takes(x):
                     return self._forward_mx(x)
                 if plan is not None and self._packed_is_current():
+                    if self._small_m_takes(x):
+                        return self._forward_small_m(x)
                     return self._forward_int8(x, plan)
                 if not differentiated and self._values_exact_in_bf16(x):
                     return self._forward_bf16_values(x)
@@ -527,6 +531,21 @@ class _LinearBase(nn.Linear):
             return _TileLinear.apply(x, w, bias)
         ops.count_vendor_gemm("linear.qat_fp32")
         return F.linear(x, w, bias)
+
+    def _small_m_takes(self, x) -> bool:
+        """config["mi355q_small_m"] = "packed" (default "off"): a forward() of at most ops.SMALL_M_MAX rows on a layer that holds its
+        weights at rest (`_w_packed`, either flavour: mi355q_weight_storage = "packed" / "hybrid") reads them straight from that form
+        (ops.bfp_linear_packed_small) instead of expanding them into the tile GEMM's operand first.  Not the mixed contraction; larger
+        batches, forward_after / forward_tiled / forward_residual and sharded inputs keep their routes."""
+        return (self.config.get("mi355q_small_m", "off") == "packed" and self._w_packed is not None and self._mixed is None
+                and x.numel() // self.in_features <= ops.SMALL_M_MAX and x.numel() > 0)
+
+    def _forward_small_m(self, x):
+        c = self.config
+        x2 = x.reshape(-1, self.in_features)
+        y = ops.bfp_linear_packed_small(x2, self._w_packed, c["data_in_width"], c["data_in_exponent_width"], c["data_in_exponent_bias"],
+                                        self.bias, out=self._take_out(x2.shape[0]))
+        return y.reshape(*x.shape[:-1], self.out_features)
 
     def _qat_on_tile_gemm(self, xq) -> bool:
         """QAT (is_ptq = False, linear.py:72-76: x, W and b re-quantised every call, straight-through gradients): the product
