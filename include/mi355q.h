@@ -33,16 +33,11 @@
  *     have to grow them under capture runs unsplit instead; buffers a capture has seen are never freed), and the
  *     zero-block map of the exact quantiser mode on tensors of 128 MiB and more (without it that mode reads x a second
  *     time instead).
- *   - Environment switches (diagnostics and A/B runs only; the default route never needs one): MI355Q_V9=0 keeps every
- *     launch on the round-2 tile kernel (mi355q_gemm_v8.hip) -- by default every launch of the 256 x 256 tile, grouped or
- *     not, with or without exception lists, the bf16 flavour too, with K % 128 == 0 and >= 4 K-steps per slice takes
- *     mi355q_gemm_v9.hip; MI355Q_V9_FIX=0 sends the launches with lists back to v8; MI355Q_V10=1|2|3|4 (+ MI355Q_V10_NS) pins a
- *     geometry of the small-tile kernel (mi355q_gemm_v10.hip), MI355Q_V10_AUTO=0 keeps launches off it; MI355Q_V8_TILE_ROWS,
- *     MI355Q_V8_SPLITS pin the tile GEMM's tile height / split-K (tests do); MI355Q_MATMUL_RW=1|2 the row groups
- *     per wave of the short-contraction tile product; MI355Q_MATMUL_TILE=0 sends the plain attention
- *     products back to kernel 2 of mi355q_matmul.hip; MI355Q_V8_STAMPS / MI355Q_V8_CLOCK / MI355Q_V9_STAMPS / MI355Q_V9_DBG /
- *     MI355Q_MATMUL_DBG are the phase-stamp diagnostics behind DESIGN.md section 5.  (Round 5 removed MI355Q_V8_SCHED,
- *     MI355Q_V8_SMALL_SCHED, MI355Q_V8_DBG, MI355Q_V9_GROUPS, MI355Q_QROWS_GRID, MI355Q_QV_PIECES, MI355Q_FIXUP_GRID, MI355Q_CORR.)
+ *   - Environment switches (diagnostics and A/B runs only; the default route never needs one): the tile GEMM's are listed,
+ *     with what each does, above read_tile_env() in llm-mixed-q_amd/csrc/mi355q_gemm_dispatch.hip (all read on every launch;
+ *     DESIGN.md 7a has the routing they act on).  Elsewhere: MI355Q_MATMUL_RW=1|2 the row groups per wave of the
+ *     short-contraction tile product; MI355Q_MATMUL_TILE=0 sends the plain attention products back to kernel 2 of
+ *     mi355q_matmul.hip; MI355Q_V9_STAMPS / MI355Q_MATMUL_DBG are phase-stamp diagnostics.
  */
 #ifndef MI355Q_H
 #define MI355Q_H

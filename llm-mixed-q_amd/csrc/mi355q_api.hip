@@ -444,7 +444,7 @@ int mi355q_bfp_gemm(const int8_t* xm, const uint8_t* xe, const int8_t* wm, const
     if (x_mbits < 1 || x_mbits > 7 || w_mbits < 1 || w_mbits > 7) return MI355Q_E_BADARG;
     if ((reinterpret_cast<uintptr_t>(xm) | reinterpret_cast<uintptr_t>(wm)) % 16) return MI355Q_E_ALIGN;
     GemmArgs a{xm, xe, wm, we, bias, y, M, N, K, ldy, x_exp_bias + x_mbits + w_exp_bias + w_mbits};
-    return launch_bfp_gemm(a, g_gemm_variant.load(), static_cast<hipStream_t>(stream));
+    return launch_bfp_gemm(a, static_cast<hipStream_t>(stream));
 }
 
 size_t mi355q_bfp_rowflag_bytes(int64_t rows, int64_t K) {
@@ -623,7 +623,7 @@ static int gemm_aligned_impl(const mi355q_bfp_operand* x, const mi355q_bfp_opera
         a.w_bcap = bucket_cap_of(w->list_cap);          // (before the early return: the kernel below indexes w's buckets)
         if (residual && x->row_aligned == 2) return MI355Q_E_UNSUPPORTED;      // (the residual add rides the one-launch route's stores only)
         if (x->row_aligned == 2)            // unaligned activations: the blockwise-exact kernel, w's exception blocks per tile
-            return launch_bfp_gemm_aligned(a, x->rowflag, w->rowflag, nullptr, w->list, 0, 0, st);
+            return launch_bfp_gemm_aligned(a, x->rowflag, w->rowflag, nullptr, w->list, st);
         if (x->list_cap < 0 || x->list_cap > ROW_BCAP_MAX) return MI355Q_E_BADARG;
         a.x_bcap = bucket_cap_of(x->list_cap);
         // x's exception blocks: in-LDS vectors of the GEMM (120-entry buckets) or the row post-pass (larger buckets)
@@ -633,15 +633,15 @@ static int gemm_aligned_impl(const mi355q_bfp_operand* x, const mi355q_bfp_opera
         a.resid = residual;
         a.ldr = ldr;
         if (variant == 2 || !fast_ok)
-            return launch_bfp_gemm_aligned(a, x->rowflag, w->rowflag, x->list, w->list, 0, 0, st);
-        if (variant == 8) return launch_bfp_gemm_v8(a, x->gscale, w->gscale, nullptr, nullptr, 0, st);
+            return launch_bfp_gemm_aligned(a, x->rowflag, w->rowflag, x->list, w->list, st);
+        if (variant == 8) return launch_bfp_gemm_v8(a, x->gscale, w->gscale, nullptr, nullptr, st);
         // ONE launch: the row-scale GEMM forms the correction vectors of its tile's exception blocks itself and adds them
         // in its epilogue; if an exception bucket overflowed anywhere its workgroups form the whole product
         // blockwise-exact between them instead (decided on the device)
         a.x_mbits = x->mbits;
         a.w_mbits = w->mbits;
         hipEvent_t te = g_timing.begin(st);
-        int rc = launch_bfp_gemm_v8(a, x->gscale, w->gscale, x->list, w->list, 0, st, x->rowflag, w->rowflag);
+        int rc = launch_bfp_gemm_v8(a, x->gscale, w->gscale, x->list, w->list, st, x->rowflag, w->rowflag);
         g_timing.end(te, st);
         if (rc == 0 && a.x_post) rc = launch_bfp_gemm_rowpost(a, x->list, w->list, x->gscale, w->gscale, st);
         return rc;
@@ -773,8 +773,7 @@ static int gemm_aligned_multi_impl(const mi355q_bfp_operand* x, const mi355q_bfp
     }
     a.x_mbits = x->mbits;
     a.w_mbits = w[0]->mbits;
-    return launch_bfp_gemm_v8(a, x->gscale, w[0]->gscale, x->list, w[0]->list, 0, static_cast<hipStream_t>(stream), x->rowflag,
-                              w[0]->rowflag);
+    return launch_bfp_gemm_v8(a, x->gscale, w[0]->gscale, x->list, w[0]->list, static_cast<hipStream_t>(stream), x->rowflag, w[0]->rowflag);
 }
 
 int mi355q_bfp_gemm_aligned_multi(const mi355q_bfp_operand* x, const mi355q_bfp_operand* const* w, const float* const* bias,

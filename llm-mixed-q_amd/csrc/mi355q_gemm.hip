@@ -202,34 +202,30 @@ int launch_bfp_align_rows(const int8_t* mi, const uint8_t* ei, int8_t* mt, uint8
     return (int)hipGetLastError();
 }
 
-// Blockwise-exact GEMM over aligned operands.  guard != 0: act only as the fallback of the int32-chain kernel
-// (when an exception list overflowed).  Exception blocks of either operand are added back per tile.
+// Blockwise-exact GEMM over ROW-aligned operands.  Exception blocks of either operand are added back per tile.
 __global__ __launch_bounds__(256, 2) void bfp_gemm_v2(const GemmArgs a, const uint8_t* __restrict__ xf,
                                                       const uint8_t* __restrict__ wf, const int* __restrict__ xlist,
-                                                      const int* __restrict__ wlist, int list_cap, int guard) {
+                                                      const int* __restrict__ wlist) {
     __shared__ V2Smem sm;
-    if (guard && xlist[0] <= list_cap && wlist[0] <= list_cap) return;
     bfp_gemm_v2_body(a, xf, wf, sm, blockIdx.x);
     if (xlist || wlist) {
         long long m0, n0;
         v2_tile_origin(a, blockIdx.x, m0, n0);
         __threadfence();
         __syncthreads();
-        if (a.row_mode) tile_fix_body(a, row_bucket(xlist, m0, a.x_bcap), row_bucket(wlist, n0, a.w_bcap), a.x_bcap, a.w_bcap, m0, n0);
-        else tile_fix_body(a, xlist, wlist, list_cap, list_cap, m0, n0);
+        tile_fix_body(a, row_bucket(xlist, m0, a.x_bcap), row_bucket(wlist, n0, a.w_bcap), a.x_bcap, a.w_bcap, m0, n0);
     }
 }
 
 
 int launch_bfp_gemm_aligned(const GemmArgs& a, const uint8_t* xf, const uint8_t* wf, const int* xlist,
-                            const int* wlist, int list_cap, int guard, hipStream_t st) {
+                            const int* wlist, hipStream_t st) {
     const unsigned tiles = (unsigned)(((a.M + V2_BM - 1) / V2_BM) * ((a.N + V2_BN - 1) / V2_BN));
-    hipLaunchKernelGGL(bfp_gemm_v2, tiles, 256, 0, st, a, xf, wf, xlist, wlist, list_cap, guard);
+    hipLaunchKernelGGL(bfp_gemm_v2, tiles, 256, 0, st, a, xf, wf, xlist, wlist);
     return (int)hipGetLastError();
 }
 
-int launch_bfp_gemm(const GemmArgs& a, int variant, hipStream_t st) {
-    (void)variant;
+int launch_bfp_gemm(const GemmArgs& a, hipStream_t st) {
     dim3 grid((unsigned)((a.N + V1_BN - 1) / V1_BN), (unsigned)((a.M + V1_BM - 1) / V1_BM));
     hipLaunchKernelGGL(bfp_gemm_v1, grid, 256, 0, st, a);
     return (int)hipGetLastError();

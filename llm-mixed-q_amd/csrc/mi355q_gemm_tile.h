@@ -1,7 +1,7 @@
 // mi355q_gemm_tile.h -- what the tile-GEMM translation units share (mi355q_gemm_v8.hip: 128-row tiles and the
 // staggered schedules; mi355q_gemm_v9.hip: the 256 x 256 tile of the benchmark path): the LDS constants of the v8
-// kernel, the exception-entry accessors, the atomics last resort, the in-launch blockwise fallback and the split-K
-// workspace.
+// kernel, the exception-entry accessors, the atomics last resort, the in-launch blockwise fallback and the plan-driven
+// launchers.
 #ifndef MI355Q_GEMM_TILE_H
 #define MI355Q_GEMM_TILE_H
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 #include "mi355q_internal.h"
 #include "mi355q_gemm_v2.h"
 #include "mi355q_fix.h"
+#include "mi355q_gemm_plan.h"
 
 namespace mi355q {
 
@@ -89,25 +90,17 @@ __device__ __forceinline__ void v8_fallback(const GemmArgs& a, const uint8_t* __
     }
 }
 
-// ---- split-K workspace: raw accumulator slabs + one ticket per tile, owned by the library, one per (device, stream),
-//      grow-only; tickets are zero whenever no launch is in flight (the reducer of a tile clears its ticket).
-struct SplitWorkspace {
-    void* slabs = nullptr;
-    int* tickets = nullptr;
-    size_t slab_bytes = 0;
-    int ntickets = 0;
-};
-SplitWorkspace* split_workspace(hipStream_t st, size_t slab_bytes, int ntickets);
-int choose_splits(long long tiles, int nsteps_all, bool need_even, int min_steps = 8);
-// the 256 x 256 tile (mi355q_gemm_v9.hip): K % 128 == 0, a.splits / a.slabs / a.tickets set by the caller
+// ---- the launchers of the three kernel families: each takes a finished plan (mi355q_gemm_plan.h, made and carried out in
+//      mi355q_gemm_dispatch.hip) and a.splits / a.slabs / a.tickets as the split-K workspace gave them, and decides nothing
+// mi355q_gemm_v8.hip: 128 x 256 tiles, K % 128 == 64, the MI355Q_V9=0 and diagnostic flavours of the 256 x 256 tile
+int launch_v8_kernel(const TilePlan& p, const GemmArgs& a, const float* sx, const float* sw, const int* xlist, const int* wlist, hipStream_t st,
+                     const uint8_t* xf, const uint8_t* wf, bool bf16);
+// mi355q_gemm_v9.hip: the 256 x 256 tile, K % 128 == 0, at least four K-steps a slice
 int launch_bfp_gemm_v9(const GemmArgs& a, const float* sx, const float* sw, const int* xlist, const int* wlist, hipStream_t st,
                        const uint8_t* xf, const uint8_t* wf, bool bf16);
-
-// the small tiles (mi355q_gemm_v10.hip; geometry 1: 128 x 256, 2: 256 x 128, 3: 128 x 128): K % 64 == 0, a.splits / a.slabs /
-// a.tickets set by the caller (slabs of one tile's fp32 / int32 accumulators)
-int launch_bfp_gemm_v10(const GemmArgs& a, const float* sx, const float* sw, const int* xlist, const int* wlist, hipStream_t st,
-                        const uint8_t* xf, const uint8_t* wf, bool bf16, int geom);
-void v10_tile_shape(int geom, int& bm, int& bn);
+// mi355q_gemm_v10.hip: the small tiles, K % 64 == 0 (slabs of one tile's fp32 / int32 accumulators)
+int launch_bfp_gemm_v10(const TilePlan& p, const GemmArgs& a, const float* sx, const float* sw, const int* xlist, const int* wlist,
+                        hipStream_t st, const uint8_t* xf, const uint8_t* wf, bool bf16);
 
 }  // namespace mi355q
 #endif

@@ -35,7 +35,6 @@
 // Roofline: int8 / bf16 MFMA, 2*M*N*K ops.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include <type_traits>
 #include <utility>
 
@@ -823,14 +822,9 @@ __global__ __launch_bounds__(64 * NWM * NWN * KG) __attribute__((amdgpu_waves_pe
     }
 }
 
-// geometry: 1 = 128 x 256 (1 x 4 waves of 128 x 64), 2 = 256 x 128 (2 x 2 of 128 x 64), 3 = 128 x 128 (2 x 2 of 64 x 64),
-// 4 = 128 x 64 (2 x 2 of 64 x 32: grids that 128 x 128 tiles leave on half the compute units or fewer)
-// 5 / 6 (round 6): 128 x 128 / 128 x 256 with TWO K-GROUPS in an 8-wave workgroup -- grids of at most one workgroup a compute unit
-void v10_tile_shape(int geom, int& bm, int& bn) {
-    bm = geom == 2 ? 256 : 128;
-    bn = (geom == 1 || geom == 6) ? 256 : (geom == 4 ? 64 : 128);
-}
-
+// geometry (v10_tile_shape, mi355q_gemm_plan.h): 1 = 128 x 256 (1 x 4 waves of 128 x 64), 2 = 256 x 128 (2 x 2 of 128 x 64),
+// 3 = 128 x 128 (2 x 2 of 64 x 64), 4 = 128 x 64 (2 x 2 of 64 x 32: grids that 128 x 128 tiles leave on half the compute units
+// or fewer), 5 / 6 = 128 x 128 / 128 x 256 with TWO K-GROUPS in an 8-wave workgroup -- grids of at most one workgroup a compute unit
 template <int NWM, int NWN, int TI, int NS, int OCC, int TJ = 4, int KG = 1>
 static int v10_launch(const GemmArgs& a, const float* sx, const float* sw, const int* xlist, const int* wlist, hipStream_t st,
                       const uint8_t* xf, const uint8_t* wf, bool bf16, unsigned grid) {
@@ -850,54 +844,34 @@ static int v10_launch(const GemmArgs& a, const float* sx, const float* sw, const
     return (int)hipGetLastError();
 }
 
-// a.splits / a.slabs / a.tickets set by the caller (slabs of BM x BN x 4 bytes); K % 64 == 0
 static unsigned long long* g_v10_stamps = nullptr;      // diagnostic (-DV10_STAMPS builds, tools/dbg/v10_stamps.py)
 
-int launch_bfp_gemm_v10(const GemmArgs& a_in, const float* sx, const float* sw, const int* xlist, const int* wlist, hipStream_t st,
-                        const uint8_t* xf, const uint8_t* wf, bool bf16, int geom) {
+// the v10 kernel a plan names (family 10: geometry, ring depth NS, workgroups a compute unit OCC); a.splits / a.slabs / a.tickets
+// set by the caller (slabs of BM x BN x 4 bytes); K % 64 == 0
+int launch_bfp_gemm_v10(const TilePlan& p, const GemmArgs& a_in, const float* sx, const float* sw, const int* xlist, const int* wlist,
+                        hipStream_t st, const uint8_t* xf, const uint8_t* wf, bool bf16) {
     GemmArgs a = a_in;
     a.stamps = g_v10_stamps;
-    const bool fix = xlist && wlist;
-    if (fix && (!xf || !wf)) return MI355Q_E_BADARG;
-    int bm, bn;
-    v10_tile_shape(geom, bm, bn);
-    const unsigned tiles = (unsigned)(((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn));
-    const unsigned grid = tiles * (a.ngroup > 1 ? a.ngroup : 1) * (a.splits > 1 ? a.splits : 1);
-    // ring depth: NS - 2 K-steps of LDS-DMA stay in flight across a barrier.  Two (three) workgroups a compute unit cover each
-    // other's waits with a shallow ring; a workgroup that has its compute unit to itself (grids of <= 256 tiles: the shard and
-    // projection shapes this kernel is for) needs the flight time of an L2 round trip under load in K-steps of 256-512 clocks:
-    // profiles/r05_small_tiles.txt.  MI355Q_V10_NS pins a depth for sweeps.
-    const int ns_env = getenv("MI355Q_V10_NS") ? atoi(getenv("MI355Q_V10_NS")) : 0;
-    const bool deep = ns_env ? ns_env > 4 : grid <= 256;       // (one workgroup a compute unit at most)
-    const int ns = ns_env ? ns_env : 0;
+#define V10_ARGS a, sx, sw, xlist, wlist, st, xf, wf, bf16, p.grid
 #ifndef V10_ONLY_G3N4
-    if (geom == 1) {
-        if (ns == 6) return v10_launch<1, 4, 8, 6, 1>(a, sx, sw, xlist, wlist, st, xf, wf, bf16, grid);
-        return deep ? v10_launch<1, 4, 8, 4, 1>(a, sx, sw, xlist, wlist, st, xf, wf, bf16, grid)
-                    : v10_launch<1, 4, 8, 3, 2>(a, sx, sw, xlist, wlist, st, xf, wf, bf16, grid);
-    }
-    if (geom == 2) {
-        return deep ? v10_launch<2, 2, 8, 4, 1>(a, sx, sw, xlist, wlist, st, xf, wf, bf16, grid)
-                    : v10_launch<2, 2, 8, 3, 2>(a, sx, sw, xlist, wlist, st, xf, wf, bf16, grid);
-    }
-    if (geom == 3) {
-        if (ns == 8) return v10_launch<2, 2, 4, 8, 1>(a, sx, sw, xlist, wlist, st, xf, wf, bf16, grid);
-        return deep ? v10_launch<2, 2, 4, 6, 1>(a, sx, sw, xlist, wlist, st, xf, wf, bf16, grid)
-                    : v10_launch<2, 2, 4, 4, 2>(a, sx, sw, xlist, wlist, st, xf, wf, bf16, grid);
-    }
-    if (geom == 4) {
-        return deep ? v10_launch<2, 2, 4, 6, 1, 2>(a, sx, sw, xlist, wlist, st, xf, wf, bf16, grid)
-                    : v10_launch<2, 2, 4, 4, 2, 2>(a, sx, sw, xlist, wlist, st, xf, wf, bf16, grid);
-    }
-    if (geom == 5 || geom == 6) {
-        if (a.splits > 1 || (a.K % 128) != 0) return MI355Q_E_UNSUPPORTED;
-        return geom == 5 ? v10_launch<2, 2, 4, 4, 1, 4, 2>(a, sx, sw, xlist, wlist, st, xf, wf, bf16, grid)
-                         : v10_launch<1, 4, 8, 3, 1, 4, 2>(a, sx, sw, xlist, wlist, st, xf, wf, bf16, grid);
+    switch (p.geom * 100 + p.ns * 10 + p.occ) {
+    case 161: return v10_launch<1, 4, 8, 6, 1>(V10_ARGS);
+    case 141: return v10_launch<1, 4, 8, 4, 1>(V10_ARGS);
+    case 132: return v10_launch<1, 4, 8, 3, 2>(V10_ARGS);
+    case 241: return v10_launch<2, 2, 8, 4, 1>(V10_ARGS);
+    case 232: return v10_launch<2, 2, 8, 3, 2>(V10_ARGS);
+    case 381: return v10_launch<2, 2, 4, 8, 1>(V10_ARGS);
+    case 361: return v10_launch<2, 2, 4, 6, 1>(V10_ARGS);
+    case 342: return v10_launch<2, 2, 4, 4, 2>(V10_ARGS);
+    case 461: return v10_launch<2, 2, 4, 6, 1, 2>(V10_ARGS);
+    case 442: return v10_launch<2, 2, 4, 4, 2, 2>(V10_ARGS);
+    case 541: return v10_launch<2, 2, 4, 4, 1, 4, 2>(V10_ARGS);
+    case 631: return v10_launch<1, 4, 8, 3, 1, 4, 2>(V10_ARGS);
     }
 #else
-    (void)deep; (void)ns;
-    if (geom == 3) return v10_launch<2, 2, 4, 4, 2>(a, sx, sw, xlist, wlist, st, xf, wf, bf16, grid);
+    if (p.geom == 3) return v10_launch<2, 2, 4, 4, 2>(V10_ARGS);
 #endif
+#undef V10_ARGS
     return MI355Q_E_BADARG;
 }
 

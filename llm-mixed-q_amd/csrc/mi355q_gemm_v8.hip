@@ -23,16 +23,12 @@
 // column.  Tiles with more entries than the spare area holds form the vectors in the stage area after the K loop; beyond
 // that the products are added with atomics after the stores.  If a bucket overflowed anywhere (uniform over the grid) the
 // launch's workgroups share the blockwise-exact product instead (v8_fallback).  Under-filled grids split K over several
-// workgroups per tile (slabs + tickets, choose_splits).
+// workgroups per tile (slabs + tickets).  Which launches come here, in which flavour, is decided in mi355q_gemm_plan.h.
 // Roofline: int8 MFMA, 2*M*N*K ops; y leaves as full fp32 (64 MiB at 4096^2: ~10 us of HBM write time).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
-#include <map>
-#include <mutex>
 #include <type_traits>
 #include <utility>
-#include <vector>
 
 #include "mi355q_gemm_tile.h"
 
@@ -674,287 +670,26 @@ __global__ __launch_bounds__(V8_NT, 1) void bfp_gemm_v8(const GemmArgs a_in, con
     }
 }
 
-
-// ---- split-K workspace: raw accumulator slabs + one ticket per tile, owned by the library, one per (device, stream),
-//      grow-only; tickets are zero whenever no launch is in flight (the reducer of a tile clears its ticket).
-//      Under stream capture (a HIP graph being recorded) nothing is allocated or freed: a shape that needs growth then
-//      gets no workspace (null: the caller launches unsplit), and a workspace that a capture has been handed is never
-//      freed afterwards -- an instantiated graph keeps its pointers -- growth retires the old buffers instead.
-SplitWorkspace* split_workspace(hipStream_t st, size_t slab_bytes, int ntickets) {
-    struct Owned { SplitWorkspace w; bool slabs_in_graph = false, tickets_in_graph = false; };      // (per buffer: ADVICE r3)
-    static std::mutex mu;
-    static std::map<std::pair<int, hipStream_t>, Owned> all;
-    static std::vector<void*> retired;                     // (buffers a recorded graph may still use: kept for good)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-    std::lock_guard<std::mutex> lock(mu);
-    Owned& o = all[{dev, st}];
-    SplitWorkspace& w = o.w;
-    const bool grow = w.slab_bytes < slab_bytes || w.ntickets < ntickets;
-    if (grow && capturing) return nullptr;
-    if (w.slab_bytes < slab_bytes) {
-        if (w.slabs) {
-            if (o.slabs_in_graph) retired.push_back(w.slabs);
-            else (void)hipFree(w.slabs);                  // (synchronises: nothing of this workspace is in flight after)
-        }
-        w.slabs = nullptr;
-        w.slab_bytes = 0;
-        o.slabs_in_graph = false;                         // (a fresh buffer: no graph knows it yet)
-        if (hipMalloc(&w.slabs, slab_bytes) != hipSuccess) return nullptr;
-        w.slab_bytes = slab_bytes;
-    }
-    if (w.ntickets < ntickets) {
-        if (w.tickets) {
-            if (o.tickets_in_graph) retired.push_back(w.tickets);
-            else (void)hipFree(w.tickets);
-        }
-        w.tickets = nullptr;
-        w.ntickets = 0;
-        o.tickets_in_graph = false;
-        const int n = (ntickets + 1023) / 1024 * 1024;
-        if (hipMalloc(reinterpret_cast<void**>(&w.tickets), (size_t)n * 4) != hipSuccess) return nullptr;
-        if (hipMemsetAsync(w.tickets, 0, (size_t)n * 4, st) != hipSuccess) return nullptr;
-        w.ntickets = n;
-    }
-    if (capturing) o.slabs_in_graph = o.tickets_in_graph = true;
-    return &w;
-}
-// slices per tile for an under-filled grid: the largest S with tiles * S <= 256 (one workgroup per compute unit), whole
-// and, where the schedule needs it, even numbers of K-steps per slice, at least 8 of them
-// `min_steps`: K-steps a slice must keep.  Splitting costs the slabs' round trip through memory (S x the output, written
-// and read), the agent-scope release / acquire and, in the flavour that carries exception lists, every slice's own
-// bookkeeping prologue: measured 16-22 us at 128 tiles x 2 slices, so a row-scale int8 product is split only while a
-// slice keeps 32 steps (2048^3: 27.7 us unsplit, 38.3 split in two; 4096 x 4096 x 512: 46.7 unsplit, 40.2 in two)
-int choose_splits(long long tiles, int nsteps_all, bool need_even, int min_steps) {
-    static const int forced = getenv("MI355Q_V8_SPLITS") ? atoi(getenv("MI355Q_V8_SPLITS")) : 0;
-    if (forced) min_steps = 8;
-    int best = 1;
-    for (int S = 2; S <= 16; ++S) {
-        if (nsteps_all % S) continue;
-        const int steps = nsteps_all / S;
-        if (steps < min_steps) break;
-        if (need_even && (steps & 1)) continue;
-        if (forced ? S > forced : tiles * S > 256) break;
-        best = S;
-    }
-    return best;
-}
-
-// the small tiles of mi355q_gemm_v10.hip under a forced geometry (MI355Q_V10 = 1 | 2 | 3 | 4; sweeps and tests) -- split-K as the
-// environment pins it (MI355Q_V8_SPLITS) or none
-static int v10_forced_launch(const GemmArgs& a_in, const float* sx, const float* sw, const int* xlist, const int* wlist, hipStream_t st,
-                             const uint8_t* xf, const uint8_t* wf, bool bf16, int geom) {
-    GemmArgs a = a_in;
-    int bm, bn;
-    v10_tile_shape(geom, bm, bn);
-    const long long tiles = ((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn) * (a.ngroup > 1 ? a.ngroup : 1);
-    const int forced = getenv("MI355Q_V8_SPLITS") ? atoi(getenv("MI355Q_V8_SPLITS")) : 0;
-    const int nsteps_all = (int)(a.K >> 6);
-    int S = forced > 1 ? forced : 1;
-    while (S > 1 && (nsteps_all % S || nsteps_all / S < 2)) --S;
-    a.splits = 1;
-    if (geom >= 5) {                                // (the K-group geometries: never split across workgroups; whole pairs of K-steps)
-        S = 1;
-        if (a.K % 128) geom = geom == 5 ? 3 : 1;
-    }
-    if (S > 1) {
-        SplitWorkspace* w = split_workspace(st, (size_t)tiles * S * bm * bn * 4, 2 * (int)tiles);      // (two ticket words a tile)
-        if (w) {
-            a.splits = S;
-            a.slabs = w->slabs;
-            a.tickets = w->tickets;
-        }
-    }
-    return launch_bfp_gemm_v10(a, sx, sw, xlist, wlist, st, xf, wf, bf16, geom);
-}
-static int v10_forced() {                       // (read per launch: the tests pin one geometry after the other in one process)
-    const char* e = getenv("MI355Q_V10");
-    const int g = e ? atoi(e) : 0;
-    return g >= 1 && g <= 6 ? g : 0;
-}
-
-int launch_bfp_gemm_v8(const GemmArgs& a_in, const float* sx, const float* sw, const int* xlist, const int* wlist,
-                       int list_cap, hipStream_t st, const uint8_t* xf, const uint8_t* wf) {
-    (void)list_cap;
-    if (v10_forced() && a_in.K % 64 == 0 && (!(xlist && wlist) || (xf && wf))) return v10_forced_launch(a_in, sx, sw, xlist, wlist, st, xf, wf, false, v10_forced());
-    // Round 5: grids of at most 128 tiles of 256 x 256 -- half the compute units or fewer -- take 128 x 128 tiles, two
-    // four-wave workgroups a compute unit, unsplit (mi355q_gemm_v10.hip; profiles/r05_small_tiles.txt: 4096 x 512 x 4096 36.7 ->
-    // 27.7 us, Llama-7B v_proj 47.1 -> 41.7, 2048^3 23.6 -> 19.0).  MI355Q_V10_AUTO=0 keeps the round-4 choice for A/B runs; a
-    // pinned tile height (MI355Q_V8_TILE_ROWS, tests of the other kernels) does too.
-    {
-        static const int v10_auto = getenv("MI355Q_V10_AUTO") ? atoi(getenv("MI355Q_V10_AUTO")) : 1;
-        const long long t256 = ((a_in.M + 255) / 256) * ((a_in.N + 255) / 256) * (a_in.ngroup > 1 ? a_in.ngroup : 1);
-        const char* pinned = getenv("MI355Q_V8_TILE_ROWS");
-        if (v10_auto && t256 <= 128 && a_in.K % 64 == 0 && !(pinned && atoi(pinned)) && !getenv("MI355Q_V8_SPLITS") && (!(xlist && wlist) || (xf && wf)) &&
-            !getenv("MI355Q_V8_CLOCK") && !getenv("MI355Q_V8_STAMPS")) {
-            GemmArgs a = a_in;
-            a.splits = 1;
-            // (128 x 64 tiles where 128 x 128 ones would fill half the compute units or fewer -- end of round 5:
-            //  4096 x 512 x 4096 26.4 -> 22.4 us at W6A6, 20.1 -> 16.7 at W4A4; level from ~176 tiles of 128 x 128 on)
-            const long long g3 = ((a.M + 127) / 128) * ((a.N + 127) / 128) * (a.ngroup > 1 ? a.ngroup : 1);
-            // (round 6: 129 .. 256 tiles of 128 x 128 -- one four-wave workgroup a compute unit, every wave alone on its SIMD -- as
-            //  8-wave workgroups of two K-groups: 4096 x 1024 x 4096 30.2 -> 27.4 us, Llama up / P = 8 27.5 -> 25.1, 2048^3 20.2 -> 19.5;
-            //  profiles/r06_shard_shapes.txt.  MI355Q_V10_KG=0: the round-5 choice, A/B runs)
-            static const int kg_auto = getenv("MI355Q_V10_KG") ? atoi(getenv("MI355Q_V10_KG")) : 1;
-            const int geom = g3 <= 128 ? 4 : (kg_auto && g3 <= 256 && a.K % 128 == 0 && a.ngroup <= 1 ? 5 : 3);
-            return launch_bfp_gemm_v10(a, sx, sw, xlist, wlist, st, xf, wf, false, geom);
-        }
-    }
-    GemmArgs a = a_in;
-    const int ngroup = a.ngroup > 1 ? a.ngroup : 1;            // grouped launch: that many weight operands' column tiles
-    // 256 x 256 tiles unless they would leave too many of the 256 compute units idle: a 128 x 256 tile does half the
-    // work in 0.8 of the time (measured: 48 vs 58 us at 2048 x 4096 x 4096; the fragment reads and LDS-DMA issue of a
-    // K-step are shared by half as many MFMAs)
-    const long long tn = (a.N + V8_BN - 1) / V8_BN * ngroup;
-    const long long t256 = ((a.M + 255) / 256) * tn, t128 = ((a.M + 127) / 128) * tn;
-    const double cost256 = (double)((t256 + 255) / 256) * 1.0, cost128 = (double)((t128 + 255) / 256) * 0.82;
-    const char* force = getenv("MI355Q_V8_TILE_ROWS");          // (tests pin either flavour)
-    const bool small = force && atoi(force) ? atoi(force) == 128 : cost128 < cost256;
-    // K-loop schedule of the 128 x 256 tile: 2 = the pipelined one of the 256 x 256 tile (round 4, default), 1 = one phase per step
-    constexpr int small_sched = 2;          // (the one-phase schedule only serves K % 128 == 64 now; its switch went in round 5)
-    unsigned tiles = (unsigned)(small ? t128 : t256);
-    {   // under-filled grid: split K (the 128-row tile's schedule takes any slice length, the 256-row one even ones)
-        constexpr int sched_ = 2;
-        const int S = choose_splits(tiles, (int)(a.K >> 6), sched_ == 2 && (!small || small_sched == 2), xlist && wlist ? 32 : 8);
-        a.splits = 1;
-        if (S > 1) {
-            SplitWorkspace* w = split_workspace(st, (size_t)tiles * S * (small ? 128 : 256) * 256 * 4, (int)tiles);
-            if (w) {                                       // (none -- growth under graph capture, or no memory: unsplit)
-                a.splits = S;
-                a.slabs = w->slabs;
-                a.tickets = w->tickets;
-                tiles *= S;
-            }
-        }
-    }
-    // diagnostic builds: MI355Q_V8_CLOCK prints the clock held over the K loop (no add-back),
-    // MI355Q_V8_STAMPS the duration of the kernel's phases
-    static const bool want_clock = getenv("MI355Q_V8_CLOCK") != nullptr, want_stamps = getenv("MI355Q_V8_STAMPS") != nullptr;
-    const bool fix = xlist && wlist;
-    if (fix && (!xf || !wf)) return MI355Q_E_BADARG;
-    a.dbg = 0;
-    // K-loop schedule of the 256 x 256 tile: 2 = pipelined (one barrier per K-step, default: 71.0 vs 72.8 us at 4096^3),
-    // 0 = two staggered wave groups, four barriers per K-step (kept for A/B runs: MI355Q_V8_SCHED=0)
-    constexpr int sched = 2;             // (the four-barrier schedule only serves K % 128 == 64 now; its switch went in round 5)
-    const unsigned grid = tiles;            // (on a bucket overflow the tile workgroups themselves form the product blockwise)
-    // the 256 x 256 tile has its own kernel since round 3 (mi355q_gemm_v9.hip); MI355Q_V9=0 keeps the round-2 one for A/B runs
-    static const int use_v9 = getenv("MI355Q_V9") ? atoi(getenv("MI355Q_V9")) : 1;
-    static const int v9_dbg = getenv("MI355Q_V9_DBG") ? atoi(getenv("MI355Q_V9_DBG")) : 0;
-    if (use_v9) a.dbg = v9_dbg;
-    // (grouped launches stay here: their outputs are promised bit-identical to the separate calls, which may take 128-row tiles)
-    // products WITH exception lists stay on the kernel below unless MI355Q_V9_FIX=1: on one box, bench.py, the two take 67.0
-    // (here) and 70.0 us (there; profiles/r03_v9_exception_designs.txt); without lists the new kernel takes 55-57 against 57.4
-    // launches WITH exception lists: the 256 x 256 kernel of mi355q_gemm_v9.hip (add-back behind its K loop, nothing in front
-    // of it) where the lists are all but empty -- operands of <= 5 bits, whose int8 container leaves a window of >= 4
-    // exponents: 54.0-55.0 us at 4096^3 W4A4 / W5A5 against 55.8-56.5 here -- and this kernel (add-back in the prologue,
-    // hidden behind the first stages) where every tile has its twenty entries: W6A6 62.3 against 65.0 (back-to-back
-    // launches, tools/dbg/v9_widths.py).  MI355Q_V9_FIX=0 / 1 pins either.
-    // Round 4: the 256 x 256 kernel takes EVERY launch with lists -- its add-back now rides the K loop's tail (the gathers of the
-    // tile's first 24 entries in the LDS-DMA slots of the three K-steps past the end, one vector per entry formed by all waves,
-    // a one-pass store epilogue): W6A6 62.1 against 63.1 us here on one box, 60.7 against 62.0 on another
-    // (profiles/r04_v9_tail_prefetch.txt).  MI355Q_V9_FIX=0 keeps the round-2 kernel for A/B runs.
-    static const int v9_fix_env = getenv("MI355Q_V9_FIX") ? atoi(getenv("MI355Q_V9_FIX")) : -1;
-    const bool v9_fix = v9_fix_env >= 0 ? v9_fix_env != 0 : true;
-    // (grouped launches stay on the kernel below: their outputs are promised bit-identical to the separate calls, which may take
-    //  128-row tiles there -- the two kernels add a row's corrections in different fp32 orders)
-    // (round 5: grouped launches too -- the small-tile kernel their separate launches may take adds a row's corrections in this
-    //  kernel's order, tests/test_gpu_gemm.py::test_small_tiles_equal_the_256_tile_bit_for_bit)
-        if (use_v9 && (v9_fix || !fix) && !small && sched == 2 && a.K % 128 == 0 && (a.K >> 6) / (a.splits > 1 ? a.splits : 1) >= 4 && !want_clock && !want_stamps)
-        return launch_bfp_gemm_v9(a, sx, sw, xlist, wlist, st, xf, wf, false);
-    if (small) {
-        const bool piped = small_sched == 2 && a.K % 128 == 0 && (((a.K >> 6) / (a.splits > 1 ? a.splits : 1)) & 1) == 0;
-        if (fix && piped) hipLaunchKernelGGL((bfp_gemm_v8<1, 4, 2>), grid, V8_NT, 0, st, a, sx, sw, xlist, wlist, xf, wf);
-        else if (piped) hipLaunchKernelGGL((bfp_gemm_v8<0, 4, 2>), grid, V8_NT, 0, st, a, sx, sw, xlist, wlist, xf, wf);
-        else if (fix) hipLaunchKernelGGL((bfp_gemm_v8<1, 4>), grid, V8_NT, 0, st, a, sx, sw, xlist, wlist, xf, wf);
-        else hipLaunchKernelGGL((bfp_gemm_v8<0, 4>), grid, V8_NT, 0, st, a, sx, sw, xlist, wlist, xf, wf);
-    } else if (fix && want_stamps && sched == 2) hipLaunchKernelGGL((bfp_gemm_v8<3, 8, 2>), grid, V8_NT, 0, st, a, sx, sw, xlist, wlist, xf, wf);
-    else if (fix && want_stamps) hipLaunchKernelGGL((bfp_gemm_v8<3, 8>), grid, V8_NT, 0, st, a, sx, sw, xlist, wlist, xf, wf);
-    else if (fix && sched == 2) hipLaunchKernelGGL((bfp_gemm_v8<1, 8, 2>), grid, V8_NT, 0, st, a, sx, sw, xlist, wlist, xf, wf);
-    else if (fix) hipLaunchKernelGGL((bfp_gemm_v8<1, 8>), grid, V8_NT, 0, st, a, sx, sw, xlist, wlist, xf, wf);
-    else if (want_clock && sched == 2) hipLaunchKernelGGL((bfp_gemm_v8<2, 8, 2>), grid, V8_NT, 0, st, a, sx, sw, xlist, wlist, xf, wf);
-    else if (want_clock) hipLaunchKernelGGL((bfp_gemm_v8<2, 8>), grid, V8_NT, 0, st, a, sx, sw, xlist, wlist, xf, wf);
-    else if (sched == 2 && a.K % 128 == 0) hipLaunchKernelGGL((bfp_gemm_v8<0, 8, 2>), grid, V8_NT, 0, st, a, sx, sw, xlist, wlist, xf, wf);
-    else hipLaunchKernelGGL((bfp_gemm_v8<0, 8>), grid, V8_NT, 0, st, a, sx, sw, xlist, wlist, xf, wf);
-    return (int)hipGetLastError();
-}
-
-// y = x . w^T (+ bias) on TILED bf16 operands (the same 1-KiB pieces: 16 rows x 32 values): a.xm / a.wm point at the
-// bf16 pieces and a.K is the contraction length IN BYTES (2 K).  K % 32 == 0.
-int launch_bf16_gemm_tiled(const GemmArgs& a_in, hipStream_t st) {
-    if (v10_forced() && a_in.K % 64 == 0) return v10_forced_launch(a_in, nullptr, nullptr, nullptr, nullptr, st, nullptr, nullptr, true, v10_forced());
-    GemmArgs a = a_in;
-    const long long tn = (a.N + V8_BN - 1) / V8_BN;
-    const long long t256 = ((a.M + 255) / 256) * tn, t128 = ((a.M + 127) / 128) * tn;
-    // Tile height and split together, by a small cost model fitted to tools/timing/sweep_bf16_tile_split.py (us): rounds x steps
-    // per slice x 0.70 (256 rows) or 0.56 (128 rows) per K-step, plus, when split, 12 + 0.7 per MiB of slab traffic (S x
-    // the fp32 output through memory twice).  It ranks the measured settings of the post-activation layer shapes
-    // correctly: 2048 x 11008 x 4096 -> 256 rows in two slices (177 vs 192 us), 2048 x 8192 x 2048 -> 256 rows in four.
-    const char* force = getenv("MI355Q_V8_TILE_ROWS");          // (sweeps pin either flavour)
-    const int nsteps_all = (int)(a.K >> 6);
-    const double out_mib = (double)a.M * (double)a.N * 4.0 / 1048576.0;
-    bool small = false;
-    int S = 1;
-    double best_t = 1e30;
-    for (int kind = 0; kind < 2; ++kind) {                      // 0: 256 rows, 1: 128 rows
-        if (force && atoi(force) && (atoi(force) == 128) != (kind == 1)) continue;
-        const long long t = kind ? t128 : t256;
-        const int smax = choose_splits(t, nsteps_all, kind == 0 && a.K % 128 == 0);
-        for (int sp = 1; sp <= smax; ++sp) {
-            if (getenv("MI355Q_V8_SPLITS") && sp != smax) continue;                      // (sweeps pin the split too)
-            if (nsteps_all % sp || (kind == 0 && a.K % 128 == 0 && ((nsteps_all / sp) & 1))) continue;
-            const double rounds = (double)((t * sp + 255) / 256);
-            const double est = rounds * (nsteps_all / sp) * (kind ? 0.56 : 0.70) + (sp > 1 ? 12.0 + 0.7 * out_mib * sp : 0.0);
-            if (est < best_t) { best_t = est; small = kind == 1; S = sp; }
-        }
-    }
-    // Round 5: the small tiles of mi355q_gemm_v10.hip, unsplit, where their estimate is lower -- per K-step and tile 0.19 us
-    // (128 x 128, up to two a compute unit side by side) / 0.39 us (128 x 256, one a compute unit), + 8 us per launch
-    // (profiles/r05_small_tiles.txt: 2048 x 2048 x 8192 81.3 -> 59.0 us, Llama-7B o_proj 74.8 -> 54.6, down_proj 156 -> 142)
-    {
-        static const int v10_auto = getenv("MI355Q_V10_AUTO") ? atoi(getenv("MI355Q_V10_AUTO")) : 1;
-        if (v10_auto && !force && !getenv("MI355Q_V8_SPLITS") && a.K % 64 == 0) {
-            const long long g3 = ((a.M + 127) / 128) * ((a.N + 127) / 128), g1 = ((a.M + 127) / 128) * ((a.N + 255) / 256);
-            // (128 x 128: 0.23 us a K-step alone on a compute unit, 0.43 for two side by side -- rounds of 512 tiles; beyond ~1000 tiles the
-            //  256 x 256 kernel is ahead again although the line says otherwise: 2048 x 11008 x 4096 took 200 us here against its 165-179,
-            //  hence the margin.  profiles/r05_shard_shapes.txt, r05_column_offsets.txt)
-            // (end of round 5: 128 x 64 tiles where 128 x 128 ones fill half the compute units or fewer -- 0.12 us a K-step:
-            //  4096 x 512 x 4096 30.1 -> 23.1 us, 2048 x 768 x 3072 22.7 -> 17.4, 2048 x 256 x 2048 16.0 -> 11.9)
-            const double est3 = (g3 <= 128 ? nsteps_all * 0.12 : g3 <= 256 ? nsteps_all * 0.23 : nsteps_all * 0.43 * (double)((g3 + 511) / 512)) + 8.0;
-            const double est1 = g1 <= 256 ? nsteps_all * 0.39 + 8.0 : 1e30;
-            // (round 6: two K-groups in an 8-wave workgroup for 129 .. 256 tiles of 128 x 128 -- 0.20 us a K-step: 2048 x 2048 x 8192
-            //  64.0 -> 58.4 us, profiles/r06_shard_shapes.txt)
-            static const int kg_auto = getenv("MI355Q_V10_KG") ? atoi(getenv("MI355Q_V10_KG")) : 1;
-            const double est5 = kg_auto && g3 > 128 && g3 <= 256 && a.K % 128 == 0 && a.x_segs <= 1 ? nsteps_all * 0.20 + 8.0 : 1e30;
-            if (est3 * 1.12 < best_t || est1 * 1.12 < best_t || est5 * 1.12 < best_t) {
-                a.splits = 1;
-                const int geom = est5 < est3 && est5 < est1 ? 5 : (est1 < est3 ? 1 : (g3 <= 128 ? 4 : 3));
-                return launch_bfp_gemm_v10(a, nullptr, nullptr, nullptr, nullptr, st, nullptr, nullptr, true, geom);
-            }
-        }
-    }
-    unsigned tiles = (unsigned)(small ? t128 : t256);
-    {
-        a.splits = 1;
-        if (S > 1) {
-            SplitWorkspace* w = split_workspace(st, (size_t)tiles * S * (small ? 128 : 256) * 256 * 4, (int)tiles);
-            if (w) {                                       // (none -- growth under graph capture, or no memory: unsplit)
-                a.splits = S;
-                a.slabs = w->slabs;
-                a.tickets = w->tickets;
-                tiles *= S;
-            }
-        }
-    }
-    constexpr int small_sched = 2;          // (the one-phase schedule only serves K % 128 == 64 now; its switch went in round 5)
-    static const bool use_v9_bf16 = !(getenv("MI355Q_V9") && atoi(getenv("MI355Q_V9")) == 0);        // (read once: ADVICE r4)
-    if (small && small_sched == 2 && a.K % 128 == 0 && (((a.K >> 6) / (a.splits > 1 ? a.splits : 1)) & 1) == 0)
-        hipLaunchKernelGGL((bfp_gemm_v8<0, 4, 2, true>), tiles, V8_NT, 0, st, a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    else if (small) hipLaunchKernelGGL((bfp_gemm_v8<0, 4, 1, true>), tiles, V8_NT, 0, st, a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    else if (a.x_segs <= 1 && a.K % 128 == 0 && (a.K >> 6) / (a.splits > 1 ? a.splits : 1) >= 4 && use_v9_bf16) return launch_bfp_gemm_v9(a, nullptr, nullptr, nullptr, nullptr, st, nullptr, nullptr, true);
-    else if (a.K % 128 == 0) hipLaunchKernelGGL((bfp_gemm_v8<0, 8, 2, true>), tiles, V8_NT, 0, st, a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    else hipLaunchKernelGGL((bfp_gemm_v8<0, 8, 0, true>), tiles, V8_NT, 0, st, a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+// the v8 kernel a plan names (family 8: mi355q_gemm_plan.h); a.splits / a.slabs / a.tickets set by the caller
+int launch_v8_kernel(const TilePlan& p, const GemmArgs& a, const float* sx, const float* sw, const int* xlist, const int* wlist, hipStream_t st,
+                     const uint8_t* xf, const uint8_t* wf, bool bf16) {
+#define V8_CASE(FIXMODE, TI, SCHED, BF16) \
+    if (p.fixmode == FIXMODE && p.ti == TI && p.sched == SCHED && bf16 == BF16) hipLaunchKernelGGL((bfp_gemm_v8<FIXMODE, TI, SCHED, BF16>), p.grid, V8_NT, 0, st, a, sx, sw, xlist, wlist, xf, wf); else
+    V8_CASE(1, 4, 2, false)
+    V8_CASE(0, 4, 2, false)
+    V8_CASE(1, 4, 1, false)
+    V8_CASE(0, 4, 1, false)
+    V8_CASE(3, 8, 2, false)
+    V8_CASE(1, 8, 2, false)
+    V8_CASE(2, 8, 2, false)
+    V8_CASE(0, 8, 2, false)
+    V8_CASE(0, 8, 0, false)
+    V8_CASE(0, 4, 2, true)
+    V8_CASE(0, 4, 1, true)
+    V8_CASE(0, 8, 2, true)
+    V8_CASE(0, 8, 0, true)
+    return MI355Q_E_BADARG;
+#undef V8_CASE
     return (int)hipGetLastError();
 }
 

@@ -125,15 +125,15 @@ struct GemmArgs {
     int q_mbits, q_emin, q_emax;
     int epi_op;       // 1: silu(gate) * up on interleaved gate / up columns (yb [M, N / 2]); 2: relu (yb [M, N])
 };
-int launch_bfp_gemm(const GemmArgs& a, int variant, hipStream_t st);
+int launch_bfp_gemm(const GemmArgs& a, hipStream_t st);
 int launch_bfp_gemm_aligned(const GemmArgs& a, const uint8_t* xf, const uint8_t* wf, const int* xlist,
-                            const int* wlist, int list_cap, int guard, hipStream_t st);
+                            const int* wlist, hipStream_t st);
 int launch_bfp_align_rows(const int8_t* mi, const uint8_t* ei, int8_t* mt, uint8_t* eo, uint8_t* flag, float* rscale,
                           int exp_offset, int* list, long long rows, long long K, hipStream_t st, int bcap);
 int launch_bfp_gemm_rowpost(const GemmArgs& a, const int* xlist, const int* wlist, const float* xscale, const float* wscale,
                             hipStream_t st);
 int launch_bfp_gemm_v8(const GemmArgs& a, const float* sx, const float* sw, const int* xlist, const int* wlist,
-                       int list_cap, hipStream_t st, const uint8_t* xf = nullptr, const uint8_t* wf = nullptr);
+                       hipStream_t st, const uint8_t* xf = nullptr, const uint8_t* wf = nullptr);
 // the mixed contraction of the 256 x 256 tile kernel (mi355q_gemm_v9m.hip): a.K1 / a.xm1 / a.wm1 set
 int launch_bfp_gemm_v9_mixed(const GemmArgs& a, const float* sx, const float* sw, const int* xlist, const int* wlist, hipStream_t st,
                              const uint8_t* xf, const uint8_t* wf);

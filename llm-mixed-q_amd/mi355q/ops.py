@@ -680,7 +680,7 @@ ROW_TILE_ENTRIES_SLOW = 96      # ... from the stage area behind the K loop (gat
 
 
 def gemm_tile_rows(M: int, N: int) -> int:
-    """rows of the tile the row-scale GEMM takes for an M x N output (the launch rule of mi355q_gemm_v8.hip: 256 x 256
+    """rows of the tile the row-scale GEMM takes for an M x N output (the launch rule of csrc/mi355q_gemm_plan.h: 256 x 256
     unless 128 x 256 fills the 256 compute units better).  A 128-row tile sees about half of a 256-row bucket's entries."""
     tn = -(-N // 256)
     t256, t128 = -(-M // 256) * tn, -(-M // 128) * tn
