@@ -23,6 +23,7 @@ import torch.nn.functional as F
 
 from ... import ops
 from ..quantizers import QUANTIZER_MAP
+from . import linear_policy as policy
 
 # config-key suffixes each quantiser takes, per operand prefix (linear.py:113-203)
 _PARAMS = {
@@ -133,7 +134,7 @@ class _LinearBase(nn.Linear):
         self._pending_flavour = None
         self._master = None
         self._fp32_released = False
-        self._x_cap = {"rows_post": ops.ROW_BUCKET_CAP_MAX, "blocks": ops.ROW_NO_ALIGN}.get(self.align, ops.ACTIVATION_BUCKET_CAP)
+        self._x_cap = policy.initial_x_cap(self.align)
         if not self.bypass:
             self._setup_quantizers(config)
         if self._packs_at_load():
@@ -184,29 +185,9 @@ class _LinearBase(nn.Linear):
         cached = self.__dict__.get("_plan_cache")
         if cached is not None and cached[0] == key:
             return cached[1]
-        plan = self._int8_plan_uncached(x)
+        plan = policy.int8_plan(self.config, self.arith, self.in_features, self.out_features, *key[:2])
         self.__dict__["_plan_cache"] = (key, plan)
         return plan
-
-    def _int8_plan_uncached(self, x: torch.Tensor):
-        c, K = self.config, self.in_features
-        if K % 64 or not (2 <= c["data_in_width"] <= 8 and 2 <= c["weight_width"] <= 8):
-            return None
-        if not (1 <= c["data_in_exponent_width"] <= 8 and 1 <= c["weight_exponent_width"] <= 8):
-            return None
-        xs = [1, K] if x.ndim == 2 else [1, x.shape[-2], K]
-        if x.ndim > 3:
-            return None
-        if ops.resolve_blocking(xs, c["data_in_block_size"], True)[3:] != (1, 16):
-            return None
-        if ops.resolve_blocking([self.out_features, K], c["weight_block_size"], False)[3:] != (1, 16):
-            return None
-        xb, wb = c["data_in_exponent_bias"], c["weight_exponent_bias"]
-        xb = 2 ** (c["data_in_exponent_width"] - 1) - 1 if xb in (None, "none", "None") else xb
-        wb = 2 ** (c["weight_exponent_width"] - 1) - 1 if wb in (None, "none", "None") else wb
-        if xb < 0 or wb < 0:
-            return None                  # packed operands store biased uint8 exponent codes: non-negative biases only
-        return c["data_in_width"] - 1, c["weight_width"] - 1, xb, wb
 
     @torch.no_grad()
     def _quantise_weights_once(self, pack: bool, x_sample=None):
@@ -241,8 +222,9 @@ class _LinearBase(nn.Linear):
 
     def _pack_operands(self, wm, we, x_sample):
         c = self.config
-        self._align_weights(wm, we, self._choose_align_mode(wm, we, x_sample))
-        versions = (self.weight._version, None if self.bias is None else self.bias._version)
+        self._choose_align_mode(wm, we, x_sample)
+        self._align_weights(wm, we)
+        versions = self._versions()
         if self._mixed is not None:
             self._mixed["version"] = versions
         # "packed": every layer at rest as width-bit mantissas + a byte per block, expanded per forward; "hybrid" (round 6): only the
@@ -258,8 +240,7 @@ class _LinearBase(nn.Linear):
                 self._w_packed = ops.pack_block_exponent_weights(wm, we, c["weight_width"], self._weight_bias_value())
                 self._packed = (None, self._w_packed.packed, *versions)
             else:
-                self._w_bf16 = (ops.bf16_tile(self.weight.data), self.weight._version)
-                self._packed = (None, self._w_bf16[0], *versions)
+                self._packed = (None, self._tiled_bf16_weights(None), *versions)
         elif packed_storage and self._x_cap != ops.ROW_NO_ALIGN:
             self._w_packed = ops.pack_row_aligned_weights(wm, we, self._packed[0], c["weight_width"], self._weight_bias_value())
             self._packed = (None, self._w_packed.packed, *versions)
@@ -271,58 +252,34 @@ class _LinearBase(nn.Linear):
         wm, we = self._pending_flavour
         self._pending_flavour = None
         if not self._fp32_released and self._packed is not None:
-            self._x_cap = {"rows_post": ops.ROW_BUCKET_CAP_MAX, "blocks": ops.ROW_NO_ALIGN}.get(self.align, ops.ACTIVATION_BUCKET_CAP)
+            self._x_cap = policy.initial_x_cap(self.align)
             self._pack_operands(wm, we, x)
 
     def _weight_bias_value(self):
-        c = self.config
-        wb = c["weight_exponent_bias"]
-        return 2 ** (c["weight_exponent_width"] - 1) - 1 if wb in (None, "none", "None") else wb
+        return policy.weight_bias(self.config)
+
+    def _versions(self):
+        return (self.weight._version, None if self.bias is None else self.bias._version)
 
     def _choose_align_mode(self, wm, we, x_sample):
-        if self.align == "groups":
-            raise ValueError('mi355q_align = "groups" was removed in round 5 (use "auto", "rows", "rows_post" or "blocks")')
-        if not ops.row_align_supported(self.in_features):
-            # contractions past the row format's 16384 (Llama-30B/65B down_proj): every block keeps its exponent
-            self._x_cap = ops.ROW_NO_ALIGN
-            return "rows"
-        if self.align in ("rows", "rows_post", "blocks"):
-            return "rows"
-        c = self.config
-        # one-off host reads at pack time: overflow words and the fullest exception bucket of either operand.  Rows pay
-        # off while a 256 x 256 tile's entries (x bucket + w bucket) fit the GEMM's in-LDS add-back.
-        wa = ops.bfp_align_rows(wm, we, c["weight_width"] - 1, self._weight_bias_value())
-        w_over, w_max = ops.row_list_fill(wa.sparse, self.out_features)
-        if w_over != 0 or w_max > ops.ROW_TILE_ENTRIES_FAST:
-            # weights whose exception blocks do not fit a tile's LDS add-back (outlier input channels put one in every
-            # row): the outlier block columns as class 1 of the mixed contraction if that leaves a class 0 that fits, else no
-            # alignment -- the blockwise / bf16 product does not care how exponents are distributed
-            if not self._try_mixed(wm, we, x_sample):
-                self._x_cap = ops.ROW_NO_ALIGN
-            return "rows"
-        if x_sample is not None:
-            # activations: the GEMM's in-LDS add-back while a tile's entries fit it; otherwise (post-activation inputs:
-            # hundreds of exception blocks per 256 rows after a ReLU, no usable row window at all after a SiLU gate) no
-            # alignment -- measured faster than the row post-pass wherever that one applies (tools/timing/time_linear_modes.py;
-            # "rows_post" remains available explicitly)
-            xa = ops.block_fp_quantize_aligned_rows(x_sample.reshape(-1, self.in_features), c["data_in_width"],
-                                                    c["data_in_exponent_width"], c["data_in_exponent_bias"],
-                                                    bucket_cap=ops.ROW_BUCKET_CAP_MAX)
-            x_over, x_max = ops.row_list_fill(xa.sparse, xa.rows, xa.list_cap)
-            # (a 128-row tile carries about half of its 256-row bucket's activation entries; 15 % margin for the busier
-            # half.  Measured at 2048 x 4096 -> 4096, tools/timing/time_exception_density.py: the row-scale route wins up to a
-            # fullest activation bucket of ~60 there, the per-block route beyond ~85)
-            # Between 48 and 96 entries a tile forms its vectors behind the K loop: still ahead of the per-block route where
-            # that one runs 256-row tiles (2048 x 4096 -> 11008: 163 vs 208 us at a fullest bucket of 87), behind it on
-            # 128-row tiles (2048 x 4096 -> 4096: 100 vs 91 us).
-            tile_rows = ops.gemm_tile_rows(xa.rows, self.out_features)
-            n_tile = w_max + int(x_max * (0.5 * 1.15 if tile_rows == 128 else 1.0) + 0.999)
-            fits = x_over == 0 and (n_tile <= ops.ROW_TILE_ENTRIES_FAST or
-                                    (tile_rows == 256 and n_tile <= ops.ROW_TILE_ENTRIES_SLOW - 8))
-            self._x_cap = ops.ROW_BUCKET_CAP if fits else ops.ROW_NO_ALIGN
-            if not fits and self._try_mixed(wm, we, x_sample):
-                self._x_cap = ops.ROW_BUCKET_CAP
-        return "rows"
+        """rows, per-block exponents or the mixed split (`policy.align_decision`), from one-off host reads at pack time: the overflow
+        word and the fullest exception bucket of the weights and -- where those fit -- of the sample activations"""
+        c, K, N = self.config, self.in_features, self.out_features
+        w_fill = x_fill = None
+        M = 0
+        if policy.align_is_measured(K, self.align):
+            wa = ops.bfp_align_rows(wm, we, c["weight_width"] - 1, self._weight_bias_value())
+            w_fill = ops.row_list_fill(wa.sparse, N)
+            if x_sample is not None and policy.rows_fit(w_fill):
+                xa = ops.block_fp_quantize_aligned_rows(x_sample.reshape(-1, K), *self.consumer_quantiser(), bucket_cap=ops.ROW_BUCKET_CAP_MAX)
+                x_fill, M = ops.row_list_fill(xa.sparse, xa.rows, xa.list_cap), xa.rows
+        d = policy.align_decision(K, N, M, self.align, w_fill, x_fill)
+        cap = d.x_cap
+        if d.try_mixed:
+            after = d.x_cap_if_mixed if self._try_mixed(wm, we, x_sample) else d.x_cap_if_not
+            cap = cap if after is None else after
+        if cap is not None:
+            self._x_cap = cap
 
     @staticmethod
     def _outlier_share(codes, spare: int):
@@ -342,34 +299,26 @@ class _LinearBase(nn.Linear):
         per packing from the first activations, like the row / block decision itself; results never depend on it."""
         c, K = self.config, self.in_features
         self._mixed = None
-        if (c.get("mi355q_mixed", "auto") in (False, "off", None) or self.align != "auto" or x_sample is None or K % 128 or K < 512
-                or not ops.row_align_supported(K) or c.get("mi355q_weight_storage", "int8") == "packed"
-                or c["data_in_width"] > 8 or c["weight_width"] > 8 or not x_sample.is_cuda or x_sample.dtype != torch.float32):
+        if (x_sample is None or not policy.mixed_config_ok(c, K, self.align) or not x_sample.is_cuda or x_sample.dtype != torch.float32):
             return False
         nb = K // 16
         x2 = x_sample.reshape(-1, K)
-        _, _, xe = ops.block_fp_quantize(x2, c["data_in_width"], c["data_in_exponent_width"], c["data_in_exponent_bias"], [1, 16], True,
-                                         want_fake=False, want_packed=True)
+        _, _, xe = ops.block_fp_quantize(x2, *self.consumer_quantiser(), [1, 16], True, want_fake=False, want_packed=True)
         share = torch.maximum(self._outlier_share(xe.view(-1, nb), 8 - c["data_in_width"]),
                               self._outlier_share(we.view(-1, nb), 8 - c["weight_width"]))
-        n1 = int((share > 0.25).sum())
+        n1 = policy.mixed_class1_blocks(int((share > policy.MIXED_OUTLIER_SHARE).sum()), nb)
         if n1 == 0:
-            return False
-        n1 = -(-n1 // 8) * 8                                  # whole pairs of 64-byte K-steps in both classes
-        if n1 > nb // 2 or nb - n1 < 16:
             return False
         blocks1 = torch.topk(share, n1).indices.cpu().tolist()
         classes = ops.ColumnClasses(K, blocks1, x2.device)
         N = self.out_features
         wa0 = ops.bfp_align_rows(wm.view(N, K)[:, classes.cols0].contiguous(), we.view(N, nb)[:, classes.blocks0].contiguous(),
                                  c["weight_width"] - 1, self._weight_bias_value())
-        w_over, w_max = ops.row_list_fill(wa0.sparse, N)
-        if w_over != 0 or w_max > ops.ROW_TILE_ENTRIES_FAST:
+        w_fill = ops.row_list_fill(wa0.sparse, N)
+        if not policy.rows_fit(w_fill):
             return False
-        x0, _ = ops.block_fp_quantize_classes(x2, classes, c["data_in_width"], c["data_in_exponent_width"], c["data_in_exponent_bias"],
-                                              bucket_cap=ops.ROW_BUCKET_CAP_MAX)
-        x_over, x_max = ops.row_list_fill(x0.sparse, x0.rows, x0.list_cap)
-        if x_over != 0 or w_max + x_max > ops.ROW_TILE_ENTRIES_FAST:
+        x0, _ = ops.block_fp_quantize_classes(x2, classes, *self.consumer_quantiser(), bucket_cap=ops.ROW_BUCKET_CAP_MAX)
+        if not policy.mixed_fits(w_fill, ops.row_list_fill(x0.sparse, x0.rows, x0.list_cap)):
             return False
         # (the weights' class-1 operand: the fake-quantised values already in .weight, as tiled bf16)
         w1 = ops.bf16_tile(self.weight.data[:, classes.cols1].contiguous())
@@ -377,24 +326,53 @@ class _LinearBase(nn.Linear):
         return True
 
     def _uses_bf16_route(self) -> bool:
-        c = self.config
-        return (self._align_mode == "rows" and self._x_cap == ops.ROW_NO_ALIGN and self.in_features % 32 == 0
-                and (c.get("mi355q_blocks_gemm", "bf16") == "bf16" or not ops.row_align_supported(self.in_features))
-                and c["data_in_width"] <= 9 and c["weight_width"] <= 9)
+        return self._align_mode == "rows" and policy.uses_bf16_route(self.config, self.in_features, self._x_cap)
 
-    def _align_weights(self, wm, we, mode):
-        c = self.config
-        self._align_mode = mode
+    def _hold_packed(self, wa, tiled):
+        """the layer's packed weights: the aligned operand (None where the route needs none) and the tiled buffer.  The one place
+        `_align_mode` leaves None: "rows" says that the layer holds packed operands (`_x_cap` and `_mixed` say which route)"""
+        self._align_mode, self._packed = "rows", (wa, tiled, *self._versions())
+
+    def _align_weights(self, wm, we):
         if not ops.row_align_supported(self.in_features):     # (bf16 route only: `_pack_operands` sets the operand)
-            self._packed = (None, None, self.weight._version, None if self.bias is None else self.bias._version)
-            return
-        wa = ops.bfp_align_rows(wm, we, c["weight_width"] - 1, self._weight_bias_value())
-        self._packed = (wa, wa.tiled, self.weight._version, None if self.bias is None else self.bias._version)
+            return self._hold_packed(None, None)
+        wa = ops.bfp_align_rows(wm, we, self.config["weight_width"] - 1, self._weight_bias_value())
+        self._hold_packed(wa, wa.tiled)
 
     def _packed_is_current(self) -> bool:
         p = self._packed
         return (p is not None and p[2] == self.weight._version and p[1].device == self.weight.device
                 and (self.bias is None or p[3] == self.bias._version))
+
+    def _settled(self, pending_ok: bool = False) -> bool:
+        """a block_fp PTQ layer in its steady state: weights quantised in place, the packed operand current, and the flavour a
+        layer packed on arrival still owes its first forward decided (`pending_ok`: or not)"""
+        return (self.arith == "block_fp" and self.is_ptq and not self.bypass and not self.weight_requires_quantisation
+                and (pending_ok or self._pending_flavour is None) and self._packed_is_current())
+
+    def _on_row_route(self) -> bool:
+        return self._align_mode == "rows" and not self._uses_bf16_route()
+
+    def _on_plain_row_route(self, packed_ok: bool = False) -> bool:
+        """the row-scale int8 route with 120-entry activation buckets, no mixed split and the int8 operand resident (`packed_ok`: or
+        at rest in its row-scale flavour, once the first forward has settled that)"""
+        return (self._on_row_route() and self._mixed is None and self._x_cap == ops.ROW_BUCKET_CAP
+                and (self._w_packed is None or (packed_ok and self._w_packed.row_scale_flavour and self._pending_flavour is None)))
+
+    def _same_x_quantiser(self, other) -> bool:
+        return self.consumer_quantiser() == other.consumer_quantiser()
+
+    def _tiled_bf16_weights(self, device, contiguous: bool = False, released: str = None):
+        """the quantised weights (.weight) as the tiled bf16 operand, tiled again when they were written or moved (`device` None:
+        now).  `contiguous`: the caller accepts strided weights; `released`: what the caller can no longer do once the fp32 weights
+        are gone (None: it never asked)"""
+        w = self._w_bf16
+        if w is None or w[1] != self.weight._version or w[0].device != device:
+            if released is not None and self._fp32_released:
+                raise RuntimeError(f"mi355q: the fp32 weights were released; this layer cannot {released} any more")
+            data = self.weight.data.contiguous() if contiguous else self.weight.data
+            self._w_bf16 = (ops.bf16_tile(data), self.weight._version)
+        return self._w_bf16[0]
 
     @torch.no_grad()
     def _repack_quantised_weights(self, x_sample):
@@ -403,11 +381,10 @@ class _LinearBase(nn.Linear):
         SURVEY 8a quirk 7), so the route from here on is the per-block-exponent one (tiled bf16).  Weights edited in
         place after the first forward are NOT repacked: like the reference they are used as they are (fp32 GEMM) until
         requantize()."""
-        if self.in_features % 32 or self.config["weight_width"] > 9 or self.config["data_in_width"] > 9:
+        if not policy.bf16_operands_ok(self.config, self.in_features):
             return False
-        self._align_mode, self._x_cap, self._mixed = "rows", ops.ROW_NO_ALIGN, None
-        self._w_bf16 = (ops.bf16_tile(self.weight.data.contiguous()), self.weight._version)
-        self._packed = (None, self._w_bf16[0], self.weight._version, None if self.bias is None else self.bias._version)
+        self._x_cap, self._mixed = ops.ROW_NO_ALIGN, None
+        self._hold_packed(None, self._tiled_bf16_weights(None, contiguous=True))
         return True
 
     def requantize(self, config: dict = None):
@@ -438,7 +415,7 @@ class _LinearBase(nn.Linear):
         self.weight_requires_quantisation = True if self.is_ptq else False
         self._packed, self._align_mode, self._calls, self._row_overflows = None, None, 0, 0
         self._w_bf16, self._w_packed, self._pending_flavour, self._mixed = None, None, None, None
-        self._x_cap = {"rows_post": ops.ROW_BUCKET_CAP_MAX, "blocks": ops.ROW_NO_ALIGN}.get(self.align, ops.ACTIVATION_BUCKET_CAP)
+        self._x_cap = policy.initial_x_cap(self.align)
 
     @torch.no_grad()
     def pack_now(self, x_sample=None):
@@ -483,9 +460,7 @@ class _LinearBase(nn.Linear):
         if isinstance(x, ShardedRows):
             # the gathered output of a row-sharded layer, still in the collective's rank-major layout: the row-aligned int8
             # route reads it in place; every other route takes the re-assembled tensor
-            if (not self.bypass and self.is_ptq and not self.weight_requires_quantisation and self._packed_is_current()
-                    and self._pending_flavour is None
-                    and self._align_mode == "rows" and not self._uses_bf16_route()):
+            if self._settled() and self._on_row_route():
                 plan = self._int8_plan(x.buf[0])
                 if plan is not None:
                     with torch.no_grad():
@@ -537,14 +512,11 @@ class _LinearBase(nn.Linear):
         weights at rest (`_w_packed`, either flavour: mi355q_weight_storage = "packed" / "hybrid") reads them straight from that form
         (ops.bfp_linear_packed_small) instead of expanding them into the tile GEMM's operand first.  Not the mixed contraction; larger
         batches, forward_after / forward_tiled / forward_residual and sharded inputs keep their routes."""
-        return (self.config.get("mi355q_small_m", "off") == "packed" and self._w_packed is not None and self._mixed is None
-                and x.numel() // self.in_features <= ops.SMALL_M_MAX and x.numel() > 0)
+        return self._w_packed is not None and self._mixed is None and policy.small_m_takes(self.config, self.in_features, x.numel())
 
     def _forward_small_m(self, x):
-        c = self.config
         x2 = x.reshape(-1, self.in_features)
-        y = ops.bfp_linear_packed_small(x2, self._w_packed, c["data_in_width"], c["data_in_exponent_width"], c["data_in_exponent_bias"],
-                                        self.bias, out=self._take_out(x2.shape[0]))
+        y = ops.bfp_linear_packed_small(x2, self._w_packed, *self.consumer_quantiser(), self.bias, out=self._take_out(x2.shape[0]))
         return y.reshape(*x.shape[:-1], self.out_features)
 
     def _qat_on_tile_gemm(self, xq) -> bool:
@@ -553,21 +525,10 @@ class _LinearBase(nn.Linear):
         GEMM at a sixteenth of its rate -- when the quantised values are exact in bf16 (block_fp of <= 9 bits, minifloats of
         <= 7 mantissa bits, powers of two) and every contraction length is a whole number of 64-byte K-steps.
         config["mi355q_qat_gemm"] = "fp32" keeps F.linear."""
-        c = self.config
-        if c.get("mi355q_qat_gemm", "bf16") not in ("bf16", "bf16_always") or not (xq.is_cuda and xq.dtype == torch.float32 and self.weight.dtype == torch.float32):
+        if not (xq.is_cuda and xq.dtype == torch.float32 and self.weight.dtype == torch.float32):
             return False
-        if self.arith == "block_fp":
-            if not (2 <= c["data_in_width"] <= 9 and 2 <= c["weight_width"] <= 9):
-                return False
-        elif not self._values_exact_in_bf16(xq):
-            return False
-        M = xq.numel() // self.in_features
-        if not (self.in_features % 32 == 0 and self.out_features % 32 == 0 and M % 32 == 0 and M > 0):
-            return False
-        # three products + the tiling / plane-split launches around them: ahead of the fp32 library GEMM from ~2^34 multiply-adds a
-        # product (profiles/r05_qat_gemm.jsonl: 2048 x 1024 x 4096 0.97-1.09x, 2048 x 4096 x 4096 2.0x, 512 x 1024 x 4096 0.4-0.6x);
-        # mi355q_qat_gemm = "bf16_always" takes it regardless (tests)
-        return c.get("mi355q_qat_gemm", "bf16") == "bf16_always" or M * self.in_features * self.out_features >= (1 << 34)
+        return policy.qat_on_tile_gemm(self.config, self.arith, self.in_features, self.out_features, xq.numel() // self.in_features,
+                                       self.arith != "block_fp" and self._values_exact_in_bf16(xq))
 
     # -- W4A4 on the MX scaled matrix instruction ------------------------------------------------------------------------
     def _mx_config_ok(self) -> bool:
@@ -575,29 +536,19 @@ class _LinearBase(nn.Linear):
         three exponents of reach inside a 32-group; at 5 bits the reach is two and Gaussian data already trips it), [1,16] blocks
         along in_features, in_features % 128 == 0, launches of >= 192 tiles of 256 x 256 (below that the small-tile int8 kernel
         wins: profiles/r05_mx_w4a4.txt); True -- every launch that fits the format (<= 5 bits); False -- never"""
-        c = self.config
-        knob = c.get("mi355q_mx", "auto")
-        if knob in (False, "off", None) or self.arith != "block_fp" or not self.is_ptq or self.bypass:
-            return False
-        wmax = 5 if knob is True else 4
-        return (ops.mx_supported(self.in_features, c["data_in_width"], c["weight_width"]) and c["data_in_width"] <= wmax
-                and c["weight_width"] <= wmax and self.weight.is_cuda and self.weight.dtype == torch.float32
-                and c.get("mi355q_weight_storage", "int8") != "packed" and not getattr(self, "_fp32_released", False))
+        return (policy.mx_config_ok(self.config, self.arith, self.is_ptq, self.bypass, self.in_features)
+                and self.weight.is_cuda and self.weight.dtype == torch.float32 and not self._fp32_released)
 
     def _mx_takes(self, x) -> bool:
         if not (x.is_cuda and x.dtype == torch.float32 and 2 <= x.ndim <= 3) or self._mx_w is None or self._fp32_released:
             return False
         if self._mx_w.c16.device != x.device or self._mx_version != self.weight._version:
             return False
-        if self.config.get("mi355q_mx", "auto") is True:
-            return True
-        M = x.numel() // self.in_features
-        return -(-M // 256) * -(-self.out_features // 256) >= 192
+        return policy.mx_takes(self.config, x.numel() // self.in_features, self.out_features)
 
     def _forward_mx(self, x):
-        c = self.config
         x2 = x.reshape(-1, self.in_features).contiguous()
-        xop = ops.block_fp_quantize_mx(x2, c["data_in_width"], c["data_in_exponent_width"], c["data_in_exponent_bias"])
+        xop = ops.block_fp_quantize_mx(x2, *self.consumer_quantiser())
         y = ops.mx_gemm(xop, self._mx_w, self.weight.data, self.bias)
         # a 32-group of the activations that does not fit the format sends the launch to its exact (slow) route: look at the
         # flag on a doubling schedule of calls and leave this route if it is ever up (never while a graph is being recorded)
@@ -613,19 +564,8 @@ class _LinearBase(nn.Linear):
         powers of two, fixed point of at most 9 bits -- are exact in bf16 and a product of two of them exact in fp32, so
         `F.linear(x_q, W_q, b_q)` is the bf16 flavour of the tile GEMM (fp32 accumulation, fp32 output) instead of a
         library fp32 GEMM at a seventh of its rate.  config["mi355q_values_gemm"] = "fp32" keeps F.linear."""
-        c = self.config
-        if c.get("mi355q_values_gemm", "bf16") != "bf16":
-            return False
-        if self.arith in ("block_minifloat", "minifloat_ieee", "minifloat_denorm"):     # <= 7 mantissa bits
-            if not all(0 <= c[f"{p}_width"] - c[f"{p}_exponent_width"] - 1 <= 7 for p in ("data_in", "weight")):
-                return False
-        elif self.arith == "integer":                          # fixed point of <= 9 bits: <= 8 significant bits
-            if not all(2 <= c[f"{p}_width"] <= 9 for p in ("data_in", "weight")):
-                return False
-        elif self.arith != "block_log":                        # (signed powers of two)
-            return False
-        return (xq.is_cuda and xq.dtype == torch.float32 and self.weight.dtype == torch.float32 and xq.ndim >= 2
-                and self.in_features % 32 == 0 and not self.weight_requires_quantisation)
+        return (policy.values_exact_in_bf16(self.config, self.arith, self.in_features) and xq.is_cuda and xq.dtype == torch.float32
+                and self.weight.dtype == torch.float32 and xq.ndim >= 2 and not self.weight_requires_quantisation)
 
     @torch.no_grad()
     def _forward_quantised_gather(self, x):
@@ -633,22 +573,19 @@ class _LinearBase(nn.Linear):
         per rank): the bf16 flavour of the tile GEMM with x in column segments against the tiled quantised weights"""
         c = self.config
         if (self.arith != "block_fp" or self.bypass or not self.is_ptq
-                or x.quantiser != (c["data_in_width"], c["data_in_exponent_width"], c["data_in_exponent_bias"]) or x.features != self.in_features):
+                or x.quantiser != self.consumer_quantiser() or x.features != self.in_features):
             raise RuntimeError("mi355q: this quantised gather was prepared for another layer / quantiser")
         if not 2 <= c["weight_width"] <= 9:
             raise RuntimeError(f"mi355q: a quantised gather feeds the bf16 tile GEMM, whose operands hold block_fp values of at most 9 "
                                f"bits exactly; this layer's weight_width is {c['weight_width']} (shard it with gather='dense')")
         if self.weight_requires_quantisation:
             self._quantise_weights_once(pack=False)          # (linear.py:66-70: weights and bias quantised in place; no int8 operand needed)
-        if self._w_bf16 is None or self._w_bf16[1] != self.weight._version or self._w_bf16[0].device != x.device:
-            if getattr(self, "_fp32_released", False):
-                raise RuntimeError("mi355q: the fp32 weights were released; this layer cannot take the bf16 route any more")
-            self._w_bf16 = (ops.bf16_tile(self.weight.data), self.weight._version)
+        wt = self._tiled_bf16_weights(x.device, released="take the bf16 route")
         M = 1
         for d in x.lead:
             M *= int(d)
         P = x.buf.shape[0]
-        y = ops.bf16_gemm_tiled(x.buf if P > 1 else x.buf[0], self._w_bf16[0], M, self.out_features, self.in_features, self.bias,
+        y = ops.bf16_gemm_tiled(x.buf if P > 1 else x.buf[0], wt, M, self.out_features, self.in_features, self.bias,
                                 segments=P)
         return y.reshape(*x.lead, self.out_features)
 
@@ -657,25 +594,18 @@ class _LinearBase(nn.Linear):
         contraction is padded with all-zero blocks -- they quantise to zeros and add nothing -- and runs on the bf16 flavour of
         the tile GEMM (a block_fp value of width <= 9 is exact in bf16, products exact in fp32) instead of dropping to the
         library fp32 GEMM.  config["mi355q_pad_k"] = False keeps F.linear."""
-        c, K = self.config, self.in_features
-        if self.arith != "block_fp" or not c.get("mi355q_pad_k", True) or K % 16 or K % 64 == 0:
-            return False
-        if not (x.is_cuda and x.dtype == torch.float32 and self.weight.dtype == torch.float32 and 2 <= x.ndim <= 3):
-            return False
-        if not (2 <= c["data_in_width"] <= 9 and 2 <= c["weight_width"] <= 9) or self.weight_requires_quantisation:
-            return False
-        xs = [1, K] if x.ndim == 2 else [1, x.shape[-2], K]
-        return (ops.resolve_blocking(xs, c["data_in_block_size"], True)[3:] == (1, 16)
-                and ops.resolve_blocking([self.out_features, K], c["weight_block_size"], False)[3:] == (1, 16))
+        return (x.is_cuda and x.dtype == torch.float32 and self.weight.dtype == torch.float32 and not self.weight_requires_quantisation
+                and policy.padded_block_fp_ok(self.config, self.arith, self.in_features, self.out_features, x.ndim,
+                                              x.shape[-2] if x.ndim == 3 else 0))
 
     def _forward_block_fp_padded(self, x):
-        c, K = self.config, self.in_features
+        K = self.in_features
         Kp = (K + 63) // 64 * 64
         x2 = F.pad(x.reshape(-1, K), (0, Kp - K))
         w = self.__dict__.get("_w_bf16_padded")
         if w is None or w[1] != self.weight._version or w[0].device != x.device:
             w = self.__dict__["_w_bf16_padded"] = (ops.bf16_tile(F.pad(self.weight.data, (0, Kp - K))), self.weight._version)
-        xt = ops.block_fp_quantize_bf16_tiled(x2, c["data_in_width"], c["data_in_exponent_width"], c["data_in_exponent_bias"])
+        xt = ops.block_fp_quantize_bf16_tiled(x2, *self.consumer_quantiser())
         y = ops.bf16_gemm_tiled(xt, w[0], x2.shape[0], self.out_features, Kp, self.bias)
         return y.reshape(*x.shape[:-1], self.out_features)
 
@@ -683,8 +613,7 @@ class _LinearBase(nn.Linear):
         """x (NOT yet quantised) -> x quantiser -> tiled bf16 -> tile GEMM against the tiled quantised weights"""
         c = self.config
         x2 = x.reshape(-1, self.in_features).contiguous()
-        if self._w_bf16 is None or self._w_bf16[1] != self.weight._version or self._w_bf16[0].device != x.device:
-            self._w_bf16 = (ops.bf16_tile(self.weight.data.contiguous()), self.weight._version)
+        wt = self._tiled_bf16_weights(x.device, contiguous=True)
         xs = [1, self.in_features] if x.ndim == 2 else [1, x.shape[-2], self.in_features]
         if (self.arith == "block_minifloat" and x.ndim <= 3
                 and ops.resolve_blocking(xs, c["data_in_block_size"], True)[3:] == (1, 16)):
@@ -694,7 +623,7 @@ class _LinearBase(nn.Linear):
         else:
             # (block_log's all-zero blocks take their value from a reduction over the whole tensor: its own two launches)
             xt = ops.bf16_tile(self.x_quantizer(x).reshape(-1, self.in_features).contiguous())
-        y = ops.bf16_gemm_tiled(xt, self._w_bf16[0], x2.shape[0], self.out_features, self.in_features, self.bias)
+        y = ops.bf16_gemm_tiled(xt, wt, x2.shape[0], self.out_features, self.in_features, self.bias)
         return y.reshape(*x.shape[:-1], self.out_features)
 
     def forward_after(self, x, op, other=None, residual=None):
@@ -723,9 +652,7 @@ class _LinearBase(nn.Linear):
         if isinstance(x, ShardedRows):
             # fc1's gathered output in the collective's rank-major layout (sharded.shard_model(gather="segments")): the
             # row-aligned route reads the P segments in place with the relu in front; anything else re-assembles it
-            if (op == "relu" and not self.bypass and self.is_ptq and not self.weight_requires_quantisation
-                    and self._packed_is_current() and self._pending_flavour is None
-                    and self._align_mode == "rows" and not self._uses_bf16_route()):
+            if op == "relu" and self._settled() and self._on_row_route():
                 plan = self._int8_plan(x.buf[0])
                 if plan is not None:
                     with torch.no_grad():
@@ -733,15 +660,12 @@ class _LinearBase(nn.Linear):
             x = x.dense()
         # (a layer packed when its weights arrived still carries both flavours: its first forward must see the POST-op
         #  activations to settle the route and drop the other one -- ADVICE r3 -- so it goes through forward() once)
-        fused = (self.arith == "block_fp" and self.is_ptq and not self.bypass and not self.weight_requires_quantisation
-                 and getattr(self, "_pending_flavour", None) is None
-                 and x.is_cuda and x.dtype == torch.float32 and not (torch.is_grad_enabled() and (x.requires_grad or (
+        fused = (self._settled() and x.is_cuda and x.dtype == torch.float32 and not (torch.is_grad_enabled() and (x.requires_grad or (
                      other is not None and other.requires_grad)))
                  and (other is None or (other.shape == x.shape and other.dtype == x.dtype and other.device == x.device)))
         if fused:
             plan = self._int8_plan(x)
-            fused = (plan is not None and self._packed_is_current()
-                     and (self._uses_bf16_route() or self._align_mode == "rows"))
+            fused = plan is not None and self._align_mode == "rows"
         if fused:
             with torch.no_grad():
                 o2 = None if other is None else other.reshape(-1, self.in_features)
@@ -756,34 +680,43 @@ class _LinearBase(nn.Linear):
         """the quantised weights as the tiled bf16 operand of the per-block-exponent route"""
         if self._w_packed is not None and not self._w_packed.row_scale_flavour:
             return self._w_packed.expand()                   # width-bit storage -> scratch tiled bf16
-        if self._w_bf16 is None or self._w_bf16[1] != self.weight._version or self._w_bf16[0].device != device:
-            if self._fp32_released:
-                raise RuntimeError("mi355q: the fp32 weights were released; this layer cannot switch routes any more")
-            self._w_bf16 = (ops.bf16_tile(self.weight.data), self.weight._version)
-        return self._w_bf16[0]
+        return self._tiled_bf16_weights(device, released="switch routes")
 
     def _residual_fits(self, x, residual) -> bool:
         """can `residual + self(x)` run as one launch?  (the per-block-exponent route's product adds it in its stores)"""
-        return (residual is not None and self.is_ptq and not self.bypass and not self.weight_requires_quantisation
-                and self._pending_flavour is None and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32
-                and self._packed_is_current() and self._int8_plan(x) is not None
-                and (self._uses_bf16_route() or self._residual_rides_the_int8_product())
-                and residual.dtype == torch.float32 and residual.device == x.device
-                and tuple(residual.shape) == tuple(x.shape[:-1]) + (self.out_features,) and residual.is_contiguous()
-                and self.out_features % 4 == 0 and residual.data_ptr() % 16 == 0
-                and not (torch.is_grad_enabled() and (x.requires_grad or residual.requires_grad)))
+        return (residual is not None and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and self._settled()
+                and self._int8_plan(x) is not None and (self._uses_bf16_route() or self._residual_rides_the_int8_product())
+                and self._residual_operand_ok(residual, x.shape[:-1]) and residual.device == x.device
+                and not (torch.is_grad_enabled() and x.requires_grad))
 
     def _residual_rides_the_int8_product(self) -> bool:
         """the row-scale int8 route in its one-launch form (ops.bfp_gemm_aligned(residual=...), round 6): 120-entry activation buckets,
         K a multiple of 128, not the mixed contraction; dense input (a ShardedRows input keeps the separate add)"""
-        return (self._align_mode == "rows" and self._mixed is None and self._x_cap == ops.ROW_BUCKET_CAP and self.in_features % 128 == 0
-                and self._packed is not None)
+        return (self._align_mode == "rows" and self._mixed is None and self._packed is not None
+                and policy.residual_rides_the_int8_product(self.in_features, self._x_cap))
 
     def _residual_operand_ok(self, residual, lead) -> bool:
-        """`residual` can ride in the bf16 product's stores (mi355q_bf16_gemm_tiled_res): fp32, contiguous, [.., out_features]"""
+        """`residual` can ride in a product's stores (mi355q_bf16_gemm_tiled_res): fp32, contiguous, [.., out_features]"""
         return (torch.is_tensor(residual) and residual.is_cuda and residual.dtype == torch.float32 and residual.is_contiguous()
                 and tuple(residual.shape) == tuple(lead) + (self.out_features,) and self.out_features % 4 == 0
                 and residual.data_ptr() % 16 == 0 and not (torch.is_grad_enabled() and residual.requires_grad))
+
+    def _consumer_product(self, xt, rows, lead, residual, device):
+        """this layer's product on the per-block route from its OWN quantised activations as a tiled bf16 buffer, reshaped to
+        [*lead, out_features]; `residual` rides in the stores where it can (`_residual_operand_ok`) and is added behind otherwise"""
+        with torch.no_grad():
+            res2 = residual.reshape(-1, self.out_features) if residual is not None and self._residual_operand_ok(residual, lead) else None
+            y = ops.bf16_gemm_tiled(xt, self._bf16_weight_operand(device), rows, self.out_features, self.in_features, self.bias,
+                                    out=self._take_out(rows), residual=res2)
+        y = y.reshape(*lead, self.out_features)
+        return y if residual is None or res2 is not None else residual + y
+
+    @staticmethod
+    def _norm_pre(norm):
+        """`norm` = (weight, eps): LlamaRMSNorm, (weight, bias, eps): nn.LayerNorm -> the activation quantisers' `pre=`"""
+        if norm is None:
+            return None
+        return ("rmsnorm", norm[0], norm[1]) if len(norm) == 2 else ("layernorm", norm[0], norm[2], norm[1])
 
     def forward_residual(self, x, residual):
         """residual + self(x) (modeling_llama.py:259, modeling_opt.py:375, 425: the add a decoder layer puts behind o_proj / fc2) --
@@ -796,9 +729,7 @@ class _LinearBase(nn.Linear):
     def accepts_tiled_input(self) -> bool:
         """can a producer hand this layer its quantised activations as a tiled bf16 operand (`forward_tiled`)?  block_fp PTQ on the
         per-block-exponent route with its weights packed: the attention pass then writes o_proj's operand itself."""
-        return (self.arith == "block_fp" and self.is_ptq and not self.bypass and not self.weight_requires_quantisation
-                and self._pending_flavour is None and self._packed_is_current() and self._uses_bf16_route()
-                and self.config["data_in_width"] <= 9 and self.in_features % 32 == 0
+        return (self._settled() and self._uses_bf16_route() and self.config["data_in_width"] <= 9 and self.in_features % 32 == 0
                 and ops.resolve_blocking([1, self.in_features], self.config["data_in_block_size"], True)[3:] == (1, 16))
 
     def consumer_quantiser(self):
@@ -811,12 +742,7 @@ class _LinearBase(nn.Linear):
         the producer (ops.bfp_attention(consumer=self.consumer_quantiser())): the per-block product alone.  `lead`: the leading shape
         of the result (rows = prod(lead))."""
         assert self.accepts_tiled_input() and xt.cols == self.in_features
-        with torch.no_grad():
-            res2 = residual.reshape(-1, self.out_features) if residual is not None and self._residual_operand_ok(residual, lead) else None
-            y = ops.bf16_gemm_tiled(xt.buf, self._bf16_weight_operand(xt.buf.device), xt.rows, self.out_features, self.in_features, self.bias,
-                                    out=self._take_out(xt.rows), residual=res2)
-        y = y.reshape(*lead, self.out_features)
-        return y if residual is None or res2 is not None else residual + y
+        return self._consumer_product(xt.buf, xt.rows, lead, residual, xt.buf.device)
 
     def _take_out(self, rows):
         """where the caller wants this call's product stored (sharded.RowShardedLinear: its rank's segment of the all-gather buffer,
@@ -827,8 +753,7 @@ class _LinearBase(nn.Linear):
         return None
 
     def _forward_int8(self, x, plan, pre=None, residual=None):
-        x_mbits, w_mbits, xb, wb = plan
-        c = self.config
+        quantiser = self.consumer_quantiser()
         from ...sharded import ShardedRows
         segments = isinstance(x, ShardedRows)                  # (forward() sends these here on the row-aligned route only)
         x2 = x.buf if segments else x.reshape(-1, self.in_features)
@@ -840,52 +765,47 @@ class _LinearBase(nn.Linear):
             # config["mi355q_blocks_gemm"] = "int8": the blockwise-exact int8 kernel instead (exact integer block dots,
             # several times slower).
             wt = self._bf16_weight_operand(x.device)
-            xt = ops.block_fp_quantize_bf16_tiled(x2.contiguous(), c["data_in_width"], c["data_in_exponent_width"],
-                                                  c["data_in_exponent_bias"], pre=pre)
+            xt = ops.block_fp_quantize_bf16_tiled(x2.contiguous(), *quantiser, pre=pre)
             y = ops.bf16_gemm_tiled(xt, wt, x2.shape[0], self.out_features, self.in_features, self.bias, out=self._take_out(x2.shape[0]),
                                     residual=None if residual is None else residual.reshape(-1, self.out_features))
             return y.reshape(*x.shape[:-1], self.out_features)
-        if self._mixed is not None and self._mixed["version"] == (self.weight._version, None if self.bias is None else self.bias._version):
+        if self._mixed is not None and self._mixed["version"] == self._versions():
             return self._forward_mixed(x, x2, segments, pre, residual)
         assert residual is None or not segments, "a residual behind a segmented input: the caller adds"
         # one fused kernel: quantise + pack + row-align + tile
-        xa = ops.block_fp_quantize_aligned_rows(x2, c["data_in_width"], c["data_in_exponent_width"],
-                                                c["data_in_exponent_bias"], bucket_cap=self._x_cap, pre=pre,
-                                                segments=segments)
+        xa = ops.block_fp_quantize_aligned_rows(x2, *quantiser, bucket_cap=self._x_cap, pre=pre, segments=segments)
         wa = self._w_packed.expand() if self._w_packed is not None else self._packed[0]
         y = ops.bfp_gemm_aligned(xa, wa, self.bias, out=self._take_out(x2.shape[0]),
                                  residual=None if residual is None else residual.reshape(-1, self.out_features))
-        if self.align == "auto" and self._x_cap != ops.ROW_NO_ALIGN:
-            # results never depend on the mode (an overflowing exception bucket only sends the GEMM to its slow
-            # blockwise kernel); look at the overflow word on a doubling schedule and leave row mode if it repeats
-            # (not while a HIP graph is being recorded: the read is a host synchronisation)
-            self._calls += 0 if ops._capturing() else 1
-            if not ops._capturing() and self._calls & (self._calls - 1) == 0 and int(xa.sparse[0]) != 0:
-                self._row_overflows += 1
-                if self._row_overflows >= 2:
-                    self._x_cap = ops.ROW_NO_ALIGN                # activations stopped fitting: no alignment from now on
+        if self.align == "auto" and self._x_cap != ops.ROW_NO_ALIGN and self._overflow_repeats(xa.sparse):
+            self._x_cap = ops.ROW_NO_ALIGN                    # activations stopped fitting: no alignment from now on
         return y.reshape(*x.shape[:-1], self.out_features)
+
+    def _overflow_repeats(self, sparse) -> bool:
+        """results never depend on the mode (an overflowing exception bucket only sends the GEMM to its slow blockwise kernel, the
+        mixed launch to its exact fallback): look at the overflow word on a doubling schedule of calls, and say when it was up
+        twice -- the layer then leaves row mode (not while a HIP graph is being recorded: the read is a host synchronisation)"""
+        if ops._capturing():
+            return False
+        self._calls += 1
+        if self._calls & (self._calls - 1) == 0 and int(sparse[0]) != 0:
+            self._row_overflows += 1
+            return self._row_overflows >= 2
+        return False
 
     def _forward_mixed(self, x, x2, segments, pre, residual):
         """the mixed contraction: one pass of the class-aware quantiser over x, one launch of the tile kernel (class 0 on the int8
         MFMA, class 1 on the bf16 MFMA); an elementwise step in front, row segments or a residual behind run as torch ops here"""
-        c, m = self.config, self._mixed
+        m = self._mixed
         if segments:
             x2 = x.dense().reshape(-1, self.in_features)
         if pre is not None:
             x2 = F.relu(x2) if pre[0] == "relu" else F.silu(x2) * pre[1].reshape(-1, self.in_features)
-        x0, x1 = ops.block_fp_quantize_classes(x2, m["classes"], c["data_in_width"], c["data_in_exponent_width"], c["data_in_exponent_bias"],
-                                               bucket_cap=self._x_cap)
+        x0, x1 = ops.block_fp_quantize_classes(x2, m["classes"], *self.consumer_quantiser(), bucket_cap=self._x_cap)
         y = ops.bfp_gemm_mixed(x0, m["wa0"], x1, m["w1"], m["classes"].K1, self.bias, out=self._take_out(x2.shape[0]))
         assert y is not None, "mi355q: the mixed contraction was chosen for a shape the library does not take"
-        if self.align == "auto":
-            # (as on the row route: an overflowing class-0 bucket only sends the launch to its exact fallback; look at the overflow
-            #  word on a doubling schedule of calls and leave for the per-block route if it repeats)
-            self._calls += 0 if ops._capturing() else 1
-            if not ops._capturing() and self._calls & (self._calls - 1) == 0 and int(x0.sparse[0]) != 0:
-                self._row_overflows += 1
-                if self._row_overflows >= 2:
-                    self._mixed, self._x_cap = None, ops.ROW_NO_ALIGN
+        if self.align == "auto" and self._overflow_repeats(x0.sparse):
+            self._mixed, self._x_cap = None, ops.ROW_NO_ALIGN     # (as on the row route; from now on the per-block route)
         lead = x.shape[:-1]
         y = y.reshape(*lead, self.out_features)
         return y if residual is None else residual + y
@@ -907,259 +827,6 @@ class _LinearBase(nn.Linear):
             self.config.get("bias_width", "NA"))
 
 
-def gated_mlp(x, gate, up, down, norm=None, residual=None):
-    """down(silu(gate(x)) * up(x)) [+ residual] for block_fp PTQ layers (modeling_llama.py:216, the Llama MLP) as TWO launches
-    behind the activation quantiser instead of four: x -- with LlamaRMSNorm applied by its quantiser when `norm` = (weight, eps) --
-    against gate's and up's weights INTERLEAVED in chunks of 16 rows (ops.interleave_gate_up, built once per pair), whose store
-    epilogue forms silu(gate) * up in registers, quantises it with down's activation quantiser and writes down's tiled bf16
-    operand (ops.bfp_gemm_aligned_gated: the two [tokens, intermediate] fp32 tensors are never written, the separate
-    silu-mul-quantise launch -- 180 MB read, 45 MB written per Llama-7B layer at 2048 tokens -- is gone); then down's product on the
-    bf16 flavour of the tile GEMM, the residual in its stores.  Same bits as grouped_linear + down.forward_after.  Returns None
-    whenever the pair / the consumer does not qualify (first PTQ forward, gate / up not on the row-scale int8 route, down not on
-    the per-block route, shapes, autograd ...): the caller then takes that path."""
-    from ...sharded import RowShardedLinear
-    layers = (gate, up, down)
-    if any(isinstance(l, RowShardedLinear) or not isinstance(l, _LinearBase) for l in layers):
-        return None
-    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and 2 <= x.ndim <= 3) or (torch.is_grad_enabled() and x.requires_grad):
-        return None
-    if not all(l.arith == "block_fp" and l.is_ptq and not l.bypass and not l.weight_requires_quantisation and l._pending_flavour is None
-               and l._packed_is_current() for l in layers):
-        return None
-    c, dc = gate.config, down.config
-    if (c.get("mi355q_fused_gate_up", True) in (False, "off") or not dc.get("mi355q_fused_activation", False) or dc["data_in_width"] > 9
-            or gate.in_features != up.in_features or gate.out_features != up.out_features or down.in_features != gate.out_features
-            or gate.in_features % 128 or gate.in_features < 256 or gate.out_features % 128 or (gate.bias is None) != (up.bias is None)
-            or (norm is not None and len(norm) != 2)):
-        return None
-    plan = gate._int8_plan(x)
-    if plan is None or up._int8_plan(x) != plan or down._int8_plan(x.new_empty((1, down.in_features))) is None:
-        return None
-    if not all(l._align_mode == "rows" and not l._uses_bf16_route() and l._mixed is None and l._w_packed is None
-               and l._x_cap == ops.ROW_BUCKET_CAP for l in (gate, up)):
-        return None
-    if not all(gate.config[k] == up.config[k] for k in ("data_in_width", "data_in_exponent_width", "data_in_exponent_bias")):
-        return None
-    if not down._uses_bf16_route() or (down._w_packed is not None and down._w_packed.row_scale_flavour):
-        return None
-    with torch.no_grad():
-        pair = gate.__dict__.get("_gated_pair")
-        key = (id(up), gate.weight._version, up.weight._version, gate._packed[0].tiled.data_ptr(), up._packed[0].tiled.data_ptr(),
-               None if gate.bias is None else gate.bias._version, None if up.bias is None else up.bias._version)
-        if pair is None or pair[0] != key:
-            w_gu = ops.interleave_gate_up(gate._packed[0], up._packed[0])
-            b_gu = None
-            if w_gu is not None and gate.bias is not None:
-                I = gate.out_features
-                b_gu = torch.stack((gate.bias.data.reshape(I // 16, 16), up.bias.data.reshape(I // 16, 16)), dim=1).reshape(-1).contiguous()
-            pair = gate.__dict__["_gated_pair"] = (key, w_gu, b_gu)
-        _, w_gu, b_gu = pair
-        if w_gu is None:
-            return None
-        x2 = x.reshape(-1, gate.in_features)
-        xa = ops.block_fp_quantize_aligned_rows(x2, c["data_in_width"], c["data_in_exponent_width"], c["data_in_exponent_bias"],
-                                                bucket_cap=gate._x_cap, pre=None if norm is None else ("rmsnorm", norm[0], norm[1]))
-        xt = ops.bfp_gemm_aligned_gated(xa, w_gu, dc["data_in_width"], dc["data_in_exponent_width"], dc["data_in_exponent_bias"], b_gu)
-        if xt is None:
-            return None
-        M = x2.shape[0]
-        res2 = None
-        if residual is not None and down._residual_operand_ok(residual, x.shape[:-1]):
-            res2 = residual.reshape(-1, down.out_features)
-        y = ops.bf16_gemm_tiled(xt, down._bf16_weight_operand(x.device), M, down.out_features, down.in_features, down.bias,
-                                out=down._take_out(M), residual=res2)
-        y = y.reshape(*x.shape[:-1], down.out_features)
-        return y if residual is None or res2 is not None else residual + y
-
-
-def relu_mlp(x, fc1, fc2, norm=None, residual=None):
-    """fc2(relu(fc1(x))) [+ residual] for block_fp PTQ layers (modeling_opt.py:412-420, the OPT MLP) as TWO launches behind the
-    activation quantiser: fc1's product with relu and fc2's activation quantiser in its store epilogue (ops.bfp_gemm_aligned_relu:
-    the [tokens, ffn] fp32 tensor is never written, the relu-quantise launch is gone), then fc2's product on the bf16 flavour of the
-    tile GEMM.  `norm` = (weight, bias, eps): OPT's final_layer_norm applied by fc1's quantiser.  Same bits as fc1 + fc2.forward_after.
-    Returns None whenever the layers do not qualify (the caller then takes that path): gated_mlp's conditions with one producer."""
-    from ...sharded import RowShardedLinear
-    if any(isinstance(l, RowShardedLinear) or not isinstance(l, _LinearBase) for l in (fc1, fc2)):
-        return None
-    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and 2 <= x.ndim <= 3) or (torch.is_grad_enabled() and x.requires_grad):
-        return None
-    if not all(l.arith == "block_fp" and l.is_ptq and not l.bypass and not l.weight_requires_quantisation and l._pending_flavour is None
-               and l._packed_is_current() for l in (fc1, fc2)):
-        return None
-    c, dc = fc1.config, fc2.config
-    if (c.get("mi355q_fused_gate_up", True) in (False, "off") or not dc.get("mi355q_fused_activation", False) or dc["data_in_width"] > 9
-            or fc2.in_features != fc1.out_features or fc1.in_features % 128 or fc1.in_features < 256 or fc1.out_features % 32
-            or (norm is not None and len(norm) != 3)):
-        return None
-    if fc1._int8_plan(x) is None or fc2._int8_plan(x.new_empty((1, fc2.in_features))) is None:
-        return None
-    if not (fc1._align_mode == "rows" and not fc1._uses_bf16_route() and fc1._mixed is None and fc1._w_packed is None
-            and fc1._x_cap == ops.ROW_BUCKET_CAP):
-        return None
-    if not fc2._uses_bf16_route() or (fc2._w_packed is not None and fc2._w_packed.row_scale_flavour):
-        return None
-    with torch.no_grad():
-        x2 = x.reshape(-1, fc1.in_features)
-        xa = ops.block_fp_quantize_aligned_rows(x2, c["data_in_width"], c["data_in_exponent_width"], c["data_in_exponent_bias"],
-                                                bucket_cap=fc1._x_cap,
-                                                pre=None if norm is None else ("layernorm", norm[0], norm[2], norm[1]))
-        xt = ops.bfp_gemm_aligned_relu(xa, fc1._packed[0], dc["data_in_width"], dc["data_in_exponent_width"], dc["data_in_exponent_bias"],
-                                       fc1.bias)
-        if xt is None:
-            return None
-        M = x2.shape[0]
-        res2 = residual.reshape(-1, fc2.out_features) if residual is not None and fc2._residual_operand_ok(residual, x.shape[:-1]) else None
-        y = ops.bf16_gemm_tiled(xt, fc2._bf16_weight_operand(x.device), M, fc2.out_features, fc2.in_features, fc2.bias,
-                                out=fc2._take_out(M), residual=res2)
-        y = y.reshape(*x.shape[:-1], fc2.out_features)
-        return y if residual is None or res2 is not None else residual + y
-
-
-FP32_SPLIT_MIN_ROWS = 128     # (fewer tokens: the product is bound by the weight bytes, and the split operand is 3 x the fp32 one)
-
-
-def fp32_linear(x, linear: nn.Linear, mode: str = "split"):
-    """F.linear(x, linear.weight, linear.bias) for a layer the reference leaves UNQUANTISED -- the language-model head
-    (modeling_llama.py:772,866; modeling_opt.py:942-944: nn.Linear in fp32) -- as an fp32-equivalent product on the bf16 MFMA:
-    both operands as three bf16 parts, the six part products side by side along K in ONE launch of the bf16 tile GEMM
-    (ops.fp32_split_tile / fp32_gemm_split; csrc/mi355q_split.hip).  Closer to an fp64 product than the vendor fp32 GEMM and 1.7 x
-    faster at Llama-7B's head.  The weights' operand is built once and kept on the module (rebuilt when the parameter is written).
-    `mode` "vendor", gradients wanted, a CPU tensor, fewer than FP32_SPLIT_MIN_ROWS tokens or in_features % 32 != 0: torch's
-    F.linear, counted as a vendor GEMM."""
-    w = linear.weight
-    M = x.numel() // max(1, x.shape[-1])
-    ok = (mode == "split" and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32 and w.device == x.device
-          and linear.in_features % 32 == 0 and M >= FP32_SPLIT_MIN_ROWS and not (torch.is_grad_enabled() and (x.requires_grad or w.requires_grad)))
-    if not ok:
-        ops.count_vendor_gemm("fp32_linear (unquantised layer, vendor fp32 GEMM)")
-        return F.linear(x, w, linear.bias)
-    try:
-        key = (w.data_ptr(), w._version, str(w.device))
-    except RuntimeError:                      # (inference-mode tensors have no version counter: keyed by storage alone)
-        key = (w.data_ptr(), None, str(w.device))
-    cached = linear.__dict__.get("_mi355q_split_weight")
-    if cached is None or cached[0] != key:
-        with torch.no_grad():
-            cached = (key, ops.fp32_split_tile(w.detach().contiguous(), 1))
-        linear.__dict__["_mi355q_split_weight"] = cached
-    with torch.no_grad():
-        x2 = x.reshape(-1, linear.in_features).contiguous()
-        y = ops.fp32_gemm_split(ops.fp32_split_tile(x2, 0), cached[1], M, linear.out_features, linear.in_features, bias=linear.bias)
-    return y.reshape(*x.shape[:-1], linear.out_features)
-
-
-def grouped_linear(x, layers, norm=None):
-    """[layer(x) for layer in layers] for block_fp PTQ Linear layers that take the SAME input and have the same shape and
-    widths -- the q / k / v projections of an attention block, gate / up of a gated MLP, which the reference's modules
-    call one after the other (modeling_opt.py:231-245, modeling_llama.py:216, 283-287) -- as ONE activation quantisation
-    and ONE launch of the tile GEMM over all their column tiles (ops.bfp_gemm_aligned_multi): the separate products
-    leave compute units idle (2048 -> 2048: 128 tiles each) or waste most of a second round (4096 -> 11008: 344 tiles).
-    Bit-identical to the separate calls; falls back to them whenever the group does not qualify (first PTQ forward,
-    other arithmetics, the per-block bf16 route, differing shapes ...).
-
-    `norm` = (weight, eps): the layers take LlamaRMSNorm(x) (modeling_llama.py:81-92, 236-238: the input of q / k / v and of
-    gate / up, which nothing else reads), `norm` = (weight, bias, eps): nn.LayerNorm(x) (OPT's self_attn_layer_norm in
-    front of q / k / v and final_layer_norm in front of fc1, modeling_opt.py:391-415) -- and the quantiser, which holds a
-    whole row per workgroup, applies the norm itself, so the normalised tensor is never written.  Then the mean of squares is summed in the kernel's own fixed
-    order: results agree with the separate norm to within the last-bit differences any two fp32 summation orders
-    show (torch's own CPU and GPU reductions included), not bit for bit."""
-    layers = list(layers)
-    from ...sharded import RowShardedLinear
-    if all(isinstance(l, RowShardedLinear) for l in layers):
-        if all(l.keep_local for l in layers):
-            # head-sharded q / k / v (sharded.shard_model(heads=True)): the rank's own heads, no collective here
-            return grouped_linear(x, [l.local for l in layers], norm=norm)
-        # row-sharded projections (sharded.shard_model): this rank's shards as one group, one all-gather per projection
-        for l in layers:                                       # (each product straight into its rank's segment of its gather buffer)
-            l._aim_at_gather_buffer(x)
-        try:
-            ys = grouped_linear(x, [l.local for l in layers], norm=norm)
-        finally:
-            for l in layers:
-                l.local._out_hint = None
-        if len(layers) == 2 and layers[0].gather == "quantised" and layers[0].consumer_pre == "silu_mul":
-            # Llama's gate / up in front of down_proj (sharded.shard_model(gather="quantised")): both shards of a rank cover the
-            # same columns, so silu(gate) * up and down_proj's quantiser run on the rank's own slice; ONE all-gather, of the
-            # tiled bf16 operand.  The second result is None: down_proj.forward_after(gate, "silu_mul", None) reads the first
-            return [layers[0].gather_output(ys[0], other=ys[1]), None]
-        return [l.gather_output(y) for l, y in zip(layers, ys)]
-    first = layers[0]
-
-    def normed():
-        if len(norm) == 3:
-            return F.layer_norm(x, (x.shape[-1],), norm[0], norm[1], norm[2])
-        w, eps = norm
-        v = x.to(torch.float32).pow(2).mean(-1, keepdim=True)
-        return w * (x * torch.rsqrt(v + eps)).to(x.dtype)
-    ok = (len(layers) in ((1, 2, 3) if norm is not None else (2, 3)) and all(isinstance(l, _LinearBase) and l.arith == "block_fp" and l.is_ptq and not l.bypass
-                                         and not l.weight_requires_quantisation for l in layers)
-          and not (torch.is_grad_enabled() and x.requires_grad))
-    if ok:
-        plan = first._int8_plan(x)
-        ok = plan is not None and (norm is None or (x.is_cuda and x.dtype == torch.float32)) and all(
-            l._packed_is_current() and l._align_mode == "rows" and not l._uses_bf16_route() and l._mixed is None
-            and (l._w_packed is None or (l._w_packed.row_scale_flavour and l._pending_flavour is None))
-            and l.in_features == first.in_features and l.out_features == first.out_features and l._x_cap == first._x_cap
-            and l._x_cap == ops.ROW_BUCKET_CAP and l._int8_plan(x) == plan
-            and all(l.config[k] == first.config[k] for k in ("data_in_width", "data_in_exponent_width", "data_in_exponent_bias"))
-            for l in layers)
-    if ok:
-        c = first.config
-        x2 = x.reshape(-1, first.in_features)
-        with torch.no_grad():
-            xa = ops.block_fp_quantize_aligned_rows(x2, c["data_in_width"], c["data_in_exponent_width"], c["data_in_exponent_bias"],
-                                                    bucket_cap=first._x_cap,
-                                                    pre=None if norm is None else (
-                                                        ("rmsnorm", norm[0], norm[1]) if len(norm) == 2 else
-                                                        ("layernorm", norm[0], norm[2], norm[1])))
-            # one launch, or the split of the group that takes fewer rounds over the chip (ops.grouped_launch_plan)
-            # (width-bit storage: a launch's members expand into scratch slots 0 .. g - 1 first -- round 5; before, a packed layer
-            #  kept its group off this path: separate launches, the norm by six torch kernels)
-            outs, at = [], 0
-            for g in ops.grouped_launch_plan(x2.shape[0], first.out_features, len(layers)):
-                part = layers[at:at + g]
-                at += g
-                was = [l._w_packed.expand(i) if l._w_packed is not None else l._packed[0] for i, l in enumerate(part)]
-                hints = [l._take_out(x2.shape[0]) for l in part]
-                if g == 1:
-                    ys = [ops.bfp_gemm_aligned(xa, was[0], part[0].bias, out=hints[0])]
-                else:
-                    ys = ops.bfp_gemm_aligned_multi(xa, was, [l.bias for l in part], outs=hints)
-                if ys is None:
-                    outs = None
-                    break
-                outs.extend(ys)
-        if outs is not None:
-            return [y.reshape(*x.shape[:-1], first.out_features) for y in outs]
-    # The per-block-exponent route (bf16 tile GEMM: inputs no row window fits -- every Linear of a model whose hidden channels
-    # differ in magnitude): ONE activation operand for the group, LlamaRMSNorm applied by its quantiser; the products stay separate
-    # launches.  (Before round 5 such a group fell back to the torch norm -- six elementwise kernels -- and quantised x once per layer.)
-    if (len(layers) >= 1 and (norm is None or len(norm) == 2) and x.is_cuda and x.dtype == torch.float32 and 2 <= x.ndim <= 3
-            and not (torch.is_grad_enabled() and x.requires_grad)
-            and all(isinstance(l, _LinearBase) and l.arith == "block_fp" and l.is_ptq and not l.bypass and not l.weight_requires_quantisation
-                    and l._pending_flavour is None for l in layers)):
-        plan = first._int8_plan(x)
-        if (plan is not None and all(l._packed_is_current() and l._uses_bf16_route() and l.in_features == first.in_features
-                                     and (l._w_packed is None or not l._w_packed.row_scale_flavour or len(layers) == 1)
-                                     and l._int8_plan(x) == plan
-                                     and all(l.config[k] == first.config[k] for k in ("data_in_width", "data_in_exponent_width", "data_in_exponent_bias"))
-                                     for l in layers)
-                and (norm is not None or len(layers) > 1)):
-            c = first.config
-            x2 = x.reshape(-1, first.in_features).contiguous()
-            with torch.no_grad():
-                xt = ops.block_fp_quantize_bf16_tiled(x2, c["data_in_width"], c["data_in_exponent_width"], c["data_in_exponent_bias"],
-                                                      pre=None if norm is None else ("rmsnorm", norm[0], norm[1]))
-                outs = []
-                for l in layers:           # (a packed layer's expand() shares one scratch operand: each product before the next expand)
-                    y = ops.bf16_gemm_tiled(xt, l._bf16_weight_operand(x.device), x2.shape[0], l.out_features, l.in_features, l.bias,
-                                            out=l._take_out(x2.shape[0]))
-                    outs.append(y.reshape(*x.shape[:-1], l.out_features))
-            return outs
-    h = x if norm is None else normed()
-    return [l(h) for l in layers]
-
-
 def _linear_class(name: str, arith: str):
     return type(name, (_LinearBase,), {"arith": arith, "__module__": __name__,
                                        "__doc__": f"nn.Linear with {arith} input / weight / bias quantisers"})
@@ -1172,3 +839,5 @@ LinearInteger = _linear_class("LinearInteger", "integer")
 LinearLog = _linear_class("LinearLog", "log")
 LinearMinifloatDenorm = _linear_class("LinearMinifloatDenorm", "minifloat_denorm")
 LinearMinifloatIEEE = _linear_class("LinearMinifloatIEEE", "minifloat_ieee")
+
+from .linear_fused import FP32_SPLIT_MIN_ROWS, fp32_linear, gated_mlp, grouped_linear, relu_mlp  # noqa: E402,F401  (written on _LinearBase)
