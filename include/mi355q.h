@@ -581,6 +581,47 @@ int mi355q_bfp_attention_fused(const float* q, const float* k, const float* v, c
                                const float* cos, const float* sin, const int64_t* position_ids, int64_t table_rows, int32_t heads,
                                void* stream);
 
+/* ---- incremental decoding: block_fp KV cache and split-key decode attention ------------------------------------------
+ * The reference decodes with `past_key_value`: torch.cat of fp32 K / V (models/llama_quantized/modeling_llama.py:301-306, the
+ * same in modeling_opt.py), then the core above (modeling_llama.py:309-344) on the concatenated tensors of length L.  The cache
+ * here holds what the core's quantisers make of them, per b = batch x head, capacity C keys (C % 16 == 0, D % 32 == 0,
+ * D <= 128, widths <= 9, B <= 65535, else MI355Q_E_UNSUPPORTED), as bf16 in the decode kernels' MFMA fragment order (layout:
+ * csrc/mi355q_decode.h): V's blocks run along D at a fixed key and are final when written; K^T's blocks are 16 consecutive
+ * KEYS at a fixed d, so the last block (L % 16 keys) is open -- its fp32 rows stay in `stage` and it is quantised again on
+ * every append until it is full (absent keys are the blocking's zero padding).  The length L is the caller's.
+ *
+ * Sizes of the three buffers (16-byte aligned device memory).  vq must hold FINITE bf16 values before the first append -- zero
+ * it once: a slot of the last 32-key pair that no key has reached meets a probability of exactly 0, and 0 x NaN / Inf is not 0.
+ * Stale finite values are harmless: restarting at a shorter L without clearing anything is allowed (append rewrites every K
+ * tile it touches in full, absent keys as zeros; V slots behind L only ever meet probability 0).  kq and stage need no
+ * initial contents. */
+int mi355q_bfp_kv_cache_bytes(int64_t B, int64_t C, int64_t D, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_bytes);
+/* Replaces the concatenation (modeling_llama.py:301-306) and the K / V halves of the quantisers of bmm_0 / bmm_1
+ * (quantized_functions/matmul.py:146-196): n >= 1 new fp32 rows k, v [B, n, D] become keys L .. L + n - 1 (n may be a whole
+ * prompt; n == 0 is a successful no-op).  strides = {k batch, k row, v batch, v row} in elements (innermost 1, multiples of 4), NULL = contiguous.  Uses the
+ * y-side (weight_*) parameters of qk_params / pv_params, laid out as for the one-pass core.  L + n > C: MI355Q_E_UNSUPPORTED
+ * and nothing is written. */
+int mi355q_bfp_kv_append(void* kq, void* vq, float* stage, const float* k, const float* v, int64_t B, int64_t C, int64_t D,
+                         int64_t L, int64_t n, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
+                         void* stream);
+/* Test and debug hook: the cache's quantised K and V back as fp32 [B, L, D]. */
+int mi355q_bfp_kv_decode_fp32(const void* kq, const void* vq, float* k_out, float* v_out, int64_t B, int64_t C, int64_t D, int64_t L,
+                              void* stream);
+/* Replaces the core (modeling_llama.py:309-344; modeling_opt.py:246-312) for the last M positions of a sequence whose L keys
+ * are in the cache: q fp32 [B, M, D], 1 <= M <= 16, L >= M (else MI355Q_E_UNSUPPORTED); causal != 0: query i sees keys
+ * 0 .. L - M + i, else all L; q_scale / scale_div as in mi355q_bfp_attention_fused (0 = none); no additive mask.  out fp32
+ * [B, M, D]; strides = {q batch, q row, out batch, out row} (multiples of 4), NULL = contiguous.  Keys are split over S
+ * workgroups per head: scores and per-split (max, sum of exponentials) first, then -- the statistics combined in split order --
+ * probabilities quantised per 16-key block times V, and the partial outputs summed in split order: the same inputs give the
+ * same bits on every run.  S = a pure function of (B, L, D), or `splits` > 0 (clamped to 1 .. ceil(L / 32), evened out); the
+ * workspace is sized for the same `splits`. */
+int mi355q_bfp_attention_decode_splits(int64_t B, int64_t L, int64_t D, int32_t splits);
+size_t mi355q_bfp_attention_decode_workspace_bytes(int64_t B, int64_t L, int64_t D, int32_t splits);
+int mi355q_bfp_attention_decode(const float* q, const void* kq, const void* vq, int32_t causal, float q_scale, float scale_div,
+                                float* out, void* workspace, int64_t B, int64_t M, int64_t L, int64_t C, int64_t D,
+                                const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides, int32_t splits,
+                                void* stream);
+
 /* ---- the un-blocked quantisers -------------------------------------------------------------------------------------
  * replaces: quantizers/minifloat.py:134-196 (minifloat_ieee_quantizer: implicit leading one, subnormals at the lowest
  *           exponent), :21-86 (minifloat_denorm_quantizer: no implicit one, exponent ceil(log2(|x| + 1e-9)) per element)

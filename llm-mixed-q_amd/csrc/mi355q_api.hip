@@ -12,6 +12,7 @@
 
 #include "mi355q_internal.h"
 #include "mi355q_gemv.h"
+#include "mi355q_decode.h"
 #include "mi355q_align_row.h"
 
 using namespace mi355q;
@@ -1001,6 +1002,105 @@ int mi355q_bfp_attention_fused(const float* q, const float* k, const float* v, c
                                 scale_div, static_cast<hipStream_t>(stream), strides ? st6 : nullptr, cos, sin,
                                 reinterpret_cast<const long long*>(position_ids), table_rows, heads, static_cast<uint16_t*>(out_bf16_tiled),
                                 out_bf16_tiled ? &ao : nullptr, q_scale);
+}
+
+// ---- incremental decoding: block_fp KV cache + split-key decode attention (mi355q_decode.hip) ----------------------------
+namespace {
+// the block_fp quantiser of one operand: {width, exponent width, exponent bias} at pr
+int decode_quant_args(const int32_t* pr, QuantArgs& a) {
+    if (pr[0] < 2 || pr[1] < 1 || pr[1] > 8) return MI355Q_E_BADARG;
+    if (pr[0] > 9) return MI355Q_E_UNSUPPORTED;               // a quantised value must fit bf16's 8 significant bits
+    int bias = pr[2];
+    if (bias == MI355Q_BIAS_DEFAULT) bias = (1 << (pr[1] - 1)) - 1;
+    a.b0 = 1; a.b1 = 16;
+    a.code_bias = bias;
+    a.e_min = -bias;
+    a.e_max = (1 << pr[1]) - 1 - bias;
+    set_mantissa(a, pr[0] - 1);
+    return 0;
+}
+int decode_cache_shape(int64_t B, int64_t C, int64_t D) {
+    if (B < 1 || C < 1 || D < 1 || B > 65535) return MI355Q_E_BADARG;
+    if (C % 16 != 0 || D % 32 != 0 || D > 128 || C > (1LL << 30)) return MI355Q_E_UNSUPPORTED;
+    return 0;
+}
+}  // namespace
+
+int mi355q_bfp_kv_cache_bytes(int64_t B, int64_t C, int64_t D, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_bytes) {
+    if (!k_bytes || !v_bytes || !stage_bytes) return MI355Q_E_BADARG;
+    const int rc = decode_cache_shape(B, C, D);
+    if (rc) return rc;
+    *k_bytes = kv_k_bytes(B, C, D);
+    *v_bytes = kv_v_bytes(B, C, D);
+    *stage_bytes = kv_stage_bytes(B, D);
+    return 0;
+}
+
+int mi355q_bfp_kv_append(void* kq, void* vq, float* stage, const float* k, const float* v, int64_t B, int64_t C, int64_t D,
+                         int64_t L, int64_t n, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
+                         void* stream) {
+    int rc = decode_cache_shape(B, C, D);
+    if (rc) return rc;
+    if (L < 0 || n < 0 || !qk_params || !pv_params) return MI355Q_E_BADARG;
+    if (L + n > C) return MI355Q_E_UNSUPPORTED;               // (nothing is written)
+    if (n == 0) return 0;
+    if (!kq || !vq || !stage || !k || !v) return MI355Q_E_BADARG;
+    QuantArgs ak{}, av{};
+    if ((rc = decode_quant_args(qk_params + 3, ak)) != 0 || (rc = decode_quant_args(pv_params + 3, av)) != 0) return rc;
+    if ((reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) | reinterpret_cast<uintptr_t>(stage) |
+         reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v)) % 16)
+        return MI355Q_E_ALIGN;
+    long long st4[4] = {n * D, D, n * D, D};
+    if (strides)
+        for (int i = 0; i < 4; ++i) {
+            if (strides[i] % 4) return MI355Q_E_ALIGN;
+            st4[i] = strides[i];
+        }
+    const KvCache c{static_cast<uint16_t*>(kq), static_cast<uint16_t*>(vq), stage, B, C, (int)D};
+    return launch_kv_append(c, ak, av, k, v, st4[0], st4[1], st4[2], st4[3], L, n, static_cast<hipStream_t>(stream));
+}
+
+int mi355q_bfp_kv_decode_fp32(const void* kq, const void* vq, float* k_out, float* v_out, int64_t B, int64_t C, int64_t D, int64_t L,
+                              void* stream) {
+    const int rc = decode_cache_shape(B, C, D);
+    if (rc) return rc;
+    if (L < 0 || L > C) return MI355Q_E_BADARG;
+    if (L == 0) return 0;
+    if (!kq || !vq || !k_out || !v_out) return MI355Q_E_BADARG;
+    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
+    return launch_kv_decode_fp32(c, k_out, v_out, L, static_cast<hipStream_t>(stream));
+}
+
+int mi355q_bfp_attention_decode_splits(int64_t B, int64_t L, int64_t D, int32_t splits) { return decode_splits(B, L, D, splits); }
+
+size_t mi355q_bfp_attention_decode_workspace_bytes(int64_t B, int64_t L, int64_t D, int32_t splits) {
+    if (B <= 0 || L <= 0 || D <= 0 || D % 32 != 0 || D > 128) return 0;
+    return decode_workspace_bytes(B, L, D, splits);
+}
+
+int mi355q_bfp_attention_decode(const float* q, const void* kq, const void* vq, int32_t causal, float q_scale, float scale_div,
+                                float* out, void* workspace, int64_t B, int64_t M, int64_t L, int64_t C, int64_t D,
+                                const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides, int32_t splits,
+                                void* stream) {
+    if (M < 0 || L < 0 || splits < 0) return MI355Q_E_BADARG;
+    int rc = decode_cache_shape(B, C, D);
+    if (rc) return rc;
+    if (M < 1 || M > 16 || L < M) return MI355Q_E_UNSUPPORTED;      // (the last M <= 16 positions against all L keys)
+    if (L > C || !q || !kq || !vq || !out || !workspace || !qk_params || !pv_params) return MI355Q_E_BADARG;
+    QuantArgs aq{}, ap{};
+    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) |
+         reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) % 16)
+        return MI355Q_E_ALIGN;
+    long long st4[4];
+    if (strides)
+        for (int i = 0; i < 4; ++i) {
+            if (strides[i] % 4) return MI355Q_E_ALIGN;
+            st4[i] = strides[i];
+        }
+    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
+    return launch_bfp_attention_decode(aq, ap, c, q, out, workspace, M, L, causal != 0, q_scale, scale_div, strides ? st4 : nullptr,
+                                       splits, static_cast<hipStream_t>(stream));
 }
 
 // block_minifloat (fmt 1) / block_log (fmt 2) products: the same two kernels with the other quantisers' block parameters

@@ -1,0 +1,70 @@
+// Incremental decoding (mi355q_decode.hip): the block_fp KV cache and the split-key decode attention, what the C-ABI wrapper
+// needs of them.
+//
+// Cache layout, per b = batch x head, capacity C keys (C % 16 == 0), head_dim D (D % 32 == 0, D <= 128); all quantised values
+// are bf16 (exact for widths <= 9) and sit in the order the decode kernels' MFMA operands want them, 16 bytes a lane:
+//   kq    [B][C / 16][D / 32][64 lanes][8]   Qb(k^T): piece (b, key tile t, chunk c) = 1 KiB; lane (key 16 t + lane % 16,
+//                                            g = lane / 16) holds d = 32 c + 8 g .. + 7.  A [1,16] block of k^T is the 16 keys of
+//                                            a tile at one d: keys the cache does not hold yet are the blocking's zero padding
+//                                            (stored as zeros, outside the block maximum).
+//   vq    [B][ceil(C / 32)][D / 16][64][8]   Qd(v): piece (b, key pair s = 32 keys, dt) = 1 KiB; lane (d = 16 dt + lane % 16,
+//                                            g = lane / 16) holds slot j <-> key 32 s + 16 (j / 4) + 4 g + (j & 3).  A block is
+//                                            16 d of one key: final once written.  The storage starts out ZEROED (a slot that no
+//                                            key has reached meets a probability of exactly 0, and must be finite).
+//   stage [B][16][D] fp32                    the rows of the OPEN key tile (L % 16 keys): a block of 16 keys is final only once
+//                                            it is full, until then every append re-quantises it from these rows.
+// Values are those of attn_pack_k / attn_pack_v (|x| <= 1e-8 passes through, rounded to bf16) with ONE difference: a zero is
+// always stored as +0.  A negative value whose mantissa rounds to 0 is -0 in the prefill fragments (copysign) and +0 in the
+// oracle's block_fp_quantize (its mantissas are integers); the products cannot tell, the bit-for-bit cache tests can.
+// The length L lives on the host: an append at L writes keys L .. L + n - 1, a decode at L reads keys 0 .. L - 1.
+#ifndef MI355Q_DECODE_H
+#define MI355Q_DECODE_H
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mi355q_internal.h"
+
+namespace mi355q {
+
+struct KvCache {
+    uint16_t* kq;
+    uint16_t* vq;
+    float* stage;
+    long long B, C;
+    int D;
+};
+inline long long kv_k_bytes(long long B, long long C, long long D) { return B * C * D * 2; }
+inline long long kv_v_bytes(long long B, long long C, long long D) { return B * ((C + 31) / 32) * 32 * D * 2; }
+inline long long kv_stage_bytes(long long B, long long D) { return B * 16 * D * 4; }
+
+// keys L .. L + n - 1 from fp32 rows k / v [B, n, D] (element strides of batch and row; innermost 1)
+int launch_kv_append(const KvCache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
+                     long long kst, long long vsb, long long vst, long long L, long long n, hipStream_t st);
+// the cache's quantised values back as fp32 [B, L, D] (tests, debugging)
+int launch_kv_decode_fp32(const KvCache& c, float* k_out, float* v_out, long long L, hipStream_t st);
+
+// S of a decode over L keys: a pure function of (B, L, D); `override` > 0 asks for that many (clamped, then evened out so
+// that no split is empty).  1 <= S <= ceil(L / 32).
+int decode_splits(long long B, long long L, long long D, int override);
+size_t decode_workspace_bytes(long long B, long long L, long long D, int splits);
+
+struct DecodeArgs {
+    const float* q;           // [B, M, D] by strides
+    const uint16_t* kq;
+    const uint16_t* vq;
+    float* out;               // [B, M, D] by strides
+    float* scores;            // workspace: [B][NT][64][4] the score tiles as their MFMA lanes hold them
+    float* stats;             //            [B][S][16][2] a split's (max, sum of exp(x - max)) per query
+    float* part;              //            [B][S][D / 16][64][4] a split's partial output
+    long long M, L, NT, NP, NTC, NPC;
+    long long qsb, qsm, osb, osm;
+    int causal;
+    float q_scale, scale_div; // 0: none
+    int D, S, pps;            // pps = key pairs per split
+};
+int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out,
+                                void* workspace, long long M, long long L, int causal, float q_scale, float scale_div,
+                                const long long* strides, int splits, hipStream_t st);
+
+}  // namespace mi355q
+#endif

@@ -1,0 +1,384 @@
+// mi355q_decode.hip -- incremental decoding of the quantised attention core: a block_fp KV cache and a split-key decode kernel.
+//
+// The reference decodes with `past_key_value`: torch.cat of fp32 K / V (models/llama_quantized/modeling_llama.py:301-306, the
+// same in modeling_opt.py) in front of the core (modeling_llama.py:309-344), whose four block_fp quantisers then see the
+// concatenated tensors of length L.  Here the cache holds what those quantisers make of K and V (layout: mi355q_decode.h):
+//   v [.., L, D]    blocks along D at a fixed key: a key's values are quantised once, when it is appended
+//   k^T [.., D, L]  blocks of 16 consecutive KEYS at a fixed d: the last, open block (L % 16 keys) changes its shared exponents
+//                   with every key -- its fp32 rows stay in a staging area and the block is quantised again on every append
+//                   until it is full (absent keys = the blocking's zero padding: zeros, outside the maximum)
+// and the decode kernels read quantised bf16 only: 2 B per cached value instead of 4 B read + a pack launch per step.
+// Decode, 1 <= M <= 16 queries (the last M positions) against L keys, keys split over S workgroups per head so that a small batch
+// still fills the chip.  The softmax is normalised in fp32 BEFORE the probabilities are quantised (blocks of 16 keys of a query),
+// so row maximum and sum over all L keys must be final first: two phases, no grid-wide barrier, no waiting on other workgroups.
+//   phase A (decode_scores_kernel, grid S x B): scores of the split's key tiles -> workspace, as their MFMA lanes hold them;
+//            the split's per-query (max, sum of exp(x - max)) over VISIBLE keys (key < L and inside the causal horizon)
+//   phase B (decode_pv_kernel, grid S x B): the S statistics combined in split order; probabilities per 16-key block, quantised,
+//            times the V fragments -> the split's partial output (S == 1: the output itself)
+//   phase C (decode_sum_kernel, grid B): partial outputs summed in split order -- the same inputs give the same bits every run.
+// MFMA roles as in mi355q_attention.hip (v_mfma_f32_16x16x32_bf16, the queries are the 16 columns): a lane's own values of the score
+// tiles 2 s, 2 s + 1 are the slots of its P fragment, and vq is stored with the same slot order.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mi355q.h"
+#include "mi355q_internal.h"
+#include "mi355q_quant_dev.h"
+#include "mi355q_attn_dev.h"
+#include "mi355q_decode.h"
+
+namespace mi355q {
+
+// ---- append ---------------------------------------------------------------------------------------------------------------
+struct AppendArgs {
+    KvCache c;
+    const float* k;
+    const float* v;
+    long long ksb, kst, vsb, vst;
+    long long L, n, t0, t1;     // key tiles touched: t0 = L / 16 .. t1 = (L + n - 1) / 16
+    int kblocks;
+};
+
+__global__ __launch_bounds__(256) void kv_append_kernel(const QuantArgs ak, const QuantArgs av, const AppendArgs a) {
+    const int tid = threadIdx.x, D = a.c.D;
+    const long long b = blockIdx.y, NTC = a.c.C >> 4, NPC = (a.c.C + 31) >> 5;
+    if ((int)blockIdx.x < a.kblocks) {
+        // K: thread (tile, d) walks the 16 keys of its block: staged rows in front of L, new rows, zeros behind L + n
+        const int per = 256 / D, sub = tid / D, d = tid - sub * D;
+        const long long t = a.t0 + (long long)blockIdx.x * per + sub;
+        if (sub >= per || t > a.t1) return;
+        float* __restrict__ stg = a.c.stage + b * 16 * D + d;
+        float x[16];
+        float bmax = 0.f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const long long key = t * 16 + e;
+            float val = 0.f;
+            if (key >= a.L && key < a.L + a.n) val = a.k[b * a.ksb + (key - a.L) * a.kst + d];
+            else if (key < a.L) val = stg[e * D];
+            x[e] = val;
+            bmax = fmaxf(bmax, fabsf(val));
+        }
+        // the open tile's rows for the next append, when the tile that reads staged rows is the one that writes them (the usual
+        // decode step); an append that runs into a later tile leaves them to kv_stage_kernel, behind this launch
+        if (a.t0 == a.t1) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const long long key = t * 16 + e;
+                if (key >= a.L && key < a.L + a.n) stg[e * D] = x[e];
+            }
+        }
+        const int mbits = (int)__builtin_log2f(ak.shift);
+        const int p = at_block_exponent_mem(bmax, ak);
+        const int c = d >> 5, g = (d >> 3) & 3, j = d & 7;
+        uint16_t* __restrict__ dst = a.c.kq + ((b * NTC + t) * (D >> 5) + c) * 512 + 16 * g * 8 + j;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const float q = bmax != 0.f ? at_quant(x[e], mbits - p, p - mbits, ak.mant_max) + 0.0f : 0.f;   // (+ 0: see the layout note)
+            dst[e * 8] = (uint16_t)(pack_bf16(q, 0.f) & 0xFFFFu);
+        }
+    } else {
+        // V: thread (new key, 16-d block) quantises one block
+        const int DT = D >> 4;
+        const long long item = ((long long)blockIdx.x - a.kblocks) * 256 + tid;
+        if (item >= a.n * DT) return;
+        const long long kl = item / DT, key = a.L + kl;
+        const int dt = (int)(item - kl * DT);
+        float x[16];
+        float bmax = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float4 f = *reinterpret_cast<const float4*>(a.v + b * a.vsb + kl * a.vst + dt * 16 + 4 * i);
+            x[4 * i] = f.x; x[4 * i + 1] = f.y; x[4 * i + 2] = f.z; x[4 * i + 3] = f.w;
+            bmax = fmaxf(bmax, fmaxf(fmaxf(fabsf(f.x), fabsf(f.y)), fmaxf(fabsf(f.z), fabsf(f.w))));
+        }
+        const int mbits = (int)__builtin_log2f(av.shift);
+        const int p = at_block_exponent_mem(bmax, av);
+        const long long s = key >> 5;
+        const int h = (int)(key >> 4) & 1, g = (int)(key & 15) >> 2, j = 4 * h + (int)(key & 3);
+        uint16_t* __restrict__ dst = a.c.vq + ((b * NPC + s) * DT + dt) * 512 + 16 * g * 8 + j;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const float q = bmax != 0.f ? at_quant(x[c], mbits - p, p - mbits, av.mant_max) + 0.0f : 0.f;
+            dst[c * 8] = (uint16_t)(pack_bf16(q, 0.f) & 0xFFFFu);
+        }
+    }
+}
+
+// the new open tile's fp32 rows -> staging, for an append that crossed a tile boundary: they overlap the rows tile t0 of
+// kv_append_kernel reads, so they are written behind it.  grid (rows, B), D threads.
+__global__ void kv_stage_kernel(const AppendArgs a) {
+    const long long b = blockIdx.y, key = a.t1 * 16 + blockIdx.x;      // (>= L: tile t1 lies behind tile t0 = L / 16)
+    a.c.stage[(b * 16 + blockIdx.x) * a.c.D + threadIdx.x] = a.k[b * a.ksb + (key - a.L) * a.kst + threadIdx.x];
+}
+
+int launch_kv_append(const KvCache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
+                     long long kst, long long vsb, long long vst, long long L, long long n, hipStream_t st) {
+    AppendArgs a{};
+    a.c = c; a.k = k; a.v = v;
+    a.ksb = ksb; a.kst = kst; a.vsb = vsb; a.vst = vst;
+    a.L = L; a.n = n; a.t0 = L / 16; a.t1 = (L + n - 1) / 16;
+    const int per = 256 / c.D;
+    const long long kblocks = (a.t1 - a.t0 + 1 + per - 1) / per, vblocks = (n * (c.D / 16) + 255) / 256;
+    if (kblocks + vblocks > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
+    a.kblocks = (int)kblocks;
+    hipLaunchKernelGGL(kv_append_kernel, dim3((unsigned)(kblocks + vblocks), (unsigned)c.B), dim3(256), 0, st, ak, av, a);
+    const unsigned open_rows = (unsigned)((L + n) % 16);                // (0: tile t1 is full, nothing to stage)
+    if (a.t1 > a.t0 && open_rows) hipLaunchKernelGGL(kv_stage_kernel, dim3(open_rows, (unsigned)c.B), dim3(c.D), 0, st, a);
+    return (int)hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void kv_decode_fp32_kernel(const KvCache c, float* __restrict__ k_out, float* __restrict__ v_out,
+                                                             long long L) {
+    const int D = c.D;
+    const long long b = blockIdx.y, NTC = c.C >> 4, NPC = (c.C + 31) >> 5;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= L * D) return;
+    const long long key = idx / D;
+    const int d = (int)(idx - key * D);
+    const uint16_t kb = c.kq[((b * NTC + (key >> 4)) * (D >> 5) + (d >> 5)) * 512 + ((key & 15) + 16 * ((d >> 3) & 3)) * 8 + (d & 7)];
+    const int h = (int)(key >> 4) & 1, g = (int)(key & 15) >> 2, j = 4 * h + (int)(key & 3);
+    const uint16_t vb = c.vq[((b * NPC + (key >> 5)) * (D >> 4) + (d >> 4)) * 512 + ((d & 15) + 16 * g) * 8 + j];
+    k_out[(b * L + key) * D + d] = __uint_as_float((unsigned)kb << 16);
+    v_out[(b * L + key) * D + d] = __uint_as_float((unsigned)vb << 16);
+}
+
+int launch_kv_decode_fp32(const KvCache& c, float* k_out, float* v_out, long long L, hipStream_t st) {
+    const long long blocks = (L * c.D + 255) / 256;
+    if (blocks > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
+    hipLaunchKernelGGL(kv_decode_fp32_kernel, dim3((unsigned)blocks, (unsigned)c.B), dim3(256), 0, st, c, k_out, v_out, L);
+    return (int)hipGetLastError();
+}
+
+// ---- decode ---------------------------------------------------------------------------------------------------------------
+int decode_splits(long long B, long long L, long long D, int override) {
+    (void)D;
+    if (B < 1 || L < 1) return 1;
+    const long long NP = (L + 31) / 32;
+    // enough workgroups for two a compute unit (256 of them) at at least two key pairs each; never more than 64 statistics to combine
+    long long want = override > 0 ? override : (512 + B - 1) / B;
+    if (override <= 0 && want > NP / 2) want = NP / 2;
+    if (want > 64) want = 64;
+    if (want > NP) want = NP;
+    if (want < 1) want = 1;
+    const long long pps = (NP + want - 1) / want;
+    return (int)((NP + pps - 1) / pps);
+}
+
+size_t decode_workspace_bytes(long long B, long long L, long long D, int splits) {
+    if (B <= 0 || L <= 0 || D <= 0) return 0;
+    const long long S = decode_splits(B, L, D, splits), NT = (L + 15) / 16;
+    return (size_t)(B * NT * 256 + B * S * 32 + B * S * (D / 16) * 256) * 4;
+}
+
+// this lane's horizon: the last key its query (column c16 of the MFMA tiles) sees
+__device__ __forceinline__ long long dec_horizon(const DecodeArgs& g, long long qrow) {
+    return g.causal ? g.L - g.M + qrow : g.L - 1;
+}
+
+template <int DC>
+__global__ __launch_bounds__(256) void decode_scores_kernel(const QuantArgs aq, const DecodeArgs g) {
+    __shared__ float sm_[4][64], sl_[4][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c16 = lane & 15, lg = lane >> 4;
+    const long long b = blockIdx.y, s = blockIdx.x;
+    const long long qrow = min((long long)c16, g.M - 1);
+    // Q fragments, quantised in registers (mi355q_attention.hip): lane (query c16, g) holds d = 32 c + 8 g .. + 7
+    bf16x8 qf[DC];
+    {
+        const int mb = (int)__builtin_log2f(aq.shift);
+        const float* __restrict__ qp = g.q + b * g.qsb + qrow * g.qsm;
+#pragma unroll
+        for (int c = 0; c < DC; ++c) {
+            float4 lo = *reinterpret_cast<const float4*>(qp + 32 * c + 8 * lg);
+            float4 hi = *reinterpret_cast<const float4*>(qp + 32 * c + 8 * lg + 4);
+            if (g.q_scale != 0.f) {
+                lo.x *= g.q_scale; lo.y *= g.q_scale; lo.z *= g.q_scale; lo.w *= g.q_scale;
+                hi.x *= g.q_scale; hi.y *= g.q_scale; hi.z *= g.q_scale; hi.w *= g.q_scale;
+            }
+            float bmax = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fmaxf(fabsf(lo.z), fabsf(lo.w))),
+                               fmaxf(fmaxf(fabsf(hi.x), fabsf(hi.y)), fmaxf(fabsf(hi.z), fabsf(hi.w))));
+            bmax = at_max2_16(bmax);
+            const int p = at_block_exponent_mem(bmax, aq);
+            const int up = mb - p, dn = p - mb;
+            uint4 pk;
+            pk.x = pack_bf16(at_quant(lo.x, up, dn, aq.mant_max), at_quant(lo.y, up, dn, aq.mant_max));
+            pk.y = pack_bf16(at_quant(lo.z, up, dn, aq.mant_max), at_quant(lo.w, up, dn, aq.mant_max));
+            pk.z = pack_bf16(at_quant(hi.x, up, dn, aq.mant_max), at_quant(hi.y, up, dn, aq.mant_max));
+            pk.w = pack_bf16(at_quant(hi.z, up, dn, aq.mant_max), at_quant(hi.w, up, dn, aq.mant_max));
+            qf[c] = __builtin_bit_cast(bf16x8, pk);
+        }
+    }
+    const long long kvis = dec_horizon(g, qrow);
+    const float scale_inv = g.scale_div != 0.f ? 1.0f / g.scale_div : 0.f;
+    const long long t_lo = 2 * g.pps * s, t_hi = min(g.NT, t_lo + 2 * g.pps);
+    const uint16_t* __restrict__ kfb = g.kq + b * g.NTC * DC * 512 + lane * 8;
+    float* __restrict__ sc = g.scores + b * g.NT * 256 + lane * 4;
+    // running (max, sum of exp(x - max)) of this lane's visible scores, re-based when the maximum moves
+    float m_run = -INFINITY, l_run = 0.f;
+    for (long long t = t_lo + wave; t < t_hi; t += 4) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < DC; ++c)
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(kfb + (t * DC + c) * 512), qf[c], acc, 0, 0, 0);
+        if (g.scale_div != 0.f) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[e] = at_div(acc[e], g.scale_div, scale_inv);
+        }
+        *reinterpret_cast<float4*>(sc + t * 256) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        const long long key0 = t * 16 + 4 * lg;
+        float tm = -INFINITY;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (key0 + e <= kvis) tm = fmaxf(tm, acc[e]);
+        if (tm > m_run) {
+            l_run = m_run == -INFINITY ? 0.f : l_run * at_exp_neg(m_run - tm);
+            m_run = tm;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (key0 + e <= kvis) l_run += at_exp_neg(acc[e] - m_run);
+    }
+    sm_[wave][lane] = m_run;
+    sl_[wave][lane] = l_run;
+    __syncthreads();
+    if (tid < 16) {
+        // the 16 (wave, lane group) pairs of query tid, in a fixed order
+        float mx = -INFINITY;
+        for (int w = 0; w < 4; ++w)
+            for (int q4 = 0; q4 < 4; ++q4) mx = fmaxf(mx, sm_[w][tid + 16 * q4]);
+        float sum = 0.f;
+        for (int w = 0; w < 4; ++w)
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const float m = sm_[w][tid + 16 * q4];
+                if (m != -INFINITY) sum += sl_[w][tid + 16 * q4] * at_exp_neg(m - mx);
+            }
+        float* st = g.stats + ((b * g.S + s) * 16 + tid) * 2;
+        st[0] = mx;
+        st[1] = sum;
+    }
+}
+
+template <int DC>
+__global__ __launch_bounds__(256) void decode_pv_kernel(const QuantArgs ap, const DecodeArgs g) {
+    constexpr int DT = DC * 2;
+    __shared__ f32x4 red[4][DT][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c16 = lane & 15, lg = lane >> 4;
+    const long long b = blockIdx.y, s = blockIdx.x;
+    const long long qrow = min((long long)c16, g.M - 1);
+    const long long kvis = dec_horizon(g, qrow);
+    // the row's statistics over all L keys: the S splits in split order (every query sees key 0: the first split's max is finite)
+    const float* __restrict__ stp = g.stats + (b * g.S * 16 + c16) * 2;
+    float row_max = -INFINITY;
+    for (int i = 0; i < g.S; ++i) row_max = fmaxf(row_max, stp[i * 32]);
+    float row_sum = 0.f;
+    for (int i = 0; i < g.S; ++i) {
+        const float m = stp[i * 32];
+        if (m != -INFINITY) row_sum += stp[i * 32 + 1] * at_exp_neg(m - row_max);
+    }
+    const float row_inv = 1.0f / row_sum;
+    const int mbp = (int)__builtin_log2f(ap.shift);
+    const long long p_lo = g.pps * s, p_hi = min(g.NP, p_lo + g.pps);
+    const uint16_t* __restrict__ vfb = g.vq + b * g.NPC * DT * 512 + lane * 8;
+    const float* __restrict__ sc = g.scores + b * g.NT * 256 + lane * 4;
+    f32x4 o[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (long long pr_i = p_lo + wave; pr_i < p_hi; pr_i += 4) {
+        uint4 vb[DT];
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) vb[dt] = *reinterpret_cast<const uint4*>(vfb + (pr_i * DT + dt) * 512);
+        float pq[8];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const long long t = 2 * pr_i + h;                  // (uniform over the wave; the last pair's second tile may not exist)
+            float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (t < g.NT) x = *reinterpret_cast<const float4*>(sc + t * 256);
+            const float xs[4] = {x.x, x.y, x.z, x.w};
+            const long long key0 = t * 16 + 4 * lg;
+            float pr[4];
+            float bmax = 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                pr[e] = (t < g.NT && key0 + e <= kvis) ? at_div(at_exp_neg(xs[e] - row_max), row_sum, row_inv) : 0.f;
+                bmax = fmaxf(bmax, pr[e]);
+            }
+            bmax = at_max4(bmax);
+            const int p = at_block_exponent_mem(bmax, ap);
+            const float sc_up = __builtin_ldexpf(1.0f, mbp - p), sc_dn = __builtin_ldexpf(1.0f, p - mbp), eps_up = EPS9 * sc_up;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pq[4 * h + e] = at_quant_pos(pr[e], sc_up, eps_up, sc_dn, ap.mant_max);
+        }
+        uint4 pk;
+        pk.x = pack_bf16(pq[0], pq[1]); pk.y = pack_bf16(pq[2], pq[3]);
+        pk.z = pack_bf16(pq[4], pq[5]); pk.w = pack_bf16(pq[6], pq[7]);
+        const bf16x8 pf = __builtin_bit_cast(bf16x8, pk);
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+            o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vb[dt]), pf, o[dt], 0, 0, 0);
+    }
+    // the four waves' partial outputs, summed in wave order
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) red[wave][dt][lane] = o[dt];
+    __syncthreads();
+    for (int dt = wave; dt < DT; dt += 4) {
+        f32x4 sum = red[0][dt][lane];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) sum += red[w][dt][lane];
+        if (g.S == 1) {
+            if (c16 < g.M)
+                *reinterpret_cast<float4*>(g.out + b * g.osb + c16 * g.osm + 16 * dt + 4 * lg) = make_float4(sum[0], sum[1], sum[2], sum[3]);
+        } else {
+            *reinterpret_cast<f32x4*>(g.part + (((b * g.S + s) * DT + dt) * 64 + lane) * 4) = sum;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void decode_sum_kernel(const DecodeArgs g) {
+    const int DT = g.D >> 4;
+    const long long b = blockIdx.x;
+    for (int item = threadIdx.x; item < DT * 64; item += 256) {
+        const int dt = item >> 6, lane = item & 63, c16 = lane & 15, lg = lane >> 4;
+        const float* __restrict__ pp = g.part + ((b * g.S * DT + dt) * 64 + lane) * 4;
+        float4 sum = *reinterpret_cast<const float4*>(pp);
+        for (int s = 1; s < g.S; ++s) {
+            const float4 x = *reinterpret_cast<const float4*>(pp + (long long)s * DT * 256);
+            sum.x += x.x; sum.y += x.y; sum.z += x.z; sum.w += x.w;
+        }
+        if (c16 < g.M) *reinterpret_cast<float4*>(g.out + b * g.osb + c16 * g.osm + 16 * dt + 4 * lg) = sum;
+    }
+}
+
+int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out,
+                                void* workspace, long long M, long long L, int causal, float q_scale, float scale_div,
+                                const long long* strides, int splits, hipStream_t st) {
+    DecodeArgs g{};
+    g.q = q; g.kq = c.kq; g.vq = c.vq; g.out = out;
+    g.M = M; g.L = L; g.D = c.D;
+    g.NT = (L + 15) / 16; g.NP = (L + 31) / 32; g.NTC = c.C / 16; g.NPC = (c.C + 31) / 32;
+    g.S = decode_splits(c.B, L, c.D, splits);
+    g.pps = (int)((g.NP + g.S - 1) / g.S);
+    g.qsb = strides ? strides[0] : M * c.D; g.qsm = strides ? strides[1] : c.D;
+    g.osb = strides ? strides[2] : M * c.D; g.osm = strides ? strides[3] : c.D;
+    g.causal = causal; g.q_scale = q_scale; g.scale_div = scale_div;
+    g.scores = static_cast<float*>(workspace);
+    g.stats = g.scores + c.B * g.NT * 256;
+    g.part = g.stats + c.B * g.S * 32;
+    const dim3 grid((unsigned)g.S, (unsigned)c.B);
+#define MI355Q_DECODE_GO(DC_)                                                                     \
+    hipLaunchKernelGGL((decode_scores_kernel<DC_>), grid, dim3(256), 0, st, aq, g);               \
+    hipLaunchKernelGGL((decode_pv_kernel<DC_>), grid, dim3(256), 0, st, ap, g)
+    switch (c.D / 32) {
+        case 1: MI355Q_DECODE_GO(1); break;
+        case 2: MI355Q_DECODE_GO(2); break;
+        case 3: MI355Q_DECODE_GO(3); break;
+        case 4: MI355Q_DECODE_GO(4); break;
+        default: return MI355Q_E_UNSUPPORTED;
+    }
+#undef MI355Q_DECODE_GO
+    if (g.S > 1) hipLaunchKernelGGL(decode_sum_kernel, dim3((unsigned)c.B), dim3(256), 0, st, g);
+    return (int)hipGetLastError();
+}
+
+}  // namespace mi355q

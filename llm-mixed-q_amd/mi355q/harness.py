@@ -110,6 +110,17 @@ class _Attention(nn.Module):
         o = o.view(B, nh, T, self.hd).transpose(1, 2).reshape(B, T, nh * self.hd)
         return out(o)
 
+    def decode(self, x, state, idx):
+        """the new tokens' attention against the cache of layer `idx` (DecodeState): the reference's `past_key_value` branch
+        (modeling_opt.py:208-245) -- projections of the new tokens only, keys and values appended, then the core"""
+        if getattr(self, "mi355q_head_shard", None) is not None:
+            raise NotImplementedError("incremental decoding of head-sharded models")
+        B, n, _ = x.shape
+        heads = lambda t: t.view(B, n, self.nh, self.hd).transpose(1, 2)
+        q, k, v = heads(self.q_proj(x) * self.scaling), heads(self.k_proj(x)), heads(self.v_proj(x))
+        o = state.attend(idx, q, k, v, self.qc["bmm_0"], self.qc["bmm_1"], None, "bmm")
+        return self.out_proj(o.transpose(1, 2).reshape(B, n, self.nh * self.hd))
+
 
 class _DecoderLayer(nn.Module):
     def __init__(self, cfg: TinyOPTConfig, qc: dict):
@@ -151,6 +162,12 @@ class _DecoderLayer(nn.Module):
         else:
             h = h + self.fc2(F.relu(self.fc1(self.final_layer_norm(h))))
         return h.view(shape)
+
+    def decode(self, x, state, idx):
+        x = x + self.self_attn.decode(self.self_attn_layer_norm(x), state, idx)
+        shape = x.shape
+        h = x.reshape(-1, shape[-1])
+        return (h + self.fc2(F.relu(self.fc1(self.final_layer_norm(h))))).view(shape)
 
 
 class TinyOPTForCausalLM(nn.Module):
@@ -195,7 +212,11 @@ class TinyOPTForCausalLM(nn.Module):
             out[k if k.startswith("lm_head") else "model.decoder." + k] = v
         return out
 
-    def forward(self, input_ids, labels=None):
+    def forward(self, input_ids, labels=None, cache=None):
+        """`cache` (a DecodeState): input_ids holds only the NEW tokens, whose positions start at the cache's length; returns their
+        logits (the prompt goes through the same call).  None: the whole sequence, as ever."""
+        if cache is not None:
+            return _forward_cached(self, input_ids, labels, cache)
         B, T = input_ids.shape
         pos = torch.arange(T, device=input_ids.device)
         x = self.embed_tokens(input_ids) + self.embed_positions(pos)[None]
@@ -302,6 +323,19 @@ class _LlamaAttention(nn.Module):
             o = get_quantized_func("matmul", c1)(p, v, config=c1)
         return out(o.transpose(1, 2).reshape(B, T, nh * self.hd))
 
+    def decode(self, x, state, idx, position_ids):
+        """the new tokens' attention against the cache of layer `idx` (modeling_llama.py:282-306): the rotary embedding through the
+        registry's function at the new positions, the TURNED k into the cache as in the reference, then the core"""
+        if getattr(self, "mi355q_head_shard", None) is not None:
+            raise NotImplementedError("incremental decoding of head-sharded models")
+        B, n, _ = x.shape
+        heads = lambda t: t.view(B, n, self.nh, self.hd).transpose(1, 2)
+        q, k, v = heads(self.q_proj(x)), heads(self.k_proj(x)), heads(self.v_proj(x))
+        rc, end = self.qc["rotary_positional_encoding"], state.length + n
+        q, k = get_quantized_func("rotary_positional_encoding", rc)(q, k, self.cos[:, :, :end], self.sin[:, :, :end], position_ids, config=rc)
+        o = state.attend(idx, q, k, v, self.qc["matmul_0"], self.qc["matmul_1"], math.sqrt(self.hd), "matmul")
+        return self.o_proj(o.transpose(1, 2).reshape(B, n, self.nh * self.hd))
+
 
 class _LlamaLayer(nn.Module):
     def __init__(self, cfg: TinyLlamaConfig, qc: dict):
@@ -342,6 +376,11 @@ class _LlamaLayer(nn.Module):
             return self.down_proj.forward_after(gate, "silu_mul", up, residual=x) if fres else x + self.down_proj.forward_after(gate, "silu_mul", up)
         return x + self.down_proj(F.silu(gate) * up)                      # (modeling_llama.py:208-240)
 
+    def decode(self, x, state, idx, position_ids):
+        x = x + self.self_attn.decode(self.input_layernorm(x), state, idx, position_ids)
+        h = self.post_attention_layernorm(x)
+        return x + self.down_proj(F.silu(self.gate_proj(h)) * self.up_proj(h))
+
 
 class TinyLlamaForCausalLM(nn.Module):
     def __init__(self, cfg: TinyLlamaConfig, quant_config: dict):
@@ -377,7 +416,10 @@ class TinyLlamaForCausalLM(nn.Module):
             out[k if k.startswith("lm_head") else "model." + k] = v.detach()
         return out
 
-    def forward(self, input_ids, labels=None):
+    def forward(self, input_ids, labels=None, cache=None):
+        """`cache` (a DecodeState): see TinyOPTForCausalLM.forward"""
+        if cache is not None:
+            return _forward_cached(self, input_ids, labels, cache)
         B, T = input_ids.shape
         position_ids = torch.arange(T, device=input_ids.device)[None].expand(B, T)
         x = self.embed_tokens(input_ids)
@@ -390,6 +432,116 @@ class TinyLlamaForCausalLM(nn.Module):
         if labels is not None:
             loss = F.cross_entropy(logits[:, :-1].reshape(-1, logits.shape[-1]), labels[:, 1:].reshape(-1))
         return logits, loss
+
+
+# ---- incremental decoding ---------------------------------------------------------------------------------------------------
+class DecodeState:
+    """One cache per layer and the current length, for `model(new_ids, cache=state)`.
+    mode "block_fp": ops.KVCache + the split-key decode kernel -- both attention products block_fp [1,16] with widths <= 9 and a
+        head_dim the kernel takes, else ValueError here, naming the reason.
+    mode "fp32": the reference's literal route for ANY arithmetic (modeling_llama.py:301-344): torch.cat of fp32 K / V per layer, the
+        products through the registry's functions, the causal mask [n, L] with the offset of modeling_llama.py:53-79."""
+
+    def __init__(self, model, batch: int, capacity: int, mode: str = "block_fp"):
+        from .quantize.quantized_functions import decode_cache_params
+        if mode not in ("block_fp", "fp32"):
+            raise ValueError(f"DecodeState: mode {mode!r} is neither 'block_fp' nor 'fp32'")
+        attns = [layer.self_attn for layer in model.layers]
+        if any(getattr(a, "mi355q_head_shard", None) is not None for a in attns):
+            raise NotImplementedError("incremental decoding of head-sharded models")
+        self.mode, self.batch, self.length = mode, int(batch), 0
+        self.capacity = (int(capacity) + 15) // 16 * 16
+        if self.capacity > model.cfg.max_positions + 15:
+            raise ValueError(f"DecodeState: capacity {capacity} exceeds the model's {model.cfg.max_positions} positions")
+        self.kv = [None] * len(attns)
+        if mode == "block_fp":
+            dev = next(model.parameters()).device
+            for i, a in enumerate(attns):
+                c0, c1 = (a.qc["bmm_0"], a.qc["bmm_1"]) if "bmm_0" in a.qc else (a.qc["matmul_0"], a.qc["matmul_1"])
+                try:
+                    qk, pv = decode_cache_params(c0, c1, a.hd)
+                except ValueError as e:
+                    raise ValueError(f"DecodeState(mode='block_fp'), layer {i}: {e}") from None
+                self.kv[i] = ops.KVCache(self.batch * a.nh, self.capacity, a.hd, qk, pv, dev)
+
+    def reset(self) -> None:
+        self.length = 0
+        for i, c in enumerate(self.kv):
+            if self.mode == "block_fp":
+                c.reset()
+            else:
+                self.kv[i] = None
+
+    def attend(self, idx, q, k, v, c0, c1, scale_div, style):
+        """q, k, v [B, heads, n, hd] of the new tokens (q scaled / turned already) -> attention output [B, heads, n, hd]"""
+        B, nh, n, hd = q.shape
+        if self.length + n > self.capacity:
+            raise ValueError(f"DecodeState: {self.length} + {n} tokens exceed the capacity {self.capacity}")
+        if self.mode == "block_fp":
+            cache = self.kv[idx]
+            assert cache.length == self.length
+            if self.length and n > ops.DECODE_MAX_QUERIES:      # (before the append: a refused call leaves every layer's cache as it was)
+                raise NotImplementedError(f"{n} new tokens behind a non-empty block_fp cache (at most {ops.DECODE_MAX_QUERIES} a call)")
+            cache.append(k, v)
+            if self.length == 0:
+                # the prompt's own queries against the prompt: the existing attention function (M = n)
+                return get_quantized_func("attention", c1)(q, k, v, c0, c1, causal=True, scale_div=scale_div).reshape(B, nh, n, hd)
+            return get_quantized_func("attention_decode", c1)(q, cache, c0, c1, causal=True, scale_div=scale_div).reshape(B, nh, n, hd)
+        if self.kv[idx] is not None:
+            k, v = torch.cat([self.kv[idx][0], k], dim=2), torch.cat([self.kv[idx][1], v], dim=2)
+        self.kv[idx] = (k, v)
+        L = k.shape[2]
+        if style == "bmm":
+            fold = lambda t: t.reshape(B * nh, t.shape[2], hd)
+            q, k, v = fold(q), fold(k), fold(v)
+        w = get_quantized_func(style, c0)(q, k.transpose(-1, -2), config=c0)
+        if scale_div:
+            w = w / scale_div
+        mask = torch.full((n, L), torch.finfo(w.dtype).min, device=w.device).triu(1 + L - n)
+        w = torch.max(w + mask, w.new_full((), torch.finfo(w.dtype).min))
+        p = F.softmax(w, dim=-1, dtype=torch.float32).to(q.dtype)
+        return get_quantized_func(style, c1)(p, v, config=c1).view(B, nh, n, hd)
+
+
+def _forward_cached(model, input_ids, labels, state: DecodeState):
+    if labels is not None:
+        raise ValueError("forward(cache=...): labels belong to the full forward")
+    B, n = input_ids.shape
+    if B != state.batch:
+        raise ValueError(f"forward(cache=...): batch {B}, the cache was made for {state.batch}")
+    if state.length + n > model.cfg.max_positions:
+        raise ValueError(f"forward(cache=...): {state.length} + {n} tokens exceed the model's {model.cfg.max_positions} positions")
+    pos = torch.arange(state.length, state.length + n, device=input_ids.device)
+    if isinstance(model, TinyOPTForCausalLM):
+        x = model.embed_tokens(input_ids) + model.embed_positions(pos)[None]
+        for i, layer in enumerate(model.layers):
+            x = layer.decode(x, state, i)
+        x = model.final_layer_norm(x)
+    else:
+        position_ids = pos[None].expand(B, n).contiguous()
+        x = model.embed_tokens(input_ids)
+        for i, layer in enumerate(model.layers):
+            x = layer.decode(x, state, i, position_ids)
+        x = model.norm(x)
+    state.length += n
+    return fp32_linear(x, model.lm_head, model.mi355q_lm_head), None
+
+
+@torch.no_grad()
+def generate(model, prompt_ids, new_tokens: int, mode: str = "block_fp"):
+    """greedy decoding: the prompt in one cached call, then one token a call.  Returns (ids [B, prompt + new_tokens], logits
+    [B, new_tokens, vocab]: the logits each new token was picked from)."""
+    B, T = prompt_ids.shape
+    state = DecodeState(model, B, T + new_tokens, mode)
+    ids, steps = prompt_ids, []
+    logits = model(prompt_ids, cache=state)[0][:, -1]
+    for i in range(new_tokens):
+        steps.append(logits)
+        tok = logits.argmax(-1, keepdim=True)
+        ids = torch.cat([ids, tok], dim=1)
+        if i + 1 < new_tokens:
+            logits = model(tok, cache=state)[0][:, -1]
+    return ids, torch.stack(steps, dim=1)
 
 
 @torch.no_grad()

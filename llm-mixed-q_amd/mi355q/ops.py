@@ -1425,6 +1425,164 @@ def bfp_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, qk_params, 
     return out if tiled is None else TiledBf16(tiled, M, B * D)
 
 
+# ---- incremental decoding: block_fp KV cache + split-key decode attention (csrc/mi355q_decode.hip) ----------------------------
+DECODE_MAX_QUERIES = 16          # rows of q one decode call takes (the 16 columns of the MFMA tiles)
+_DECODE_WS = _StreamCache(8)
+_DECODE_MAX_SPLITS = 64
+
+
+def _decode_params(params, what):
+    p = tuple(params)
+    if len(p) != 6:
+        raise ValueError(f"{what}: (x width, x exponent width, x exponent bias, y width, y exponent width, y exponent bias) expected")
+    for i in (0, 3):
+        if not 2 <= int(p[i]) <= 9:
+            raise ValueError(f"{what}: width {p[i]} outside 2 .. 9 (a quantised value must be exact in bf16)")
+        if not 1 <= int(p[i + 1]) <= 8:
+            raise ValueError(f"{what}: exponent width {p[i + 1]} outside 1 .. 8")
+    return p
+
+
+def decode_splits(B: int, L: int, D: int, splits: int = None) -> int:
+    """workgroups per head that share the L keys of a decode call: a pure function of (B, L, D) -- or `splits`, clamped to
+    1 .. ceil(L / 32) and evened out so that no split is empty"""
+    return int(_lib.load_library().mi355q_bfp_attention_decode_splits(int(B), int(L), int(D), int(splits or 0)))
+
+
+class KVCache:
+    """What the reference's `past_key_value` (torch.cat of fp32 K / V, modeling_llama.py:301-306) becomes under the block_fp [1,16]
+    quantisers of bmm_0 / bmm_1: per b = batch x head, quantised K and V as bf16 in the decode kernel's fragment order, plus the
+    fp32 rows of the open 16-key block of K^T, which is quantised again on every append until it is full (include/mi355q.h).
+    qk_params / pv_params as for bfp_attention; `length` lives on the host."""
+
+    def __init__(self, B: int, capacity: int, D: int, qk_params, pv_params, device):
+        import ctypes
+        B, capacity, D = int(B), int(capacity), int(D)
+        if not 1 <= B <= 65535:
+            raise ValueError(f"KVCache: B = {B} outside 1 .. 65535")
+        if D < 32 or D % 32 != 0 or D > ATTENTION_MAX_HEAD_DIM:
+            raise ValueError(f"KVCache: head_dim {D} is not a multiple of 32 up to {ATTENTION_MAX_HEAD_DIM}")
+        if capacity < 16 or capacity % 16 != 0:
+            raise ValueError(f"KVCache: capacity {capacity} is not a positive multiple of 16")
+        self.qk_params = _decode_params(qk_params, "KVCache qk_params")
+        self.pv_params = _decode_params(pv_params, "KVCache pv_params")
+        self.B, self.capacity, self.D, self.device = B, capacity, D, torch.device(device)
+        self.length = 0
+        nb = [ctypes.c_int64(0) for _ in range(3)]
+        _lib.check(_lib.load_library().mi355q_bfp_kv_cache_bytes(B, capacity, D, *[ctypes.addressof(n) for n in nb]), "mi355q_bfp_kv_cache_bytes")
+        # (zeroed: a V slot no key has reached meets a probability of exactly 0 and must be finite)
+        self.kq, self.vq, self.stage = (torch.zeros(n.value, dtype=torch.uint8, device=self.device) for n in nb)
+        self._pa = (ctypes.c_int32 * 6)(*[_default_bias(p) if i % 3 == 2 else int(p) for i, p in enumerate(self.qk_params)])
+        self._pb = (ctypes.c_int32 * 6)(*[_default_bias(p) if i % 3 == 2 else int(p) for i, p in enumerate(self.pv_params)])
+
+    def reset(self) -> None:
+        # nothing to clear: append rewrites every K tile it touches in full, and a V slot behind `length` only ever meets a
+        # probability of exactly 0 -- what it needs is to be finite, which zeroed storage and older quantised values both are
+        self.length = 0
+
+    def _rows(self, t, what):
+        if not isinstance(t, torch.Tensor) or t.ndim < 3:
+            raise ValueError(f"KVCache.append: {what} must be a tensor [..., n, D]")
+        if t.shape[-1] != self.D or t.shape[:-2].numel() != self.B:
+            raise ValueError(f"KVCache.append: {what} {tuple(t.shape)} does not match B = {self.B}, D = {self.D}")
+        return t
+
+    def append(self, k: torch.Tensor, v: torch.Tensor) -> None:
+        """n >= 1 new fp32 rows k, v [B, n, D] (or [1, H, n, D] head views, read in place) become keys length .. length + n - 1"""
+        import ctypes
+        k, v = self._rows(k, "k"), self._rows(v, "v")
+        n = k.shape[-2]
+        if v.shape[-2] != n or n < 1:
+            raise ValueError(f"KVCache.append: {n} rows of k, {v.shape[-2]} of v (at least one, and as many of each)")
+        if self.length + n > self.capacity:
+            raise ValueError(f"KVCache.append: {self.length} + {n} keys exceed the capacity {self.capacity}")
+        for t in (k, v):
+            if not t.is_cuda or t.dtype != torch.float32 or t.device != self.device:
+                raise ValueError(f"KVCache.append: fp32 tensors on {self.device} only (got {t.dtype} on {t.device}); there is no CPU fallback")
+        k3, ksb, kst = _as_heads_view(k)
+        v3, vsb, vst = _as_heads_view(v)
+        strides = (ctypes.c_int64 * 4)(ksb, kst, vsb, vst)
+        with _on_device(self.device):
+            rc = _lib.load_library().mi355q_bfp_kv_append(_ptr(self.kq), _ptr(self.vq), _ptr(self.stage), _ptr(k3), _ptr(v3), self.B, self.capacity,
+                                                          self.D, self.length, n, ctypes.addressof(self._pa), ctypes.addressof(self._pb),
+                                                          ctypes.addressof(strides), _stream_ptr(self.device))
+        _lib.check(rc, "mi355q_bfp_kv_append")
+        self.length += n
+
+    def dequantised(self):
+        """the cache's quantised K and V as fp32 [B, length, D] (tests, debugging)"""
+        if not self.kq.is_cuda:
+            raise ValueError("KVCache.dequantised: the cache is not on a GPU; there is no CPU fallback")
+        k = torch.empty(self.B, self.length, self.D, dtype=torch.float32, device=self.device)
+        v = torch.empty_like(k)
+        with _on_device(self.device):
+            rc = _lib.load_library().mi355q_bfp_kv_decode_fp32(_ptr(self.kq), _ptr(self.vq), _ptr(k), _ptr(v), self.B, self.capacity, self.D,
+                                                               self.length, _stream_ptr(self.device))
+        _lib.check(rc, "mi355q_bfp_kv_decode_fp32")
+        return k, v
+
+
+def _decode_check(q, cache, splits=None):
+    """the reasons bfp_attention_decode declines (q, cache), None when it takes them; nothing here touches the device"""
+    if not isinstance(cache, KVCache):
+        return "cache is not a KVCache"
+    if not isinstance(q, torch.Tensor) or q.ndim < 3:
+        return "q must be a tensor [..., M, D]"
+    M, D = q.shape[-2:]
+    if not 1 <= M <= DECODE_MAX_QUERIES:
+        return f"M = {M} queries outside 1 .. {DECODE_MAX_QUERIES}"
+    if D != cache.D or q.shape[:-2].numel() != cache.B:
+        return f"q {tuple(q.shape)} does not match the cache's B = {cache.B}, D = {cache.D}"
+    if cache.length < M:
+        return f"{cache.length} cached keys for {M} queries (the queries' own keys are appended first)"
+    if splits is not None and int(splits) < 1:
+        return f"splits = {splits} < 1"
+    if not q.is_cuda or q.dtype != torch.float32 or q.device != cache.device:
+        return f"fp32 tensors on {cache.device} only (got {q.dtype} on {q.device}); there is no CPU fallback"
+    return None
+
+
+def bfp_attention_decode_supported(q, cache) -> bool:
+    return _decode_check(q, cache) is None
+
+
+def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True, scale_div: float = None, q_scale: float = None,
+                         token_major: bool = False, splits: int = None):
+    """The attention core (modeling_llama.py:309-344) for the LAST M <= 16 positions of a sequence whose L = cache.length keys are in
+    `cache` (their own keys included: append first): q [..., M, D] fp32; causal: query i sees keys 0 .. L - M + i, else all L.
+    scale_div / q_scale / token_major as bfp_attention.  Keys are split over `splits` workgroups per head (default: decode_splits);
+    statistics and partial outputs are combined in split order, so equal inputs give equal bits.  No additive mask."""
+    import ctypes
+    why = _decode_check(q, cache, splits)
+    if why is not None:
+        raise ValueError(f"mi355q.bfp_attention_decode: {why}")
+    M, D = q.shape[-2:]
+    q3, qsb, qsm = _as_heads_view(q)
+    B, L, C = cache.B, cache.length, cache.capacity
+    if token_major and q.ndim == 4 and q.shape[0] == 1:
+        H = q.shape[1]
+        out = torch.empty(1, M, H, D, dtype=torch.float32, device=q.device).permute(0, 2, 1, 3)
+        osb, osm = D, H * D
+    else:
+        out = torch.empty(*q.shape, dtype=torch.float32, device=q.device)
+        osb, osm = M * D, D
+    lib = _lib.load_library()
+    sp = _stream_ptr(q.device)
+    key = (q.device.index, sp, B, C, D)
+    ws = _DECODE_WS.get(key)
+    if ws is None:      # (any L <= C, any number of splits: score tiles + statistics + partial outputs)
+        ws = _DECODE_WS.put(key, torch.empty(B * (C // 16) * 1024 + B * _DECODE_MAX_SPLITS * (128 + (D // 16) * 1024), dtype=torch.uint8,
+                                             device=q.device))
+    strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
+    with _on_device(q.device):
+        rc = lib.mi355q_bfp_attention_decode(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), int(bool(causal)), float(q_scale) if q_scale else 0.0,
+                                             float(scale_div) if scale_div else 0.0, _ptr(out), _ptr(ws), B, M, L, C, D,
+                                             ctypes.addressof(cache._pa), ctypes.addressof(cache._pb), ctypes.addressof(strides),
+                                             int(splits or 0), sp)
+    _lib.check(rc, "mi355q_bfp_attention_decode")
+    return out
+
+
 class TiledBf16:
     """quantised activations [rows, cols] as the tiled bf16 operand of the per-block product (block_fp_quantize_bf16_tiled's output with
     its shape): what a producer hands a Linear that runs on that route (`Linear.forward_tiled`)"""

@@ -251,6 +251,36 @@ def attention_block_fp(q, k, v, config_qk, config_pv, mask=None, causal=False, s
     return QUANTIZED_FUNC_MAP[style][config_pv["name"]](p, v, config=config_pv)
 
 
+def decode_cache_params(config_qk, config_pv, head_dim):
+    """(qk_params, pv_params) of ops.KVCache / ops.bfp_attention_decode for the two products' configs -- or ValueError naming why the
+    block_fp cache does not serve them (every other arithmetic decodes on the reference's route: torch.cat of fp32 K / V)"""
+    from ... import ops
+    for which, c in (("first", config_qk), ("second", config_pv)):
+        if c.get("name") != "block_fp" or c.get("bypass", False):
+            raise ValueError(f"block_fp KV cache: the {which} attention product is {'bypassed' if c.get('bypass', False) else c.get('name')}, not block_fp")
+        for side in ("data_in", "weight"):
+            bs = list(c[f"{side}_block_size"])
+            if ops.resolve_blocking([2, 32, 32], bs, True)[3:] != (1, 16):
+                raise ValueError(f"block_fp KV cache: {side}_block_size {bs} of the {which} product is not [1, 16]")
+            if not 2 <= int(c[f"{side}_width"]) <= 9:
+                raise ValueError(f"block_fp KV cache: {side}_width {c[f'{side}_width']} of the {which} product is outside 2 .. 9 (not exact in bf16)")
+    if head_dim % 32 != 0 or head_dim > ops.ATTENTION_MAX_HEAD_DIM:
+        raise ValueError(f"block_fp KV cache: head_dim {head_dim} is not a multiple of 32 up to {ops.ATTENTION_MAX_HEAD_DIM}")
+    par = lambda c: (c["data_in_width"], c["data_in_exponent_width"], c["data_in_exponent_bias"], c["weight_width"],
+                     c["weight_exponent_width"], c["weight_exponent_bias"])
+    return par(config_qk), par(config_pv)
+
+
+def attention_decode_block_fp(q, cache, config_qk, config_pv, causal=True, scale_div=None, q_scale=None):
+    """The attention core for the last M <= 16 positions against an `ops.KVCache` that already holds their keys (what the reference
+    computes from `past_key_value`, modeling_llama.py:301-344): ops.bfp_attention_decode.  An addition to the registry (key
+    "attention_decode"); no additive mask, and no other route -- a cache is block_fp by construction (decode_cache_params)."""
+    from ... import ops
+    decode_cache_params(config_qk, config_pv, q.shape[-1])
+    return ops.bfp_attention_decode(q, cache, causal=causal, scale_div=scale_div, q_scale=q_scale,
+                                    token_major=bool(config_pv.get("mi355q_token_major_output", False)))
+
+
 def _make(arith, style):
     def f(x, y, config):
         return _generic_matmul(x, y, config, arith, style)
@@ -374,4 +404,10 @@ QUANTIZED_FUNC_MAP = {
         "log": apply_rotary_pos_emb_log, "minifloat_denorm": apply_rotary_pos_emb_minifloat_denorm,
         "minifloat_ieee": apply_rotary_pos_emb_minifloat_ieee,
     },
+}
+
+# Additions that take something other than tensors (a KV cache): looked up by get_quantized_func like the map above, kept apart
+# from it because QUANTIZED_FUNC_MAP's keys are pinned to the reference's ops plus the softmax / attention folds.
+EXTRA_FUNC_MAP = {
+    "attention_decode": {"block_fp": attention_decode_block_fp},
 }
