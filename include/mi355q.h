@@ -622,6 +622,32 @@ int mi355q_bfp_attention_decode(const float* q, const void* kq, const void* vq, 
                                 const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides, int32_t splits,
                                 void* stream);
 
+/* Ragged batches: the same three with ONE LENGTH PER CACHE ROW, read by the kernels from device memory -- `lengths`, int32 [B]
+ * (b = batch x head), 4-byte aligned -- so that each sequence of a batch decodes as if it were alone (a left-padded batch would
+ * put pad keys into the 16-key blocks of K^T, where they move the real keys' shared exponent) and one captured graph serves
+ * growing lengths.  The host passes bounds only: they size grids and the workspace; nothing is ever addressed from them, and a
+ * key index >= C is dropped in the kernel.  The lengths are the caller's: no call advances them.
+ *
+ * append: `lengths` holds the lengths BEFORE the append.  Row b takes its first counts[b] (int32 [B] on the device; NULL: n for
+ *   every row; clamped to 0 .. n) of the n input rows as keys lengths[b] .. lengths[b] + counts[b] - 1; input rows behind
+ *   counts[b] are padding and never read; counts[b] == 0 leaves the row's kq, vq and stage untouched.  `max_length` is the
+ *   caller's upper bound on `lengths`: max_length + n > C is MI355Q_E_UNSUPPORTED and nothing is written.
+ * decode_fp32: k_out, v_out [B, max_length, D], zeros behind each row's length (max_length <= C).
+ * decode: `lengths` holds the lengths INCLUDING the M queries' own keys (append first).  Row b's queries are its last M
+ *   positions and see keys 0 .. lengths[b] - 1 (causal: query i sees 0 .. lengths[b] - M + i).  `max_length` (M <= max_length
+ *   <= C) bounds `lengths` (a larger entry is read as max_length); S, the split partition and the workspace are those of
+ *   mi355q_bfp_attention_decode at L = max_length.  A row with lengths[b] < M -- an empty slot -- yields zeros and reads nothing.
+ *   With every length equal to max_length the output is that of mi355q_bfp_attention_decode, bit for bit. */
+int mi355q_bfp_kv_append_ragged(void* kq, void* vq, float* stage, const float* k, const float* v, const int32_t* lengths,
+                                const int32_t* counts, int64_t B, int64_t C, int64_t D, int64_t n, int64_t max_length,
+                                const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides, void* stream);
+int mi355q_bfp_kv_decode_fp32_ragged(const void* kq, const void* vq, const int32_t* lengths, float* k_out, float* v_out, int64_t B,
+                                     int64_t C, int64_t D, int64_t max_length, void* stream);
+int mi355q_bfp_attention_decode_ragged(const float* q, const void* kq, const void* vq, const int32_t* lengths, int32_t causal,
+                                       float q_scale, float scale_div, float* out, void* workspace, int64_t B, int64_t M,
+                                       int64_t max_length, int64_t C, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
+                                       const int64_t* strides, int32_t splits, void* stream);
+
 /* ---- the un-blocked quantisers -------------------------------------------------------------------------------------
  * replaces: quantizers/minifloat.py:134-196 (minifloat_ieee_quantizer: implicit leading one, subnormals at the lowest
  *           exponent), :21-86 (minifloat_denorm_quantizer: no implicit one, exponent ceil(log2(|x| + 1e-9)) per element)

@@ -1103,6 +1103,68 @@ int mi355q_bfp_attention_decode(const float* q, const void* kq, const void* vq, 
                                        splits, static_cast<hipStream_t>(stream));
 }
 
+// ---- ragged batches: the same three with per-row lengths on the device (mi355q_decode.h) ---------------------------------
+int mi355q_bfp_kv_append_ragged(void* kq, void* vq, float* stage, const float* k, const float* v, const int32_t* lengths,
+                                const int32_t* counts, int64_t B, int64_t C, int64_t D, int64_t n, int64_t max_length,
+                                const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides, void* stream) {
+    int rc = decode_cache_shape(B, C, D);
+    if (rc) return rc;
+    if (max_length < 0 || n < 0 || !qk_params || !pv_params) return MI355Q_E_BADARG;
+    if (max_length + n > C) return MI355Q_E_UNSUPPORTED;      // (nothing is written)
+    if (n == 0) return 0;
+    if (!kq || !vq || !stage || !k || !v || !lengths) return MI355Q_E_BADARG;
+    QuantArgs ak{}, av{};
+    if ((rc = decode_quant_args(qk_params + 3, ak)) != 0 || (rc = decode_quant_args(pv_params + 3, av)) != 0) return rc;
+    if ((reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) | reinterpret_cast<uintptr_t>(stage) |
+         reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v)) % 16 ||
+        (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(counts)) % 4)
+        return MI355Q_E_ALIGN;
+    long long st4[4] = {n * D, D, n * D, D};
+    if (strides)
+        for (int i = 0; i < 4; ++i) {
+            if (strides[i] % 4) return MI355Q_E_ALIGN;
+            st4[i] = strides[i];
+        }
+    const KvCache c{static_cast<uint16_t*>(kq), static_cast<uint16_t*>(vq), stage, B, C, (int)D};
+    return launch_kv_append_ragged(c, ak, av, k, v, st4[0], st4[1], st4[2], st4[3], lengths, counts, n, static_cast<hipStream_t>(stream));
+}
+
+int mi355q_bfp_kv_decode_fp32_ragged(const void* kq, const void* vq, const int32_t* lengths, float* k_out, float* v_out, int64_t B,
+                                     int64_t C, int64_t D, int64_t max_length, void* stream) {
+    const int rc = decode_cache_shape(B, C, D);
+    if (rc) return rc;
+    if (max_length < 0 || max_length > C) return MI355Q_E_BADARG;
+    if (max_length == 0) return 0;
+    if (!kq || !vq || !k_out || !v_out || !lengths) return MI355Q_E_BADARG;
+    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
+    return launch_kv_decode_fp32(c, k_out, v_out, max_length, static_cast<hipStream_t>(stream), lengths);
+}
+
+int mi355q_bfp_attention_decode_ragged(const float* q, const void* kq, const void* vq, const int32_t* lengths, int32_t causal,
+                                       float q_scale, float scale_div, float* out, void* workspace, int64_t B, int64_t M,
+                                       int64_t max_length, int64_t C, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
+                                       const int64_t* strides, int32_t splits, void* stream) {
+    if (M < 0 || max_length < 0 || splits < 0) return MI355Q_E_BADARG;
+    int rc = decode_cache_shape(B, C, D);
+    if (rc) return rc;
+    if (M < 1 || M > 16 || max_length < M) return MI355Q_E_UNSUPPORTED;
+    if (max_length > C || !q || !kq || !vq || !lengths || !out || !workspace || !qk_params || !pv_params) return MI355Q_E_BADARG;
+    QuantArgs aq{}, ap{};
+    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) |
+         reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) % 16 || reinterpret_cast<uintptr_t>(lengths) % 4)
+        return MI355Q_E_ALIGN;
+    long long st4[4];
+    if (strides)
+        for (int i = 0; i < 4; ++i) {
+            if (strides[i] % 4) return MI355Q_E_ALIGN;
+            st4[i] = strides[i];
+        }
+    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
+    return launch_bfp_attention_decode(aq, ap, c, q, out, workspace, M, max_length, causal != 0, q_scale, scale_div,
+                                       strides ? st4 : nullptr, splits, static_cast<hipStream_t>(stream), lengths);
+}
+
 // block_minifloat (fmt 1) / block_log (fmt 2) products: the same two kernels with the other quantisers' block parameters
 static int values_matmul_impl(int fmt, bool softmax, const float* mask, long long causal_off, const float* x, const float* y,
                               float* out, void* workspace, int64_t B, int64_t M, int64_t K, int64_t N, int32_t x_width,

@@ -17,6 +17,18 @@
 // always stored as +0.  A negative value whose mantissa rounds to 0 is -0 in the prefill fragments (copysign) and +0 in the
 // oracle's block_fp_quantize (its mantissas are integers); the products cannot tell, the bit-for-bit cache tests can.
 // The length L lives on the host: an append at L writes keys L .. L + n - 1, a decode at L reads keys 0 .. L - 1.
+//
+// Ragged batches (the *_ragged launches): every cache row b has its own length, lengths[b] in a DEVICE int32 array [B] that the
+// kernels read (once a workgroup, kept scalar) in place of the host's L; the host passes only upper bounds, which size grids and
+// the workspace and never decide what is addressed:
+//   append   row b takes counts[b] (device int32 [B]; NULL: n) of the n input rows as keys lengths[b] .. lengths[b] + counts[b] - 1:
+//            lengths holds the lengths BEFORE the append.  The open-tile logic above runs per row (t0, t1 and the open rows come
+//            from lengths[b], counts[b]); counts[b] == 0 leaves the row's kq, vq and stage untouched; a key index >= C is dropped.
+//   decode   row b sees keys 0 .. lengths[b] - 1, its M queries are its last M positions: lengths holds the lengths INCLUDING
+//            the queries' own keys.  lengths[b] is clamped to max_length; a row with lengths[b] < M yields zeros.  The split
+//            partition comes from max_length: a split behind a row's last tile writes (-inf, 0) statistics and a zero partial
+//            output and reads no kq / vq.  The scores workspace keeps the stride of NT(max_length) tiles a row.
+// A row decodes as if it were alone: nothing another row holds (or a pad key would be) enters its blocks' shared exponents.
 #ifndef MI355Q_DECODE_H
 #define MI355Q_DECODE_H
 #include <hip/hip_runtime.h>
@@ -40,8 +52,12 @@ inline long long kv_stage_bytes(long long B, long long D) { return B * 16 * D * 
 // keys L .. L + n - 1 from fp32 rows k / v [B, n, D] (element strides of batch and row; innermost 1)
 int launch_kv_append(const KvCache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
                      long long kst, long long vsb, long long vst, long long L, long long n, hipStream_t st);
-// the cache's quantised values back as fp32 [B, L, D] (tests, debugging)
-int launch_kv_decode_fp32(const KvCache& c, float* k_out, float* v_out, long long L, hipStream_t st);
+// ragged: row b's first counts[b] (NULL: n) input rows behind ITS length lengths[b] (device arrays [B])
+int launch_kv_append_ragged(const KvCache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
+                            long long kst, long long vsb, long long vst, const int32_t* lengths, const int32_t* counts, long long n,
+                            hipStream_t st);
+// the cache's quantised values back as fp32 [B, L, D] (tests, debugging); lengths != NULL: zeros behind row b's lengths[b]
+int launch_kv_decode_fp32(const KvCache& c, float* k_out, float* v_out, long long L, hipStream_t st, const int32_t* lengths = nullptr);
 
 // S of a decode over L keys: a pure function of (B, L, D); `override` > 0 asks for that many (clamped, then evened out so
 // that no split is empty).  1 <= S <= ceil(L / 32).
@@ -61,10 +77,12 @@ struct DecodeArgs {
     int causal;
     float q_scale, scale_div; // 0: none
     int D, S, pps;            // pps = key pairs per split
+    const int32_t* lengths;   // ragged: [B] on the device, L / NT / NP above are those of max_length (partition, strides); else NULL
 };
+// lengths != NULL: the ragged form, L = max_length
 int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out,
                                 void* workspace, long long M, long long L, int causal, float q_scale, float scale_div,
-                                const long long* strides, int splits, hipStream_t st);
+                                const long long* strides, int splits, hipStream_t st, const int32_t* lengths = nullptr);
 
 }  // namespace mi355q
 #endif

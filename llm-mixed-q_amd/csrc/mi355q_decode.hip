@@ -16,6 +16,9 @@
 //   phase B (decode_pv_kernel, grid S x B): the S statistics combined in split order; probabilities per 16-key block, quantised,
 //            times the V fragments -> the split's partial output (S == 1: the output itself)
 //   phase C (decode_sum_kernel, grid B): partial outputs summed in split order -- the same inputs give the same bits every run.
+// Ragged batches (layout note in mi355q_decode.h): the same kernels with RG = true read the row's length from a device array --
+// one load a workgroup, kept scalar -- where the uniform instantiations (RG = false) read the host's L; a row's workgroups skip
+// the key tiles the row does not have, and a row of length 0 (a finished sequence) costs a few empty workgroups.
 // MFMA roles as in mi355q_attention.hip (v_mfma_f32_16x16x32_bf16, the queries are the 16 columns): a lane's own values of the score
 // tiles 2 s, 2 s + 1 are the slots of its P fragment, and vq is stored with the same slot order.
 #include <hip/hip_runtime.h>
@@ -37,16 +40,35 @@ struct AppendArgs {
     long long ksb, kst, vsb, vst;
     long long L, n, t0, t1;     // key tiles touched: t0 = L / 16 .. t1 = (L + n - 1) / 16
     int kblocks;
+    const int32_t* lengths;     // ragged (RG): row b's L = lengths[b], its n = counts[b] (NULL: n) <= n; t0, t1 follow in the kernel
+    const int32_t* counts;
 };
 
+// row b's (L, n) of a ragged append, scalar; false: nothing to do (negative values are taken as 0, a count above n as n)
+__device__ __forceinline__ bool append_row(const AppendArgs& a, long long b, long long& L, long long& n) {
+    L = max(__builtin_amdgcn_readfirstlane(a.lengths[b]), 0);
+    if (a.counts) n = min((long long)max(__builtin_amdgcn_readfirstlane(a.counts[b]), 0), a.n);
+    return n > 0;
+}
+
+template <bool RG>
 __global__ __launch_bounds__(256) void kv_append_kernel(const QuantArgs ak, const QuantArgs av, const AppendArgs a) {
     const int tid = threadIdx.x, D = a.c.D;
     const long long b = blockIdx.y, NTC = a.c.C >> 4, NPC = (a.c.C + 31) >> 5;
+    long long L = a.L, n = a.n, t0 = a.t0, t1 = a.t1;
+    if constexpr (RG) {
+        if (!append_row(a, b, L, n)) return;
+        t0 = L >> 4;
+        t1 = (L + n - 1) >> 4;
+    }
     if ((int)blockIdx.x < a.kblocks) {
         // K: thread (tile, d) walks the 16 keys of its block: staged rows in front of L, new rows, zeros behind L + n
         const int per = 256 / D, sub = tid / D, d = tid - sub * D;
-        const long long t = a.t0 + (long long)blockIdx.x * per + sub;
-        if (sub >= per || t > a.t1) return;
+        const long long t = t0 + (long long)blockIdx.x * per + sub;
+        if (sub >= per || t > t1) return;
+        if constexpr (RG) {
+            if (t >= NTC) return;                              // (keys behind the capacity are dropped, whatever the host vouched for)
+        }
         float* __restrict__ stg = a.c.stage + b * 16 * D + d;
         float x[16];
         float bmax = 0.f;
@@ -54,18 +76,18 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const QuantArgs ak, cons
         for (int e = 0; e < 16; ++e) {
             const long long key = t * 16 + e;
             float val = 0.f;
-            if (key >= a.L && key < a.L + a.n) val = a.k[b * a.ksb + (key - a.L) * a.kst + d];
-            else if (key < a.L) val = stg[e * D];
+            if (key >= L && key < L + n) val = a.k[b * a.ksb + (key - L) * a.kst + d];
+            else if (key < L) val = stg[e * D];
             x[e] = val;
             bmax = fmaxf(bmax, fabsf(val));
         }
         // the open tile's rows for the next append, when the tile that reads staged rows is the one that writes them (the usual
         // decode step); an append that runs into a later tile leaves them to kv_stage_kernel, behind this launch
-        if (a.t0 == a.t1) {
+        if (t0 == t1) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const long long key = t * 16 + e;
-                if (key >= a.L && key < a.L + a.n) stg[e * D] = x[e];
+                if (key >= L && key < L + n) stg[e * D] = x[e];
             }
         }
         const int mbits = (int)__builtin_log2f(ak.shift);
@@ -82,8 +104,11 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const QuantArgs ak, cons
         const int DT = D >> 4;
         const long long item = ((long long)blockIdx.x - a.kblocks) * 256 + tid;
         if (item >= a.n * DT) return;
-        const long long kl = item / DT, key = a.L + kl;
+        const long long kl = item / DT, key = L + kl;
         const int dt = (int)(item - kl * DT);
+        if constexpr (RG) {
+            if (kl >= n || key >= a.c.C) return;               // (input rows behind the row's count are padding: never read)
+        }
         float x[16];
         float bmax = 0.f;
 #pragma unroll
@@ -107,9 +132,18 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const QuantArgs ak, cons
 
 // the new open tile's fp32 rows -> staging, for an append that crossed a tile boundary: they overlap the rows tile t0 of
 // kv_append_kernel reads, so they are written behind it.  grid (rows, B), D threads.
+template <bool RG>
 __global__ void kv_stage_kernel(const AppendArgs a) {
-    const long long b = blockIdx.y, key = a.t1 * 16 + blockIdx.x;      // (>= L: tile t1 lies behind tile t0 = L / 16)
-    a.c.stage[(b * 16 + blockIdx.x) * a.c.D + threadIdx.x] = a.k[b * a.ksb + (key - a.L) * a.kst + threadIdx.x];
+    const long long b = blockIdx.y;
+    long long L = a.L, n = a.n, t1 = a.t1;
+    if constexpr (RG) {
+        // grid: the most rows any row can have open; this row's own crossing and open rows decide
+        if (!append_row(a, b, L, n)) return;
+        t1 = (L + n - 1) >> 4;
+        if (t1 <= (L >> 4) || (long long)blockIdx.x >= ((L + n) & 15) || t1 >= (a.c.C >> 4)) return;
+    }
+    const long long key = t1 * 16 + blockIdx.x;                        // (>= L: tile t1 lies behind tile t0 = L / 16)
+    a.c.stage[(b * 16 + blockIdx.x) * a.c.D + threadIdx.x] = a.k[b * a.ksb + (key - L) * a.kst + threadIdx.x];
 }
 
 int launch_kv_append(const KvCache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
@@ -122,20 +156,47 @@ int launch_kv_append(const KvCache& c, const QuantArgs& ak, const QuantArgs& av,
     const long long kblocks = (a.t1 - a.t0 + 1 + per - 1) / per, vblocks = (n * (c.D / 16) + 255) / 256;
     if (kblocks + vblocks > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
     a.kblocks = (int)kblocks;
-    hipLaunchKernelGGL(kv_append_kernel, dim3((unsigned)(kblocks + vblocks), (unsigned)c.B), dim3(256), 0, st, ak, av, a);
+    hipLaunchKernelGGL(kv_append_kernel<false>, dim3((unsigned)(kblocks + vblocks), (unsigned)c.B), dim3(256), 0, st, ak, av, a);
     const unsigned open_rows = (unsigned)((L + n) % 16);                // (0: tile t1 is full, nothing to stage)
-    if (a.t1 > a.t0 && open_rows) hipLaunchKernelGGL(kv_stage_kernel, dim3(open_rows, (unsigned)c.B), dim3(c.D), 0, st, a);
+    if (a.t1 > a.t0 && open_rows) hipLaunchKernelGGL(kv_stage_kernel<false>, dim3(open_rows, (unsigned)c.B), dim3(c.D), 0, st, a);
     return (int)hipGetLastError();
 }
 
+// Grids from n alone: n keys touch at most (n + 14) / 16 + 1 tiles wherever they start, and an append that crosses a tile edge
+// leaves at most min(n - 1, 15) rows open (one key at least lies in tile t0).  The staging pass stays a second launch: tile t1's
+// rows overwrite the staged rows that tile t0's threads of the same row read.  n == 1, the decode step, never crosses.
+int launch_kv_append_ragged(const KvCache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
+                            long long kst, long long vsb, long long vst, const int32_t* lengths, const int32_t* counts, long long n,
+                            hipStream_t st) {
+    AppendArgs a{};
+    a.c = c; a.k = k; a.v = v;
+    a.ksb = ksb; a.kst = kst; a.vsb = vsb; a.vst = vst;
+    a.n = n; a.lengths = lengths; a.counts = counts;
+    const int per = 256 / c.D;
+    const long long kblocks = ((n + 14) / 16 + 1 + per - 1) / per, vblocks = (n * (c.D / 16) + 255) / 256;
+    if (kblocks + vblocks > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
+    a.kblocks = (int)kblocks;
+    hipLaunchKernelGGL(kv_append_kernel<true>, dim3((unsigned)(kblocks + vblocks), (unsigned)c.B), dim3(256), 0, st, ak, av, a);
+    if (n > 1) hipLaunchKernelGGL(kv_stage_kernel<true>, dim3((unsigned)(n - 1 < 15 ? n - 1 : 15), (unsigned)c.B), dim3(c.D), 0, st, a);
+    return (int)hipGetLastError();
+}
+
+template <bool RG>
 __global__ __launch_bounds__(256) void kv_decode_fp32_kernel(const KvCache c, float* __restrict__ k_out, float* __restrict__ v_out,
-                                                             long long L) {
+                                                             long long L, const int32_t* __restrict__ lengths) {
     const int D = c.D;
     const long long b = blockIdx.y, NTC = c.C >> 4, NPC = (c.C + 31) >> 5;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= L * D) return;
     const long long key = idx / D;
     const int d = (int)(idx - key * D);
+    if constexpr (RG) {
+        if (key >= __builtin_amdgcn_readfirstlane(lengths[b])) {      // (L = max_length <= C: zeros behind the row's own length)
+            k_out[(b * L + key) * D + d] = 0.f;
+            v_out[(b * L + key) * D + d] = 0.f;
+            return;
+        }
+    }
     const uint16_t kb = c.kq[((b * NTC + (key >> 4)) * (D >> 5) + (d >> 5)) * 512 + ((key & 15) + 16 * ((d >> 3) & 3)) * 8 + (d & 7)];
     const int h = (int)(key >> 4) & 1, g = (int)(key & 15) >> 2, j = 4 * h + (int)(key & 3);
     const uint16_t vb = c.vq[((b * NPC + (key >> 5)) * (D >> 4) + (d >> 4)) * 512 + ((d & 15) + 16 * g) * 8 + j];
@@ -143,10 +204,12 @@ __global__ __launch_bounds__(256) void kv_decode_fp32_kernel(const KvCache c, fl
     v_out[(b * L + key) * D + d] = __uint_as_float((unsigned)vb << 16);
 }
 
-int launch_kv_decode_fp32(const KvCache& c, float* k_out, float* v_out, long long L, hipStream_t st) {
+int launch_kv_decode_fp32(const KvCache& c, float* k_out, float* v_out, long long L, hipStream_t st, const int32_t* lengths) {
     const long long blocks = (L * c.D + 255) / 256;
     if (blocks > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
-    hipLaunchKernelGGL(kv_decode_fp32_kernel, dim3((unsigned)blocks, (unsigned)c.B), dim3(256), 0, st, c, k_out, v_out, L);
+    const dim3 grid((unsigned)blocks, (unsigned)c.B);
+    if (lengths) hipLaunchKernelGGL(kv_decode_fp32_kernel<true>, grid, dim3(256), 0, st, c, k_out, v_out, L, lengths);
+    else hipLaunchKernelGGL(kv_decode_fp32_kernel<false>, grid, dim3(256), 0, st, c, k_out, v_out, L, lengths);
     return (int)hipGetLastError();
 }
 
@@ -172,16 +235,40 @@ size_t decode_workspace_bytes(long long B, long long L, long long D, int splits)
 }
 
 // this lane's horizon: the last key its query (column c16 of the MFMA tiles) sees
-__device__ __forceinline__ long long dec_horizon(const DecodeArgs& g, long long qrow) {
-    return g.causal ? g.L - g.M + qrow : g.L - 1;
+__device__ __forceinline__ long long dec_horizon(const DecodeArgs& g, long long L, long long qrow) {
+    return g.causal ? L - g.M + qrow : L - 1;
 }
 
-template <int DC>
+// the keys row b holds.  Ragged: its own length, one scalar load a workgroup, never above max_length (= g.L: the partition and the
+// workspace strides are made for that); a row shorter than its M queries -- an empty slot, a finished sequence -- counts as 0
+// keys: every split of it is empty and its output is zeros.
+template <bool RG>
+__device__ __forceinline__ long long dec_length(const DecodeArgs& g, long long b) {
+    if constexpr (RG) {
+        const long long L = min((long long)max(__builtin_amdgcn_readfirstlane(g.lengths[b]), 0), g.L);
+        return L < g.M ? 0 : L;
+    } else {
+        return g.L;
+    }
+}
+
+template <int DC, bool RG>
 __global__ __launch_bounds__(256) void decode_scores_kernel(const QuantArgs aq, const DecodeArgs g) {
     __shared__ float sm_[4][64], sl_[4][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c16 = lane & 15, lg = lane >> 4;
     const long long b = blockIdx.y, s = blockIdx.x;
+    const long long L = dec_length<RG>(g, b), NT = RG ? (L + 15) >> 4 : g.NT;
+    if constexpr (RG) {
+        if (2 * g.pps * s >= NT) {      // a split wholly behind the row's last tile: the empty statistics, no kq read
+            if (tid < 16) {
+                float* st = g.stats + ((b * g.S + s) * 16 + tid) * 2;
+                st[0] = -INFINITY;
+                st[1] = 0.f;
+            }
+            return;
+        }
+    }
     const long long qrow = min((long long)c16, g.M - 1);
     // Q fragments, quantised in registers (mi355q_attention.hip): lane (query c16, g) holds d = 32 c + 8 g .. + 7
     bf16x8 qf[DC];
@@ -209,9 +296,9 @@ __global__ __launch_bounds__(256) void decode_scores_kernel(const QuantArgs aq, 
             qf[c] = __builtin_bit_cast(bf16x8, pk);
         }
     }
-    const long long kvis = dec_horizon(g, qrow);
+    const long long kvis = dec_horizon(g, L, qrow);
     const float scale_inv = g.scale_div != 0.f ? 1.0f / g.scale_div : 0.f;
-    const long long t_lo = 2 * g.pps * s, t_hi = min(g.NT, t_lo + 2 * g.pps);
+    const long long t_lo = 2 * g.pps * s, t_hi = min(NT, t_lo + 2 * g.pps);
     const uint16_t* __restrict__ kfb = g.kq + b * g.NTC * DC * 512 + lane * 8;
     float* __restrict__ sc = g.scores + b * g.NT * 256 + lane * 4;
     // running (max, sum of exp(x - max)) of this lane's visible scores, re-based when the maximum moves
@@ -259,16 +346,32 @@ __global__ __launch_bounds__(256) void decode_scores_kernel(const QuantArgs aq, 
     }
 }
 
-template <int DC>
+template <int DC, bool RG>
 __global__ __launch_bounds__(256) void decode_pv_kernel(const QuantArgs ap, const DecodeArgs g) {
     constexpr int DT = DC * 2;
     __shared__ f32x4 red[4][DT][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c16 = lane & 15, lg = lane >> 4;
     const long long b = blockIdx.y, s = blockIdx.x;
+    const long long L = dec_length<RG>(g, b), NT = RG ? (L + 15) >> 4 : g.NT, NP = RG ? (L + 31) >> 5 : g.NP;
+    const long long p_lo = g.pps * s, p_hi = min(NP, p_lo + g.pps);
+    if constexpr (RG) {
+        if (p_lo >= p_hi) {             // an empty split (every split of an empty row): a zero partial output, no vq read
+            const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int dt = wave; dt < DT; dt += 4) {
+                if (g.S == 1) {
+                    if (c16 < g.M) *reinterpret_cast<float4*>(g.out + b * g.osb + c16 * g.osm + 16 * dt + 4 * lg) = zero;
+                } else {
+                    *reinterpret_cast<float4*>(g.part + (((b * g.S + s) * DT + dt) * 64 + lane) * 4) = zero;
+                }
+            }
+            return;
+        }
+    }
     const long long qrow = min((long long)c16, g.M - 1);
-    const long long kvis = dec_horizon(g, qrow);
-    // the row's statistics over all L keys: the S splits in split order (every query sees key 0: the first split's max is finite)
+    const long long kvis = dec_horizon(g, L, qrow);
+    // the row's statistics over all L keys: the S splits in split order (every query sees key 0: the first split's max is finite;
+    // splits behind a ragged row's last tile hold (-inf, 0) and are skipped like any split without a visible key)
     const float* __restrict__ stp = g.stats + (b * g.S * 16 + c16) * 2;
     float row_max = -INFINITY;
     for (int i = 0; i < g.S; ++i) row_max = fmaxf(row_max, stp[i * 32]);
@@ -279,7 +382,6 @@ __global__ __launch_bounds__(256) void decode_pv_kernel(const QuantArgs ap, cons
     }
     const float row_inv = 1.0f / row_sum;
     const int mbp = (int)__builtin_log2f(ap.shift);
-    const long long p_lo = g.pps * s, p_hi = min(g.NP, p_lo + g.pps);
     const uint16_t* __restrict__ vfb = g.vq + b * g.NPC * DT * 512 + lane * 8;
     const float* __restrict__ sc = g.scores + b * g.NT * 256 + lane * 4;
     f32x4 o[DT];
@@ -294,14 +396,14 @@ __global__ __launch_bounds__(256) void decode_pv_kernel(const QuantArgs ap, cons
         for (int h = 0; h < 2; ++h) {
             const long long t = 2 * pr_i + h;                  // (uniform over the wave; the last pair's second tile may not exist)
             float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (t < g.NT) x = *reinterpret_cast<const float4*>(sc + t * 256);
+            if (t < NT) x = *reinterpret_cast<const float4*>(sc + t * 256);
             const float xs[4] = {x.x, x.y, x.z, x.w};
             const long long key0 = t * 16 + 4 * lg;
             float pr[4];
             float bmax = 0.f;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                pr[e] = (t < g.NT && key0 + e <= kvis) ? at_div(at_exp_neg(xs[e] - row_max), row_sum, row_inv) : 0.f;
+                pr[e] = (t < NT && key0 + e <= kvis) ? at_div(at_exp_neg(xs[e] - row_max), row_sum, row_inv) : 0.f;
                 bmax = fmaxf(bmax, pr[e]);
             }
             bmax = at_max4(bmax);
@@ -352,9 +454,9 @@ __global__ __launch_bounds__(256) void decode_sum_kernel(const DecodeArgs g) {
 
 int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out,
                                 void* workspace, long long M, long long L, int causal, float q_scale, float scale_div,
-                                const long long* strides, int splits, hipStream_t st) {
+                                const long long* strides, int splits, hipStream_t st, const int32_t* lengths) {
     DecodeArgs g{};
-    g.q = q; g.kq = c.kq; g.vq = c.vq; g.out = out;
+    g.q = q; g.kq = c.kq; g.vq = c.vq; g.out = out; g.lengths = lengths;
     g.M = M; g.L = L; g.D = c.D;
     g.NT = (L + 15) / 16; g.NP = (L + 31) / 32; g.NTC = c.C / 16; g.NPC = (c.C + 31) / 32;
     g.S = decode_splits(c.B, L, c.D, splits);
@@ -367,8 +469,13 @@ int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const 
     g.part = g.stats + c.B * g.S * 32;
     const dim3 grid((unsigned)g.S, (unsigned)c.B);
 #define MI355Q_DECODE_GO(DC_)                                                                     \
-    hipLaunchKernelGGL((decode_scores_kernel<DC_>), grid, dim3(256), 0, st, aq, g);               \
-    hipLaunchKernelGGL((decode_pv_kernel<DC_>), grid, dim3(256), 0, st, ap, g)
+    if (lengths) {                                                                                \
+        hipLaunchKernelGGL((decode_scores_kernel<DC_, true>), grid, dim3(256), 0, st, aq, g);     \
+        hipLaunchKernelGGL((decode_pv_kernel<DC_, true>), grid, dim3(256), 0, st, ap, g);         \
+    } else {                                                                                      \
+        hipLaunchKernelGGL((decode_scores_kernel<DC_, false>), grid, dim3(256), 0, st, aq, g);    \
+        hipLaunchKernelGGL((decode_pv_kernel<DC_, false>), grid, dim3(256), 0, st, ap, g);        \
+    }
     switch (c.D / 32) {
         case 1: MI355Q_DECODE_GO(1); break;
         case 2: MI355Q_DECODE_GO(2); break;

@@ -212,11 +212,15 @@ class TinyOPTForCausalLM(nn.Module):
             out[k if k.startswith("lm_head") else "model.decoder." + k] = v
         return out
 
-    def forward(self, input_ids, labels=None, cache=None):
+    def forward(self, input_ids, labels=None, cache=None, counts=None):
         """`cache` (a DecodeState): input_ids holds only the NEW tokens, whose positions start at the cache's length; returns their
-        logits (the prompt goes through the same call).  None: the whole sequence, as ever."""
+        logits (the prompt goes through the same call).  None: the whole sequence, as ever.
+        `counts` (with a cache): a ragged batch -- input_ids [B, n] is right-padded and row b holds counts[b] real tokens, at
+        positions lengths[b] .. lengths[b] + counts[b] - 1 of ITS sequence; logits at padded positions are unspecified."""
         if cache is not None:
-            return _forward_cached(self, input_ids, labels, cache)
+            return _forward_cached(self, input_ids, labels, cache, counts)
+        if counts is not None:
+            raise ValueError("forward(counts=...) belongs to a cached call (cache=DecodeState)")
         B, T = input_ids.shape
         pos = torch.arange(T, device=input_ids.device)
         x = self.embed_tokens(input_ids) + self.embed_positions(pos)[None]
@@ -331,7 +335,7 @@ class _LlamaAttention(nn.Module):
         B, n, _ = x.shape
         heads = lambda t: t.view(B, n, self.nh, self.hd).transpose(1, 2)
         q, k, v = heads(self.q_proj(x)), heads(self.k_proj(x)), heads(self.v_proj(x))
-        rc, end = self.qc["rotary_positional_encoding"], state.length + n
+        rc, end = self.qc["rotary_positional_encoding"], state.position_end(n)
         q, k = get_quantized_func("rotary_positional_encoding", rc)(q, k, self.cos[:, :, :end], self.sin[:, :, :end], position_ids, config=rc)
         o = state.attend(idx, q, k, v, self.qc["matmul_0"], self.qc["matmul_1"], math.sqrt(self.hd), "matmul")
         return self.o_proj(o.transpose(1, 2).reshape(B, n, self.nh * self.hd))
@@ -416,10 +420,12 @@ class TinyLlamaForCausalLM(nn.Module):
             out[k if k.startswith("lm_head") else "model." + k] = v.detach()
         return out
 
-    def forward(self, input_ids, labels=None, cache=None):
-        """`cache` (a DecodeState): see TinyOPTForCausalLM.forward"""
+    def forward(self, input_ids, labels=None, cache=None, counts=None):
+        """`cache` (a DecodeState), `counts`: see TinyOPTForCausalLM.forward"""
         if cache is not None:
-            return _forward_cached(self, input_ids, labels, cache)
+            return _forward_cached(self, input_ids, labels, cache, counts)
+        if counts is not None:
+            raise ValueError("forward(counts=...) belongs to a cached call (cache=DecodeState)")
         B, T = input_ids.shape
         position_ids = torch.arange(T, device=input_ids.device)[None].expand(B, T)
         x = self.embed_tokens(input_ids)
@@ -440,7 +446,13 @@ class DecodeState:
     mode "block_fp": ops.KVCache + the split-key decode kernel -- both attention products block_fp [1,16] with widths <= 9 and a
         head_dim the kernel takes, else ValueError here, naming the reason.
     mode "fp32": the reference's literal route for ANY arithmetic (modeling_llama.py:301-344): torch.cat of fp32 K / V per layer, the
-        products through the registry's functions, the causal mask [n, L] with the offset of modeling_llama.py:53-79."""
+        products through the registry's functions, the causal mask [n, L] with the offset of modeling_llama.py:53-79.
+    Ragged batches (`model(ids, cache=state, counts=[...])`, mode "block_fp" only): `lengths` holds every sequence's own length on the
+    host, and two int32 device tensors [batch x heads] hold them per cache row as the kernels read them -- "before" this call (every
+    layer's append) and "after" it (every layer's decode; 0 for a row that takes no token in this call, which then costs nothing).
+    They are shared by all layers and written once a call.  Each sequence decodes as if it were alone: no pad key ever enters a
+    block of the cache.  The reference's left padding + attention_mask is NOT reproduced -- under block quantisation a pad key
+    shares a 16-key block with real keys and moves their exponent."""
 
     def __init__(self, model, batch: int, capacity: int, mode: str = "block_fp"):
         from .quantize.quantized_functions import decode_cache_params
@@ -450,6 +462,7 @@ class DecodeState:
         if any(getattr(a, "mi355q_head_shard", None) is not None for a in attns):
             raise NotImplementedError("incremental decoding of head-sharded models")
         self.mode, self.batch, self.length = mode, int(batch), 0
+        self.lengths, self.ragged, self._call = [0] * self.batch, False, None
         self.capacity = (int(capacity) + 15) // 16 * 16
         if self.capacity > model.cfg.max_positions + 15:
             raise ValueError(f"DecodeState: capacity {capacity} exceeds the model's {model.cfg.max_positions} positions")
@@ -463,18 +476,88 @@ class DecodeState:
                 except ValueError as e:
                     raise ValueError(f"DecodeState(mode='block_fp'), layer {i}: {e}") from None
                 self.kv[i] = ops.KVCache(self.batch * a.nh, self.capacity, a.hd, qk, pv, dev)
+            if len({a.nh for a in attns}) == 1:                # (else: no ragged use; the per-row tensors are one set for all layers)
+                self.heads = attns[0].nh
+                self.rows_before, self.rows_after, self._rows_counts = (torch.zeros(self.batch * self.heads, dtype=torch.int32, device=dev)
+                                                                        for _ in range(3))
 
     def reset(self) -> None:
         self.length = 0
+        self.lengths, self.ragged, self._call = [0] * self.batch, False, None
         for i, c in enumerate(self.kv):
             if self.mode == "block_fp":
                 c.reset()
             else:
                 self.kv[i] = None
 
+    def position_end(self, n: int) -> int:
+        """rows of the rotary tables a call with n new tokens reads"""
+        return (max(self.lengths) if self._call is not None else self.length) + n
+
+    def begin_ragged(self, counts, n: int, max_positions: int):
+        """One ragged call: checks, the route, and the per-row tensors -- before any layer's cache is written.  -> positions [B, n]
+        (host list of lists; padded positions repeat the row's last one)"""
+        if self.mode != "block_fp":
+            raise NotImplementedError("counts= with mode='fp32': the reference serves unequal prompts by left padding + attention_mask, "
+                                      "which under block quantisation gives different numbers (a pad key shares a 16-key block of K^T "
+                                      "with real keys and moves their exponent); ragged batches run on the block_fp cache only")
+        if not hasattr(self, "rows_before"):
+            raise NotImplementedError("ragged batches of a model whose layers differ in their number of heads")
+        counts = [int(c) for c in counts]
+        if len(counts) != self.batch or any(not 0 <= c <= n for c in counts):
+            raise ValueError(f"forward(counts=...): {len(counts)} counts outside 0 .. {n} for a batch of {self.batch}")
+        before = list(self.lengths)
+        after = [l + c for l, c in zip(before, counts)]
+        if max(after) > min(self.capacity, max_positions) or max(before) + n > self.capacity:
+            raise ValueError(f"forward(counts=...): lengths {before} + {n} tokens exceed the capacity {self.capacity} "
+                             f"or the model's {max_positions} positions")
+        active = [b for b, c in enumerate(counts) if c > 0]
+        if all(l == 0 for l in before):
+            route = "prefill"
+        elif all(before[b] > 0 and counts[b] == n for b in active) and n <= ops.DECODE_MAX_QUERIES:
+            route = "decode"
+        elif any(before[b] == 0 for b in active):
+            raise NotImplementedError(f"a mixed call: rows {[b for b in active if before[b] == 0]} start a sequence while others continue theirs "
+                                      "(prefill and decode in one call)")
+        elif n > ops.DECODE_MAX_QUERIES:
+            raise NotImplementedError(f"{n} new tokens behind non-empty block_fp cache rows (at most {ops.DECODE_MAX_QUERIES} a call)")
+        else:
+            raise NotImplementedError(f"unequal counts {counts} behind non-empty rows: the decode kernel takes the same number of "
+                                      "queries for every row that takes any")
+        rows = lambda xs: torch.tensor(xs, dtype=torch.int32).repeat_interleave(self.heads)
+        self.rows_before.copy_(rows(before))
+        self.rows_after.copy_(rows([a if c > 0 else 0 for a, c in zip(after, counts)]))      # (a row without a token: no decode work)
+        self._rows_counts.copy_(rows(counts))
+        self._call = dict(route=route, counts=counts, after=after, max_before=max(before), max_after=max(after))
+        self.ragged = True
+        return [[min(l + j, max(l + c - 1, 0)) for j in range(n)] for l, c in zip(before, counts)]
+
+    def end_ragged(self) -> None:
+        self.lengths, self._call = self._call["after"], None
+        self.length = max(self.lengths)
+
+    def _attend_ragged(self, idx, q, k, v, c0, c1, scale_div):
+        B, nh, n, hd = q.shape
+        call, cache = self._call, self.kv[idx]
+        full = all(c == n for c in call["counts"])
+        cache.append(k, v, lengths=self.rows_before, counts=None if full else self._rows_counts, max_length=call["max_before"])
+        if call["route"] == "decode":
+            return get_quantized_func("attention_decode", c1)(q, cache, c0, c1, causal=True, scale_div=scale_div, lengths=self.rows_after,
+                                                              max_length=call["max_after"]).reshape(B, nh, n, hd)
+        # ragged prefill: every sequence's own queries against its own keys, one call of the existing attention function each (what
+        # the sequence alone runs); prefill is not the hot path here
+        o = q.new_zeros(B, nh, n, hd)
+        for b, c in enumerate(call["counts"]):
+            if c:
+                o[b, :, :c] = get_quantized_func("attention", c1)(q[b:b + 1, :, :c], k[b:b + 1, :, :c], v[b:b + 1, :, :c], c0, c1, causal=True,
+                                                                  scale_div=scale_div).reshape(nh, c, hd)
+        return o
+
     def attend(self, idx, q, k, v, c0, c1, scale_div, style):
         """q, k, v [B, heads, n, hd] of the new tokens (q scaled / turned already) -> attention output [B, heads, n, hd]"""
         B, nh, n, hd = q.shape
+        if self._call is not None:
+            return self._attend_ragged(idx, q, k, v, c0, c1, scale_div)
         if self.length + n > self.capacity:
             raise ValueError(f"DecodeState: {self.length} + {n} tokens exceed the capacity {self.capacity}")
         if self.mode == "block_fp":
@@ -503,12 +586,33 @@ class DecodeState:
         return get_quantized_func(style, c1)(p, v, config=c1).view(B, nh, n, hd)
 
 
-def _forward_cached(model, input_ids, labels, state: DecodeState):
+def _forward_cached(model, input_ids, labels, state: DecodeState, counts=None):
     if labels is not None:
         raise ValueError("forward(cache=...): labels belong to the full forward")
     B, n = input_ids.shape
     if B != state.batch:
         raise ValueError(f"forward(cache=...): batch {B}, the cache was made for {state.batch}")
+    if counts is None and state.ragged:
+        counts = [n] * B                                    # (a state whose rows differ in length has no common position range)
+    if counts is not None:
+        # ragged: per-row positions; the route is chosen and refused before any layer's cache is written
+        position_ids = torch.tensor(state.begin_ragged(counts, n, model.cfg.max_positions), dtype=torch.long).to(input_ids.device)
+        try:
+            if isinstance(model, TinyOPTForCausalLM):
+                x = model.embed_tokens(input_ids) + model.embed_positions(position_ids)
+                for i, layer in enumerate(model.layers):
+                    x = layer.decode(x, state, i)
+                x = model.final_layer_norm(x)
+            else:
+                x = model.embed_tokens(input_ids)
+                for i, layer in enumerate(model.layers):
+                    x = layer.decode(x, state, i, position_ids)
+                x = model.norm(x)
+        except BaseException:
+            state._call = None
+            raise
+        state.end_ragged()
+        return fp32_linear(x, model.lm_head, model.mi355q_lm_head), None
     if state.length + n > model.cfg.max_positions:
         raise ValueError(f"forward(cache=...): {state.length} + {n} tokens exceed the model's {model.cfg.max_positions} positions")
     pos = torch.arange(state.length, state.length + n, device=input_ids.device)
@@ -524,13 +628,33 @@ def _forward_cached(model, input_ids, labels, state: DecodeState):
             x = layer.decode(x, state, i, position_ids)
         x = model.norm(x)
     state.length += n
+    state.lengths = [state.length] * B
     return fp32_linear(x, model.lm_head, model.mi355q_lm_head), None
 
 
 @torch.no_grad()
 def generate(model, prompt_ids, new_tokens: int, mode: str = "block_fp"):
     """greedy decoding: the prompt in one cached call, then one token a call.  Returns (ids [B, prompt + new_tokens], logits
-    [B, new_tokens, vocab]: the logits each new token was picked from)."""
+    [B, new_tokens, vocab]: the logits each new token was picked from).
+    `prompt_ids` may be a list of 1-D id tensors of DIFFERENT lengths (mode "block_fp"): one ragged prefill, then one token a row a
+    call, every sequence decoded as if it were alone; returns (a list of id tensors [len_b + new_tokens], logits as above)."""
+    if isinstance(prompt_ids, (list, tuple)):
+        lens = [int(p.numel()) for p in prompt_ids]
+        B, dev = len(lens), prompt_ids[0].device
+        state = DecodeState(model, B, max(lens) + new_tokens, mode)
+        ids = torch.zeros(B, max(lens), dtype=prompt_ids[0].dtype, device=dev)
+        for b, p in enumerate(prompt_ids):
+            ids[b, :lens[b]] = p
+        out = model(ids, cache=state, counts=lens)[0]
+        logits = out[torch.arange(B, device=dev), torch.tensor(lens, device=dev) - 1]      # (each row's last REAL position)
+        rows, steps = [p.reshape(-1) for p in prompt_ids], []
+        for i in range(new_tokens):
+            steps.append(logits)
+            tok = logits.argmax(-1, keepdim=True)
+            rows = [torch.cat([r, t]) for r, t in zip(rows, tok)]
+            if i + 1 < new_tokens:
+                logits = model(tok, cache=state, counts=[1] * B)[0][:, -1]
+        return rows, torch.stack(steps, dim=1)
     B, T = prompt_ids.shape
     state = DecodeState(model, B, T + new_tokens, mode)
     ids, steps = prompt_ids, []

@@ -1449,11 +1449,40 @@ def decode_splits(B: int, L: int, D: int, splits: int = None) -> int:
     return int(_lib.load_library().mi355q_bfp_attention_decode_splits(int(B), int(L), int(D), int(splits or 0)))
 
 
+def _ragged_check(cache, lengths, counts, max_length, rows, what):
+    """the reasons a ragged call declines its per-row lengths (counts: the append's), None when it takes them.  `rows`: the append's n
+    (max_length + n must fit the capacity) or the decode's M (M <= max_length <= capacity).  Nothing here touches the device, and
+    nothing ever reads `lengths` back: `max_length` is the caller's word for their upper bound."""
+    for name, t in (("lengths", lengths), ("counts", counts)):
+        if t is None and name == "counts":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            return f"{name} must be an int32 tensor [{cache.B}] (got {getattr(t, 'dtype', type(t).__name__)})"
+        if tuple(t.shape) != (cache.B,) or not t.is_contiguous():
+            return f"{name} {tuple(t.shape)} is not a contiguous [{cache.B}], one entry per cache row (batch x head)"
+        if t.device != cache.device:
+            return f"{name} is on {t.device}, the cache on {cache.device}"
+    if max_length is None:
+        return "lengths without max_length: the host upper bound on them sizes the launch (lengths are never read back)"
+    max_length = int(max_length)
+    if max_length < 0:
+        return f"max_length = {max_length} < 0"
+    if what == "append" and max_length + rows > cache.capacity:
+        return f"max_length {max_length} + {rows} new keys exceed the capacity {cache.capacity}"
+    if what != "append" and not rows <= max_length <= cache.capacity:
+        return f"max_length = {max_length} outside {rows} (the queries' own keys) .. the capacity {cache.capacity}"
+    return None
+
+
 class KVCache:
     """What the reference's `past_key_value` (torch.cat of fp32 K / V, modeling_llama.py:301-306) becomes under the block_fp [1,16]
     quantisers of bmm_0 / bmm_1: per b = batch x head, quantised K and V as bf16 in the decode kernel's fragment order, plus the
     fp32 rows of the open 16-key block of K^T, which is quantised again on every append until it is full (include/mi355q.h).
-    qk_params / pv_params as for bfp_attention; `length` lives on the host."""
+    qk_params / pv_params as for bfp_attention; `length` lives on the host.
+
+    Ragged batches: append / dequantised / bfp_attention_decode take `lengths=` (int32 [B] on the cache's device, one entry per cache
+    row) and a host bound `max_length`; the kernels read each row's length from the device, `length` is then neither used nor
+    advanced -- the caller owns the lengths -- and each row holds exactly what a cache of its own would."""
 
     def __init__(self, B: int, capacity: int, D: int, qk_params, pv_params, device):
         import ctypes
@@ -1487,14 +1516,25 @@ class KVCache:
             raise ValueError(f"KVCache.append: {what} {tuple(t.shape)} does not match B = {self.B}, D = {self.D}")
         return t
 
-    def append(self, k: torch.Tensor, v: torch.Tensor) -> None:
-        """n >= 1 new fp32 rows k, v [B, n, D] (or [1, H, n, D] head views, read in place) become keys length .. length + n - 1"""
+    def append(self, k: torch.Tensor, v: torch.Tensor, *, lengths: torch.Tensor = None, counts: torch.Tensor = None,
+               max_length: int = None) -> None:
+        """n >= 1 new fp32 rows k, v [B, n, D] (or [1, H, n, D] head views, read in place) become keys length .. length + n - 1.
+        Ragged (`lengths` int32 [B] on the device: the rows' lengths BEFORE this call): row b takes its first counts[b] rows (int32
+        [B]; None: all n; the rest is padding, never read) as keys lengths[b] .. lengths[b] + counts[b] - 1; counts[b] == 0 leaves
+        the row untouched.  `max_length`: the caller's upper bound on `lengths`, max_length + n <= capacity.  `length` stays."""
         import ctypes
         k, v = self._rows(k, "k"), self._rows(v, "v")
         n = k.shape[-2]
         if v.shape[-2] != n or n < 1:
             raise ValueError(f"KVCache.append: {n} rows of k, {v.shape[-2]} of v (at least one, and as many of each)")
-        if self.length + n > self.capacity:
+        ragged = lengths is not None
+        if ragged:
+            why = _ragged_check(self, lengths, counts, max_length, n, "append")
+            if why is not None:
+                raise ValueError(f"KVCache.append: {why}")
+        elif counts is not None or max_length is not None:
+            raise ValueError("KVCache.append: counts / max_length belong to a ragged append (lengths=)")
+        elif self.length + n > self.capacity:
             raise ValueError(f"KVCache.append: {self.length} + {n} keys exceed the capacity {self.capacity}")
         for t in (k, v):
             if not t.is_cuda or t.dtype != torch.float32 or t.device != self.device:
@@ -1502,6 +1542,14 @@ class KVCache:
         k3, ksb, kst = _as_heads_view(k)
         v3, vsb, vst = _as_heads_view(v)
         strides = (ctypes.c_int64 * 4)(ksb, kst, vsb, vst)
+        if ragged:
+            with _on_device(self.device):
+                rc = _lib.load_library().mi355q_bfp_kv_append_ragged(_ptr(self.kq), _ptr(self.vq), _ptr(self.stage), _ptr(k3), _ptr(v3),
+                                                                     _ptr(lengths), _ptr(counts), self.B, self.capacity, self.D, n,
+                                                                     int(max_length), ctypes.addressof(self._pa), ctypes.addressof(self._pb),
+                                                                     ctypes.addressof(strides), _stream_ptr(self.device))
+            _lib.check(rc, "mi355q_bfp_kv_append_ragged")
+            return
         with _on_device(self.device):
             rc = _lib.load_library().mi355q_bfp_kv_append(_ptr(self.kq), _ptr(self.vq), _ptr(self.stage), _ptr(k3), _ptr(v3), self.B, self.capacity,
                                                           self.D, self.length, n, ctypes.addressof(self._pa), ctypes.addressof(self._pb),
@@ -1509,10 +1557,25 @@ class KVCache:
         _lib.check(rc, "mi355q_bfp_kv_append")
         self.length += n
 
-    def dequantised(self):
-        """the cache's quantised K and V as fp32 [B, length, D] (tests, debugging)"""
+    def dequantised(self, lengths: torch.Tensor = None, max_length: int = None):
+        """the cache's quantised K and V as fp32 [B, length, D] (tests, debugging); ragged: [B, max_length, D], zeros behind each
+        row's lengths[b]"""
+        if lengths is not None:
+            why = _ragged_check(self, lengths, None, max_length, 0, "dequantised")
+            if why is not None:
+                raise ValueError(f"KVCache.dequantised: {why}")
+        elif max_length is not None:
+            raise ValueError("KVCache.dequantised: max_length belongs to a ragged call (lengths=)")
         if not self.kq.is_cuda:
             raise ValueError("KVCache.dequantised: the cache is not on a GPU; there is no CPU fallback")
+        if lengths is not None:
+            k = torch.empty(self.B, int(max_length), self.D, dtype=torch.float32, device=self.device)
+            v = torch.empty_like(k)
+            with _on_device(self.device):
+                rc = _lib.load_library().mi355q_bfp_kv_decode_fp32_ragged(_ptr(self.kq), _ptr(self.vq), _ptr(lengths), _ptr(k), _ptr(v), self.B,
+                                                                          self.capacity, self.D, int(max_length), _stream_ptr(self.device))
+            _lib.check(rc, "mi355q_bfp_kv_decode_fp32_ragged")
+            return k, v
         k = torch.empty(self.B, self.length, self.D, dtype=torch.float32, device=self.device)
         v = torch.empty_like(k)
         with _on_device(self.device):
@@ -1522,7 +1585,7 @@ class KVCache:
         return k, v
 
 
-def _decode_check(q, cache, splits=None):
+def _decode_check(q, cache, splits=None, lengths=None, max_length=None):
     """the reasons bfp_attention_decode declines (q, cache), None when it takes them; nothing here touches the device"""
     if not isinstance(cache, KVCache):
         return "cache is not a KVCache"
@@ -1533,7 +1596,13 @@ def _decode_check(q, cache, splits=None):
         return f"M = {M} queries outside 1 .. {DECODE_MAX_QUERIES}"
     if D != cache.D or q.shape[:-2].numel() != cache.B:
         return f"q {tuple(q.shape)} does not match the cache's B = {cache.B}, D = {cache.D}"
-    if cache.length < M:
+    if lengths is not None:
+        why = _ragged_check(cache, lengths, None, max_length, M, "decode")
+        if why is not None:
+            return why
+    elif max_length is not None:
+        return "max_length belongs to a ragged call (lengths=)"
+    elif cache.length < M:
         return f"{cache.length} cached keys for {M} queries (the queries' own keys are appended first)"
     if splits is not None and int(splits) < 1:
         return f"splits = {splits} < 1"
@@ -1547,13 +1616,16 @@ def bfp_attention_decode_supported(q, cache) -> bool:
 
 
 def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True, scale_div: float = None, q_scale: float = None,
-                         token_major: bool = False, splits: int = None):
+                         token_major: bool = False, splits: int = None, lengths: torch.Tensor = None, max_length: int = None):
     """The attention core (modeling_llama.py:309-344) for the LAST M <= 16 positions of a sequence whose L = cache.length keys are in
     `cache` (their own keys included: append first): q [..., M, D] fp32; causal: query i sees keys 0 .. L - M + i, else all L.
     scale_div / q_scale / token_major as bfp_attention.  Keys are split over `splits` workgroups per head (default: decode_splits);
-    statistics and partial outputs are combined in split order, so equal inputs give equal bits.  No additive mask."""
+    statistics and partial outputs are combined in split order, so equal inputs give equal bits.  No additive mask.
+    Ragged (`lengths` int32 [B] on the device: the rows' lengths INCLUDING the queries' own keys; `max_length`: the caller's upper
+    bound on them, which also fixes the split partition): row b's queries are ITS last M positions against ITS lengths[b] keys, as
+    if the row were alone; a row with fewer than M keys (an empty slot) returns zeros.  cache.length is not used."""
     import ctypes
-    why = _decode_check(q, cache, splits)
+    why = _decode_check(q, cache, splits, lengths, max_length)
     if why is not None:
         raise ValueError(f"mi355q.bfp_attention_decode: {why}")
     M, D = q.shape[-2:]
@@ -1574,6 +1646,14 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
         ws = _DECODE_WS.put(key, torch.empty(B * (C // 16) * 1024 + B * _DECODE_MAX_SPLITS * (128 + (D // 16) * 1024), dtype=torch.uint8,
                                              device=q.device))
     strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
+    if lengths is not None:
+        with _on_device(q.device):
+            rc = lib.mi355q_bfp_attention_decode_ragged(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), _ptr(lengths), int(bool(causal)),
+                                                        float(q_scale) if q_scale else 0.0, float(scale_div) if scale_div else 0.0,
+                                                        _ptr(out), _ptr(ws), B, M, int(max_length), C, D, ctypes.addressof(cache._pa),
+                                                        ctypes.addressof(cache._pb), ctypes.addressof(strides), int(splits or 0), sp)
+        _lib.check(rc, "mi355q_bfp_attention_decode_ragged")
+        return out
     with _on_device(q.device):
         rc = lib.mi355q_bfp_attention_decode(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), int(bool(causal)), float(q_scale) if q_scale else 0.0,
                                              float(scale_div) if scale_div else 0.0, _ptr(out), _ptr(ws), B, M, L, C, D,

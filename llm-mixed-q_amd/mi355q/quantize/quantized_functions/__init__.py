@@ -271,14 +271,16 @@ def decode_cache_params(config_qk, config_pv, head_dim):
     return par(config_qk), par(config_pv)
 
 
-def attention_decode_block_fp(q, cache, config_qk, config_pv, causal=True, scale_div=None, q_scale=None):
+def attention_decode_block_fp(q, cache, config_qk, config_pv, causal=True, scale_div=None, q_scale=None, lengths=None, max_length=None):
     """The attention core for the last M <= 16 positions against an `ops.KVCache` that already holds their keys (what the reference
     computes from `past_key_value`, modeling_llama.py:301-344): ops.bfp_attention_decode.  An addition to the registry (key
-    "attention_decode"); no additive mask, and no other route -- a cache is block_fp by construction (decode_cache_params)."""
+    "attention_decode"); no additive mask, and no other route -- a cache is block_fp by construction (decode_cache_params).
+    `lengths` / `max_length`: a ragged batch, every cache row at its own length (ops.bfp_attention_decode)."""
     from ... import ops
     decode_cache_params(config_qk, config_pv, q.shape[-1])
     return ops.bfp_attention_decode(q, cache, causal=causal, scale_div=scale_div, q_scale=q_scale,
-                                    token_major=bool(config_pv.get("mi355q_token_major_output", False)))
+                                    token_major=bool(config_pv.get("mi355q_token_major_output", False)), lengths=lengths,
+                                    max_length=max_length)
 
 
 def _make(arith, style):

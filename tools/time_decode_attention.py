@@ -8,6 +8,14 @@ memory-side cache (counted for the cache route, the smaller reader), at least `-
 `--repeats` times between HIP events.  One JSON line per case: median time per step of both routes and the spread over the repeats.
 
     python tools/time_decode_attention.py --out profiles/decode_attention.jsonl
+
+--ragged: the per-row-length forms (lengths on the device) of the same step at M = 1 against the uniform route, four cases a head_dim:
+all 32 lengths equal at L = 512 / 2048 / 4096 (the ragged kernels' only extra work is one 4-byte load a workgroup), and a mixed
+batch -- one row of 4096 keys, 31 of 512 -- against the uniform step at L = 4096, which is what a padded batch costs.  The sets are
+sized for the SMALLEST reader of a case, so every route's window reads more than the memory-side cache.  --baseline-lib names a
+second build of libmi355q.so (an earlier commit's) whose uniform route is replayed in the same interleaving, through the C ABI.
+
+    python tools/time_decode_attention.py --ragged [--baseline-lib PATH] --out profiles/decode_ragged.jsonl
 """
 import argparse
 import json
@@ -22,6 +30,116 @@ CACHE_BYTES = 256 << 20
 PAR = (6, 8, 127, 6, 8, 127)
 
 
+def _replay(graphs, repeats, calls):
+    """the graphs replayed alternately, `repeats` times each behind one warm-up replay -> {route: [us per step]}"""
+    import torch
+    times = {r: [] for r in graphs}
+    for rep in range(repeats + 1):
+        for route, gr in graphs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            gr.replay()
+            e1.record()
+            e1.synchronize()
+            if rep:
+                times[route].append(e0.elapsed_time(e1) * 1e3 / calls)
+    return times
+
+
+def _baseline_step(path):
+    """the uniform append + decode step of ANOTHER build of the library, through its C ABI (the signatures are this build's: the
+    uniform entry points have not changed)"""
+    import ctypes
+    import torch
+    from mi355q import _lib, ops
+    lib = ctypes.CDLL(str(path))
+    for name in ("mi355q_bfp_kv_append", "mi355q_bfp_attention_decode"):
+        getattr(lib, name).restype, getattr(lib, name).argtypes = _lib.SIGNATURES[name]
+
+    def step(cache, kn, vn, q, out, ws, L, scale_div):
+        B, D = cache.B, cache.D
+        sp = torch.cuda.current_stream().cuda_stream
+        rc = lib.mi355q_bfp_kv_append(cache.kq.data_ptr(), cache.vq.data_ptr(), cache.stage.data_ptr(), kn.data_ptr(), vn.data_ptr(), B,
+                                      cache.capacity, D, L - 1, 1, ctypes.addressof(cache._pa), ctypes.addressof(cache._pb), None, sp)
+        rc = rc or lib.mi355q_bfp_attention_decode(q.data_ptr(), cache.kq.data_ptr(), cache.vq.data_ptr(), 1, 0.0, scale_div, out.data_ptr(),
+                                                   ws.data_ptr(), B, 1, L, cache.capacity, D, ctypes.addressof(cache._pa),
+                                                   ctypes.addressof(cache._pb), None, 0, sp)
+        assert rc == 0, rc
+    return step
+
+
+def ragged(args):
+    import torch
+    from mi355q import ops
+    dev, B, M = "cuda:0", 32, 1
+    i32 = lambda xs: torch.tensor(list(xs), dtype=torch.int32, device=dev)
+    base = _baseline_step(args.baseline_lib) if args.baseline_lib else None
+    lines = []
+    stream = torch.cuda.Stream()
+    for D in (64, 128):
+        for case, L in (("equal", 512), ("equal", 2048), ("equal", 4096), ("mixed", 4096)):
+            lens = [L] * B if case == "equal" else [L] + [512] * (B - 1)
+            n_sets = int(CACHE_BYTES // (sum(lens) * D * 4)) + 2
+            calls = max(args.calls, n_sets)
+            g = torch.Generator(device=dev).manual_seed(L + D)
+            before, after, zeros = i32([n - 1 for n in lens]), i32(lens), i32([0] * B)
+            sets = []
+            for _ in range(n_sets):
+                k, v = (torch.randn(B, L, D, device=dev, generator=g) for _ in range(2))
+                own = ops.KVCache(B, L, D, PAR, PAR, dev)                    # every row at its own length
+                own.append(k, v, lengths=zeros, counts=after, max_length=0)
+                if case == "mixed":                                            # the padded batch: every row at L
+                    full = ops.KVCache(B, L, D, PAR, PAR, dev)
+                    full.append(k, v)
+                else:
+                    full = own
+                last = torch.tensor([n - 1 for n in lens], device=dev)[:, None, None].expand(B, 1, D)
+                sets.append((own, full, k.gather(1, last).contiguous(), v.gather(1, last).contiguous(), k[:, L - 1:].clone(), v[:, L - 1:].clone()))
+                del k, v
+            q = torch.randn(B, M, D, device=dev, generator=g)
+            # (the baseline's output and workspace: score tiles + 64 splits' statistics and partial outputs, as ops sizes its own)
+            out = torch.empty(B, M, D, device=dev)
+            ws = torch.empty(B * (L // 16) * 1024 + B * 64 * (128 + (D // 16) * 1024), dtype=torch.uint8, device=dev)
+
+            def step(route, i):
+                own, full, kn, vn, kf, vf = sets[i % n_sets]
+                if route == "ragged":
+                    own.append(kn, vn, lengths=before, max_length=L - 1)
+                    return ops.bfp_attention_decode(q, own, causal=True, scale_div=math.sqrt(D), lengths=after, max_length=L)
+                if route == "baseline_uniform":
+                    return base(full, kf, vf, q, out, ws, L, math.sqrt(D))
+                full.length = L - M
+                full.append(kf, vf)
+                return ops.bfp_attention_decode(q, full, causal=True, scale_div=math.sqrt(D))
+
+            graphs = {}
+            for route in ("uniform", "ragged") + (("baseline_uniform",) if base else ()):
+                stream.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(stream):
+                    for i in range(n_sets):
+                        step(route, i)
+                torch.cuda.current_stream().wait_stream(stream)
+                torch.cuda.synchronize()
+                gr = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gr, stream=stream):
+                    for i in range(calls):
+                        step(route, i)
+                graphs[route] = gr
+            times = _replay(graphs, args.repeats, calls)
+            line = dict(case=case, B=B, D=D, M=M, L=L, keys=sum(lens), splits=ops.decode_splits(B, L, D), sets=n_sets, calls=calls, repeats=args.repeats)
+            for route, t in times.items():
+                line[route + "_us"] = round(statistics.median(t), 2)
+                line[route + "_spread_us"] = round(max(t) - min(t), 2)
+            line["ragged_over_uniform"] = round(line["ragged_us"] / line["uniform_us"], 3)
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+            del graphs, sets
+            torch.cuda.empty_cache()
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text("".join(json.dumps(l) + "\n" for l in lines))
+
+
 def main():
     import torch
     from mi355q import ops
@@ -29,7 +147,11 @@ def main():
     ap.add_argument("--calls", type=int, default=60)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--ragged", action="store_true", help="per-row lengths against the uniform route (module docstring)")
+    ap.add_argument("--baseline-lib", default=None, help="--ragged: another build of libmi355q.so whose uniform route is timed alongside")
     args = ap.parse_args()
+    if args.ragged:
+        return ragged(args)
     dev, B = "cuda:0", 32
     lines = []
     stream = torch.cuda.Stream()
