@@ -78,10 +78,10 @@ def _quantised_kv(k, v, width):
     return np.ascontiguousarray(np.swapaxes(kq, 1, 2)), vq
 
 
-@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("D", [32, 64, 96, 128])
 @pytest.mark.parametrize("width", [4, 6, 9])
 def test_cache_is_the_oracles_quantiser_bit_for_bit(D, width):
-    """keys appended in pieces: after every piece the cache holds what block_fp_quantize makes of k^T[:, :, :L] (16-key blocks, the open
+    """(D = 32, 96: the append's 8 and 2 tiles per workgroup, the latter with idle threads.)  keys appended in pieces: after every piece the cache holds what block_fp_quantize makes of k^T[:, :, :L] (16-key blocks, the open
     one re-quantised) and of v[:, :L]; one append of everything gives the same bytes"""
     import torch
     from mi355q import ops

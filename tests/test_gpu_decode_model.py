@@ -128,6 +128,83 @@ def test_two_layers_cache_route_matches_the_reference_route(family):
     assert _rel(la.cpu().numpy(), lb.cpu().numpy()) <= bound
 
 
+# ---- the decode step on packed weights: mi355q_small_m = "packed" on mi355q_weight_storage = "packed" ------------------------------
+PACKED = dict(W6, mi355q_weight_storage="packed", mi355q_small_m="packed", mi355q_mixed=False)
+KEY_OFF = dict(W6, mi355q_weight_storage="packed", mi355q_mixed=False)
+LINEARS_A_LAYER = dict(llama=7, opt=6)                    # q, k, v, o, gate, up, down / q, k, v, out, fc1, fc2: K in {128, 256}
+
+
+def _layer_linears(model):
+    """the quantised Linears of the decoder layers (the head is an unquantised nn.Linear)"""
+    return [m for layer in model.layers for m in layer.modules() if hasattr(m, "_small_m_takes")]
+
+
+def _assert_packed(linears):
+    for l in linears:
+        assert l._w_packed is not None and l._mixed is None, f"a Linear {l.in_features} -> {l.out_features} keeps no packed weights"
+
+
+def _teacher_forced_on_the_packed_route(model, ids, family, layers):
+    """_teacher_forced(mode "block_fp") with the route asserted: the prompt's 2 x 21 rows take the tile GEMMs and leave every
+    Linear of the layers with packed weights; every decode step launches the small-batch product once a Linear, no more, no less"""
+    import torch
+    from mi355q import harness as H
+    from mi355q import ops
+    linears = _layer_linears(model)
+    assert len(linears) == layers * LINEARS_A_LAYER[family]
+    state = H.DecodeState(model, ids.shape[0], ids.shape[1], "block_fp")
+    with torch.no_grad():
+        before = ops.small_m_calls()
+        out = [model(ids[:, :PROMPT], cache=state)[0][:, -1]]
+        assert ops.small_m_calls() == before, "more than 16 rows took the small-batch route"
+        _assert_packed(linears)
+        for t in range(PROMPT, PROMPT + STEPS):
+            before = ops.small_m_calls()
+            out.append(model(ids[:, t:t + 1], cache=state)[0][:, -1])
+            assert state.length == t + 1
+            assert ops.small_m_calls() - before == len(linears), (t, ops.small_m_calls() - before, len(linears))
+    return torch.stack(out, 1).cpu().numpy()
+
+
+@pytest.mark.parametrize("family", ["llama", "opt"])
+def test_one_layer_steps_on_packed_weights_match_the_oracles_full_forward(family):
+    """test_one_layer_steps_match_the_oracles_full_forward with every projection of the decode steps on the small-batch product
+    that reads width-bit packed weights in place (K = 128 and 256: one partial chunk, one wave), feeding the block_fp cache and the
+    decode attention: every step's logits within 1e-3 * max(1, max|ref|) of the oracle's last-position logits on ids[:t + 1]"""
+    _, oracle = _model(family, 1)
+    model, _ = _model(family, 1, d=PACKED)                # (the same seed: the same weights)
+    ids = _ids()
+    ref = _oracle_steps(oracle, ids)
+    got = _teacher_forced_on_the_packed_route(model.to(DEV), ids.to(DEV), family, 1)
+    for s in range(STEPS + 1):
+        err = _rel(got[:, s], ref[:, s])
+        print(family, "packed route, step", s, "rel", err)
+        assert err < 1e-3, (s, err)
+
+
+@pytest.mark.parametrize("family", ["llama", "opt"])
+def test_two_layers_packed_route_matches_the_key_off_model(family):
+    """Two layers, mode "block_fp": the packed-route model against the model of the same weights and storage without the
+    mi355q_small_m key, at every step.  The bound is the one test_two_layers_cache_route_matches_the_reference_route forms: e1 = the
+    worst relative logit difference of the mode "fp32" route from the oracle on the one-layer model, measured here; 2 e1, floor 1e-3,
+    times max(1, max|ref|).  Both figures are printed."""
+    m1, oracle1 = _model(family, 1)
+    ids = _ids()
+    ref1 = _oracle_steps(oracle1, ids)
+    e1 = max(_rel(a, b) for a, b in zip(np.moveaxis(_teacher_forced(m1.to(DEV), ids.to(DEV), "fp32"), 1, 0), np.moveaxis(ref1, 1, 0)))
+    bound = max(2 * e1, 1e-3)
+    packed, _ = _model(family, 2, d=PACKED)
+    off, _ = _model(family, 2, d=KEY_OFF)
+    a = _teacher_forced_on_the_packed_route(packed.to(DEV), ids.to(DEV), family, 2)
+    from mi355q import ops
+    before = ops.small_m_calls()
+    b = _teacher_forced(off.to(DEV), ids.to(DEV), "block_fp")
+    assert ops.small_m_calls() == before, "the key-off model took the small-batch route"
+    worst = max(_rel(a[:, s], b[:, s]) for s in range(STEPS + 1))
+    print(family, "one-layer fp32 route vs oracle", e1, "bound", bound, "two-layer packed route vs key off", worst)
+    assert worst <= bound, (worst, bound)
+
+
 def test_declines():
     """a block_minifloat model has no block_fp cache (ValueError naming the reason); the "fp32" route serves it and matches the
     model's own full forward at the last position, one layer, within 5e-4 * max(1, max|ref|) -- the tolerance of

@@ -88,10 +88,10 @@ APPENDS = ([0, 0, 15, 16, 20, 10],      # a tile filled but for one key (15), fi
 FINAL = [0, 1, 16, 17, 33, 40]
 
 
-@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("D", [32, 64, 96, 128])
 @pytest.mark.parametrize("width", [4, 6, 9])
 def test_cache_rows_are_the_one_row_caches_bit_for_bit(D, width):
-    """three ragged appends; after each, row b's quantised K and V (as uint32) and its staged rows are those of a uniform one-row
+    """(D = 32, 96: the ragged append at 8 and 2 tiles per workgroup.)  three ragged appends; after each, row b's quantised K and V (as uint32) and its staged rows are those of a uniform one-row
     cache fed the same keys by the existing append; a row with count 0 keeps its bytes; input rows behind a row's count are NaN
     and never arrive"""
     import torch
@@ -156,11 +156,14 @@ def _case(M, D):
 
 
 @pytest.mark.parametrize("splits", [None, 1, 4])
-@pytest.mark.parametrize("D", [64, 128])
-@pytest.mark.parametrize("M", [1, 16])
+@pytest.mark.parametrize("D", [32, 64, 96, 128])
+@pytest.mark.parametrize("M", [1, 7, 16])
 def test_ragged_decode_vs_oracle_row_by_row(M, D, splits):
     """B = 8, lengths M (or 16), 16, 17, 31, 32, 33, 100, 257: every row against the oracle on ITS keys.  Four splits over
-    max_length = 257 (nine key pairs -> three splits of three pairs): every row but the last has entirely empty splits."""
+    max_length = 257 (nine key pairs -> three splits of three pairs): every row but the last has entirely empty splits.
+    D = 32 and 96 are the ragged kernels' one- and three-chunk instantiations; M = 7 puts each row's causal horizon L_b - 7 + i
+    inside, at and across tile and pair edges (rows of 7, 16, 17, 31, 32, 33, 100, 257 keys) with the query columns 7 .. 15 of
+    the MFMA tiles clamped."""
     import torch
     from mi355q import ops
     q, k, v, lengths, ref, cache = _case(M, D)
@@ -169,6 +172,32 @@ def test_ragged_decode_vs_oracle_row_by_row(M, D, splits):
     assert np.isfinite(out).all()
     for b, L in enumerate(lengths):
         print("row", b, "length", L, end=": ")
+        _check(out[b], ref[b])
+
+
+@functools.lru_cache(maxsize=None)
+def _case_noncausal(M, D):
+    """the same rows, the OPT form: q * D^-0.5 in front of the quantiser, every key of the row visible to every query"""
+    q, k, v, lengths, _, cache = _case(M, D)
+    scaling = np.float32(D ** -0.5)
+    ref = [_oracle(q[b:b + 1] * scaling, k[b:b + 1, :L], v[b:b + 1, :L], _cfg(6), _cfg(6), causal=False)[0] for b, L in enumerate(lengths)]
+    for a in ref:
+        a.setflags(write=False)
+    return q, lengths, ref, cache, float(scaling)
+
+
+@pytest.mark.parametrize("splits", [None, 4])
+@pytest.mark.parametrize("D", [32, 128])
+def test_ragged_noncausal_decode_with_q_scale_vs_oracle_row_by_row(D, splits):
+    """causal=False, q_scale = D^-0.5, M = 7, the lengths above: every row against the oracle on ITS keys, the bounds above"""
+    import torch
+    from mi355q import ops
+    q, lengths, ref, cache, scaling = _case_noncausal(7, D)
+    out = ops.bfp_attention_decode(torch.from_numpy(q).to(DEV), cache, causal=False, q_scale=scaling, splits=splits,
+                                   lengths=_i32(lengths), max_length=257).cpu().numpy()
+    assert np.isfinite(out).all()
+    for b, L in enumerate(lengths):
+        print("non-causal row", b, "length", L, end=": ")
         _check(out[b], ref[b])
 
 
@@ -205,13 +234,12 @@ def test_equal_lengths_give_the_uniform_kernels_bits(L, splits):
     assert torch.equal(same.kq, cache.kq) and torch.equal(same.vq, cache.vq)
 
 
-@pytest.mark.parametrize("M", [1, 3])
-def test_one_split_rows_equal_the_one_row_uniform_decode(M):
+@pytest.mark.parametrize("M,D", [pytest.param(1, 64, id="1"), pytest.param(3, 64, id="3"), pytest.param(7, 96, id="7-D96")])
+def test_one_split_rows_equal_the_one_row_uniform_decode(M, D):
     """splits = 1: row b's bytes are those of the uniform kernel on a one-row cache of length L_b (with more splits an empty split's +0
     partial output can turn a -0 into +0: those cases are held to the oracle above)"""
     import torch
     from mi355q import ops
-    D = 64
     q, k, v = _inputs(8, M, 257, D, seed=M)
     lengths = _lengths(M)
     cache = _ragged_cache(k, v, lengths, capacity=272)

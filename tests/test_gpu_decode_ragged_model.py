@@ -91,25 +91,25 @@ def _padded(rows):
     return ids
 
 
-@pytest.mark.parametrize("family", ["llama", "opt"])
-def test_every_sequence_of_a_ragged_batch_decodes_as_if_alone(family):
-    """Two layers.  Each prompt alone through generate(..., "block_fp"); then the three together, teacher-forced with the alone
-    runs' tokens: at every step each row's logits agree with its alone run within the bound above (not bitwise: the Linears' route
-    depends on the batch's shape).  The rows are 5 .. 16, 16 .. 27 and 23 .. 34 keys long: they fill, start and cross a 16-key
-    block, and cross the 32-key pair, at different steps.  Then generate() on the list of prompts.
-    Measured on an MI355X: one-layer fp32 route against the oracle 4.4e-7 (llama), 3.9e-7 (opt), so the bound is its floor 1e-3;
-    ragged batch against the alone runs, worst over rows and steps, 2.0e-7 (llama), 1.7e-7 (opt)."""
+def _as_if_alone(family, model, what, linears=None):
+    """the property below on `model`; `linears` (the layers' quantised Linears, for a model on the packed small-batch route): the ragged
+    prefill's 3 x 23 rows take the tile GEMMs and leave every one of them with packed weights, and every decode step launches the
+    small-batch product exactly once a Linear"""
     import torch
     from mi355q import harness as H
+    from mi355q import ops
     e1, bound = _bound(family)
-    model, _ = _model(family, 2)
-    model = model.to(DEV)
     prompts = _prompts()
     alone = [H.generate(model, p[None], STEPS, "block_fp") for p in prompts]
     state = H.DecodeState(model, len(LENS), max(LENS) + STEPS, "block_fp")
     worst = 0.0
     with torch.no_grad():
+        calls = ops.small_m_calls()
         out = model(_padded(prompts), cache=state, counts=list(LENS))[0]
+        if linears is not None:
+            assert ops.small_m_calls() == calls, "more than 16 rows took the small-batch route"
+            for l in linears:
+                assert l._w_packed is not None and l._mixed is None, f"a Linear {l.in_features} -> {l.out_features} keeps no packed weights"
         step = torch.stack([out[b, n - 1] for b, n in enumerate(LENS)])
         for s in range(STEPS):
             assert state.lengths == [n + s for n in LENS]
@@ -119,8 +119,11 @@ def test_every_sequence_of_a_ragged_batch_decodes_as_if_alone(family):
                 assert err <= bound, (family, "step", s, "row", b, err, bound)
             if s + 1 < STEPS:
                 tok = torch.stack([alone[b][0][0, n + s] for b, n in enumerate(LENS)])[:, None]
+                calls = ops.small_m_calls()
                 step = model(tok, cache=state, counts=[1] * len(LENS))[0][:, -1]
-    print(family, "one-layer fp32 route vs oracle", e1, "bound", bound, "ragged batch vs alone, worst over rows and steps", worst)
+                if linears is not None:
+                    assert ops.small_m_calls() - calls == len(linears), (s, ops.small_m_calls() - calls, len(linears))
+    print(family, what, "one-layer fp32 route vs oracle", e1, "bound", bound, "ragged batch vs alone, worst over rows and steps", worst)
     assert all(c.length == 0 for c in state.kv)                 # the caller -- the state -- owns the lengths
     # generate on the list
     rows, logits = H.generate(model, prompts, STEPS)
@@ -132,6 +135,34 @@ def test_every_sequence_of_a_ragged_batch_decodes_as_if_alone(family):
         assert gap > bound * max(1.0, float(first.abs().max())), f"row {b}: top-2 gap {gap} of the alone run: pick another seed"
         assert torch.equal(rows[b][:n], prompts[b]) and int(rows[b][n]) == int(alone[b][0][0, n]), f"row {b}: first new token differs"
         assert _rel(logits[b, 0].cpu().numpy(), first.cpu().numpy()) <= bound
+
+
+@pytest.mark.parametrize("family", ["llama", "opt"])
+def test_every_sequence_of_a_ragged_batch_decodes_as_if_alone(family):
+    """Two layers.  Each prompt alone through generate(..., "block_fp"); then the three together, teacher-forced with the alone
+    runs' tokens: at every step each row's logits agree with its alone run within the bound above (not bitwise: the Linears' route
+    depends on the batch's shape).  The rows are 5 .. 16, 16 .. 27 and 23 .. 34 keys long: they fill, start and cross a 16-key
+    block, and cross the 32-key pair, at different steps.  Then generate() on the list of prompts.
+    Measured on an MI355X: one-layer fp32 route against the oracle 4.4e-7 (llama), 3.9e-7 (opt), so the bound is its floor 1e-3;
+    ragged batch against the alone runs, worst over rows and steps, 2.0e-7 (llama), 1.7e-7 (opt)."""
+    model, _ = _model(family, 2)
+    _as_if_alone(family, model.to(DEV), "default route:")
+
+
+PACKED = dict(W6, mi355q_weight_storage="packed", mi355q_small_m="packed", mi355q_mixed=False)
+
+
+@pytest.mark.parametrize("family", ["llama", "opt"])
+def test_every_sequence_of_a_ragged_batch_on_packed_weights_decodes_as_if_alone(family):
+    """The same property, the same bound, with every projection of the decode steps (3 rows a call) on the small-batch product that
+    reads width-bit packed weights in place (mi355q_small_m = "packed" on mi355q_weight_storage = "packed"), feeding the ragged
+    cache append and the ragged decode attention.  The alone runs of the 5- and 16-token prompts take that product in their
+    prefill as well (at most 16 rows)."""
+    model, _ = _model(family, 2, d=PACKED)
+    model = model.to(DEV)
+    linears = [m for layer in model.layers for m in layer.modules() if hasattr(m, "_small_m_takes")]
+    assert len(linears) == 2 * dict(llama=7, opt=6)[family]
+    _as_if_alone(family, model, "packed small-batch route:", linears)
 
 
 def _cache_bytes(state):

@@ -64,3 +64,60 @@ def test_ops_constants_and_module_key_default():
     assert not lin._small_m_takes(torch.zeros(1, 64))        # key absent: off
     lin2 = Q.get_quantized_cls("linear", dict(cfg, mi355q_small_m="packed"))(64, 32, bias=True, config=dict(cfg, mi355q_small_m="packed"))
     assert not lin2._small_m_takes(torch.zeros(1, 64))       # nothing packed: the old routes
+
+
+# ---- the launch geometry of launch_bfp_gemm_packed_small (csrc/mi355q_gemv.hip), restated -----------------------------------------
+GEMV_MAX_WAVES, GEMV_MAX_WAVES_SLOW, GEMV_CHUNK_BLOCKS = 16, 8, 32
+
+
+def geometry(K: int):
+    """K -> (fast, nchunks, chunks_per_wave, waves, last chunk partial): chunks of 512 values, K % 128 == 0 the fast path with up
+    to 16 waves, other K % 64 == 0 the halfword path with up to 8"""
+    assert K > 0 and K % 64 == 0
+    nkb = K // 16
+    nchunks = -(-nkb // GEMV_CHUNK_BLOCKS)
+    fast = K % 128 == 0
+    max_waves = GEMV_MAX_WAVES if fast else GEMV_MAX_WAVES_SLOW
+    cpw = -(-nchunks // max_waves)
+    return fast, nchunks, cpw, -(-nchunks // cpw), nkb % GEMV_CHUNK_BLOCKS != 0
+
+
+def test_restated_geometry_reads_the_sources_constants():
+    src = (ROOT / "llm-mixed-q_amd" / "csrc" / "mi355q_gemv.hip").read_text()
+    for name, value in (("GEMV_MAX_WAVES", GEMV_MAX_WAVES), ("GEMV_MAX_WAVES_SLOW", GEMV_MAX_WAVES_SLOW), ("GEMV_CHUNK_BLOCKS", GEMV_CHUNK_BLOCKS)):
+        assert re.search(rf"constexpr int {name} = {value};", src), name
+    assert geometry(4096) == (True, 8, 1, 8, False) and geometry(11008) == (True, 22, 2, 11, True)      # (what the older tests reach)
+    assert geometry(320) == (False, 1, 1, 1, True)
+    assert geometry(8192) == (True, 16, 1, 16, False) and geometry(8704) == (True, 17, 2, 9, False)
+    assert geometry(16896) == (True, 33, 3, 11, False) and geometry(4160) == (False, 9, 2, 5, True)
+
+
+def test_the_gpu_path_tables_k_list_hits_every_geometry_class():
+    """every class of tests/test_gpu_small_m_paths.py's table, from its K lists: an edit of a list that empties a class fails here,
+    on the CPU"""
+    from tests import test_gpu_small_m_paths as P
+    from mi355q import ops
+    fast = [geometry(K) for K in P.FAST_K]
+    slow = [geometry(K) for K in P.HALF_K]
+    assert all(g[0] for g in fast) and not any(g[0] for g in slow), "a K on the wrong path's list"
+    classes = {
+        "fast: one partial chunk, one wave": any(g[1:] == (1, 1, 1, True) for g in fast),
+        "fast: full chunk(s) then a partial one": any(g[1] > 1 and g[4] for g in fast),
+        "fast: 16 waves, one chunk each": any(g[2:4] == (1, 16) for g in fast),
+        "fast: two chunks a wave": any(g[2] == 2 for g in fast),
+        "fast: three or more chunks a wave": any(g[2] >= 3 for g in fast),
+        "fast: a last wave with fewer chunks than the others": any(g[1] % g[2] for g in fast),
+        "halfword: the smallest K": 64 in P.HALF_K,
+        "halfword: a full chunk taken masked": any(g[1] > 1 for g in slow),
+        "halfword: a tail with a half-filled lane group": any((K // 16) % 32 % 8 == 4 for K in P.HALF_K),
+        "halfword: several waves, more than one chunk each": any(g[2] > 1 and g[3] > 1 for g in slow),
+        "a K beyond the row format (per-block flavour only)": any(not ops.row_align_supported(K) for K in P.FAST_K),
+    }
+    assert all(classes.values()), [k for k, v in classes.items() if not v]
+    assert set(P.WIDTH_K) <= set(P.FAST_K) | set(P.HALF_K) and any(geometry(K)[2:4] == (1, 16) for K in P.WIDTH_K)
+    assert any(not geometry(K)[0] for K in P.WIDTH_K) and set(P.WIDTHS_ONCE) | set(P.WIDTHS) == set(range(2, 9))
+    for K in P.REPRODUCIBLE_K:                               # the two wave reductions: 16 fast waves, several halfword waves
+        assert geometry(K)[3] > 1
+    assert {geometry(K)[0] for K in P.REPRODUCIBLE_K} == {True, False} and any(geometry(K)[3] == 16 for K in P.REPRODUCIBLE_K)
+    assert geometry(P.N_EDGE_K)[0] and P.N_EDGE_K <= 4096 and ops.row_align_supported(P.N_EDGE_K)
+    assert any(N < 16 for N in P.N_EDGES) and any(N % 16 and N > 256 for N in P.N_EDGES) and any(N % 16 and 16 < N < 256 for N in P.N_EDGES)
