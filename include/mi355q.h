@@ -648,6 +648,23 @@ int mi355q_bfp_attention_decode_ragged(const float* q, const void* kq, const voi
                                        int64_t max_length, int64_t C, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
                                        const int64_t* strides, int32_t splits, void* stream);
 
+/* Chunked prefill: the core (modeling_llama.py:309-344; modeling_opt.py:246-312) for ANY number of new tokens behind the cache --
+ * the reference's `past_key_value` call with n new tokens and a past of L - n (modeling_llama.py:301-344: K^T quantised over all L
+ * keys, which the append has done, open block included; the mask with the offset of modeling_llama.py:53-79).  q fp32 [B, M, D],
+ * 1 <= M <= max_length <= C, no other bound on M (else MI355Q_E_UNSUPPORTED / MI355Q_E_BADARG as for the ragged decode).
+ * Row b holds L_b = lengths[b] keys, its queries' own keys included (append first), and asks m_b = counts[b] queries,
+ * q[b, 0 .. m_b - 1]: its last m_b positions.  `lengths` / `counts`: int32 [B] on the device, 4-byte aligned; lengths == NULL is
+ * the uniform form L_b = max_length, counts == NULL is m_b = M (counts without lengths: MI355Q_E_BADARG).  L_b is clamped to
+ * max_length, m_b to M; the host's M and max_length size the grid and never decide what is addressed.  causal != 0: query i sees
+ * keys 0 .. L_b - m_b + i, else all L_b.  Output rows i >= m_b are written as zeros; a row with m_b == 0 or m_b > L_b -- an empty
+ * slot -- reads nothing and returns zeros.  q_scale / scale_div / strides as in mi355q_bfp_attention_decode; no additive mask, no
+ * workspace: a workgroup (one row, up to 64 queries) walks the key tiles twice, statistics first, and the same inputs give the
+ * same bits on every run.  A row's result does not depend on the other rows. */
+int mi355q_bfp_attention_extend(const float* q, const void* kq, const void* vq, const int32_t* lengths, const int32_t* counts,
+                                int32_t causal, float q_scale, float scale_div, float* out, int64_t B, int64_t M, int64_t max_length,
+                                int64_t C, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
+                                void* stream);
+
 /* ---- the un-blocked quantisers -------------------------------------------------------------------------------------
  * replaces: quantizers/minifloat.py:134-196 (minifloat_ieee_quantizer: implicit leading one, subnormals at the lowest
  *           exponent), :21-86 (minifloat_denorm_quantizer: no implicit one, exponent ceil(log2(|x| + 1e-9)) per element)

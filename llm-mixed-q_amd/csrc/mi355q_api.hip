@@ -13,6 +13,7 @@
 #include "mi355q_internal.h"
 #include "mi355q_gemv.h"
 #include "mi355q_decode.h"
+#include "mi355q_extend.h"
 #include "mi355q_align_row.h"
 
 using namespace mi355q;
@@ -1163,6 +1164,32 @@ int mi355q_bfp_attention_decode_ragged(const float* q, const void* kq, const voi
     const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
     return launch_bfp_attention_decode(aq, ap, c, q, out, workspace, M, max_length, causal != 0, q_scale, scale_div,
                                        strides ? st4 : nullptr, splits, static_cast<hipStream_t>(stream), lengths);
+}
+
+// ---- chunked prefill: any number of queries per row behind the cache (mi355q_extend.h) ------------------------------------
+int mi355q_bfp_attention_extend(const float* q, const void* kq, const void* vq, const int32_t* lengths, const int32_t* counts,
+                                int32_t causal, float q_scale, float scale_div, float* out, int64_t B, int64_t M, int64_t max_length,
+                                int64_t C, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
+                                void* stream) {
+    if (M < 0 || max_length < 0) return MI355Q_E_BADARG;
+    int rc = decode_cache_shape(B, C, D);
+    if (rc) return rc;
+    if (M < 1 || max_length < M) return MI355Q_E_UNSUPPORTED;
+    if (max_length > C || !q || !kq || !vq || !out || !qk_params || !pv_params || (counts && !lengths)) return MI355Q_E_BADARG;
+    QuantArgs aq{}, ap{};
+    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) |
+         reinterpret_cast<uintptr_t>(out)) % 16 || (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(counts)) % 4)
+        return MI355Q_E_ALIGN;
+    long long st4[4];
+    if (strides)
+        for (int i = 0; i < 4; ++i) {
+            if (strides[i] % 4) return MI355Q_E_ALIGN;
+            st4[i] = strides[i];
+        }
+    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
+    return launch_bfp_attention_extend(aq, ap, c, q, out, M, max_length, causal != 0, q_scale, scale_div, strides ? st4 : nullptr,
+                                       lengths, counts, static_cast<hipStream_t>(stream));
 }
 
 // block_minifloat (fmt 1) / block_log (fmt 2) products: the same two kernels with the other quantisers' block parameters

@@ -1,0 +1,229 @@
+// mi355q_extend.hip -- chunked prefill: the quantised attention core for any number of new tokens behind a block_fp KV cache.
+//
+// The reference's `past_key_value` route (models/llama_quantized/modeling_llama.py:301-344, the same in modeling_opt.py) takes n new
+// tokens behind a past of L - n: K^T is quantised over all L keys (the append has done that, open block included), the mask has the
+// offset of modeling_llama.py:53-79.  The decode kernels (mi355q_decode.hip) serve n <= 16 with a score workspace of 1 KiB per
+// (row, key tile, query tile); for a chunk of hundreds of queries that is gigabytes, so this kernel keeps no scores: it is
+// bfp_attention_stream_kernel (mi355q_attention.hip) on the cache's fragments.
+//   A workgroup is one (row b, block of up to 64 queries), a wave 16 queries (the 16 columns of v_mfma_f32_16x16x32_bf16).  The four
+//   waves walk the key tiles together, 32 keys a step; the step's K pieces (and, in pass 2, the V pieces of the key pair) come into
+//   LDS by LDS-DMA one step ahead, one barrier a step.  Pass 1 keeps a running maximum and sum of exponentials per lane over the
+//   VISIBLE keys; pass 2 forms the scores again from the same operands (the same bits), turns them into probabilities with the final
+//   statistics, quantises per block of 16 keys of a query, multiplies with V.  No workspace, no exchange between waves.
+// Per-row scalars (L_b, m_b) are read once a workgroup and stay scalar; everything that decides the step count is scalar, so all four
+// waves reach every barrier the same number of times.  What the stream kernel leaves open and this one closes:
+//   out-of-row reads   a K piece is addressed at tile min(t, need - 1), need <= ceil(L_b / 16) <= C / 16: never a tile of the next row
+//                      or behind the allocation (kv_k_bytes has no slack); the clamped piece's scores are discarded (t >= need).
+//                      V pairs: st < ceil(need / 2) <= ceil(C / 32).
+//   divergent barriers the step count comes from the workgroup's LAST REAL query; a wave whose 16 queries lie behind m_b computes the
+//                      last real query again and stores zeros.  A workgroup wholly behind m_b stores zeros and leaves before the
+//                      first barrier.
+//   missing V pieces   the last pair's second tile may not exist (t >= need): its probabilities are exact zeros, the stored V there
+//                      is finite (zeroed storage or older quantised values).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mi355q.h"
+#include "mi355q_internal.h"
+#include "mi355q_quant_dev.h"
+#include "mi355q_attn_dev.h"
+#include "mi355q_extend.h"
+
+namespace mi355q {
+
+template <int DC>
+__global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantArgs aq, const QuantArgs ap, const ExtendArgs g) {
+    constexpr int DT = DC * 2, KSTEP = 2 * DC * 1024, VSTEP = DT * 1024, STEP = KSTEP + VSTEP;      // bytes per 32 keys
+    using gptr_t = const __attribute__((address_space(1))) void*;
+    using lptr_t = __attribute__((address_space(3))) void*;
+    __shared__ __attribute__((aligned(16))) unsigned char stage[2][STEP];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c16 = lane & 15, lg = lane >> 4;
+    // work items (query block, row) in one grid dimension, the heaviest query block of every row first (causal: the last one)
+    const int xrank = (int)blockIdx.x / g.nb;
+    const long long b = (int)blockIdx.x - xrank * g.nb;
+    const long long wg0 = (long long)(g.causal ? g.nxb - 1 - xrank : xrank) * 64;
+    const long long m0 = wg0 + 16 * wave;
+    // the row's keys and queries: one scalar load each a workgroup
+    long long L = g.L, m = g.M;
+    if (g.lengths) L = min((long long)max(__builtin_amdgcn_readfirstlane(g.lengths[b]), 0), g.L);
+    if (g.counts) m = min((long long)max(__builtin_amdgcn_readfirstlane(g.counts[b]), 0), g.M);
+    if (m > L) m = 0;                                       // (an empty slot: zeros, no fragment read)
+    float* __restrict__ op = g.out + b * g.osb + (m0 + c16) * g.osm + 4 * lg;
+    if (wg0 >= m) {                                         // wholly behind the row's queries: zeros, before the first barrier
+        if (m0 + c16 < g.M) {
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) *reinterpret_cast<float4*>(op + 16 * dt) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        return;
+    }
+    const long long qrow = min(m0 + c16, m - 1);            // (a lane behind m_b repeats the last real query; it stores zeros)
+    // Q fragments, quantised in registers: lane (query c16, g) holds d = 32 c + 8 g .. + 7
+    bf16x8 qf[DC];
+    {
+        const int mb = (int)__builtin_log2f(aq.shift);
+        const float* __restrict__ qp = g.q + b * g.qsb + qrow * g.qsm;
+#pragma unroll
+        for (int c = 0; c < DC; ++c) {
+            float4 lo = *reinterpret_cast<const float4*>(qp + 32 * c + 8 * lg);
+            float4 hi = *reinterpret_cast<const float4*>(qp + 32 * c + 8 * lg + 4);
+            if (g.q_scale != 0.f) {
+                lo.x *= g.q_scale; lo.y *= g.q_scale; lo.z *= g.q_scale; lo.w *= g.q_scale;
+                hi.x *= g.q_scale; hi.y *= g.q_scale; hi.z *= g.q_scale; hi.w *= g.q_scale;
+            }
+            float bmax = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fmaxf(fabsf(lo.z), fabsf(lo.w))),
+                               fmaxf(fmaxf(fabsf(hi.x), fabsf(hi.y)), fmaxf(fabsf(hi.z), fabsf(hi.w))));
+            bmax = at_max2_16(bmax);
+            const int p = at_block_exponent_mem(bmax, aq);
+            const int up = mb - p, dn = p - mb;
+            uint4 pk;
+            pk.x = pack_bf16(at_quant(lo.x, up, dn, aq.mant_max), at_quant(lo.y, up, dn, aq.mant_max));
+            pk.y = pack_bf16(at_quant(lo.z, up, dn, aq.mant_max), at_quant(lo.w, up, dn, aq.mant_max));
+            pk.z = pack_bf16(at_quant(hi.x, up, dn, aq.mant_max), at_quant(hi.y, up, dn, aq.mant_max));
+            pk.w = pack_bf16(at_quant(hi.z, up, dn, aq.mant_max), at_quant(hi.w, up, dn, aq.mant_max));
+            qf[c] = __builtin_bit_cast(bf16x8, pk);
+        }
+    }
+    // this lane's horizon, and the tiles the WORKGROUP walks: up to the horizon of its last real query (scalar; 1 <= need <= C / 16)
+    const long long kvis = g.causal ? L - m + qrow : L - 1;
+    const long long need = (g.causal ? L - m + min(wg0 + 63, m - 1) : L - 1) / 16 + 1;
+    const int nsteps = (int)((need + 1) / 2);
+    const unsigned char* __restrict__ kfb = reinterpret_cast<const unsigned char*>(g.kq) + b * g.NTC * DC * 1024 + lane * 16;
+    const unsigned char* __restrict__ vfb = reinterpret_cast<const unsigned char*>(g.vq) + b * g.NPC * DT * 1024 + lane * 16;
+    const float scale_inv = g.scale_div != 0.f ? 1.0f / g.scale_div : 0.f;
+
+    // LDS-DMA of one step: the K pieces of tiles 2 st, 2 st + 1 (DC KiB each) and, when with_v, the V pieces of pair st (DT KiB);
+    // piece p by wave p % 4.  An odd tile count: the last step's second tile is tile need - 1 once more, never one behind the row.
+    auto dma = [&](int st, int buf, bool with_v) {
+#pragma unroll
+        for (int p = 0; p < 2 * DC; ++p)
+            if ((p & 3) == wave) {
+                const long long t = min(2ll * st + p / DC, need - 1);
+                __builtin_amdgcn_global_load_lds((gptr_t)(kfb + (t * DC + p % DC) * 1024), (lptr_t)(&stage[buf][p * 1024]), 16, 0, 0);
+            }
+        if (with_v) {
+#pragma unroll
+            for (int p = 0; p < DT; ++p)
+                if ((p & 3) == wave)
+                    __builtin_amdgcn_global_load_lds((gptr_t)(vfb + ((long long)st * DT + p) * 1024), (lptr_t)(&stage[buf][KSTEP + p * 1024]),
+                                                     16, 0, 0);
+        }
+    };
+    // scores of the step's two tiles for this lane's query: sv[h][e] <-> key 32 st + 16 h + 4 lg + e; -inf: not a visible key
+    auto scores = [&](int st, int buf, f32x4 (&sv)[2]) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < DC; ++c) {
+                const uint4 kv = *reinterpret_cast<const uint4*>(&stage[buf][(h * DC + c) * 1024 + lane * 16]);
+                s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kv), qf[c], s, 0, 0, 0);
+            }
+            const long long t = 2ll * st + h, key0 = t * 16 + 4 * lg;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float x = g.scale_div != 0.f ? at_div(s[e], g.scale_div, scale_inv) : s[e];
+                sv[h][e] = (t < need && key0 + e <= kvis) ? x : -INFINITY;
+            }
+        }
+    };
+
+    // ---- pass 1: running maximum and sum of exponentials per lane
+    float m_run = -INFINITY, l_run = 0.f;
+    dma(0, 0, false);
+    for (int st = 0; st < nsteps; ++st) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (st + 1 < nsteps) dma(st + 1, (st + 1) & 1, false);
+        f32x4 sv[2];
+        scores(st, st & 1, sv);
+        const float tmax = fmaxf(fmaxf(fmaxf(sv[0][0], sv[0][1]), fmaxf(sv[0][2], sv[0][3])),
+                                 fmaxf(fmaxf(sv[1][0], sv[1][1]), fmaxf(sv[1][2], sv[1][3])));
+        if (__any(tmax > m_run)) {                          // re-base (exp(-inf) = 0 takes care of the first tile)
+            const float m_new = fmaxf(m_run, tmax);
+            l_run = m_new == -INFINITY ? 0.f : l_run * at_exp_neg(m_run - m_new);
+            m_run = m_new;
+        }
+        float add = 0.f;
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) add += sv[h][e] == -INFINITY ? 0.f : at_exp_neg(sv[h][e] - m_run);
+        l_run += add;
+    }
+    // (every query sees key 0: the row maximum is finite)
+    const float row_max = at_max4(m_run);
+    const float row_sum = at_sum4(m_run == -INFINITY ? 0.f : l_run * at_exp_neg(m_run - row_max));
+    const float row_inv = 1.0f / row_sum;
+    __syncthreads();                                        // (every wave is out of the last step's buffer)
+
+    // ---- pass 2: the scores again, probabilities, quantised, times V
+    f32x4 o[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int mbp = (int)__builtin_log2f(ap.shift);
+    dma(0, 0, true);
+    for (int st = 0; st < nsteps; ++st) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (st + 1 < nsteps) dma(st + 1, (st + 1) & 1, true);
+        f32x4 sv[2];
+        scores(st, st & 1, sv);
+        float pq[8];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            float pr[4];
+            float bmax = 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                pr[e] = sv[h][e] == -INFINITY ? 0.f : at_div(at_exp_neg(sv[h][e] - row_max), row_sum, row_inv);
+                bmax = fmaxf(bmax, pr[e]);
+            }
+            bmax = at_max4(bmax);
+            const int p = at_block_exponent_mem(bmax, ap);
+            const float sc_up = __builtin_ldexpf(1.0f, mbp - p), sc_dn = __builtin_ldexpf(1.0f, p - mbp), eps_up = EPS9 * sc_up;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) pq[4 * h + e] = at_quant_pos(pr[e], sc_up, eps_up, sc_dn, ap.mant_max);
+        }
+        uint4 pk;
+        pk.x = pack_bf16(pq[0], pq[1]); pk.y = pack_bf16(pq[2], pq[3]);
+        pk.z = pack_bf16(pq[4], pq[5]); pk.w = pack_bf16(pq[6], pq[7]);
+        const bf16x8 pf = __builtin_bit_cast(bf16x8, pk);
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) {
+            const uint4 vv = *reinterpret_cast<const uint4*>(&stage[st & 1][KSTEP + dt * 1024 + lane * 16]);
+            o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vv), pf, o[dt], 0, 0, 0);
+        }
+    }
+    if (m0 + c16 < g.M) {
+        const bool real = m0 + c16 < m;                     // (rows behind m_b: zeros)
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+            *reinterpret_cast<float4*>(op + 16 * dt) = real ? make_float4(o[dt][0], o[dt][1], o[dt][2], o[dt][3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+int launch_bfp_attention_extend(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out, long long M,
+                                long long max_length, int causal, float q_scale, float scale_div, const long long* strides,
+                                const int32_t* lengths, const int32_t* counts, hipStream_t st) {
+    ExtendArgs g{};
+    g.q = q; g.kq = c.kq; g.vq = c.vq; g.out = out; g.lengths = lengths; g.counts = counts;
+    g.M = M; g.L = max_length; g.NTC = c.C / 16; g.NPC = (c.C + 31) / 32;
+    g.qsb = strides ? strides[0] : M * c.D; g.qsm = strides ? strides[1] : c.D;
+    g.osb = strides ? strides[2] : M * c.D; g.osm = strides ? strides[3] : c.D;
+    g.causal = causal; g.q_scale = q_scale; g.scale_div = scale_div;
+    const long long nxb = (M + 63) / 64;
+    if (c.B * nxb > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
+    g.nb = (int)c.B; g.nxb = (int)nxb;
+    const dim3 grid((unsigned)(c.B * nxb));
+    switch (c.D / 32) {
+        case 1: hipLaunchKernelGGL(bfp_attention_extend_kernel<1>, grid, dim3(256), 0, st, aq, ap, g); break;
+        case 2: hipLaunchKernelGGL(bfp_attention_extend_kernel<2>, grid, dim3(256), 0, st, aq, ap, g); break;
+        case 3: hipLaunchKernelGGL(bfp_attention_extend_kernel<3>, grid, dim3(256), 0, st, aq, ap, g); break;
+        case 4: hipLaunchKernelGGL(bfp_attention_extend_kernel<4>, grid, dim3(256), 0, st, aq, ap, g); break;
+        default: return MI355Q_E_UNSUPPORTED;
+    }
+    return (int)hipGetLastError();
+}
+
+}  // namespace mi355q

@@ -82,6 +82,8 @@ SIGNATURES = {
     "mi355q_bfp_kv_decode_fp32_ragged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     "mi355q_bfp_attention_decode_ragged": (C.c_int, [_vp, _vp, _vp, _vp, _i32, C.c_float, C.c_float, _vp, _vp, _i64, _i64, _i64, _i64,
                                                      _i64, _vp, _vp, _vp, _i32, _vp]),
+    "mi355q_bfp_attention_extend": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, C.c_float, C.c_float, _vp, _i64, _i64, _i64, _i64, _i64,
+                                              _vp, _vp, _vp, _vp]),
     "mi355q_stream_capture_id": (C.c_uint64, [_vp]),
     "mi355q_rope_apply": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "mi355q_bfp_gemm_aligned": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),

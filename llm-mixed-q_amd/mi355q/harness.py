@@ -452,9 +452,13 @@ class DecodeState:
     layer's append) and "after" it (every layer's decode; 0 for a row that takes no token in this call, which then costs nothing).
     They are shared by all layers and written once a call.  Each sequence decodes as if it were alone: no pad key ever enters a
     block of the cache.  The reference's left padding + attention_mask is NOT reproduced -- under block quantisation a pad key
-    shares a 16-key block with real keys and moves their exponent."""
+    shares a 16-key block with real keys and moves their exponent.
+    extend=True (mode "block_fp"; accepted and ignored by "fp32", which has no limit): chunked prefill.  Calls the default state
+    refuses -- more than 16 new tokens behind a non-empty cache, a mixed call (one row starts its sequence while others continue),
+    unequal counts behind non-empty rows -- run on ops.bfp_attention_extend: one ragged append, one extend call with every row's
+    own length and its own number of queries."""
 
-    def __init__(self, model, batch: int, capacity: int, mode: str = "block_fp"):
+    def __init__(self, model, batch: int, capacity: int, mode: str = "block_fp", extend: bool = False):
         from .quantize.quantized_functions import decode_cache_params
         if mode not in ("block_fp", "fp32"):
             raise ValueError(f"DecodeState: mode {mode!r} is neither 'block_fp' nor 'fp32'")
@@ -462,6 +466,7 @@ class DecodeState:
         if any(getattr(a, "mi355q_head_shard", None) is not None for a in attns):
             raise NotImplementedError("incremental decoding of head-sharded models")
         self.mode, self.batch, self.length = mode, int(batch), 0
+        self.extend = bool(extend) and mode == "block_fp"
         self.lengths, self.ragged, self._call = [0] * self.batch, False, None
         self.capacity = (int(capacity) + 15) // 16 * 16
         if self.capacity > model.cfg.max_positions + 15:
@@ -516,6 +521,8 @@ class DecodeState:
             route = "prefill"
         elif all(before[b] > 0 and counts[b] == n for b in active) and n <= ops.DECODE_MAX_QUERIES:
             route = "decode"
+        elif self.extend:
+            route = "extend"                                   # (mixed, unequal counts, n > 16: every row at its own (length, count))
         elif any(before[b] == 0 for b in active):
             raise NotImplementedError(f"a mixed call: rows {[b for b in active if before[b] == 0]} start a sequence while others continue theirs "
                                       "(prefill and decode in one call)")
@@ -544,6 +551,11 @@ class DecodeState:
         if call["route"] == "decode":
             return get_quantized_func("attention_decode", c1)(q, cache, c0, c1, causal=True, scale_div=scale_div, lengths=self.rows_after,
                                                               max_length=call["max_after"]).reshape(B, nh, n, hd)
+        if call["route"] == "extend":
+            # (max_length bounds the lengths and must hold the n query columns, which may all be padding behind the largest count)
+            return get_quantized_func("attention_extend", c1)(q, cache, c0, c1, causal=True, scale_div=scale_div, lengths=self.rows_after,
+                                                              counts=self._rows_counts, max_length=max(call["max_after"], n)
+                                                              ).reshape(B, nh, n, hd)
         # ragged prefill: every sequence's own queries against its own keys, one call of the existing attention function each (what
         # the sequence alone runs); prefill is not the hot path here
         o = q.new_zeros(B, nh, n, hd)
@@ -563,13 +575,15 @@ class DecodeState:
         if self.mode == "block_fp":
             cache = self.kv[idx]
             assert cache.length == self.length
-            if self.length and n > ops.DECODE_MAX_QUERIES:      # (before the append: a refused call leaves every layer's cache as it was)
+            wide = self.length and n > ops.DECODE_MAX_QUERIES
+            if wide and not self.extend:                        # (before the append: a refused call leaves every layer's cache as it was)
                 raise NotImplementedError(f"{n} new tokens behind a non-empty block_fp cache (at most {ops.DECODE_MAX_QUERIES} a call)")
             cache.append(k, v)
             if self.length == 0:
                 # the prompt's own queries against the prompt: the existing attention function (M = n)
                 return get_quantized_func("attention", c1)(q, k, v, c0, c1, causal=True, scale_div=scale_div).reshape(B, nh, n, hd)
-            return get_quantized_func("attention_decode", c1)(q, cache, c0, c1, causal=True, scale_div=scale_div).reshape(B, nh, n, hd)
+            return get_quantized_func("attention_extend" if wide else "attention_decode", c1)(q, cache, c0, c1, causal=True,
+                                                                                              scale_div=scale_div).reshape(B, nh, n, hd)
         if self.kv[idx] is not None:
             k, v = torch.cat([self.kv[idx][0], k], dim=2), torch.cat([self.kv[idx][1], v], dim=2)
         self.kv[idx] = (k, v)
@@ -633,20 +647,38 @@ def _forward_cached(model, input_ids, labels, state: DecodeState, counts=None):
 
 
 @torch.no_grad()
-def generate(model, prompt_ids, new_tokens: int, mode: str = "block_fp"):
+def generate(model, prompt_ids, new_tokens: int, mode: str = "block_fp", chunk: int = None):
     """greedy decoding: the prompt in one cached call, then one token a call.  Returns (ids [B, prompt + new_tokens], logits
     [B, new_tokens, vocab]: the logits each new token was picked from).
     `prompt_ids` may be a list of 1-D id tensors of DIFFERENT lengths (mode "block_fp"): one ragged prefill, then one token a row a
-    call, every sequence decoded as if it were alone; returns (a list of id tensors [len_b + new_tokens], logits as above)."""
+    call, every sequence decoded as if it were alone; returns (a list of id tensors [len_b + new_tokens], logits as above).
+    `chunk`: chunked prefill -- the prompt goes in calls of at most `chunk` tokens through a state with extend=True; for a list of
+    prompts every call gives each row whatever it has left, up to `chunk`."""
+    if chunk is not None and int(chunk) < 1:
+        raise ValueError(f"generate: chunk = {chunk} < 1")
     if isinstance(prompt_ids, (list, tuple)):
         lens = [int(p.numel()) for p in prompt_ids]
         B, dev = len(lens), prompt_ids[0].device
-        state = DecodeState(model, B, max(lens) + new_tokens, mode)
-        ids = torch.zeros(B, max(lens), dtype=prompt_ids[0].dtype, device=dev)
-        for b, p in enumerate(prompt_ids):
-            ids[b, :lens[b]] = p
-        out = model(ids, cache=state, counts=lens)[0]
-        logits = out[torch.arange(B, device=dev), torch.tensor(lens, device=dev) - 1]      # (each row's last REAL position)
+        state = DecodeState(model, B, max(lens) + new_tokens, mode, extend=chunk is not None)
+        if chunk is None:
+            ids = torch.zeros(B, max(lens), dtype=prompt_ids[0].dtype, device=dev)
+            for b, p in enumerate(prompt_ids):
+                ids[b, :lens[b]] = p
+            out = model(ids, cache=state, counts=lens)[0]
+            logits = out[torch.arange(B, device=dev), torch.tensor(lens, device=dev) - 1]      # (each row's last REAL position)
+        else:
+            done, last = [0] * B, [None] * B
+            while any(d < l for d, l in zip(done, lens)):
+                counts = [min(int(chunk), l - d) for d, l in zip(done, lens)]
+                ids = torch.zeros(B, max(counts), dtype=prompt_ids[0].dtype, device=dev)
+                for b, p in enumerate(prompt_ids):
+                    ids[b, :counts[b]] = p.reshape(-1)[done[b]:done[b] + counts[b]]
+                out = model(ids, cache=state, counts=counts)[0]
+                for b, c in enumerate(counts):
+                    done[b] += c
+                    if c and done[b] == lens[b]:
+                        last[b] = out[b, c - 1]                # (the row's last REAL position, in the call that ends its prompt)
+            logits = torch.stack(last)
         rows, steps = [p.reshape(-1) for p in prompt_ids], []
         for i in range(new_tokens):
             steps.append(logits)
@@ -656,9 +688,11 @@ def generate(model, prompt_ids, new_tokens: int, mode: str = "block_fp"):
                 logits = model(tok, cache=state, counts=[1] * B)[0][:, -1]
         return rows, torch.stack(steps, dim=1)
     B, T = prompt_ids.shape
-    state = DecodeState(model, B, T + new_tokens, mode)
+    state = DecodeState(model, B, T + new_tokens, mode, extend=chunk is not None)
     ids, steps = prompt_ids, []
-    logits = model(prompt_ids, cache=state)[0][:, -1]
+    step = int(chunk) if chunk is not None else max(T, 1)
+    for t0 in range(0, max(T, 1), step):
+        logits = model(prompt_ids[:, t0:t0 + step], cache=state)[0][:, -1]
     for i in range(new_tokens):
         steps.append(logits)
         tok = logits.argmax(-1, keepdim=True)

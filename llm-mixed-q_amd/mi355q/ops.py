@@ -1663,6 +1663,68 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     return out
 
 
+def _extend_check(q, cache, lengths=None, counts=None, max_length=None):
+    """the reasons bfp_attention_extend declines (q, cache), None when it takes them; nothing here touches the device"""
+    if not isinstance(cache, KVCache):
+        return "cache is not a KVCache"
+    if not isinstance(q, torch.Tensor) or q.ndim < 3:
+        return "q must be a tensor [..., M, D]"
+    M, D = q.shape[-2:]
+    if M < 1:
+        return f"M = {M} queries: at least one"
+    if D != cache.D or q.shape[:-2].numel() != cache.B:
+        return f"q {tuple(q.shape)} does not match the cache's B = {cache.B}, D = {cache.D}"
+    if lengths is not None:
+        why = _ragged_check(cache, lengths, counts, max_length, M, "extend")
+        if why is not None:
+            return why
+    elif counts is not None:
+        return "counts without lengths: a row's number of queries belongs to a ragged call (lengths=)"
+    elif max_length is not None:
+        return "max_length belongs to a ragged call (lengths=)"
+    elif cache.length < M:
+        return f"{cache.length} cached keys for {M} queries (the queries' own keys are appended first)"
+    if not q.is_cuda or q.dtype != torch.float32 or q.device != cache.device:
+        return f"fp32 tensors on {cache.device} only (got {q.dtype} on {q.device}); there is no CPU fallback"
+    return None
+
+
+def bfp_attention_extend(q: torch.Tensor, cache: KVCache, *, causal: bool = True, scale_div: float = None, q_scale: float = None,
+                         token_major: bool = False, lengths: torch.Tensor = None, counts: torch.Tensor = None, max_length: int = None):
+    """Chunked prefill: the attention core (modeling_llama.py:309-344) for the LAST M positions -- any M >= 1 -- of a sequence whose
+    L = cache.length keys are in `cache` (their own keys included: append first), the reference's `past_key_value` call with M new
+    tokens behind a past of L - M.  q [..., M, D] fp32; causal: query i sees keys 0 .. L - M + i, else all L.  scale_div / q_scale /
+    token_major as bfp_attention_decode.  One kernel, no workspace: a workgroup walks the keys twice (statistics, then quantised
+    probabilities times V); equal inputs give equal bits.  No additive mask.
+    Ragged (`lengths` int32 [B] on the device: the rows' lengths INCLUDING the queries' own keys; `max_length`: the caller's upper
+    bound on them): row b's queries are ITS last counts[b] positions (`counts` int32 [B] on the device; None: M for every row)
+    against ITS lengths[b] keys, as if the row were alone; output rows behind counts[b] are zeros, and a row with counts[b] == 0
+    or counts[b] > lengths[b] (an empty slot) returns zeros.  cache.length is not used."""
+    import ctypes
+    why = _extend_check(q, cache, lengths, counts, max_length)
+    if why is not None:
+        raise ValueError(f"mi355q.bfp_attention_extend: {why}")
+    M, D = q.shape[-2:]
+    q3, qsb, qsm = _as_heads_view(q)
+    if token_major and q.ndim == 4 and q.shape[0] == 1:
+        H = q.shape[1]
+        out = torch.empty(1, M, H, D, dtype=torch.float32, device=q.device).permute(0, 2, 1, 3)
+        osb, osm = D, H * D
+    else:
+        out = torch.empty(*q.shape, dtype=torch.float32, device=q.device)
+        osb, osm = M * D, D
+    strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
+    with _on_device(q.device):
+        rc = _lib.load_library().mi355q_bfp_attention_extend(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), _ptr(lengths), _ptr(counts),
+                                                             int(bool(causal)), float(q_scale) if q_scale else 0.0,
+                                                             float(scale_div) if scale_div else 0.0, _ptr(out), cache.B, M,
+                                                             int(max_length) if lengths is not None else cache.length, cache.capacity, D,
+                                                             ctypes.addressof(cache._pa), ctypes.addressof(cache._pb),
+                                                             ctypes.addressof(strides), _stream_ptr(q.device))
+    _lib.check(rc, "mi355q_bfp_attention_extend")
+    return out
+
+
 class TiledBf16:
     """quantised activations [rows, cols] as the tiled bf16 operand of the per-block product (block_fp_quantize_bf16_tiled's output with
     its shape): what a producer hands a Linear that runs on that route (`Linear.forward_tiled`)"""

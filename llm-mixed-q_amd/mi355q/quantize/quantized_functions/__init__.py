@@ -283,6 +283,19 @@ def attention_decode_block_fp(q, cache, config_qk, config_pv, causal=True, scale
                                     max_length=max_length)
 
 
+def attention_extend_block_fp(q, cache, config_qk, config_pv, causal=True, scale_div=None, q_scale=None, lengths=None, counts=None,
+                              max_length=None):
+    """The attention core for the last M positions -- any M -- against an `ops.KVCache` that already holds their keys (chunked
+    prefill; the reference's `past_key_value` call with M new tokens, modeling_llama.py:301-344): ops.bfp_attention_extend.
+    Registry key "attention_extend"; no additive mask, no other route.  `lengths` / `counts` / `max_length`: a ragged batch, every
+    cache row at its own length with its own number of queries."""
+    from ... import ops
+    decode_cache_params(config_qk, config_pv, q.shape[-1])
+    return ops.bfp_attention_extend(q, cache, causal=causal, scale_div=scale_div, q_scale=q_scale,
+                                    token_major=bool(config_pv.get("mi355q_token_major_output", False)), lengths=lengths,
+                                    counts=counts, max_length=max_length)
+
+
 def _make(arith, style):
     def f(x, y, config):
         return _generic_matmul(x, y, config, arith, style)
@@ -412,4 +425,5 @@ QUANTIZED_FUNC_MAP = {
 # from it because QUANTIZED_FUNC_MAP's keys are pinned to the reference's ops plus the softmax / attention folds.
 EXTRA_FUNC_MAP = {
     "attention_decode": {"block_fp": attention_decode_block_fp},
+    "attention_extend": {"block_fp": attention_extend_block_fp},
 }
