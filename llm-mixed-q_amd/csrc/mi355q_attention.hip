@@ -307,6 +307,10 @@ __device__ __forceinline__ void at_store_consumer(const AttnConsumer& c, const f
 }
 
 // ---- the attention pass ------------------------------------------------------------------------------------------------
+// (The two kernels of this file keep their OWN code for the Q fragments, the running softmax statistics and the block of
+//  probabilities; the decode and extend kernels share theirs in mi355q_attn_dev.h: at_quant_q_frag, at_softmax_step / _finish,
+//  at_quant_p_block, at_pack_p.  On those helpers the compiler made other code of both kernels here and both measured slower --
+//  DESIGN 7d has the figures.  A change to that arithmetic is made in the helpers AND in both kernels here.)
 // NTW = score tiles per wave (KW = 4: 8, 16, 32 <-> T <= 512, 1024, 2048; KW = 8: half of that), DC = D / 32.
 static unsigned long long* g_attn_stamps = nullptr;     // diagnostic (-DATTN_STAMPS builds)
 struct AttnArgs {

@@ -1,6 +1,12 @@
-// Device helpers shared by the attention kernels (mi355q_attention.hip: prefill; mi355q_decode.hip: KV cache and decode):
-// the block_fp element / shared-exponent arithmetic of the four quantisers, exp and quotient of the softmax, and the
-// reductions over the four lanes that hold one query's values of a 16 x 16 MFMA tile.
+// Device helpers shared by the attention kernels (mi355q_attention.hip: prefill; mi355q_decode.hip: KV cache and decode;
+// mi355q_extend.hip: chunked prefill behind the cache): the block_fp element / shared-exponent arithmetic of the four quantisers,
+// exp and quotient of the softmax, the reductions over the four lanes that hold one query's values of a 16 x 16 MFMA tile -- and,
+// built from those, what the decode and extend kernels do with them: the Q fragments (at_quant_q_frag), a block of probabilities
+// and the P fragment (at_quant_p_block, at_pack_p) and the running softmax statistics (at_softmax_step, at_softmax_finish).
+// The two prefill kernels of mi355q_attention.hip do NOT use these five: they keep the same arithmetic written out (the note at
+// "the attention pass" there), so a change to one of the five is made in those two kernels as well.
+// ExpFn, where a helper takes one: a callable (float bmax, const QuantArgs&) -> int, the shared exponent of a block with that
+// maximum: at_block_exponent_mem in every kernel that uses them today.
 #ifndef MI355Q_ATTN_DEV_H
 #define MI355Q_ATTN_DEV_H
 #include <hip/hip_runtime.h>
@@ -84,6 +90,82 @@ __device__ __forceinline__ int at_block_exponent_mem(float bmax, const QuantArgs
 __device__ __forceinline__ float at_quant_pos(float x, float sc_up, float eps_up, float sc_dn, float mant_max) {
     const float m = fminf(__builtin_rintf(__builtin_fmaf(x, sc_up, eps_up)), mant_max);
     return x <= ATOL ? x : m * sc_dn;
+}
+
+// ---- Q fragments ---------------------------------------------------------------------------------------------------------
+// The DC Q fragments of lane (query c16, lg) from its query's fp32 row qp, quantised in registers: chunk c holds d = 32 c + 8 lg .. + 7,
+// a [1,16] block is the lanes l, l ^ 16 of a chunk.  q_scale != 0: q is multiplied on the way in.
+template <int DC, class ExpFn>
+__device__ __forceinline__ void at_quant_q_frag(bf16x8 (&qf)[DC], const float* __restrict__ qp, float q_scale, int lg, const QuantArgs& aq,
+                                                ExpFn exponent) {
+    const int mb = (int)__builtin_log2f(aq.shift);
+#pragma unroll
+    for (int c = 0; c < DC; ++c) {
+        float4 lo = *reinterpret_cast<const float4*>(qp + 32 * c + 8 * lg);
+        float4 hi = *reinterpret_cast<const float4*>(qp + 32 * c + 8 * lg + 4);
+        if (q_scale != 0.f) {
+            lo.x *= q_scale; lo.y *= q_scale; lo.z *= q_scale; lo.w *= q_scale;
+            hi.x *= q_scale; hi.y *= q_scale; hi.z *= q_scale; hi.w *= q_scale;
+        }
+        float bmax = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fmaxf(fabsf(lo.z), fabsf(lo.w))),
+                           fmaxf(fmaxf(fabsf(hi.x), fabsf(hi.y)), fmaxf(fabsf(hi.z), fabsf(hi.w))));
+        bmax = at_max2_16(bmax);
+        const int p = exponent(bmax, aq);
+        const int up = mb - p, dn = p - mb;
+        uint4 pk;
+        pk.x = pack_bf16(at_quant(lo.x, up, dn, aq.mant_max), at_quant(lo.y, up, dn, aq.mant_max));
+        pk.y = pack_bf16(at_quant(lo.z, up, dn, aq.mant_max), at_quant(lo.w, up, dn, aq.mant_max));
+        pk.z = pack_bf16(at_quant(hi.x, up, dn, aq.mant_max), at_quant(hi.y, up, dn, aq.mant_max));
+        pk.w = pack_bf16(at_quant(hi.z, up, dn, aq.mant_max), at_quant(hi.w, up, dn, aq.mant_max));
+        qf[c] = __builtin_bit_cast(bf16x8, pk);
+    }
+}
+
+// ---- probabilities -------------------------------------------------------------------------------------------------------
+// One [1,16] block of probabilities = a lane's four values pr of a score tile and those of the three other lanes of its query:
+// quantised into pq[0 .. 3].  mbp = log2(ap.shift).
+template <class ExpFn>
+__device__ __forceinline__ void at_quant_p_block(const float (&pr)[4], float* pq, int mbp, const QuantArgs& ap, ExpFn exponent) {
+    float bmax = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) bmax = fmaxf(bmax, pr[e]);
+    bmax = at_max4(bmax);
+    const int p = exponent(bmax, ap);
+    const float sc_up = __builtin_ldexpf(1.0f, mbp - p), sc_dn = __builtin_ldexpf(1.0f, p - mbp), eps_up = EPS9 * sc_up;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) pq[e] = at_quant_pos(pr[e], sc_up, eps_up, sc_dn, ap.mant_max);
+}
+// the P fragment of a key pair: the quantised blocks of tiles 2 s (pq[0 .. 3]) and 2 s + 1 (pq[4 .. 7])
+__device__ __forceinline__ bf16x8 at_pack_p(const float (&pq)[8]) {
+    uint4 pk;
+    pk.x = pack_bf16(pq[0], pq[1]); pk.y = pack_bf16(pq[2], pq[3]);
+    pk.z = pack_bf16(pq[4], pq[5]); pk.w = pack_bf16(pq[6], pq[7]);
+    return __builtin_bit_cast(bf16x8, pk);
+}
+
+// ---- softmax statistics of a lane that walks its query's keys 32 a step -------------------------------------------------------
+// (m_run, l_run) = (maximum, sum of exp(x - maximum)) over the scores seen so far, from (-inf, 0); a score of -inf is not a key.
+// Re-based when the maximum of ANY lane of the wave moves (rare after the first tiles; exp(-inf) = 0 takes care of the first one).
+__device__ __forceinline__ void at_softmax_step(const f32x4 (&sv)[2], float& m_run, float& l_run) {
+    const float tmax = fmaxf(fmaxf(fmaxf(sv[0][0], sv[0][1]), fmaxf(sv[0][2], sv[0][3])),
+                             fmaxf(fmaxf(sv[1][0], sv[1][1]), fmaxf(sv[1][2], sv[1][3])));
+    if (__any(tmax > m_run)) {
+        const float m_new = fmaxf(m_run, tmax);
+        l_run = m_new == -INFINITY ? 0.f : l_run * at_exp_neg(m_run - m_new);
+        m_run = m_new;
+    }
+    float add = 0.f;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) add += sv[h][e] == -INFINITY ? 0.f : at_exp_neg(sv[h][e] - m_run);
+    l_run += add;
+}
+// the query's statistics from those of its four lanes (a query that sees a key has a finite maximum)
+__device__ __forceinline__ void at_softmax_finish(float m_run, float l_run, float& row_max, float& row_sum, float& row_inv) {
+    row_max = at_max4(m_run);
+    row_sum = at_sum4(m_run == -INFINITY ? 0.f : l_run * at_exp_neg(m_run - row_max));
+    row_inv = 1.0f / row_sum;
 }
 
 }  // namespace mi355q

@@ -79,6 +79,13 @@ struct DecodeArgs {
     int D, S, pps;            // pps = key pairs per split
     const int32_t* lengths;   // ragged: [B] on the device, L / NT / NP above are those of max_length (partition, strides); else NULL
 };
+// q's and out's element strides of batch and row from the wrapper's {q batch, q row, out batch, out row}; NULL: contiguous [B, M, D]
+// (DecodeArgs, and ExtendArgs of mi355q_extend.h)
+template <class Args>
+inline void fill_qo_strides(Args& g, const long long* strides, long long M, long long D) {
+    g.qsb = strides ? strides[0] : M * D; g.qsm = strides ? strides[1] : D;
+    g.osb = strides ? strides[2] : M * D; g.osm = strides ? strides[3] : D;
+}
 // lengths != NULL: the ragged form, L = max_length
 int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out,
                                 void* workspace, long long M, long long L, int causal, float q_scale, float scale_div,

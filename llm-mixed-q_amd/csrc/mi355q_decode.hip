@@ -51,6 +51,18 @@ __device__ __forceinline__ bool append_row(const AppendArgs& a, long long b, lon
     return n > 0;
 }
 
+// one block of 16 values x with maximum bmax, quantised: value e is the low halfword of a lane's slot, 8 halfwords apart in kq
+// (the 16 keys of a tile at one d) and in vq (the 16 d of one key) alike
+__device__ __forceinline__ void kv_store_block(uint16_t* __restrict__ dst, const float (&x)[16], float bmax, const QuantArgs& a) {
+    const int mbits = (int)__builtin_log2f(a.shift);
+    const int p = at_block_exponent_mem(bmax, a);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const float q = bmax != 0.f ? at_quant(x[e], mbits - p, p - mbits, a.mant_max) + 0.0f : 0.f;   // (+ 0: see the layout note)
+        dst[e * 8] = (uint16_t)(pack_bf16(q, 0.f) & 0xFFFFu);
+    }
+}
+
 template <bool RG>
 __global__ __launch_bounds__(256) void kv_append_kernel(const QuantArgs ak, const QuantArgs av, const AppendArgs a) {
     const int tid = threadIdx.x, D = a.c.D;
@@ -90,15 +102,8 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const QuantArgs ak, cons
                 if (key >= L && key < L + n) stg[e * D] = x[e];
             }
         }
-        const int mbits = (int)__builtin_log2f(ak.shift);
-        const int p = at_block_exponent_mem(bmax, ak);
         const int c = d >> 5, g = (d >> 3) & 3, j = d & 7;
-        uint16_t* __restrict__ dst = a.c.kq + ((b * NTC + t) * (D >> 5) + c) * 512 + 16 * g * 8 + j;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const float q = bmax != 0.f ? at_quant(x[e], mbits - p, p - mbits, ak.mant_max) + 0.0f : 0.f;   // (+ 0: see the layout note)
-            dst[e * 8] = (uint16_t)(pack_bf16(q, 0.f) & 0xFFFFu);
-        }
+        kv_store_block(a.c.kq + ((b * NTC + t) * (D >> 5) + c) * 512 + 16 * g * 8 + j, x, bmax, ak);
     } else {
         // V: thread (new key, 16-d block) quantises one block
         const int DT = D >> 4;
@@ -117,16 +122,9 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const QuantArgs ak, cons
             x[4 * i] = f.x; x[4 * i + 1] = f.y; x[4 * i + 2] = f.z; x[4 * i + 3] = f.w;
             bmax = fmaxf(bmax, fmaxf(fmaxf(fabsf(f.x), fabsf(f.y)), fmaxf(fabsf(f.z), fabsf(f.w))));
         }
-        const int mbits = (int)__builtin_log2f(av.shift);
-        const int p = at_block_exponent_mem(bmax, av);
         const long long s = key >> 5;
         const int h = (int)(key >> 4) & 1, g = (int)(key & 15) >> 2, j = 4 * h + (int)(key & 3);
-        uint16_t* __restrict__ dst = a.c.vq + ((b * NPC + s) * DT + dt) * 512 + 16 * g * 8 + j;
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            const float q = bmax != 0.f ? at_quant(x[c], mbits - p, p - mbits, av.mant_max) + 0.0f : 0.f;
-            dst[c * 8] = (uint16_t)(pack_bf16(q, 0.f) & 0xFFFFu);
-        }
+        kv_store_block(a.c.vq + ((b * NPC + s) * DT + dt) * 512 + 16 * g * 8 + j, x, bmax, av);
     }
 }
 
@@ -215,7 +213,7 @@ int launch_kv_decode_fp32(const KvCache& c, float* k_out, float* v_out, long lon
 
 // ---- decode ---------------------------------------------------------------------------------------------------------------
 int decode_splits(long long B, long long L, long long D, int override) {
-    (void)D;
+    (void)D;                            // (part of the exported signature -- ops.decode_splits, the workspace size -- though no rule uses it)
     if (B < 1 || L < 1) return 1;
     const long long NP = (L + 31) / 32;
     // enough workgroups for two a compute unit (256 of them) at at least two key pairs each; never more than 64 statistics to combine
@@ -270,32 +268,8 @@ __global__ __launch_bounds__(256) void decode_scores_kernel(const QuantArgs aq, 
         }
     }
     const long long qrow = min((long long)c16, g.M - 1);
-    // Q fragments, quantised in registers (mi355q_attention.hip): lane (query c16, g) holds d = 32 c + 8 g .. + 7
-    bf16x8 qf[DC];
-    {
-        const int mb = (int)__builtin_log2f(aq.shift);
-        const float* __restrict__ qp = g.q + b * g.qsb + qrow * g.qsm;
-#pragma unroll
-        for (int c = 0; c < DC; ++c) {
-            float4 lo = *reinterpret_cast<const float4*>(qp + 32 * c + 8 * lg);
-            float4 hi = *reinterpret_cast<const float4*>(qp + 32 * c + 8 * lg + 4);
-            if (g.q_scale != 0.f) {
-                lo.x *= g.q_scale; lo.y *= g.q_scale; lo.z *= g.q_scale; lo.w *= g.q_scale;
-                hi.x *= g.q_scale; hi.y *= g.q_scale; hi.z *= g.q_scale; hi.w *= g.q_scale;
-            }
-            float bmax = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fmaxf(fabsf(lo.z), fabsf(lo.w))),
-                               fmaxf(fmaxf(fabsf(hi.x), fabsf(hi.y)), fmaxf(fabsf(hi.z), fabsf(hi.w))));
-            bmax = at_max2_16(bmax);
-            const int p = at_block_exponent_mem(bmax, aq);
-            const int up = mb - p, dn = p - mb;
-            uint4 pk;
-            pk.x = pack_bf16(at_quant(lo.x, up, dn, aq.mant_max), at_quant(lo.y, up, dn, aq.mant_max));
-            pk.y = pack_bf16(at_quant(lo.z, up, dn, aq.mant_max), at_quant(lo.w, up, dn, aq.mant_max));
-            pk.z = pack_bf16(at_quant(hi.x, up, dn, aq.mant_max), at_quant(hi.y, up, dn, aq.mant_max));
-            pk.w = pack_bf16(at_quant(hi.z, up, dn, aq.mant_max), at_quant(hi.w, up, dn, aq.mant_max));
-            qf[c] = __builtin_bit_cast(bf16x8, pk);
-        }
-    }
+    bf16x8 qf[DC];                      // quantised in registers
+    at_quant_q_frag(qf, g.q + b * g.qsb + qrow * g.qsm, g.q_scale, lg, aq, at_block_exponent_mem);
     const long long kvis = dec_horizon(g, L, qrow);
     const float scale_inv = g.scale_div != 0.f ? 1.0f / g.scale_div : 0.f;
     const long long t_lo = 2 * g.pps * s, t_hi = min(NT, t_lo + 2 * g.pps);
@@ -400,22 +374,11 @@ __global__ __launch_bounds__(256) void decode_pv_kernel(const QuantArgs ap, cons
             const float xs[4] = {x.x, x.y, x.z, x.w};
             const long long key0 = t * 16 + 4 * lg;
             float pr[4];
-            float bmax = 0.f;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                pr[e] = (t < NT && key0 + e <= kvis) ? at_div(at_exp_neg(xs[e] - row_max), row_sum, row_inv) : 0.f;
-                bmax = fmaxf(bmax, pr[e]);
-            }
-            bmax = at_max4(bmax);
-            const int p = at_block_exponent_mem(bmax, ap);
-            const float sc_up = __builtin_ldexpf(1.0f, mbp - p), sc_dn = __builtin_ldexpf(1.0f, p - mbp), eps_up = EPS9 * sc_up;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) pq[4 * h + e] = at_quant_pos(pr[e], sc_up, eps_up, sc_dn, ap.mant_max);
+            for (int e = 0; e < 4; ++e) pr[e] = (t < NT && key0 + e <= kvis) ? at_div(at_exp_neg(xs[e] - row_max), row_sum, row_inv) : 0.f;
+            at_quant_p_block(pr, pq + 4 * h, mbp, ap, at_block_exponent_mem);
         }
-        uint4 pk;
-        pk.x = pack_bf16(pq[0], pq[1]); pk.y = pack_bf16(pq[2], pq[3]);
-        pk.z = pack_bf16(pq[4], pq[5]); pk.w = pack_bf16(pq[6], pq[7]);
-        const bf16x8 pf = __builtin_bit_cast(bf16x8, pk);
+        const bf16x8 pf = at_pack_p(pq);
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt)
             o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vb[dt]), pf, o[dt], 0, 0, 0);
@@ -461,8 +424,7 @@ int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const 
     g.NT = (L + 15) / 16; g.NP = (L + 31) / 32; g.NTC = c.C / 16; g.NPC = (c.C + 31) / 32;
     g.S = decode_splits(c.B, L, c.D, splits);
     g.pps = (int)((g.NP + g.S - 1) / g.S);
-    g.qsb = strides ? strides[0] : M * c.D; g.qsm = strides ? strides[1] : c.D;
-    g.osb = strides ? strides[2] : M * c.D; g.osm = strides ? strides[3] : c.D;
+    fill_qo_strides(g, strides, M, c.D);
     g.causal = causal; g.q_scale = q_scale; g.scale_div = scale_div;
     g.scores = static_cast<float*>(workspace);
     g.stats = g.scores + c.B * g.NT * 256;

@@ -58,32 +58,8 @@ __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantAr
         return;
     }
     const long long qrow = min(m0 + c16, m - 1);            // (a lane behind m_b repeats the last real query; it stores zeros)
-    // Q fragments, quantised in registers: lane (query c16, g) holds d = 32 c + 8 g .. + 7
-    bf16x8 qf[DC];
-    {
-        const int mb = (int)__builtin_log2f(aq.shift);
-        const float* __restrict__ qp = g.q + b * g.qsb + qrow * g.qsm;
-#pragma unroll
-        for (int c = 0; c < DC; ++c) {
-            float4 lo = *reinterpret_cast<const float4*>(qp + 32 * c + 8 * lg);
-            float4 hi = *reinterpret_cast<const float4*>(qp + 32 * c + 8 * lg + 4);
-            if (g.q_scale != 0.f) {
-                lo.x *= g.q_scale; lo.y *= g.q_scale; lo.z *= g.q_scale; lo.w *= g.q_scale;
-                hi.x *= g.q_scale; hi.y *= g.q_scale; hi.z *= g.q_scale; hi.w *= g.q_scale;
-            }
-            float bmax = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fmaxf(fabsf(lo.z), fabsf(lo.w))),
-                               fmaxf(fmaxf(fabsf(hi.x), fabsf(hi.y)), fmaxf(fabsf(hi.z), fabsf(hi.w))));
-            bmax = at_max2_16(bmax);
-            const int p = at_block_exponent_mem(bmax, aq);
-            const int up = mb - p, dn = p - mb;
-            uint4 pk;
-            pk.x = pack_bf16(at_quant(lo.x, up, dn, aq.mant_max), at_quant(lo.y, up, dn, aq.mant_max));
-            pk.y = pack_bf16(at_quant(lo.z, up, dn, aq.mant_max), at_quant(lo.w, up, dn, aq.mant_max));
-            pk.z = pack_bf16(at_quant(hi.x, up, dn, aq.mant_max), at_quant(hi.y, up, dn, aq.mant_max));
-            pk.w = pack_bf16(at_quant(hi.z, up, dn, aq.mant_max), at_quant(hi.w, up, dn, aq.mant_max));
-            qf[c] = __builtin_bit_cast(bf16x8, pk);
-        }
-    }
+    bf16x8 qf[DC];                                          // quantised in registers
+    at_quant_q_frag(qf, g.q + b * g.qsb + qrow * g.qsm, g.q_scale, lg, aq, at_block_exponent_mem);
     // this lane's horizon, and the tiles the WORKGROUP walks: up to the horizon of its last real query (scalar; 1 <= need <= C / 16)
     const long long kvis = g.causal ? L - m + qrow : L - 1;
     const long long need = (g.causal ? L - m + min(wg0 + 63, m - 1) : L - 1) / 16 + 1;
@@ -137,24 +113,10 @@ __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantAr
         if (st + 1 < nsteps) dma(st + 1, (st + 1) & 1, false);
         f32x4 sv[2];
         scores(st, st & 1, sv);
-        const float tmax = fmaxf(fmaxf(fmaxf(sv[0][0], sv[0][1]), fmaxf(sv[0][2], sv[0][3])),
-                                 fmaxf(fmaxf(sv[1][0], sv[1][1]), fmaxf(sv[1][2], sv[1][3])));
-        if (__any(tmax > m_run)) {                          // re-base (exp(-inf) = 0 takes care of the first tile)
-            const float m_new = fmaxf(m_run, tmax);
-            l_run = m_new == -INFINITY ? 0.f : l_run * at_exp_neg(m_run - m_new);
-            m_run = m_new;
-        }
-        float add = 0.f;
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) add += sv[h][e] == -INFINITY ? 0.f : at_exp_neg(sv[h][e] - m_run);
-        l_run += add;
+        at_softmax_step(sv, m_run, l_run);
     }
-    // (every query sees key 0: the row maximum is finite)
-    const float row_max = at_max4(m_run);
-    const float row_sum = at_sum4(m_run == -INFINITY ? 0.f : l_run * at_exp_neg(m_run - row_max));
-    const float row_inv = 1.0f / row_sum;
+    float row_max, row_sum, row_inv;                        // (every query sees key 0: the row maximum is finite)
+    at_softmax_finish(m_run, l_run, row_max, row_sum, row_inv);
     __syncthreads();                                        // (every wave is out of the last step's buffer)
 
     // ---- pass 2: the scores again, probabilities, quantised, times V
@@ -173,22 +135,11 @@ __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantAr
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             float pr[4];
-            float bmax = 0.f;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                pr[e] = sv[h][e] == -INFINITY ? 0.f : at_div(at_exp_neg(sv[h][e] - row_max), row_sum, row_inv);
-                bmax = fmaxf(bmax, pr[e]);
-            }
-            bmax = at_max4(bmax);
-            const int p = at_block_exponent_mem(bmax, ap);
-            const float sc_up = __builtin_ldexpf(1.0f, mbp - p), sc_dn = __builtin_ldexpf(1.0f, p - mbp), eps_up = EPS9 * sc_up;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) pq[4 * h + e] = at_quant_pos(pr[e], sc_up, eps_up, sc_dn, ap.mant_max);
+            for (int e = 0; e < 4; ++e) pr[e] = sv[h][e] == -INFINITY ? 0.f : at_div(at_exp_neg(sv[h][e] - row_max), row_sum, row_inv);
+            at_quant_p_block(pr, pq + 4 * h, mbp, ap, at_block_exponent_mem);
         }
-        uint4 pk;
-        pk.x = pack_bf16(pq[0], pq[1]); pk.y = pack_bf16(pq[2], pq[3]);
-        pk.z = pack_bf16(pq[4], pq[5]); pk.w = pack_bf16(pq[6], pq[7]);
-        const bf16x8 pf = __builtin_bit_cast(bf16x8, pk);
+        const bf16x8 pf = at_pack_p(pq);
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
             const uint4 vv = *reinterpret_cast<const uint4*>(&stage[st & 1][KSTEP + dt * 1024 + lane * 16]);
@@ -209,8 +160,7 @@ int launch_bfp_attention_extend(const QuantArgs& aq, const QuantArgs& ap, const 
     ExtendArgs g{};
     g.q = q; g.kq = c.kq; g.vq = c.vq; g.out = out; g.lengths = lengths; g.counts = counts;
     g.M = M; g.L = max_length; g.NTC = c.C / 16; g.NPC = (c.C + 31) / 32;
-    g.qsb = strides ? strides[0] : M * c.D; g.qsm = strides ? strides[1] : c.D;
-    g.osb = strides ? strides[2] : M * c.D; g.osm = strides ? strides[3] : c.D;
+    fill_qo_strides(g, strides, M, c.D);
     g.causal = causal; g.q_scale = q_scale; g.scale_div = scale_div;
     const long long nxb = (M + 63) / 64;
     if (c.B * nxb > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
