@@ -665,6 +665,31 @@ int mi355q_bfp_attention_extend(const float* q, const void* kq, const void* vq, 
                                 int64_t C, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
                                 void* stream);
 
+/* Grouped-query attention on the cache: each cache row (batch x KV head) is shared by G >= 1 query heads, as in every Llama-family
+ * model with num_key_value_heads < num_attention_heads.  B, C, D, kq, vq, `lengths` and `counts` are the CACHE's (B = batch x KV
+ * heads, one int32 entry per cache row); q and out hold B * G rows [B * G, M, D], and query row r attends to cache row r / G -- the
+ * `repeat_kv` convention, query head j on KV head j / G.  Every query row gets, bit for bit, what the ungrouped call gives it on a
+ * cache of B * G rows that holds each K / V row G times (decode: with the same number of splits); nothing is stored or read G times.
+ *
+ * decode_grouped: everything else as mi355q_bfp_attention_decode_ragged; lengths == NULL is the uniform form, every row at
+ *   max_length (mi355q_bfp_attention_decode's L).  The 16 MFMA columns that one query head fills with its M queries take
+ *   gw = mi355q_bfp_attention_decode_group_width(G, M) heads -- the largest divisor of G with gw * M <= 16 (0: G < 1 or M outside
+ *   1 .. 16) -- which share the row's K / V fragment loads; a cache row is served by G / gw LAUNCH ROWS.  The workspace and the
+ *   default number of splits are those of R = B * G / gw launch rows: mi355q_bfp_attention_decode_workspace_bytes(R, ...),
+ *   mi355q_bfp_attention_decode_splits(R, ...); R <= 65535, else MI355Q_E_UNSUPPORTED.  G = 8, M = 1: gw = 8, one launch row a cache
+ *   row.  G = 4, M = 16: gw = 1, four launch rows on the shared row -- no traffic saved, still no copies.
+ * extend_grouped: everything else as mi355q_bfp_attention_extend.  A workgroup is one (query row, block of 64 queries) and reads the
+ *   fragments of cache row r / G itself: the G heads of a group do not share loads (they are served by the caches). */
+int mi355q_bfp_attention_decode_group_width(int64_t G, int64_t M);
+int mi355q_bfp_attention_decode_grouped(const float* q, const void* kq, const void* vq, int32_t G, const int32_t* lengths,
+                                        int32_t causal, float q_scale, float scale_div, float* out, void* workspace, int64_t B,
+                                        int64_t M, int64_t max_length, int64_t C, int64_t D, const int32_t* qk_params,
+                                        const int32_t* pv_params, const int64_t* strides, int32_t splits, void* stream);
+int mi355q_bfp_attention_extend_grouped(const float* q, const void* kq, const void* vq, int32_t G, const int32_t* lengths,
+                                        const int32_t* counts, int32_t causal, float q_scale, float scale_div, float* out, int64_t B,
+                                        int64_t M, int64_t max_length, int64_t C, int64_t D, const int32_t* qk_params,
+                                        const int32_t* pv_params, const int64_t* strides, void* stream);
+
 /* ---- the un-blocked quantisers -------------------------------------------------------------------------------------
  * replaces: quantizers/minifloat.py:134-196 (minifloat_ieee_quantizer: implicit leading one, subnormals at the lowest
  *           exponent), :21-86 (minifloat_denorm_quantizer: no implicit one, exponent ceil(log2(|x| + 1e-9)) per element)

@@ -1192,6 +1192,60 @@ int mi355q_bfp_attention_extend(const float* q, const void* kq, const void* vq, 
                                        lengths, counts, static_cast<hipStream_t>(stream));
 }
 
+// ---- grouped queries: G query rows a cache row, query row r on cache row r / G (mi355q_decode.h, mi355q_extend.h) -----------
+int mi355q_bfp_attention_decode_group_width(int64_t G, int64_t M) { return decode_group_width(G, M); }
+
+int mi355q_bfp_attention_decode_grouped(const float* q, const void* kq, const void* vq, int32_t G, const int32_t* lengths,
+                                        int32_t causal, float q_scale, float scale_div, float* out, void* workspace, int64_t B,
+                                        int64_t M, int64_t max_length, int64_t C, int64_t D, const int32_t* qk_params,
+                                        const int32_t* pv_params, const int64_t* strides, int32_t splits, void* stream) {
+    if (M < 0 || max_length < 0 || splits < 0 || G < 1) return MI355Q_E_BADARG;
+    int rc = decode_cache_shape(B, C, D);
+    if (rc) return rc;
+    if (M < 1 || M > 16 || max_length < M) return MI355Q_E_UNSUPPORTED;
+    if (B * (G / decode_group_width(G, M)) > 65535) return MI355Q_E_UNSUPPORTED;     // (launch rows: the grid's second dimension)
+    if (max_length > C || !q || !kq || !vq || !out || !workspace || !qk_params || !pv_params) return MI355Q_E_BADARG;
+    QuantArgs aq{}, ap{};
+    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) |
+         reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) % 16 || reinterpret_cast<uintptr_t>(lengths) % 4)
+        return MI355Q_E_ALIGN;
+    long long st4[4];
+    if (strides)
+        for (int i = 0; i < 4; ++i) {
+            if (strides[i] % 4) return MI355Q_E_ALIGN;
+            st4[i] = strides[i];
+        }
+    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
+    return launch_bfp_attention_decode(aq, ap, c, q, out, workspace, M, max_length, causal != 0, q_scale, scale_div,
+                                       strides ? st4 : nullptr, splits, static_cast<hipStream_t>(stream), lengths, G);
+}
+
+int mi355q_bfp_attention_extend_grouped(const float* q, const void* kq, const void* vq, int32_t G, const int32_t* lengths,
+                                        const int32_t* counts, int32_t causal, float q_scale, float scale_div, float* out, int64_t B,
+                                        int64_t M, int64_t max_length, int64_t C, int64_t D, const int32_t* qk_params,
+                                        const int32_t* pv_params, const int64_t* strides, void* stream) {
+    if (M < 0 || max_length < 0 || G < 1) return MI355Q_E_BADARG;
+    int rc = decode_cache_shape(B, C, D);
+    if (rc) return rc;
+    if (M < 1 || max_length < M) return MI355Q_E_UNSUPPORTED;
+    if (max_length > C || !q || !kq || !vq || !out || !qk_params || !pv_params || (counts && !lengths)) return MI355Q_E_BADARG;
+    QuantArgs aq{}, ap{};
+    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) |
+         reinterpret_cast<uintptr_t>(out)) % 16 || (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(counts)) % 4)
+        return MI355Q_E_ALIGN;
+    long long st4[4];
+    if (strides)
+        for (int i = 0; i < 4; ++i) {
+            if (strides[i] % 4) return MI355Q_E_ALIGN;
+            st4[i] = strides[i];
+        }
+    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
+    return launch_bfp_attention_extend(aq, ap, c, q, out, M, max_length, causal != 0, q_scale, scale_div, strides ? st4 : nullptr,
+                                       lengths, counts, static_cast<hipStream_t>(stream), G);
+}
+
 // block_minifloat (fmt 1) / block_log (fmt 2) products: the same two kernels with the other quantisers' block parameters
 static int values_matmul_impl(int fmt, bool softmax, const float* mask, long long causal_off, const float* x, const float* y,
                               float* out, void* workspace, int64_t B, int64_t M, int64_t K, int64_t N, int32_t x_width,

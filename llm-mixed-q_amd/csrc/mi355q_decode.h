@@ -29,6 +29,18 @@
 //            partition comes from max_length: a split behind a row's last tile writes (-inf, 0) statistics and a zero partial
 //            output and reads no kq / vq.  The scores workspace keeps the stride of NT(max_length) tiles a row.
 // A row decodes as if it were alone: nothing another row holds (or a pad key would be) enters its blocks' shared exponents.
+//
+// Grouped queries (GQ = true kernels): a cache row (batch x KV head) is shared by G query heads, q / out hold B * G rows and query
+// row r attends to cache row r / G.  The 16 MFMA columns one query head fills with M queries take gw heads, gw = the largest
+// divisor of G with gw * M <= 16 (decode_group_width), and a cache row is served by rpc = G / gw LAUNCH ROWS:
+//   launch row y = 0 .. B * rpc - 1   reads cache row y / rpc (kq, vq, lengths[y / rpc]) and serves query rows y gw .. y gw + gw - 1
+//   column c16 < gw * M               head h = c16 / M, query c16 % M: Q fragment from q + (y gw + h) qsb + (c16 % M) qsm, output to
+//                                     out + (y gw + h) osb + (c16 % M) osm, horizon that of query c16 % M
+//   columns >= gw * M                 repeat the last real column and store nothing
+// The workspace is indexed by launch row with the per-row layout of DecodeArgs (the 16 statistics slots are the 16 columns), sized
+// and split (decode_splits without an override) for B * rpc rows.  Per cache row stay: the length, the key tiles, the split
+// partition.  Q fragments, horizon, softmax statistics and the [1,16] probability blocks are per column, the MFMA keeps columns
+// apart: each head gets the bits the GQ = false kernels give it on a private copy of the row, with the same number of splits.
 #ifndef MI355Q_DECODE_H
 #define MI355Q_DECODE_H
 #include <hip/hip_runtime.h>
@@ -78,6 +90,7 @@ struct DecodeArgs {
     float q_scale, scale_div; // 0: none
     int D, S, pps;            // pps = key pairs per split
     const int32_t* lengths;   // ragged: [B] on the device, L / NT / NP above are those of max_length (partition, strides); else NULL
+    int gw, rpc;              // grouped queries (GQ): heads a launch row serves, launch rows a cache row; gw * rpc = G.  Else 1, 1
 };
 // q's and out's element strides of batch and row from the wrapper's {q batch, q row, out batch, out row}; NULL: contiguous [B, M, D]
 // (DecodeArgs, and ExtendArgs of mi355q_extend.h)
@@ -86,10 +99,13 @@ inline void fill_qo_strides(Args& g, const long long* strides, long long M, long
     g.qsb = strides ? strides[0] : M * D; g.qsm = strides ? strides[1] : D;
     g.osb = strides ? strides[2] : M * D; g.osm = strides ? strides[3] : D;
 }
-// lengths != NULL: the ragged form, L = max_length
+// heads of a group one launch row serves: the largest divisor gw of G with gw * M <= 16 (0: G < 1 or M outside 1 .. 16)
+int decode_group_width(long long G, long long M);
+// lengths != NULL: the ragged form, L = max_length.  G >= 1: the grouped form (q / out hold c.B * G rows, the workspace is that of
+// c.B * G / decode_group_width(G, M) launch rows); G == 0: one query row a cache row
 int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out,
                                 void* workspace, long long M, long long L, int causal, float q_scale, float scale_div,
-                                const long long* strides, int splits, hipStream_t st, const int32_t* lengths = nullptr);
+                                const long long* strides, int splits, hipStream_t st, const int32_t* lengths = nullptr, int G = 0);
 
 }  // namespace mi355q
 #endif

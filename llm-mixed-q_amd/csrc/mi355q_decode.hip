@@ -19,6 +19,9 @@
 // Ragged batches (layout note in mi355q_decode.h): the same kernels with RG = true read the row's length from a device array --
 // one load a workgroup, kept scalar -- where the uniform instantiations (RG = false) read the host's L; a row's workgroups skip
 // the key tiles the row does not have, and a row of length 0 (a finished sequence) costs a few empty workgroups.
+// Grouped queries (GQ = true; column map and launch rows: mi355q_decode.h): the G query heads that share a cache row sit in the
+// columns one query head leaves unused -- gw heads x M queries a launch row -- and are served by the same K / V fragment loads.
+// Everything per query is per column, so a head's bits are those of the GQ = false kernels on a private copy of the row.
 // MFMA roles as in mi355q_attention.hip (v_mfma_f32_16x16x32_bf16, the queries are the 16 columns): a lane's own values of the score
 // tiles 2 s, 2 s + 1 are the slots of its P fragment, and vq is stored with the same slot order.
 #include <hip/hip_runtime.h>
@@ -250,13 +253,50 @@ __device__ __forceinline__ long long dec_length(const DecodeArgs& g, long long b
     }
 }
 
-template <int DC, bool RG>
+// Column c16 of the MFMA tiles -> (query row of q / out, query).  GQ = false: row y, query min(c16, M - 1).  GQ = true: launch row y
+// serves the gw query rows y gw .. y gw + gw - 1, column c16 < gw M is head c16 / M, query c16 % M; the columns behind repeat the
+// last real one (and store nothing: dec_real).
+template <bool GQ>
+__device__ __forceinline__ void dec_column(const DecodeArgs& g, long long y, int c16, long long& row, long long& qrow) {
+    if constexpr (GQ) {
+        const int M = (int)g.M, col = min(c16, g.gw * M - 1), h = col / M;
+        row = y * g.gw + h;
+        qrow = col - h * M;
+    } else {
+        row = y;
+        qrow = min((long long)c16, g.M - 1);
+    }
+}
+template <bool GQ>
+__device__ __forceinline__ bool dec_real(const DecodeArgs& g, int c16) {
+    if constexpr (GQ) return c16 < g.gw * (int)g.M;
+    else return c16 < g.M;
+}
+// where a REAL column c16 of launch row y stores its output row
+template <bool GQ>
+__device__ __forceinline__ float* dec_out(const DecodeArgs& g, long long y, int c16) {
+    if constexpr (GQ) {
+        long long row, qrow;
+        dec_column<true>(g, y, c16, row, qrow);
+        return g.out + row * g.osb + qrow * g.osm;
+    } else {
+        return g.out + y * g.osb + c16 * g.osm;
+    }
+}
+// the cache row of launch row y (scalar)
+template <bool GQ>
+__device__ __forceinline__ long long dec_cache_row(const DecodeArgs& g, long long y) {
+    if constexpr (GQ) return (long long)((unsigned)y / (unsigned)g.rpc);
+    else return y;
+}
+
+template <int DC, bool RG, bool GQ>
 __global__ __launch_bounds__(256) void decode_scores_kernel(const QuantArgs aq, const DecodeArgs g) {
     __shared__ float sm_[4][64], sl_[4][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c16 = lane & 15, lg = lane >> 4;
-    const long long b = blockIdx.y, s = blockIdx.x;
-    const long long L = dec_length<RG>(g, b), NT = RG ? (L + 15) >> 4 : g.NT;
+    const long long b = blockIdx.y, s = blockIdx.x, cb = dec_cache_row<GQ>(g, b);   // b: launch row (workspace), cb: cache row
+    const long long L = dec_length<RG>(g, cb), NT = RG ? (L + 15) >> 4 : g.NT;
     if constexpr (RG) {
         if (2 * g.pps * s >= NT) {      // a split wholly behind the row's last tile: the empty statistics, no kq read
             if (tid < 16) {
@@ -267,13 +307,14 @@ __global__ __launch_bounds__(256) void decode_scores_kernel(const QuantArgs aq, 
             return;
         }
     }
-    const long long qrow = min((long long)c16, g.M - 1);
+    long long row, qrow;
+    dec_column<GQ>(g, b, c16, row, qrow);
     bf16x8 qf[DC];                      // quantised in registers
-    at_quant_q_frag(qf, g.q + b * g.qsb + qrow * g.qsm, g.q_scale, lg, aq, at_block_exponent_mem);
+    at_quant_q_frag(qf, g.q + row * g.qsb + qrow * g.qsm, g.q_scale, lg, aq, at_block_exponent_mem);
     const long long kvis = dec_horizon(g, L, qrow);
     const float scale_inv = g.scale_div != 0.f ? 1.0f / g.scale_div : 0.f;
     const long long t_lo = 2 * g.pps * s, t_hi = min(NT, t_lo + 2 * g.pps);
-    const uint16_t* __restrict__ kfb = g.kq + b * g.NTC * DC * 512 + lane * 8;
+    const uint16_t* __restrict__ kfb = g.kq + cb * g.NTC * DC * 512 + lane * 8;
     float* __restrict__ sc = g.scores + b * g.NT * 256 + lane * 4;
     // running (max, sum of exp(x - max)) of this lane's visible scores, re-based when the maximum moves
     float m_run = -INFINITY, l_run = 0.f;
@@ -320,21 +361,21 @@ __global__ __launch_bounds__(256) void decode_scores_kernel(const QuantArgs aq, 
     }
 }
 
-template <int DC, bool RG>
+template <int DC, bool RG, bool GQ>
 __global__ __launch_bounds__(256) void decode_pv_kernel(const QuantArgs ap, const DecodeArgs g) {
     constexpr int DT = DC * 2;
     __shared__ f32x4 red[4][DT][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c16 = lane & 15, lg = lane >> 4;
-    const long long b = blockIdx.y, s = blockIdx.x;
-    const long long L = dec_length<RG>(g, b), NT = RG ? (L + 15) >> 4 : g.NT, NP = RG ? (L + 31) >> 5 : g.NP;
+    const long long b = blockIdx.y, s = blockIdx.x, cb = dec_cache_row<GQ>(g, b);
+    const long long L = dec_length<RG>(g, cb), NT = RG ? (L + 15) >> 4 : g.NT, NP = RG ? (L + 31) >> 5 : g.NP;
     const long long p_lo = g.pps * s, p_hi = min(NP, p_lo + g.pps);
     if constexpr (RG) {
         if (p_lo >= p_hi) {             // an empty split (every split of an empty row): a zero partial output, no vq read
             const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
             for (int dt = wave; dt < DT; dt += 4) {
                 if (g.S == 1) {
-                    if (c16 < g.M) *reinterpret_cast<float4*>(g.out + b * g.osb + c16 * g.osm + 16 * dt + 4 * lg) = zero;
+                    if (dec_real<GQ>(g, c16)) *reinterpret_cast<float4*>(dec_out<GQ>(g, b, c16) + 16 * dt + 4 * lg) = zero;
                 } else {
                     *reinterpret_cast<float4*>(g.part + (((b * g.S + s) * DT + dt) * 64 + lane) * 4) = zero;
                 }
@@ -342,7 +383,8 @@ __global__ __launch_bounds__(256) void decode_pv_kernel(const QuantArgs ap, cons
             return;
         }
     }
-    const long long qrow = min((long long)c16, g.M - 1);
+    long long row, qrow;
+    dec_column<GQ>(g, b, c16, row, qrow);
     const long long kvis = dec_horizon(g, L, qrow);
     // the row's statistics over all L keys: the S splits in split order (every query sees key 0: the first split's max is finite;
     // splits behind a ragged row's last tile hold (-inf, 0) and are skipped like any split without a visible key)
@@ -356,7 +398,7 @@ __global__ __launch_bounds__(256) void decode_pv_kernel(const QuantArgs ap, cons
     }
     const float row_inv = 1.0f / row_sum;
     const int mbp = (int)__builtin_log2f(ap.shift);
-    const uint16_t* __restrict__ vfb = g.vq + b * g.NPC * DT * 512 + lane * 8;
+    const uint16_t* __restrict__ vfb = g.vq + cb * g.NPC * DT * 512 + lane * 8;
     const float* __restrict__ sc = g.scores + b * g.NT * 256 + lane * 4;
     f32x4 o[DT];
 #pragma unroll
@@ -392,14 +434,15 @@ __global__ __launch_bounds__(256) void decode_pv_kernel(const QuantArgs ap, cons
 #pragma unroll
         for (int w = 1; w < 4; ++w) sum += red[w][dt][lane];
         if (g.S == 1) {
-            if (c16 < g.M)
-                *reinterpret_cast<float4*>(g.out + b * g.osb + c16 * g.osm + 16 * dt + 4 * lg) = make_float4(sum[0], sum[1], sum[2], sum[3]);
+            if (dec_real<GQ>(g, c16))
+                *reinterpret_cast<float4*>(dec_out<GQ>(g, b, c16) + 16 * dt + 4 * lg) = make_float4(sum[0], sum[1], sum[2], sum[3]);
         } else {
             *reinterpret_cast<f32x4*>(g.part + (((b * g.S + s) * DT + dt) * 64 + lane) * 4) = sum;
         }
     }
 }
 
+template <bool GQ>
 __global__ __launch_bounds__(256) void decode_sum_kernel(const DecodeArgs g) {
     const int DT = g.D >> 4;
     const long long b = blockIdx.x;
@@ -411,32 +454,46 @@ __global__ __launch_bounds__(256) void decode_sum_kernel(const DecodeArgs g) {
             const float4 x = *reinterpret_cast<const float4*>(pp + (long long)s * DT * 256);
             sum.x += x.x; sum.y += x.y; sum.z += x.z; sum.w += x.w;
         }
-        if (c16 < g.M) *reinterpret_cast<float4*>(g.out + b * g.osb + c16 * g.osm + 16 * dt + 4 * lg) = sum;
+        if (dec_real<GQ>(g, c16)) *reinterpret_cast<float4*>(dec_out<GQ>(g, b, c16) + 16 * dt + 4 * lg) = sum;
     }
 }
 
+int decode_group_width(long long G, long long M) {
+    if (G < 1 || M < 1 || M > 16) return 0;
+    for (long long gw = G < 16 / M ? G : 16 / M; gw > 1; --gw)
+        if (G % gw == 0) return (int)gw;
+    return 1;
+}
+
+// G == 0: one query row a cache row, the GQ = false kernels.  G >= 1: the grouped kernels over c.B * rpc launch rows.
 int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out,
                                 void* workspace, long long M, long long L, int causal, float q_scale, float scale_div,
-                                const long long* strides, int splits, hipStream_t st, const int32_t* lengths) {
+                                const long long* strides, int splits, hipStream_t st, const int32_t* lengths, int G) {
     DecodeArgs g{};
     g.q = q; g.kq = c.kq; g.vq = c.vq; g.out = out; g.lengths = lengths;
     g.M = M; g.L = L; g.D = c.D;
     g.NT = (L + 15) / 16; g.NP = (L + 31) / 32; g.NTC = c.C / 16; g.NPC = (c.C + 31) / 32;
-    g.S = decode_splits(c.B, L, c.D, splits);
+    g.gw = G ? decode_group_width(G, M) : 1;
+    if (g.gw < 1) return MI355Q_E_BADARG;
+    g.rpc = G ? G / g.gw : 1;
+    const long long rows = c.B * g.rpc;                     // launch rows: the workspace's and the grid's
+    if (rows > 65535) return MI355Q_E_UNSUPPORTED;
+    g.S = decode_splits(rows, L, c.D, splits);
     g.pps = (int)((g.NP + g.S - 1) / g.S);
     fill_qo_strides(g, strides, M, c.D);
     g.causal = causal; g.q_scale = q_scale; g.scale_div = scale_div;
     g.scores = static_cast<float*>(workspace);
-    g.stats = g.scores + c.B * g.NT * 256;
-    g.part = g.stats + c.B * g.S * 32;
-    const dim3 grid((unsigned)g.S, (unsigned)c.B);
-#define MI355Q_DECODE_GO(DC_)                                                                     \
-    if (lengths) {                                                                                \
-        hipLaunchKernelGGL((decode_scores_kernel<DC_, true>), grid, dim3(256), 0, st, aq, g);     \
-        hipLaunchKernelGGL((decode_pv_kernel<DC_, true>), grid, dim3(256), 0, st, ap, g);         \
-    } else {                                                                                      \
-        hipLaunchKernelGGL((decode_scores_kernel<DC_, false>), grid, dim3(256), 0, st, aq, g);    \
-        hipLaunchKernelGGL((decode_pv_kernel<DC_, false>), grid, dim3(256), 0, st, ap, g);        \
+    g.stats = g.scores + rows * g.NT * 256;
+    g.part = g.stats + rows * g.S * 32;
+    const dim3 grid((unsigned)g.S, (unsigned)rows);
+#define MI355Q_DECODE_GO2(DC_, RG_, GQ_)                                                              \
+    hipLaunchKernelGGL((decode_scores_kernel<DC_, RG_, GQ_>), grid, dim3(256), 0, st, aq, g);         \
+    hipLaunchKernelGGL((decode_pv_kernel<DC_, RG_, GQ_>), grid, dim3(256), 0, st, ap, g);
+#define MI355Q_DECODE_GO(DC_)                                                                         \
+    if (G) {                                                                                          \
+        if (lengths) { MI355Q_DECODE_GO2(DC_, true, true) } else { MI355Q_DECODE_GO2(DC_, false, true) }     \
+    } else {                                                                                          \
+        if (lengths) { MI355Q_DECODE_GO2(DC_, true, false) } else { MI355Q_DECODE_GO2(DC_, false, false) }   \
     }
     switch (c.D / 32) {
         case 1: MI355Q_DECODE_GO(1); break;
@@ -446,7 +503,11 @@ int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const 
         default: return MI355Q_E_UNSUPPORTED;
     }
 #undef MI355Q_DECODE_GO
-    if (g.S > 1) hipLaunchKernelGGL(decode_sum_kernel, dim3((unsigned)c.B), dim3(256), 0, st, g);
+#undef MI355Q_DECODE_GO2
+    if (g.S > 1) {
+        if (G) hipLaunchKernelGGL(decode_sum_kernel<true>, dim3((unsigned)rows), dim3(256), 0, st, g);
+        else hipLaunchKernelGGL(decode_sum_kernel<false>, dim3((unsigned)rows), dim3(256), 0, st, g);
+    }
     return (int)hipGetLastError();
 }
 

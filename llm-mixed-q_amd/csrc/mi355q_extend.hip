@@ -31,7 +31,10 @@
 
 namespace mi355q {
 
-template <int DC>
+// GQ = true (grouped queries): workgroup row b is a QUERY head -- q, out and the grid have B * G of them -- and reads cache row b / G:
+// its fragments, lengths[b / G], counts[b / G].  Nothing else differs, so a head's bits are those of GQ = false on a private copy of
+// the row.  The G workgroups of a group each read the row's fragments themselves (no sharing inside a workgroup).
+template <int DC, bool GQ>
 __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantArgs aq, const QuantArgs ap, const ExtendArgs g) {
     constexpr int DT = DC * 2, KSTEP = 2 * DC * 1024, VSTEP = DT * 1024, STEP = KSTEP + VSTEP;      // bytes per 32 keys
     using gptr_t = const __attribute__((address_space(1))) void*;
@@ -44,10 +47,12 @@ __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantAr
     const long long b = (int)blockIdx.x - xrank * g.nb;
     const long long wg0 = (long long)(g.causal ? g.nxb - 1 - xrank : xrank) * 64;
     const long long m0 = wg0 + 16 * wave;
+    long long cb = b;                                       // the cache row
+    if constexpr (GQ) cb = (long long)((unsigned)b / (unsigned)g.G);
     // the row's keys and queries: one scalar load each a workgroup
     long long L = g.L, m = g.M;
-    if (g.lengths) L = min((long long)max(__builtin_amdgcn_readfirstlane(g.lengths[b]), 0), g.L);
-    if (g.counts) m = min((long long)max(__builtin_amdgcn_readfirstlane(g.counts[b]), 0), g.M);
+    if (g.lengths) L = min((long long)max(__builtin_amdgcn_readfirstlane(g.lengths[cb]), 0), g.L);
+    if (g.counts) m = min((long long)max(__builtin_amdgcn_readfirstlane(g.counts[cb]), 0), g.M);
     if (m > L) m = 0;                                       // (an empty slot: zeros, no fragment read)
     float* __restrict__ op = g.out + b * g.osb + (m0 + c16) * g.osm + 4 * lg;
     if (wg0 >= m) {                                         // wholly behind the row's queries: zeros, before the first barrier
@@ -64,8 +69,8 @@ __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantAr
     const long long kvis = g.causal ? L - m + qrow : L - 1;
     const long long need = (g.causal ? L - m + min(wg0 + 63, m - 1) : L - 1) / 16 + 1;
     const int nsteps = (int)((need + 1) / 2);
-    const unsigned char* __restrict__ kfb = reinterpret_cast<const unsigned char*>(g.kq) + b * g.NTC * DC * 1024 + lane * 16;
-    const unsigned char* __restrict__ vfb = reinterpret_cast<const unsigned char*>(g.vq) + b * g.NPC * DT * 1024 + lane * 16;
+    const unsigned char* __restrict__ kfb = reinterpret_cast<const unsigned char*>(g.kq) + cb * g.NTC * DC * 1024 + lane * 16;
+    const unsigned char* __restrict__ vfb = reinterpret_cast<const unsigned char*>(g.vq) + cb * g.NPC * DT * 1024 + lane * 16;
     const float scale_inv = g.scale_div != 0.f ? 1.0f / g.scale_div : 0.f;
 
     // LDS-DMA of one step: the K pieces of tiles 2 st, 2 st + 1 (DC KiB each) and, when with_v, the V pieces of pair st (DT KiB);
@@ -154,25 +159,30 @@ __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantAr
     }
 }
 
+// G == 0: one query row a cache row (GQ = false).  G >= 1: q / out hold c.B * G rows, query row r on cache row r / G (GQ = true)
 int launch_bfp_attention_extend(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out, long long M,
                                 long long max_length, int causal, float q_scale, float scale_div, const long long* strides,
-                                const int32_t* lengths, const int32_t* counts, hipStream_t st) {
+                                const int32_t* lengths, const int32_t* counts, hipStream_t st, int G) {
     ExtendArgs g{};
     g.q = q; g.kq = c.kq; g.vq = c.vq; g.out = out; g.lengths = lengths; g.counts = counts;
     g.M = M; g.L = max_length; g.NTC = c.C / 16; g.NPC = (c.C + 31) / 32;
     fill_qo_strides(g, strides, M, c.D);
     g.causal = causal; g.q_scale = q_scale; g.scale_div = scale_div;
-    const long long nxb = (M + 63) / 64;
-    if (c.B * nxb > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
-    g.nb = (int)c.B; g.nxb = (int)nxb;
-    const dim3 grid((unsigned)(c.B * nxb));
+    const long long nxb = (M + 63) / 64, rows = c.B * (G ? G : 1);
+    if (rows * nxb > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
+    g.nb = (int)rows; g.nxb = (int)nxb; g.G = G;
+    const dim3 grid((unsigned)(rows * nxb));
+#define MI355Q_EXTEND_GO(DC_)                                                                                          \
+    if (G) hipLaunchKernelGGL((bfp_attention_extend_kernel<DC_, true>), grid, dim3(256), 0, st, aq, ap, g);            \
+    else hipLaunchKernelGGL((bfp_attention_extend_kernel<DC_, false>), grid, dim3(256), 0, st, aq, ap, g);
     switch (c.D / 32) {
-        case 1: hipLaunchKernelGGL(bfp_attention_extend_kernel<1>, grid, dim3(256), 0, st, aq, ap, g); break;
-        case 2: hipLaunchKernelGGL(bfp_attention_extend_kernel<2>, grid, dim3(256), 0, st, aq, ap, g); break;
-        case 3: hipLaunchKernelGGL(bfp_attention_extend_kernel<3>, grid, dim3(256), 0, st, aq, ap, g); break;
-        case 4: hipLaunchKernelGGL(bfp_attention_extend_kernel<4>, grid, dim3(256), 0, st, aq, ap, g); break;
+        case 1: MI355Q_EXTEND_GO(1); break;
+        case 2: MI355Q_EXTEND_GO(2); break;
+        case 3: MI355Q_EXTEND_GO(3); break;
+        case 4: MI355Q_EXTEND_GO(4); break;
         default: return MI355Q_E_UNSUPPORTED;
     }
+#undef MI355Q_EXTEND_GO
     return (int)hipGetLastError();
 }
 

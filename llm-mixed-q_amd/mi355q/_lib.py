@@ -84,6 +84,11 @@ SIGNATURES = {
                                                      _i64, _vp, _vp, _vp, _i32, _vp]),
     "mi355q_bfp_attention_extend": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, C.c_float, C.c_float, _vp, _i64, _i64, _i64, _i64, _i64,
                                               _vp, _vp, _vp, _vp]),
+    "mi355q_bfp_attention_decode_group_width": (C.c_int, [_i64, _i64]),
+    "mi355q_bfp_attention_decode_grouped": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, C.c_float, C.c_float, _vp, _vp, _i64, _i64, _i64,
+                                                      _i64, _i64, _vp, _vp, _vp, _i32, _vp]),
+    "mi355q_bfp_attention_extend_grouped": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, C.c_float, C.c_float, _vp, _i64, _i64, _i64,
+                                                      _i64, _i64, _vp, _vp, _vp, _vp]),
     "mi355q_stream_capture_id": (C.c_uint64, [_vp]),
     "mi355q_rope_apply": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "mi355q_bfp_gemm_aligned": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),

@@ -245,6 +245,11 @@ class TinyLlamaConfig:
     max_positions: int = 128
     rms_eps: float = 1e-6
     init_std: float = 0.02
+    num_kv_heads: int = None       # grouped-query attention: K / V heads, each shared by num_heads // num_kv_heads query heads; None: num_heads
+
+    def __post_init__(self):
+        if self.num_kv_heads is not None and (self.num_kv_heads < 1 or self.num_heads % self.num_kv_heads != 0):
+            raise ValueError(f"TinyLlamaConfig: num_kv_heads = {self.num_kv_heads} does not divide num_heads = {self.num_heads}")
 
 
 def expand_llama_quant_config(config: dict, num_layers: int) -> dict:
@@ -264,17 +269,28 @@ class _RMSNorm(nn.Module):
         return self.weight * (x * torch.rsqrt(v + self.eps)).to(x.dtype)
 
 
+def _repeat_kv(t, G: int):
+    """[B, nkv, n, hd] -> [B, nkv * G, n, hd], head j a copy of KV head j // G (HF Llama's repeat_kv: expand + reshape)"""
+    B, nkv, n, hd = t.shape
+    return t[:, :, None].expand(B, nkv, G, n, hd).reshape(B, nkv * G, n, hd)
+
+
 class _LlamaAttention(nn.Module):
     """Llama-style attention over the registry API the way the reference's LlamaQuantizedAttention drives it
     (modeling_llama.py:289-344): bias-free projections, rotary embedding through
-    get_quantized_func("rotary_positional_encoding"), 4-D products through get_quantized_func("matmul")."""
+    get_quantized_func("rotary_positional_encoding"), 4-D products through get_quantized_func("matmul").
+    Grouped-query attention (cfg.num_kv_heads < cfg.num_heads): k_proj / v_proj make nkv heads, query head j uses KV head
+    j // (nh // nkv) -- HF Llama's repeat_kv.  The full forward repeats k and v to nh heads right behind the head reshape; the cached
+    route keeps nkv heads and passes the group size to the cache's attention functions."""
 
     def __init__(self, cfg: TinyLlamaConfig, qc: dict):
         super().__init__()
         self.h, self.nh, self.hd = cfg.hidden_size, cfg.num_heads, cfg.hidden_size // cfg.num_heads
+        self.nkv = cfg.num_heads if cfg.num_kv_heads is None else cfg.num_kv_heads
         self.qc = qc
         for name in ("q_proj", "k_proj", "v_proj", "o_proj"):
-            setattr(self, name, get_quantized_cls("linear", qc[name])(self.h, self.h, bias=False, config=qc[name]))
+            out = self.nkv * self.hd if name in ("k_proj", "v_proj") else self.h
+            setattr(self, name, get_quantized_cls("linear", qc[name])(self.h, out, bias=False, config=qc[name]))
         inv = 1.0 / (10000.0 ** (torch.arange(0, self.hd, 2).float() / self.hd))
         t = torch.arange(cfg.max_positions).float()
         emb = torch.cat([torch.outer(t, inv)] * 2, dim=-1)
@@ -291,7 +307,7 @@ class _LlamaAttention(nn.Module):
             out = lambda o: out_(gather_heads(o, hs[0], hs[1]))
         B, T, _ = x.shape
         nh = self.nh if hs is None else self.q_proj.local.out_features // self.hd
-        shape = lambda t: t.view(B, T, nh, self.hd).transpose(1, 2)
+        shape = lambda t: t.view(B, T, -1, self.hd).transpose(1, 2)
         if self.qc["matmul_1"].get("mi355q_grouped_linear", False):
             q, k, v = (shape(t) for t in grouped_linear(x, (self.q_proj, self.k_proj, self.v_proj), norm=norm))
         else:
@@ -302,6 +318,8 @@ class _LlamaAttention(nn.Module):
                 var = x.to(torch.float32).pow(2).mean(-1, keepdim=True)
                 x = weight * (x * torch.rsqrt(var + eps)).to(x.dtype)
             q, k, v = shape(self.q_proj(x)), shape(self.k_proj(x)), shape(self.v_proj(x))
+        if self.nkv != self.nh:
+            k, v = _repeat_kv(k, self.nh // self.nkv), _repeat_kv(v, self.nh // self.nkv)
         rc = self.qc["rotary_positional_encoding"]
         c1 = self.qc["matmul_1"]
         fused = c1["name"] == "block_fp" and c1.get("mi355q_fused_attention", False)
@@ -329,11 +347,13 @@ class _LlamaAttention(nn.Module):
 
     def decode(self, x, state, idx, position_ids):
         """the new tokens' attention against the cache of layer `idx` (modeling_llama.py:282-306): the rotary embedding through the
-        registry's function at the new positions, the TURNED k into the cache as in the reference, then the core"""
+        registry's function at the new positions, the TURNED k into the cache as in the reference, then the core.  Grouped-query
+        attention: k, v stay [B, nkv, n, hd] -- the embedding is element-wise per head, so the turned k has the bits turning the
+        repeated k would give -- and the state's caches hold nkv heads"""
         if getattr(self, "mi355q_head_shard", None) is not None:
             raise NotImplementedError("incremental decoding of head-sharded models")
         B, n, _ = x.shape
-        heads = lambda t: t.view(B, n, self.nh, self.hd).transpose(1, 2)
+        heads = lambda t: t.view(B, n, -1, self.hd).transpose(1, 2)
         q, k, v = heads(self.q_proj(x)), heads(self.k_proj(x)), heads(self.v_proj(x))
         rc, end = self.qc["rotary_positional_encoding"], state.position_end(n)
         q, k = get_quantized_func("rotary_positional_encoding", rc)(q, k, self.cos[:, :, :end], self.sin[:, :, :end], position_ids, config=rc)
@@ -448,7 +468,7 @@ class DecodeState:
     mode "fp32": the reference's literal route for ANY arithmetic (modeling_llama.py:301-344): torch.cat of fp32 K / V per layer, the
         products through the registry's functions, the causal mask [n, L] with the offset of modeling_llama.py:53-79.
     Ragged batches (`model(ids, cache=state, counts=[...])`, mode "block_fp" only): `lengths` holds every sequence's own length on the
-    host, and two int32 device tensors [batch x heads] hold them per cache row as the kernels read them -- "before" this call (every
+    host, and two int32 device tensors [batch x KV heads] hold them per cache row as the kernels read them -- "before" this call (every
     layer's append) and "after" it (every layer's decode; 0 for a row that takes no token in this call, which then costs nothing).
     They are shared by all layers and written once a call.  Each sequence decodes as if it were alone: no pad key ever enters a
     block of the cache.  The reference's left padding + attention_mask is NOT reproduced -- under block quantisation a pad key
@@ -456,7 +476,10 @@ class DecodeState:
     extend=True (mode "block_fp"; accepted and ignored by "fp32", which has no limit): chunked prefill.  Calls the default state
     refuses -- more than 16 new tokens behind a non-empty cache, a mixed call (one row starts its sequence while others continue),
     unequal counts behind non-empty rows -- run on ops.bfp_attention_extend: one ragged append, one extend call with every row's
-    own length and its own number of queries."""
+    own length and its own number of queries.
+    Grouped-query attention (k, v with fewer heads than q): the caches and the per-row tensors have batch x KV heads rows, the decode
+    and extend functions get group = heads // KV heads; the prefill routes and mode "fp32" repeat k / v to the query heads at use
+    (mode "fp32" concatenates them un-repeated)."""
 
     def __init__(self, model, batch: int, capacity: int, mode: str = "block_fp", extend: bool = False):
         from .quantize.quantized_functions import decode_cache_params
@@ -480,9 +503,9 @@ class DecodeState:
                     qk, pv = decode_cache_params(c0, c1, a.hd)
                 except ValueError as e:
                     raise ValueError(f"DecodeState(mode='block_fp'), layer {i}: {e}") from None
-                self.kv[i] = ops.KVCache(self.batch * a.nh, self.capacity, a.hd, qk, pv, dev)
-            if len({a.nh for a in attns}) == 1:                # (else: no ragged use; the per-row tensors are one set for all layers)
-                self.heads = attns[0].nh
+                self.kv[i] = ops.KVCache(self.batch * getattr(a, "nkv", a.nh), self.capacity, a.hd, qk, pv, dev)
+            if len({getattr(a, "nkv", a.nh) for a in attns}) == 1:    # (else: no ragged use; the per-row tensors are one set for all layers)
+                self.heads = getattr(attns[0], "nkv", attns[0].nh)    # cache rows a sequence: the KV heads
                 self.rows_before, self.rows_after, self._rows_counts = (torch.zeros(self.batch * self.heads, dtype=torch.int32, device=dev)
                                                                         for _ in range(3))
 
@@ -546,16 +569,19 @@ class DecodeState:
     def _attend_ragged(self, idx, q, k, v, c0, c1, scale_div):
         B, nh, n, hd = q.shape
         call, cache = self._call, self.kv[idx]
+        gq = {} if k.shape[1] == nh else dict(group=nh // k.shape[1])      # (grouped queries: k, v have the KV heads only)
         full = all(c == n for c in call["counts"])
         cache.append(k, v, lengths=self.rows_before, counts=None if full else self._rows_counts, max_length=call["max_before"])
         if call["route"] == "decode":
             return get_quantized_func("attention_decode", c1)(q, cache, c0, c1, causal=True, scale_div=scale_div, lengths=self.rows_after,
-                                                              max_length=call["max_after"]).reshape(B, nh, n, hd)
+                                                              max_length=call["max_after"], **gq).reshape(B, nh, n, hd)
         if call["route"] == "extend":
             # (max_length bounds the lengths and must hold the n query columns, which may all be padding behind the largest count)
             return get_quantized_func("attention_extend", c1)(q, cache, c0, c1, causal=True, scale_div=scale_div, lengths=self.rows_after,
-                                                              counts=self._rows_counts, max_length=max(call["max_after"], n)
+                                                              counts=self._rows_counts, max_length=max(call["max_after"], n), **gq
                                                               ).reshape(B, nh, n, hd)
+        if gq:
+            k, v = _repeat_kv(k, gq["group"]), _repeat_kv(v, gq["group"])
         # ragged prefill: every sequence's own queries against its own keys, one call of the existing attention function each (what
         # the sequence alone runs); prefill is not the hot path here
         o = q.new_zeros(B, nh, n, hd)
@@ -579,14 +605,19 @@ class DecodeState:
             if wide and not self.extend:                        # (before the append: a refused call leaves every layer's cache as it was)
                 raise NotImplementedError(f"{n} new tokens behind a non-empty block_fp cache (at most {ops.DECODE_MAX_QUERIES} a call)")
             cache.append(k, v)
+            gq = {} if k.shape[1] == nh else dict(group=nh // k.shape[1])  # (grouped queries: k, v have the KV heads only)
             if self.length == 0:
                 # the prompt's own queries against the prompt: the existing attention function (M = n)
+                if gq:
+                    k, v = _repeat_kv(k, gq["group"]), _repeat_kv(v, gq["group"])
                 return get_quantized_func("attention", c1)(q, k, v, c0, c1, causal=True, scale_div=scale_div).reshape(B, nh, n, hd)
             return get_quantized_func("attention_extend" if wide else "attention_decode", c1)(q, cache, c0, c1, causal=True,
-                                                                                              scale_div=scale_div).reshape(B, nh, n, hd)
+                                                                                              scale_div=scale_div, **gq).reshape(B, nh, n, hd)
         if self.kv[idx] is not None:
             k, v = torch.cat([self.kv[idx][0], k], dim=2), torch.cat([self.kv[idx][1], v], dim=2)
         self.kv[idx] = (k, v)
+        if k.shape[1] != nh:                                    # (grouped queries: the un-repeated K / V are kept, repeated at use)
+            k, v = _repeat_kv(k, nh // k.shape[1]), _repeat_kv(v, nh // k.shape[1])
         L = k.shape[2]
         if style == "bmm":
             fold = lambda t: t.reshape(B * nh, t.shape[2], hd)

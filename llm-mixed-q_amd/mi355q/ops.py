@@ -1449,6 +1449,23 @@ def decode_splits(B: int, L: int, D: int, splits: int = None) -> int:
     return int(_lib.load_library().mi355q_bfp_attention_decode_splits(int(B), int(L), int(D), int(splits or 0)))
 
 
+def decode_group_width(G: int, M: int) -> int:
+    """query heads of a group of G that one launch row of a grouped decode serves (they share the row's K / V fragment loads): the
+    largest divisor gw of G with gw * M <= 16; a cache row takes G / gw launch rows.  0: G < 1 or M outside 1 .. 16"""
+    return int(_lib.load_library().mi355q_bfp_attention_decode_group_width(int(G), int(M)))
+
+
+def _group_check(q, cache, group):
+    """the reasons a call declines `group` query rows a cache row, None when q's leading dimensions fold to cache.B * group rows"""
+    if isinstance(group, bool) or not isinstance(group, int) or group < 1:
+        return f"group = {group!r} is not an integer >= 1 (query heads per cache row)"
+    rows = q.shape[:-2].numel()
+    if rows != cache.B * group:
+        return (f"q {tuple(q.shape)} has {rows} rows, not cache.B * group = {cache.B} * {group} = {cache.B * group} "
+                "(query row r attends to cache row r // group)")
+    return None
+
+
 def _ragged_check(cache, lengths, counts, max_length, rows, what):
     """the reasons a ragged call declines its per-row lengths (counts: the append's), None when it takes them.  `rows`: the append's n
     (max_length + n must fit the capacity) or the decode's M (M <= max_length <= capacity).  Nothing here touches the device, and
@@ -1585,7 +1602,7 @@ class KVCache:
         return k, v
 
 
-def _decode_check(q, cache, splits=None, lengths=None, max_length=None):
+def _decode_check(q, cache, splits=None, lengths=None, max_length=None, group=1):
     """the reasons bfp_attention_decode declines (q, cache), None when it takes them; nothing here touches the device"""
     if not isinstance(cache, KVCache):
         return "cache is not a KVCache"
@@ -1594,7 +1611,11 @@ def _decode_check(q, cache, splits=None, lengths=None, max_length=None):
     M, D = q.shape[-2:]
     if not 1 <= M <= DECODE_MAX_QUERIES:
         return f"M = {M} queries outside 1 .. {DECODE_MAX_QUERIES}"
-    if D != cache.D or q.shape[:-2].numel() != cache.B:
+    if type(group) is not int or group != 1:
+        why = _group_check(q, cache, group)
+        if why is not None:
+            return why
+    if D != cache.D or q.shape[:-2].numel() != cache.B * group:
         return f"q {tuple(q.shape)} does not match the cache's B = {cache.B}, D = {cache.D}"
     if lengths is not None:
         why = _ragged_check(cache, lengths, None, max_length, M, "decode")
@@ -1616,16 +1637,22 @@ def bfp_attention_decode_supported(q, cache) -> bool:
 
 
 def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True, scale_div: float = None, q_scale: float = None,
-                         token_major: bool = False, splits: int = None, lengths: torch.Tensor = None, max_length: int = None):
+                         token_major: bool = False, splits: int = None, lengths: torch.Tensor = None, max_length: int = None,
+                         group: int = 1):
     """The attention core (modeling_llama.py:309-344) for the LAST M <= 16 positions of a sequence whose L = cache.length keys are in
     `cache` (their own keys included: append first): q [..., M, D] fp32; causal: query i sees keys 0 .. L - M + i, else all L.
     scale_div / q_scale / token_major as bfp_attention.  Keys are split over `splits` workgroups per head (default: decode_splits);
     statistics and partial outputs are combined in split order, so equal inputs give equal bits.  No additive mask.
     Ragged (`lengths` int32 [B] on the device: the rows' lengths INCLUDING the queries' own keys; `max_length`: the caller's upper
     bound on them, which also fixes the split partition): row b's queries are ITS last M positions against ITS lengths[b] keys, as
-    if the row were alone; a row with fewer than M keys (an empty slot) returns zeros.  cache.length is not used."""
+    if the row were alone; a row with fewer than M keys (an empty slot) returns zeros.  cache.length is not used.
+    Grouped queries (`group` = G > 1): every cache row (batch x KV head) is shared by G query heads; q's leading dimensions fold to
+    cache.B * G rows and query row r attends to cache row r // G (repeat_kv: query head j on KV head j // G).  `lengths` stays one
+    entry per CACHE row.  decode_group_width(G, M) heads share one launch row's K / V loads; the default number of splits is that of
+    cache.B * G // decode_group_width(G, M) rows.  Each query row gets the bits group=1 gives it on a cache of cache.B * G rows
+    holding the repeated K / V, with the same `splits`."""
     import ctypes
-    why = _decode_check(q, cache, splits, lengths, max_length)
+    why = _decode_check(q, cache, splits, lengths, max_length, group)
     if why is not None:
         raise ValueError(f"mi355q.bfp_attention_decode: {why}")
     M, D = q.shape[-2:]
@@ -1640,12 +1667,24 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
         osb, osm = M * D, D
     lib = _lib.load_library()
     sp = _stream_ptr(q.device)
-    key = (q.device.index, sp, B, C, D)
+    R = B if group == 1 else B * group // decode_group_width(group, M)       # launch rows: the workspace is theirs
+    if R > 65535:
+        raise ValueError(f"mi355q.bfp_attention_decode: {R} launch rows (cache.B * group / decode_group_width) exceed 65535")
+    key = (q.device.index, sp, R, C, D)
     ws = _DECODE_WS.get(key)
     if ws is None:      # (any L <= C, any number of splits: score tiles + statistics + partial outputs)
-        ws = _DECODE_WS.put(key, torch.empty(B * (C // 16) * 1024 + B * _DECODE_MAX_SPLITS * (128 + (D // 16) * 1024), dtype=torch.uint8,
+        ws = _DECODE_WS.put(key, torch.empty(R * (C // 16) * 1024 + R * _DECODE_MAX_SPLITS * (128 + (D // 16) * 1024), dtype=torch.uint8,
                                              device=q.device))
     strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
+    if group != 1:
+        with _on_device(q.device):
+            rc = lib.mi355q_bfp_attention_decode_grouped(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), group, _ptr(lengths), int(bool(causal)),
+                                                         float(q_scale) if q_scale else 0.0, float(scale_div) if scale_div else 0.0,
+                                                         _ptr(out), _ptr(ws), B, M, int(max_length) if lengths is not None else L, C, D,
+                                                         ctypes.addressof(cache._pa), ctypes.addressof(cache._pb),
+                                                         ctypes.addressof(strides), int(splits or 0), sp)
+        _lib.check(rc, "mi355q_bfp_attention_decode_grouped")
+        return out
     if lengths is not None:
         with _on_device(q.device):
             rc = lib.mi355q_bfp_attention_decode_ragged(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), _ptr(lengths), int(bool(causal)),
@@ -1663,7 +1702,7 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     return out
 
 
-def _extend_check(q, cache, lengths=None, counts=None, max_length=None):
+def _extend_check(q, cache, lengths=None, counts=None, max_length=None, group=1):
     """the reasons bfp_attention_extend declines (q, cache), None when it takes them; nothing here touches the device"""
     if not isinstance(cache, KVCache):
         return "cache is not a KVCache"
@@ -1672,7 +1711,11 @@ def _extend_check(q, cache, lengths=None, counts=None, max_length=None):
     M, D = q.shape[-2:]
     if M < 1:
         return f"M = {M} queries: at least one"
-    if D != cache.D or q.shape[:-2].numel() != cache.B:
+    if type(group) is not int or group != 1:
+        why = _group_check(q, cache, group)
+        if why is not None:
+            return why
+    if D != cache.D or q.shape[:-2].numel() != cache.B * group:
         return f"q {tuple(q.shape)} does not match the cache's B = {cache.B}, D = {cache.D}"
     if lengths is not None:
         why = _ragged_check(cache, lengths, counts, max_length, M, "extend")
@@ -1690,7 +1733,8 @@ def _extend_check(q, cache, lengths=None, counts=None, max_length=None):
 
 
 def bfp_attention_extend(q: torch.Tensor, cache: KVCache, *, causal: bool = True, scale_div: float = None, q_scale: float = None,
-                         token_major: bool = False, lengths: torch.Tensor = None, counts: torch.Tensor = None, max_length: int = None):
+                         token_major: bool = False, lengths: torch.Tensor = None, counts: torch.Tensor = None, max_length: int = None,
+                         group: int = 1):
     """Chunked prefill: the attention core (modeling_llama.py:309-344) for the LAST M positions -- any M >= 1 -- of a sequence whose
     L = cache.length keys are in `cache` (their own keys included: append first), the reference's `past_key_value` call with M new
     tokens behind a past of L - M.  q [..., M, D] fp32; causal: query i sees keys 0 .. L - M + i, else all L.  scale_div / q_scale /
@@ -1699,9 +1743,11 @@ def bfp_attention_extend(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     Ragged (`lengths` int32 [B] on the device: the rows' lengths INCLUDING the queries' own keys; `max_length`: the caller's upper
     bound on them): row b's queries are ITS last counts[b] positions (`counts` int32 [B] on the device; None: M for every row)
     against ITS lengths[b] keys, as if the row were alone; output rows behind counts[b] are zeros, and a row with counts[b] == 0
-    or counts[b] > lengths[b] (an empty slot) returns zeros.  cache.length is not used."""
+    or counts[b] > lengths[b] (an empty slot) returns zeros.  cache.length is not used.
+    Grouped queries (`group` = G > 1) as bfp_attention_decode: q folds to cache.B * G rows, query row r on cache row r // G, `lengths`
+    and `counts` one entry per CACHE row; each query row gets the bits group=1 gives it on a cache holding the repeated K / V."""
     import ctypes
-    why = _extend_check(q, cache, lengths, counts, max_length)
+    why = _extend_check(q, cache, lengths, counts, max_length, group)
     if why is not None:
         raise ValueError(f"mi355q.bfp_attention_extend: {why}")
     M, D = q.shape[-2:]
@@ -1714,6 +1760,17 @@ def bfp_attention_extend(q: torch.Tensor, cache: KVCache, *, causal: bool = True
         out = torch.empty(*q.shape, dtype=torch.float32, device=q.device)
         osb, osm = M * D, D
     strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
+    if group != 1:
+        with _on_device(q.device):
+            rc = _lib.load_library().mi355q_bfp_attention_extend_grouped(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), group, _ptr(lengths),
+                                                                         _ptr(counts), int(bool(causal)), float(q_scale) if q_scale else 0.0,
+                                                                         float(scale_div) if scale_div else 0.0, _ptr(out), cache.B, M,
+                                                                         int(max_length) if lengths is not None else cache.length,
+                                                                         cache.capacity, D, ctypes.addressof(cache._pa),
+                                                                         ctypes.addressof(cache._pb), ctypes.addressof(strides),
+                                                                         _stream_ptr(q.device))
+        _lib.check(rc, "mi355q_bfp_attention_extend_grouped")
+        return out
     with _on_device(q.device):
         rc = _lib.load_library().mi355q_bfp_attention_extend(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), _ptr(lengths), _ptr(counts),
                                                              int(bool(causal)), float(q_scale) if q_scale else 0.0,

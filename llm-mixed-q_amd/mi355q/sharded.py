@@ -288,6 +288,8 @@ def shard_model(model: nn.Module, group=None, always_gather: bool = False, gathe
     head, so every head's result is the unsharded model's, bit for bit."""
     from .quantize.quantized_modules.linear import _LinearBase
     family = "llama" if hasattr(model.layers[0], "gate_proj") else "opt"
+    if family == "llama" and any(getattr(layer.self_attn, "nkv", layer.self_attn.nh) != layer.self_attn.nh for layer in model.layers):
+        raise NotImplementedError("shard_model: grouped-query attention (num_kv_heads != num_heads) is not sharded")
     world_ = dist.get_world_size(group) if dist.is_initialized() else 1
     for layer in model.layers:
         for owner_name, names in SHARDED_PROJECTIONS[family]:

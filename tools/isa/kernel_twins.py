@@ -1,0 +1,75 @@
+"""kernel_table.py for a change that ADDS a template parameter: the old build's kernels against their twins in the new build -- the
+instantiations whose new parameter has the value that must leave the device code alone -- and the new build's other instantiations
+against those twins.
+
+    python tools/isa/kernel_twins.py <old dir> <new dir> <suffix> [> profiles/....txt]
+
+<suffix> is what the twin's demangled template argument list ends with behind the old one's, e.g. ", false" (decode_scores_kernel<1,
+true> -> decode_scores_kernel<1, true, false>; a kernel that was no template, f -> f<false>).  Per pair: the figures of kernel_table.py
+plus the SGPR count and whether the instruction streams are the same text.  Exit status 1 if a twin is missing or differs in VGPRs,
+SGPRs, spills, scratch, LDS, MFMA or LDS-DMA counts."""
+from __future__ import annotations
+
+import re
+import sys
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+from kernel_table import demangle, parse, waves  # noqa: E402
+
+COLS = ("vgpr_count", "sgpr_count", "waves", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
+        "group_segment_fixed_size", "instructions", "v_mfma", "global_load_lds")
+SHORT = ("vgpr", "sgpr", "waves", "vspill", "sspill", "scratch", "lds", "insts", "mfma", "ldsdma")
+MUST = ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size",
+        "v_mfma", "global_load_lds")
+
+
+def body(path: Path, name: str) -> list[str]:
+    """the kernel's instructions without labels, comments and the symbol names that differ between twins"""
+    text = path.read_text()
+    start = text.index(f"\n{name}:")
+    lines = text[start:text.index(".Lfunc_end", start)].split("\n")
+    ins = [ln.split(";")[0].strip() for ln in lines if ln.startswith("\t") and ln.strip()[:1] not in (".", ";")]
+    return [re.sub(r"\.LBB\d+_", ".LBB_", i) for i in ins]
+
+
+def twin_of(old_name: str, suffix: str) -> str:
+    return old_name[:-1] + suffix + ">" if old_name.endswith(">") else old_name + "<" + suffix.lstrip(", ") + ">"
+
+
+def main() -> int:
+    old_dir, new_dir, suffix = Path(sys.argv[1]), Path(sys.argv[2]), sys.argv[3]
+    bad = 0
+    for old_s in sorted(old_dir.glob("*.s")):
+        new_s = new_dir / old_s.name
+        old, new = parse(old_s), parse(new_s)
+        on, nn = demangle(sorted(old)), demangle(sorted(new))
+        by_name = {d: m for m, d in nn.items()}
+        for rows in (old, new):
+            for r in rows.values():
+                r["waves"] = waves(r["vgpr_count"])
+        print(f"\n== {old_s.name}: {len(old)} kernels before, {len(new)} now; old / twin per column")
+        print("  ".join(f"{s:>9}" for s in SHORT) + "  same text  kernel")
+        twins = set()
+        for m in sorted(old, key=on.get):
+            t = by_name.get(twin_of(on[m], suffix)) or by_name.get(on[m])          # (a kernel the change did not touch keeps its name)
+            if t is None:
+                print(f"NO TWIN  {on[m]}")
+                bad += 1
+                continue
+            twins.add(t)
+            o, w = old[m], new[t]
+            fail = any(o[k] != w[k] for k in MUST)
+            bad += fail
+            same = body(old_s, m) == body(new_s, t)
+            print("  ".join(f"{str(o[c]) + '/' + str(w[c]):>9}" for c in COLS) + f"  {'yes' if same else 'no':>9}  {nn[t]}" + ("   <-- FAIL" if fail else ""))
+        print("-- new instantiations")
+        print("  ".join(f"{s:>9}" for s in SHORT) + "  kernel")
+        for m in sorted(set(new) - twins, key=nn.get):
+            print("  ".join(f"{new[m][c]:>9}" for c in COLS) + f"  {nn[m]}")
+    print(f"\n{'FAIL: ' + str(bad) + ' kernels' if bad else 'ok: every twin keeps the old figures'}")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
