@@ -690,6 +690,40 @@ int mi355q_bfp_attention_extend_grouped(const float* q, const void* kq, const vo
                                         int64_t M, int64_t max_length, int64_t C, int64_t D, const int32_t* qk_params,
                                         const int32_t* pv_params, const int64_t* strides, void* stream);
 
+/* Paged cache: the same cache in PAGES of P keys (P a power of two >= 32, else MI355Q_E_BADARG) drawn from pools shared by all rows,
+ * so that a row holds memory for the keys it has, a finished row's pages serve another, and rows can share a common prefix.
+ *   kq_pool [num_pages][P / 16][D / 32][64][8], vq_pool [num_pages][P / 32][D / 16][64][8]: a page holds its 1-KiB pieces in the
+ *   order of the contiguous cache (csrc/mi355q_decode.h); mi355q_bfp_kv_paged_bytes gives the sizes (stage stays per ROW, [B][16][D]
+ *   fp32: the open 16-key tile belongs to a row).  Zero vq_pool once; a recycled page needs no clearing (finite values).
+ *   block_table: int32 [B][max_pages] on the device, 4-byte aligned: the page of row b's logical page i (keys i P .. i P + P - 1).
+ *   A row's logical capacity is C = max_pages * P: what max_length is checked against (max_length > C, and max_length + n > C on the
+ *   append: MI355Q_E_BADARG, nothing is written) and what sizes the decode workspace.
+ * Always the ragged form: `lengths` (and the host bound max_length) as in the *_ragged calls, `counts` as there; G = 0 or 1 is the
+ * ungrouped form, G > 1 as in the *_grouped calls (q / out hold B * G rows, workspace and splits those of the launch rows).
+ * Only the place of a piece changes: every call gives, bit for bit, what its contiguous counterpart gives on a cache holding the same
+ * keys (decode: with the same number of splits).  The kernels look up only logical pages that hold keys of the row -- below
+ * ceil(min(lengths[b], max_length) / P); the append: the pages of the new keys, which the caller must have put in the table -- and
+ * every page id is clamped into 0 .. num_pages - 1 before it forms an address: a wrong table gives wrong numbers, never an access
+ * outside the pools.  Two rows may name the same page as long as neither appends into it. */
+int mi355q_bfp_kv_paged_bytes(int64_t num_pages, int64_t P, int64_t B, int64_t D, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_bytes);
+int mi355q_bfp_kv_append_paged(void* kq_pool, void* vq_pool, float* stage, const float* k, const float* v, const int32_t* lengths,
+                               const int32_t* counts, const int32_t* block_table, int64_t B, int64_t max_pages, int64_t num_pages,
+                               int64_t P, int64_t D, int64_t n, int64_t max_length, const int32_t* qk_params, const int32_t* pv_params,
+                               const int64_t* strides, void* stream);
+int mi355q_bfp_kv_decode_fp32_paged(const void* kq_pool, const void* vq_pool, const int32_t* lengths, const int32_t* block_table,
+                                    float* k_out, float* v_out, int64_t B, int64_t max_pages, int64_t num_pages, int64_t P, int64_t D,
+                                    int64_t max_length, void* stream);
+int mi355q_bfp_attention_decode_paged(const float* q, const void* kq_pool, const void* vq_pool, int32_t G, const int32_t* lengths,
+                                      const int32_t* block_table, int32_t causal, float q_scale, float scale_div, float* out,
+                                      void* workspace, int64_t B, int64_t M, int64_t max_length, int64_t max_pages, int64_t num_pages,
+                                      int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
+                                      int32_t splits, void* stream);
+int mi355q_bfp_attention_extend_paged(const float* q, const void* kq_pool, const void* vq_pool, int32_t G, const int32_t* lengths,
+                                      const int32_t* counts, const int32_t* block_table, int32_t causal, float q_scale, float scale_div,
+                                      float* out, int64_t B, int64_t M, int64_t max_length, int64_t max_pages, int64_t num_pages,
+                                      int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
+                                      void* stream);
+
 /* ---- the un-blocked quantisers -------------------------------------------------------------------------------------
  * replaces: quantizers/minifloat.py:134-196 (minifloat_ieee_quantizer: implicit leading one, subnormals at the lowest
  *           exponent), :21-86 (minifloat_denorm_quantizer: no implicit one, exponent ceil(log2(|x| + 1e-9)) per element)

@@ -1246,6 +1246,135 @@ int mi355q_bfp_attention_extend_grouped(const float* q, const void* kq, const vo
                                        lengths, counts, static_cast<hipStream_t>(stream), G);
 }
 
+// ---- paged cache: pools of pages and a page table per row (mi355q_decode.h); always the ragged form ---------------------------
+namespace {
+// the pools' shape and the rows' table: BADARG for a page size that is no power of two >= 32; `pg` gets the kernels' view
+int paged_shape(int64_t B, int64_t max_pages, int64_t num_pages, int64_t P, int64_t D, const int32_t* block_table, KvPages* pg) {
+    if (P < 32 || (P & (P - 1)) != 0 || B < 1 || B > 65535 || D < 1 || max_pages < 1 || num_pages < 1) return MI355Q_E_BADARG;
+    if (D % 32 != 0 || D > 128 || P > (1LL << 30) || max_pages > (1LL << 30) / P || num_pages > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
+    if (pg) {
+        int lg = 5;
+        while ((1LL << lg) < P) ++lg;
+        *pg = KvPages{block_table, (int)max_pages, (int)num_pages, lg};
+    }
+    return 0;
+}
+}  // namespace
+
+int mi355q_bfp_kv_paged_bytes(int64_t num_pages, int64_t P, int64_t B, int64_t D, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_bytes) {
+    if (!k_bytes || !v_bytes || !stage_bytes) return MI355Q_E_BADARG;
+    const int rc = paged_shape(B, 1, num_pages, P, D, nullptr, nullptr);
+    if (rc) return rc;
+    *k_bytes = kv_k_bytes(num_pages, P, D);                   // (a page is a cache row of P keys; P % 32 == 0: no rounding in V)
+    *v_bytes = kv_v_bytes(num_pages, P, D);
+    *stage_bytes = kv_stage_bytes(B, D);
+    return 0;
+}
+
+int mi355q_bfp_kv_append_paged(void* kq_pool, void* vq_pool, float* stage, const float* k, const float* v, const int32_t* lengths,
+                               const int32_t* counts, const int32_t* block_table, int64_t B, int64_t max_pages, int64_t num_pages,
+                               int64_t P, int64_t D, int64_t n, int64_t max_length, const int32_t* qk_params, const int32_t* pv_params,
+                               const int64_t* strides, void* stream) {
+    KvPages pg{};
+    int rc = paged_shape(B, max_pages, num_pages, P, D, block_table, &pg);
+    if (rc) return rc;
+    if (max_length < 0 || n < 0 || !qk_params || !pv_params) return MI355Q_E_BADARG;
+    if (max_length + n > max_pages * P) return MI355Q_E_BADARG;  // (nothing is written)
+    if (n == 0) return 0;
+    if (!kq_pool || !vq_pool || !stage || !k || !v || !lengths || !block_table) return MI355Q_E_BADARG;
+    QuantArgs ak{}, av{};
+    if ((rc = decode_quant_args(qk_params + 3, ak)) != 0 || (rc = decode_quant_args(pv_params + 3, av)) != 0) return rc;
+    if ((reinterpret_cast<uintptr_t>(kq_pool) | reinterpret_cast<uintptr_t>(vq_pool) | reinterpret_cast<uintptr_t>(stage) |
+         reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v)) % 16 ||
+        (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(block_table)) % 4)
+        return MI355Q_E_ALIGN;
+    long long st4[4] = {n * D, D, n * D, D};
+    if (strides)
+        for (int i = 0; i < 4; ++i) {
+            if (strides[i] % 4) return MI355Q_E_ALIGN;
+            st4[i] = strides[i];
+        }
+    const KvCache c{static_cast<uint16_t*>(kq_pool), static_cast<uint16_t*>(vq_pool), stage, B, max_pages * P, (int)D};
+    return launch_kv_append_ragged(c, ak, av, k, v, st4[0], st4[1], st4[2], st4[3], lengths, counts, n, static_cast<hipStream_t>(stream), &pg);
+}
+
+int mi355q_bfp_kv_decode_fp32_paged(const void* kq_pool, const void* vq_pool, const int32_t* lengths, const int32_t* block_table,
+                                    float* k_out, float* v_out, int64_t B, int64_t max_pages, int64_t num_pages, int64_t P, int64_t D,
+                                    int64_t max_length, void* stream) {
+    KvPages pg{};
+    const int rc = paged_shape(B, max_pages, num_pages, P, D, block_table, &pg);
+    if (rc) return rc;
+    if (max_length < 0 || max_length > max_pages * P) return MI355Q_E_BADARG;
+    if (max_length == 0) return 0;
+    if (!kq_pool || !vq_pool || !k_out || !v_out || !lengths || !block_table) return MI355Q_E_BADARG;
+    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq_pool)), static_cast<uint16_t*>(const_cast<void*>(vq_pool)), nullptr, B,
+                    max_pages * P, (int)D};
+    return launch_kv_decode_fp32(c, k_out, v_out, max_length, static_cast<hipStream_t>(stream), lengths, &pg);
+}
+
+int mi355q_bfp_attention_decode_paged(const float* q, const void* kq_pool, const void* vq_pool, int32_t G, const int32_t* lengths,
+                                      const int32_t* block_table, int32_t causal, float q_scale, float scale_div, float* out,
+                                      void* workspace, int64_t B, int64_t M, int64_t max_length, int64_t max_pages, int64_t num_pages,
+                                      int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
+                                      int32_t splits, void* stream) {
+    if (M < 0 || max_length < 0 || splits < 0 || G < 0) return MI355Q_E_BADARG;
+    KvPages pg{};
+    int rc = paged_shape(B, max_pages, num_pages, P, D, block_table, &pg);
+    if (rc) return rc;
+    if (max_length > max_pages * P) return MI355Q_E_BADARG;
+    if (M < 1 || M > 16 || max_length < M) return MI355Q_E_UNSUPPORTED;
+    if (G <= 1) G = 0;                                        // (0 or 1: ungrouped)
+    if (G && B * (G / decode_group_width(G, M)) > 65535) return MI355Q_E_UNSUPPORTED;
+    if (!q || !kq_pool || !vq_pool || !lengths || !block_table || !out || !workspace || !qk_params || !pv_params) return MI355Q_E_BADARG;
+    QuantArgs aq{}, ap{};
+    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq_pool) | reinterpret_cast<uintptr_t>(vq_pool) |
+         reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) % 16 ||
+        (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(block_table)) % 4)
+        return MI355Q_E_ALIGN;
+    long long st4[4];
+    if (strides)
+        for (int i = 0; i < 4; ++i) {
+            if (strides[i] % 4) return MI355Q_E_ALIGN;
+            st4[i] = strides[i];
+        }
+    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq_pool)), static_cast<uint16_t*>(const_cast<void*>(vq_pool)), nullptr, B,
+                    max_pages * P, (int)D};
+    return launch_bfp_attention_decode(aq, ap, c, q, out, workspace, M, max_length, causal != 0, q_scale, scale_div,
+                                       strides ? st4 : nullptr, splits, static_cast<hipStream_t>(stream), lengths, G, &pg);
+}
+
+int mi355q_bfp_attention_extend_paged(const float* q, const void* kq_pool, const void* vq_pool, int32_t G, const int32_t* lengths,
+                                      const int32_t* counts, const int32_t* block_table, int32_t causal, float q_scale, float scale_div,
+                                      float* out, int64_t B, int64_t M, int64_t max_length, int64_t max_pages, int64_t num_pages,
+                                      int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
+                                      void* stream) {
+    if (M < 0 || max_length < 0 || G < 0) return MI355Q_E_BADARG;
+    KvPages pg{};
+    int rc = paged_shape(B, max_pages, num_pages, P, D, block_table, &pg);
+    if (rc) return rc;
+    if (max_length > max_pages * P) return MI355Q_E_BADARG;
+    if (M < 1 || max_length < M) return MI355Q_E_UNSUPPORTED;
+    if (G <= 1) G = 0;
+    if (!q || !kq_pool || !vq_pool || !lengths || !block_table || !out || !qk_params || !pv_params) return MI355Q_E_BADARG;
+    QuantArgs aq{}, ap{};
+    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq_pool) | reinterpret_cast<uintptr_t>(vq_pool) |
+         reinterpret_cast<uintptr_t>(out)) % 16 ||
+        (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(block_table)) % 4)
+        return MI355Q_E_ALIGN;
+    long long st4[4];
+    if (strides)
+        for (int i = 0; i < 4; ++i) {
+            if (strides[i] % 4) return MI355Q_E_ALIGN;
+            st4[i] = strides[i];
+        }
+    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq_pool)), static_cast<uint16_t*>(const_cast<void*>(vq_pool)), nullptr, B,
+                    max_pages * P, (int)D};
+    return launch_bfp_attention_extend(aq, ap, c, q, out, M, max_length, causal != 0, q_scale, scale_div, strides ? st4 : nullptr,
+                                       lengths, counts, static_cast<hipStream_t>(stream), G, &pg);
+}
+
 // block_minifloat (fmt 1) / block_log (fmt 2) products: the same two kernels with the other quantisers' block parameters
 static int values_matmul_impl(int fmt, bool softmax, const float* mask, long long causal_off, const float* x, const float* y,
                               float* out, void* workspace, int64_t B, int64_t M, int64_t K, int64_t N, int32_t x_width,

@@ -41,6 +41,18 @@
 // and split (decode_splits without an override) for B * rpc rows.  Per cache row stay: the length, the key tiles, the split
 // partition.  Q fragments, horizon, softmax statistics and the [1,16] probability blocks are per column, the MFMA keeps columns
 // apart: each head gets the bits the GQ = false kernels give it on a private copy of the row, with the same number of splits.
+//
+// Paged cache (PG = true kernels, always with RG = true): kq / vq are POOLS of num_pages pages of P keys (P a power of two >= 32, so a
+// K tile, a V pair and the two tiles of one extend step never straddle a page), a page holding its pieces in the order above:
+//   kq_pool [num_pages][P / 16][D / 32][64][8]     vq_pool [num_pages][P / 32][D / 16][64][8]
+// and a device table, int32 [B][max_pages], names the page of row b's logical page i.  Only the piece's place changes:
+//   logical K tile t -> tile page * (P / 16) + t % (P / 16), logical V pair s -> pair page * (P / 32) + s % (P / 32),
+//   page = clamp(table[b][t / (P / 16)], 0, num_pages - 1): a wrong table gives wrong numbers, never an address outside the pools.
+// A kernel looks up only logical pages that hold keys of the row -- below ceil(min(lengths[b], max_length) / P) for the readers, the
+// pages of the new keys for the append -- and max_length <= C = max_pages * P keeps those inside the table's row; entries behind are
+// never read.  stage stays [B][16][D] (the open tile belongs to a row), the scores workspace stays indexed by LOGICAL tile, and
+// every value is the one the contiguous cache holds: the paged kernels give its bits.  Pages start out zeroed; a recycled page holds
+// older quantised values, finite, which is all a V slot behind a row's length needs (above).
 #ifndef MI355Q_DECODE_H
 #define MI355Q_DECODE_H
 #include <hip/hip_runtime.h>
@@ -57,6 +69,12 @@ struct KvCache {
     long long B, C;
     int D;
 };
+// the page table of a paged cache: KvCache.kq / .vq are then the pools and KvCache.C = max_pages * P, a row's logical capacity
+struct KvPages {
+    const int32_t* table;     // [B][max_pages] on the device
+    int max_pages, num_pages;
+    int lg_p;                 // log2(P), >= 5
+};
 inline long long kv_k_bytes(long long B, long long C, long long D) { return B * C * D * 2; }
 inline long long kv_v_bytes(long long B, long long C, long long D) { return B * ((C + 31) / 32) * 32 * D * 2; }
 inline long long kv_stage_bytes(long long B, long long D) { return B * 16 * D * 4; }
@@ -67,9 +85,11 @@ int launch_kv_append(const KvCache& c, const QuantArgs& ak, const QuantArgs& av,
 // ragged: row b's first counts[b] (NULL: n) input rows behind ITS length lengths[b] (device arrays [B])
 int launch_kv_append_ragged(const KvCache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
                             long long kst, long long vsb, long long vst, const int32_t* lengths, const int32_t* counts, long long n,
-                            hipStream_t st);
+                            hipStream_t st, const KvPages* pages = nullptr);
 // the cache's quantised values back as fp32 [B, L, D] (tests, debugging); lengths != NULL: zeros behind row b's lengths[b]
-int launch_kv_decode_fp32(const KvCache& c, float* k_out, float* v_out, long long L, hipStream_t st, const int32_t* lengths = nullptr);
+// pages != NULL (with lengths): the paged cache
+int launch_kv_decode_fp32(const KvCache& c, float* k_out, float* v_out, long long L, hipStream_t st, const int32_t* lengths = nullptr,
+                          const KvPages* pages = nullptr);
 
 // S of a decode over L keys: a pure function of (B, L, D); `override` > 0 asks for that many (clamped, then evened out so
 // that no split is empty).  1 <= S <= ceil(L / 32).
@@ -91,6 +111,7 @@ struct DecodeArgs {
     int D, S, pps;            // pps = key pairs per split
     const int32_t* lengths;   // ragged: [B] on the device, L / NT / NP above are those of max_length (partition, strides); else NULL
     int gw, rpc;              // grouped queries (GQ): heads a launch row serves, launch rows a cache row; gw * rpc = G.  Else 1, 1
+    KvPages pg;               // paged cache (PG): kq / vq are the pools; else zeros (behind every field the other kernels read)
 };
 // q's and out's element strides of batch and row from the wrapper's {q batch, q row, out batch, out row}; NULL: contiguous [B, M, D]
 // (DecodeArgs, and ExtendArgs of mi355q_extend.h)
@@ -102,10 +123,11 @@ inline void fill_qo_strides(Args& g, const long long* strides, long long M, long
 // heads of a group one launch row serves: the largest divisor gw of G with gw * M <= 16 (0: G < 1 or M outside 1 .. 16)
 int decode_group_width(long long G, long long M);
 // lengths != NULL: the ragged form, L = max_length.  G >= 1: the grouped form (q / out hold c.B * G rows, the workspace is that of
-// c.B * G / decode_group_width(G, M) launch rows); G == 0: one query row a cache row
+// c.B * G / decode_group_width(G, M) launch rows); G == 0: one query row a cache row.  pages != NULL (with lengths): the paged cache
 int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out,
                                 void* workspace, long long M, long long L, int causal, float q_scale, float scale_div,
-                                const long long* strides, int splits, hipStream_t st, const int32_t* lengths = nullptr, int G = 0);
+                                const long long* strides, int splits, hipStream_t st, const int32_t* lengths = nullptr, int G = 0,
+                                const KvPages* pages = nullptr);
 
 }  // namespace mi355q
 #endif

@@ -22,6 +22,9 @@
 // Grouped queries (GQ = true; column map and launch rows: mi355q_decode.h): the G query heads that share a cache row sit in the
 // columns one query head leaves unused -- gw heads x M queries a launch row -- and are served by the same K / V fragment loads.
 // Everything per query is per column, so a head's bits are those of the GQ = false kernels on a private copy of the row.
+// Paged cache (PG = true, with RG = true only; layout and address rules: mi355q_decode.h): a tile's or pair's place goes through the
+// row's page table.  In the decode loops the index is wave-uniform, so the entry is one 4-byte load kept scalar like lengths[b], asked
+// for one iteration AHEAD of the fragment loads it addresses; the score workspace keeps logical indices.
 // MFMA roles as in mi355q_attention.hip (v_mfma_f32_16x16x32_bf16, the queries are the 16 columns): a lane's own values of the score
 // tiles 2 s, 2 s + 1 are the slots of its P fragment, and vq is stored with the same slot order.
 #include <hip/hip_runtime.h>
@@ -45,7 +48,16 @@ struct AppendArgs {
     int kblocks;
     const int32_t* lengths;     // ragged (RG): row b's L = lengths[b], its n = counts[b] (NULL: n) <= n; t0, t1 follow in the kernel
     const int32_t* counts;
+    KvPages pg;                 // paged cache (PG): c.kq / c.vq are the pools, c.C = max_pages * P; else zeros
 };
+
+// Paged cache: the table entry of row b's logical page i as loaded (pg_raw: i must be a page that holds keys of the row), and the
+// physical tile (sh = lg_p - 4) or pair (sh = lg_p - 5) of logical tile / pair t from it -- the page id clamped into the pool first.
+__device__ __forceinline__ int pg_raw(const KvPages& p, long long b, long long i) { return p.table[b * p.max_pages + i]; }
+__device__ __forceinline__ long long pg_place(const KvPages& p, int raw, long long t, int sh) {
+    const long long page = min(max(raw, 0), p.num_pages - 1);
+    return (page << sh) + (t & ((1ll << sh) - 1));
+}
 
 // row b's (L, n) of a ragged append, scalar; false: nothing to do (negative values are taken as 0, a count above n as n)
 __device__ __forceinline__ bool append_row(const AppendArgs& a, long long b, long long& L, long long& n) {
@@ -66,7 +78,7 @@ __device__ __forceinline__ void kv_store_block(uint16_t* __restrict__ dst, const
     }
 }
 
-template <bool RG>
+template <bool RG, bool PG>
 __global__ __launch_bounds__(256) void kv_append_kernel(const QuantArgs ak, const QuantArgs av, const AppendArgs a) {
     const int tid = threadIdx.x, D = a.c.D;
     const long long b = blockIdx.y, NTC = a.c.C >> 4, NPC = (a.c.C + 31) >> 5;
@@ -106,7 +118,9 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const QuantArgs ak, cons
             }
         }
         const int c = d >> 5, g = (d >> 3) & 3, j = d & 7;
-        kv_store_block(a.c.kq + ((b * NTC + t) * (D >> 5) + c) * 512 + 16 * g * 8 + j, x, bmax, ak);
+        long long pt = b * NTC + t;
+        if constexpr (PG) pt = pg_place(a.pg, pg_raw(a.pg, b, t >> (a.pg.lg_p - 4)), t, a.pg.lg_p - 4);     // (t < NTC: inside the table's row)
+        kv_store_block(a.c.kq + (pt * (D >> 5) + c) * 512 + 16 * g * 8 + j, x, bmax, ak);
     } else {
         // V: thread (new key, 16-d block) quantises one block
         const int DT = D >> 4;
@@ -127,7 +141,9 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const QuantArgs ak, cons
         }
         const long long s = key >> 5;
         const int h = (int)(key >> 4) & 1, g = (int)(key & 15) >> 2, j = 4 * h + (int)(key & 3);
-        kv_store_block(a.c.vq + ((b * NPC + s) * DT + dt) * 512 + 16 * g * 8 + j, x, bmax, av);
+        long long ps = b * NPC + s;
+        if constexpr (PG) ps = pg_place(a.pg, pg_raw(a.pg, b, s >> (a.pg.lg_p - 5)), s, a.pg.lg_p - 5);     // (key < C: inside the table's row)
+        kv_store_block(a.c.vq + (ps * DT + dt) * 512 + 16 * g * 8 + j, x, bmax, av);
     }
 }
 
@@ -157,7 +173,7 @@ int launch_kv_append(const KvCache& c, const QuantArgs& ak, const QuantArgs& av,
     const long long kblocks = (a.t1 - a.t0 + 1 + per - 1) / per, vblocks = (n * (c.D / 16) + 255) / 256;
     if (kblocks + vblocks > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
     a.kblocks = (int)kblocks;
-    hipLaunchKernelGGL(kv_append_kernel<false>, dim3((unsigned)(kblocks + vblocks), (unsigned)c.B), dim3(256), 0, st, ak, av, a);
+    hipLaunchKernelGGL((kv_append_kernel<false, false>), dim3((unsigned)(kblocks + vblocks), (unsigned)c.B), dim3(256), 0, st, ak, av, a);
     const unsigned open_rows = (unsigned)((L + n) % 16);                // (0: tile t1 is full, nothing to stage)
     if (a.t1 > a.t0 && open_rows) hipLaunchKernelGGL(kv_stage_kernel<false>, dim3(open_rows, (unsigned)c.B), dim3(c.D), 0, st, a);
     return (int)hipGetLastError();
@@ -168,7 +184,7 @@ int launch_kv_append(const KvCache& c, const QuantArgs& ak, const QuantArgs& av,
 // rows overwrite the staged rows that tile t0's threads of the same row read.  n == 1, the decode step, never crosses.
 int launch_kv_append_ragged(const KvCache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
                             long long kst, long long vsb, long long vst, const int32_t* lengths, const int32_t* counts, long long n,
-                            hipStream_t st) {
+                            hipStream_t st, const KvPages* pages) {
     AppendArgs a{};
     a.c = c; a.k = k; a.v = v;
     a.ksb = ksb; a.kst = kst; a.vsb = vsb; a.vst = vst;
@@ -177,14 +193,20 @@ int launch_kv_append_ragged(const KvCache& c, const QuantArgs& ak, const QuantAr
     const long long kblocks = ((n + 14) / 16 + 1 + per - 1) / per, vblocks = (n * (c.D / 16) + 255) / 256;
     if (kblocks + vblocks > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
     a.kblocks = (int)kblocks;
-    hipLaunchKernelGGL(kv_append_kernel<true>, dim3((unsigned)(kblocks + vblocks), (unsigned)c.B), dim3(256), 0, st, ak, av, a);
+    const dim3 grid((unsigned)(kblocks + vblocks), (unsigned)c.B);
+    if (pages) {
+        a.pg = *pages;
+        hipLaunchKernelGGL((kv_append_kernel<true, true>), grid, dim3(256), 0, st, ak, av, a);
+    } else {
+        hipLaunchKernelGGL((kv_append_kernel<true, false>), grid, dim3(256), 0, st, ak, av, a);
+    }
     if (n > 1) hipLaunchKernelGGL(kv_stage_kernel<true>, dim3((unsigned)(n - 1 < 15 ? n - 1 : 15), (unsigned)c.B), dim3(c.D), 0, st, a);
     return (int)hipGetLastError();
 }
 
-template <bool RG>
-__global__ __launch_bounds__(256) void kv_decode_fp32_kernel(const KvCache c, float* __restrict__ k_out, float* __restrict__ v_out,
-                                                             long long L, const int32_t* __restrict__ lengths) {
+template <bool RG, bool PG>
+__device__ __forceinline__ void kv_decode_fp32_body(const KvCache& c, float* __restrict__ k_out, float* __restrict__ v_out, long long L,
+                                                    const int32_t* __restrict__ lengths, const KvPages& pg) {
     const int D = c.D;
     const long long b = blockIdx.y, NTC = c.C >> 4, NPC = (c.C + 31) >> 5;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -198,6 +220,15 @@ __global__ __launch_bounds__(256) void kv_decode_fp32_kernel(const KvCache c, fl
             return;
         }
     }
+    if constexpr (PG) {                                               // (key < lengths[b], key < L <= C: a page of the row's)
+        const int raw = pg_raw(pg, b, key >> pg.lg_p), h = (int)(key >> 4) & 1, g = (int)(key & 15) >> 2, j = 4 * h + (int)(key & 3);
+        const long long pt = pg_place(pg, raw, key >> 4, pg.lg_p - 4), ps = pg_place(pg, raw, key >> 5, pg.lg_p - 5);
+        const uint16_t kb = c.kq[(pt * (D >> 5) + (d >> 5)) * 512 + ((key & 15) + 16 * ((d >> 3) & 3)) * 8 + (d & 7)];
+        const uint16_t vb = c.vq[(ps * (D >> 4) + (d >> 4)) * 512 + ((d & 15) + 16 * g) * 8 + j];
+        k_out[(b * L + key) * D + d] = __uint_as_float((unsigned)kb << 16);
+        v_out[(b * L + key) * D + d] = __uint_as_float((unsigned)vb << 16);
+        return;
+    }
     const uint16_t kb = c.kq[((b * NTC + (key >> 4)) * (D >> 5) + (d >> 5)) * 512 + ((key & 15) + 16 * ((d >> 3) & 3)) * 8 + (d & 7)];
     const int h = (int)(key >> 4) & 1, g = (int)(key & 15) >> 2, j = 4 * h + (int)(key & 3);
     const uint16_t vb = c.vq[((b * NPC + (key >> 5)) * (D >> 4) + (d >> 4)) * 512 + ((d & 15) + 16 * g) * 8 + j];
@@ -205,11 +236,25 @@ __global__ __launch_bounds__(256) void kv_decode_fp32_kernel(const KvCache c, fl
     v_out[(b * L + key) * D + d] = __uint_as_float((unsigned)vb << 16);
 }
 
-int launch_kv_decode_fp32(const KvCache& c, float* k_out, float* v_out, long long L, hipStream_t st, const int32_t* lengths) {
+// (two entry points, one body: the unpaged kernels keep their argument list, and with it the code they had before there were pages)
+template <bool RG>
+__global__ __launch_bounds__(256) void kv_decode_fp32_kernel(const KvCache c, float* __restrict__ k_out, float* __restrict__ v_out,
+                                                             long long L, const int32_t* __restrict__ lengths) {
+    kv_decode_fp32_body<RG, false>(c, k_out, v_out, L, lengths, KvPages{});
+}
+__global__ __launch_bounds__(256) void kv_decode_fp32_paged_kernel(const KvCache c, float* __restrict__ k_out, float* __restrict__ v_out,
+                                                                   long long L, const int32_t* __restrict__ lengths, const KvPages pg) {
+    kv_decode_fp32_body<true, true>(c, k_out, v_out, L, lengths, pg);
+}
+
+int launch_kv_decode_fp32(const KvCache& c, float* k_out, float* v_out, long long L, hipStream_t st, const int32_t* lengths,
+                          const KvPages* pages) {
     const long long blocks = (L * c.D + 255) / 256;
     if (blocks > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
     const dim3 grid((unsigned)blocks, (unsigned)c.B);
-    if (lengths) hipLaunchKernelGGL(kv_decode_fp32_kernel<true>, grid, dim3(256), 0, st, c, k_out, v_out, L, lengths);
+    if (pages && !lengths) return MI355Q_E_BADARG;
+    if (pages) hipLaunchKernelGGL(kv_decode_fp32_paged_kernel, grid, dim3(256), 0, st, c, k_out, v_out, L, lengths, *pages);
+    else if (lengths) hipLaunchKernelGGL(kv_decode_fp32_kernel<true>, grid, dim3(256), 0, st, c, k_out, v_out, L, lengths);
     else hipLaunchKernelGGL(kv_decode_fp32_kernel<false>, grid, dim3(256), 0, st, c, k_out, v_out, L, lengths);
     return (int)hipGetLastError();
 }
@@ -290,7 +335,7 @@ __device__ __forceinline__ long long dec_cache_row(const DecodeArgs& g, long lon
     else return y;
 }
 
-template <int DC, bool RG, bool GQ>
+template <int DC, bool RG, bool GQ, bool PG>
 __global__ __launch_bounds__(256) void decode_scores_kernel(const QuantArgs aq, const DecodeArgs g) {
     __shared__ float sm_[4][64], sl_[4][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -314,15 +359,25 @@ __global__ __launch_bounds__(256) void decode_scores_kernel(const QuantArgs aq, 
     const long long kvis = dec_horizon(g, L, qrow);
     const float scale_inv = g.scale_div != 0.f ? 1.0f / g.scale_div : 0.f;
     const long long t_lo = 2 * g.pps * s, t_hi = min(NT, t_lo + 2 * g.pps);
-    const uint16_t* __restrict__ kfb = g.kq + cb * g.NTC * DC * 512 + lane * 8;
+    const uint16_t* __restrict__ kfb = g.kq + (PG ? 0 : cb * g.NTC * DC * 512) + lane * 8;
     float* __restrict__ sc = g.scores + b * g.NT * 256 + lane * 4;
     // running (max, sum of exp(x - max)) of this lane's visible scores, re-based when the maximum moves
     float m_run = -INFINITY, l_run = 0.f;
+    // paged: the table entry of the NEXT tile this wave takes is asked for while this one's fragments are loaded (t < t_hi <= NT)
+    int raw = 0;
+    if constexpr (PG) {
+        if (t_lo + wave < t_hi) raw = pg_raw(g.pg, cb, (t_lo + wave) >> (g.pg.lg_p - 4));
+    }
     for (long long t = t_lo + wave; t < t_hi; t += 4) {
+        long long pt = t;                                   // the tile's place in kq; the workspace keeps t
+        if constexpr (PG) {
+            pt = pg_place(g.pg, __builtin_amdgcn_readfirstlane(raw), t, g.pg.lg_p - 4);
+            if (t + 4 < t_hi) raw = pg_raw(g.pg, cb, (t + 4) >> (g.pg.lg_p - 4));
+        }
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int c = 0; c < DC; ++c)
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(kfb + (t * DC + c) * 512), qf[c], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(kfb + (pt * DC + c) * 512), qf[c], acc, 0, 0, 0);
         if (g.scale_div != 0.f) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc[e] = at_div(acc[e], g.scale_div, scale_inv);
@@ -361,7 +416,7 @@ __global__ __launch_bounds__(256) void decode_scores_kernel(const QuantArgs aq, 
     }
 }
 
-template <int DC, bool RG, bool GQ>
+template <int DC, bool RG, bool GQ, bool PG>
 __global__ __launch_bounds__(256) void decode_pv_kernel(const QuantArgs ap, const DecodeArgs g) {
     constexpr int DT = DC * 2;
     __shared__ f32x4 red[4][DT][64];
@@ -398,15 +453,24 @@ __global__ __launch_bounds__(256) void decode_pv_kernel(const QuantArgs ap, cons
     }
     const float row_inv = 1.0f / row_sum;
     const int mbp = (int)__builtin_log2f(ap.shift);
-    const uint16_t* __restrict__ vfb = g.vq + cb * g.NPC * DT * 512 + lane * 8;
+    const uint16_t* __restrict__ vfb = g.vq + (PG ? 0 : cb * g.NPC * DT * 512) + lane * 8;
     const float* __restrict__ sc = g.scores + b * g.NT * 256 + lane * 4;
     f32x4 o[DT];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    int raw = 0;                                            // (paged: one pair ahead, as in decode_scores_kernel; pr_i < p_hi <= NP)
+    if constexpr (PG) {
+        if (p_lo + wave < p_hi) raw = pg_raw(g.pg, cb, (p_lo + wave) >> (g.pg.lg_p - 5));
+    }
     for (long long pr_i = p_lo + wave; pr_i < p_hi; pr_i += 4) {
+        long long pp = pr_i;                                // the pair's place in vq; scores and horizon keep pr_i
+        if constexpr (PG) {
+            pp = pg_place(g.pg, __builtin_amdgcn_readfirstlane(raw), pr_i, g.pg.lg_p - 5);
+            if (pr_i + 4 < p_hi) raw = pg_raw(g.pg, cb, (pr_i + 4) >> (g.pg.lg_p - 5));
+        }
         uint4 vb[DT];
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt) vb[dt] = *reinterpret_cast<const uint4*>(vfb + (pr_i * DT + dt) * 512);
+        for (int dt = 0; dt < DT; ++dt) vb[dt] = *reinterpret_cast<const uint4*>(vfb + (pp * DT + dt) * 512);
         float pq[8];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -468,8 +532,10 @@ int decode_group_width(long long G, long long M) {
 // G == 0: one query row a cache row, the GQ = false kernels.  G >= 1: the grouped kernels over c.B * rpc launch rows.
 int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out,
                                 void* workspace, long long M, long long L, int causal, float q_scale, float scale_div,
-                                const long long* strides, int splits, hipStream_t st, const int32_t* lengths, int G) {
+                                const long long* strides, int splits, hipStream_t st, const int32_t* lengths, int G, const KvPages* pages) {
+    if (pages && !lengths) return MI355Q_E_BADARG;          // (no uniform paged launch)
     DecodeArgs g{};
+    if (pages) g.pg = *pages;
     g.q = q; g.kq = c.kq; g.vq = c.vq; g.out = out; g.lengths = lengths;
     g.M = M; g.L = L; g.D = c.D;
     g.NT = (L + 15) / 16; g.NP = (L + 31) / 32; g.NTC = c.C / 16; g.NPC = (c.C + 31) / 32;
@@ -486,14 +552,16 @@ int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const 
     g.stats = g.scores + rows * g.NT * 256;
     g.part = g.stats + rows * g.S * 32;
     const dim3 grid((unsigned)g.S, (unsigned)rows);
-#define MI355Q_DECODE_GO2(DC_, RG_, GQ_)                                                              \
-    hipLaunchKernelGGL((decode_scores_kernel<DC_, RG_, GQ_>), grid, dim3(256), 0, st, aq, g);         \
-    hipLaunchKernelGGL((decode_pv_kernel<DC_, RG_, GQ_>), grid, dim3(256), 0, st, ap, g);
+#define MI355Q_DECODE_GO2(DC_, RG_, GQ_, PG_)                                                         \
+    hipLaunchKernelGGL((decode_scores_kernel<DC_, RG_, GQ_, PG_>), grid, dim3(256), 0, st, aq, g);    \
+    hipLaunchKernelGGL((decode_pv_kernel<DC_, RG_, GQ_, PG_>), grid, dim3(256), 0, st, ap, g);
 #define MI355Q_DECODE_GO(DC_)                                                                         \
-    if (G) {                                                                                          \
-        if (lengths) { MI355Q_DECODE_GO2(DC_, true, true) } else { MI355Q_DECODE_GO2(DC_, false, true) }     \
+    if (pages) {                                                                                      \
+        if (G) { MI355Q_DECODE_GO2(DC_, true, true, true) } else { MI355Q_DECODE_GO2(DC_, true, false, true) }             \
+    } else if (G) {                                                                                   \
+        if (lengths) { MI355Q_DECODE_GO2(DC_, true, true, false) } else { MI355Q_DECODE_GO2(DC_, false, true, false) }     \
     } else {                                                                                          \
-        if (lengths) { MI355Q_DECODE_GO2(DC_, true, false) } else { MI355Q_DECODE_GO2(DC_, false, false) }   \
+        if (lengths) { MI355Q_DECODE_GO2(DC_, true, false, false) } else { MI355Q_DECODE_GO2(DC_, false, false, false) }   \
     }
     switch (c.D / 32) {
         case 1: MI355Q_DECODE_GO(1); break;

@@ -8,6 +8,7 @@
 // written as zeros; a row with m_b == 0 or m_b > L_b -- an empty slot, the decode kernels' rule -- reads no fragment and returns
 // zeros.  The host's M and max_length size the grid only; nothing is addressed from them.  No workspace: the scores are formed twice.
 // Grouped queries (G >= 1): q / out hold B * G rows, query row r reads cache row r / G and lengths[r / G], counts[r / G].
+// Paged cache (pages != NULL, lengths != NULL): the step's pieces through the row's page table (mi355q_decode.h).
 #ifndef MI355Q_EXTEND_H
 #define MI355Q_EXTEND_H
 #include <hip/hip_runtime.h>
@@ -31,11 +32,12 @@ struct ExtendArgs {
     const int32_t* lengths;   // [B] on the device or NULL
     const int32_t* counts;    // [B] on the device or NULL
     int G;                    // grouped queries (GQ): query rows a cache row; nb = B * G, lengths / counts stay [B].  Else 0
+    KvPages pg;               // paged cache (PG, mi355q_decode.h): kq / vq are the pools; else zeros
 };
 
 int launch_bfp_attention_extend(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out, long long M,
                                 long long max_length, int causal, float q_scale, float scale_div, const long long* strides,
-                                const int32_t* lengths, const int32_t* counts, hipStream_t st, int G = 0);
+                                const int32_t* lengths, const int32_t* counts, hipStream_t st, int G = 0, const KvPages* pages = nullptr);
 
 }  // namespace mi355q
 #endif

@@ -18,6 +18,14 @@
 //   divergent barriers the step count comes from the workgroup's LAST REAL query; a wave whose 16 queries lie behind m_b computes the
 //                      last real query again and stores zeros.  A workgroup wholly behind m_b stores zeros and leaves before the
 //                      first barrier.
+//   paged cache        PG = true (layout and address rules: mi355q_decode.h): a step's pieces -- K tiles 2 st and 2 st + 1, V pair st --
+//                      lie in ONE logical page, st / (P / 32), since P >= 32; and so does the clamped tile: min(2 st + 1, need - 1) is
+//                      2 st or 2 st + 1 for every st < nsteps.  So a step takes one table entry (scalar, clamped into the pool).  The
+//                      place inside the page is formed from the CLAMPED tile, as in the contiguous kernel: the piece read in place of
+//                      the missing tile is tile need - 1, one the append has written.  (The clamp acts only for odd need, and a page
+//                      holds an even number of tiles, so tile need would lie in the same page: the order decides which piece of the
+//                      page is read, not which table entry.)  The step's logical page holds key 32 st <= 16 (need - 1) <= L_b - 1: an
+//                      entry below ceil(L_b / P).  Entries are asked for two steps ahead of their DMA.
 //   missing V pieces   the last pair's second tile may not exist (t >= need): its probabilities are exact zeros, the stored V there
 //                      is finite (zeroed storage or older quantised values).
 #include <hip/hip_runtime.h>
@@ -34,7 +42,7 @@ namespace mi355q {
 // GQ = true (grouped queries): workgroup row b is a QUERY head -- q, out and the grid have B * G of them -- and reads cache row b / G:
 // its fragments, lengths[b / G], counts[b / G].  Nothing else differs, so a head's bits are those of GQ = false on a private copy of
 // the row.  The G workgroups of a group each read the row's fragments themselves (no sharing inside a workgroup).
-template <int DC, bool GQ>
+template <int DC, bool GQ, bool PG>
 __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantArgs aq, const QuantArgs ap, const ExtendArgs g) {
     constexpr int DT = DC * 2, KSTEP = 2 * DC * 1024, VSTEP = DT * 1024, STEP = KSTEP + VSTEP;      // bytes per 32 keys
     using gptr_t = const __attribute__((address_space(1))) void*;
@@ -69,26 +77,37 @@ __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantAr
     const long long kvis = g.causal ? L - m + qrow : L - 1;
     const long long need = (g.causal ? L - m + min(wg0 + 63, m - 1) : L - 1) / 16 + 1;
     const int nsteps = (int)((need + 1) / 2);
-    const unsigned char* __restrict__ kfb = reinterpret_cast<const unsigned char*>(g.kq) + cb * g.NTC * DC * 1024 + lane * 16;
-    const unsigned char* __restrict__ vfb = reinterpret_cast<const unsigned char*>(g.vq) + cb * g.NPC * DT * 1024 + lane * 16;
+    const unsigned char* __restrict__ kfb = reinterpret_cast<const unsigned char*>(g.kq) + (PG ? 0 : cb * g.NTC * DC * 1024) + lane * 16;
+    const unsigned char* __restrict__ vfb = reinterpret_cast<const unsigned char*>(g.vq) + (PG ? 0 : cb * g.NPC * DT * 1024) + lane * 16;
     const float scale_inv = g.scale_div != 0.f ? 1.0f / g.scale_div : 0.f;
 
     // LDS-DMA of one step: the K pieces of tiles 2 st, 2 st + 1 (DC KiB each) and, when with_v, the V pieces of pair st (DT KiB);
     // piece p by wave p % 4.  An odd tile count: the last step's second tile is tile need - 1 once more, never one behind the row.
-    auto dma = [&](int st, int buf, bool with_v) {
+    // paged: `page` is the step's table entry as loaded (pg_entry below); the place inside the page comes from the CLAMPED tile
+    auto dma = [&](int st, int buf, bool with_v, int page) {
+        long long pbase = 0;                                // the page's first pair in vq; twice that its first tile in kq
+        if constexpr (PG) pbase = (long long)min(max(__builtin_amdgcn_readfirstlane(page), 0), g.pg.num_pages - 1) << (g.pg.lg_p - 5);
 #pragma unroll
         for (int p = 0; p < 2 * DC; ++p)
             if ((p & 3) == wave) {
-                const long long t = min(2ll * st + p / DC, need - 1);
+                long long t = min(2ll * st + p / DC, need - 1);
+                if constexpr (PG) t = 2 * pbase + (t & ((2ll << (g.pg.lg_p - 5)) - 1));
                 __builtin_amdgcn_global_load_lds((gptr_t)(kfb + (t * DC + p % DC) * 1024), (lptr_t)(&stage[buf][p * 1024]), 16, 0, 0);
             }
         if (with_v) {
 #pragma unroll
             for (int p = 0; p < DT; ++p)
-                if ((p & 3) == wave)
-                    __builtin_amdgcn_global_load_lds((gptr_t)(vfb + ((long long)st * DT + p) * 1024), (lptr_t)(&stage[buf][KSTEP + p * 1024]),
-                                                     16, 0, 0);
+                if ((p & 3) == wave) {
+                    long long sp = st;
+                    if constexpr (PG) sp = pbase + (st & ((1 << (g.pg.lg_p - 5)) - 1));
+                    __builtin_amdgcn_global_load_lds((gptr_t)(vfb + (sp * DT + p) * 1024), (lptr_t)(&stage[buf][KSTEP + p * 1024]), 16, 0, 0);
+                }
         }
+    };
+    // the table entry of step st's page (st < nsteps: a page that holds keys of the row), 0 where there is no such step
+    auto pg_entry = [&](int st) -> int {
+        if constexpr (PG) return st < nsteps ? g.pg.table[cb * g.pg.max_pages + (st >> (g.pg.lg_p - 5))] : 0;
+        else return 0;
     };
     // scores of the step's two tiles for this lane's query: sv[h][e] <-> key 32 st + 16 h + 4 lg + e; -inf: not a visible key
     auto scores = [&](int st, int buf, f32x4 (&sv)[2]) {
@@ -111,11 +130,14 @@ __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantAr
 
     // ---- pass 1: running maximum and sum of exponentials per lane
     float m_run = -INFINITY, l_run = 0.f;
-    dma(0, 0, false);
+    int pg_next = pg_entry(1), pg_after = 0;                // entries of steps st + 1, st + 2 (the top-of-step wait covers their loads)
+    dma(0, 0, false, pg_entry(0));
     for (int st = 0; st < nsteps; ++st) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (st + 1 < nsteps) dma(st + 1, (st + 1) & 1, false);
+        if constexpr (PG) pg_after = pg_entry(st + 2);
+        if (st + 1 < nsteps) dma(st + 1, (st + 1) & 1, false, pg_next);
+        if constexpr (PG) pg_next = pg_after;
         f32x4 sv[2];
         scores(st, st & 1, sv);
         at_softmax_step(sv, m_run, l_run);
@@ -129,11 +151,14 @@ __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantAr
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int mbp = (int)__builtin_log2f(ap.shift);
-    dma(0, 0, true);
+    pg_next = pg_entry(1);
+    dma(0, 0, true, pg_entry(0));
     for (int st = 0; st < nsteps; ++st) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (st + 1 < nsteps) dma(st + 1, (st + 1) & 1, true);
+        if constexpr (PG) pg_after = pg_entry(st + 2);
+        if (st + 1 < nsteps) dma(st + 1, (st + 1) & 1, true, pg_next);
+        if constexpr (PG) pg_next = pg_after;
         f32x4 sv[2];
         scores(st, st & 1, sv);
         float pq[8];
@@ -162,8 +187,10 @@ __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantAr
 // G == 0: one query row a cache row (GQ = false).  G >= 1: q / out hold c.B * G rows, query row r on cache row r / G (GQ = true)
 int launch_bfp_attention_extend(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out, long long M,
                                 long long max_length, int causal, float q_scale, float scale_div, const long long* strides,
-                                const int32_t* lengths, const int32_t* counts, hipStream_t st, int G) {
+                                const int32_t* lengths, const int32_t* counts, hipStream_t st, int G, const KvPages* pages) {
+    if (pages && !lengths) return MI355Q_E_BADARG;          // (no uniform paged launch)
     ExtendArgs g{};
+    if (pages) g.pg = *pages;
     g.q = q; g.kq = c.kq; g.vq = c.vq; g.out = out; g.lengths = lengths; g.counts = counts;
     g.M = M; g.L = max_length; g.NTC = c.C / 16; g.NPC = (c.C + 31) / 32;
     fill_qo_strides(g, strides, M, c.D);
@@ -173,8 +200,10 @@ int launch_bfp_attention_extend(const QuantArgs& aq, const QuantArgs& ap, const 
     g.nb = (int)rows; g.nxb = (int)nxb; g.G = G;
     const dim3 grid((unsigned)(rows * nxb));
 #define MI355Q_EXTEND_GO(DC_)                                                                                          \
-    if (G) hipLaunchKernelGGL((bfp_attention_extend_kernel<DC_, true>), grid, dim3(256), 0, st, aq, ap, g);            \
-    else hipLaunchKernelGGL((bfp_attention_extend_kernel<DC_, false>), grid, dim3(256), 0, st, aq, ap, g);
+    if (pages && G) hipLaunchKernelGGL((bfp_attention_extend_kernel<DC_, true, true>), grid, dim3(256), 0, st, aq, ap, g);        \
+    else if (pages) hipLaunchKernelGGL((bfp_attention_extend_kernel<DC_, false, true>), grid, dim3(256), 0, st, aq, ap, g);      \
+    else if (G) hipLaunchKernelGGL((bfp_attention_extend_kernel<DC_, true, false>), grid, dim3(256), 0, st, aq, ap, g);          \
+    else hipLaunchKernelGGL((bfp_attention_extend_kernel<DC_, false, false>), grid, dim3(256), 0, st, aq, ap, g);
     switch (c.D / 32) {
         case 1: MI355Q_EXTEND_GO(1); break;
         case 2: MI355Q_EXTEND_GO(2); break;

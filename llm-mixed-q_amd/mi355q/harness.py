@@ -479,7 +479,9 @@ class DecodeState:
     own length and its own number of queries.
     Grouped-query attention (k, v with fewer heads than q): the caches and the per-row tensors have batch x KV heads rows, the decode
     and extend functions get group = heads // KV heads; the prefill routes and mode "fp32" repeat k / v to the query heads at use
-    (mode "fp32" concatenates them un-repeated)."""
+    (mode "fp32" concatenates them un-repeated).
+    Paged caches: PagedDecodeState below (this constructor's parameters stay as they are)."""
+    paged = False
 
     def __init__(self, model, batch: int, capacity: int, mode: str = "block_fp", extend: bool = False):
         from .quantize.quantized_functions import decode_cache_params
@@ -490,7 +492,7 @@ class DecodeState:
             raise NotImplementedError("incremental decoding of head-sharded models")
         self.mode, self.batch, self.length = mode, int(batch), 0
         self.extend = bool(extend) and mode == "block_fp"
-        self.lengths, self.ragged, self._call = [0] * self.batch, False, None
+        self.lengths, self.ragged, self._call = [0] * self.batch, self.paged, None
         self.capacity = (int(capacity) + 15) // 16 * 16
         if self.capacity > model.cfg.max_positions + 15:
             raise ValueError(f"DecodeState: capacity {capacity} exceeds the model's {model.cfg.max_positions} positions")
@@ -503,20 +505,38 @@ class DecodeState:
                     qk, pv = decode_cache_params(c0, c1, a.hd)
                 except ValueError as e:
                     raise ValueError(f"DecodeState(mode='block_fp'), layer {i}: {e}") from None
-                self.kv[i] = ops.KVCache(self.batch * getattr(a, "nkv", a.nh), self.capacity, a.hd, qk, pv, dev)
+                self.kv[i] = self._new_cache(self.batch * getattr(a, "nkv", a.nh), a.hd, qk, pv, dev)
             if len({getattr(a, "nkv", a.nh) for a in attns}) == 1:    # (else: no ragged use; the per-row tensors are one set for all layers)
                 self.heads = getattr(attns[0], "nkv", attns[0].nh)    # cache rows a sequence: the KV heads
                 self.rows_before, self.rows_after, self._rows_counts = (torch.zeros(self.batch * self.heads, dtype=torch.int32, device=dev)
                                                                         for _ in range(3))
 
+    def _new_cache(self, rows, hd, qk, pv, dev):
+        return ops.KVCache(rows, self.capacity, hd, qk, pv, dev)
+
     def reset(self) -> None:
         self.length = 0
-        self.lengths, self.ragged, self._call = [0] * self.batch, False, None
+        self.lengths, self.ragged, self._call = [0] * self.batch, self.paged, None
         for i, c in enumerate(self.kv):
             if self.mode == "block_fp":
                 c.reset()
             else:
                 self.kv[i] = None
+
+    def release(self, b: int) -> None:
+        """sequence b is finished: its length becomes 0, so that a new sequence can start in slot b while the others continue (with
+        extend=True: the mixed route); paged caches give its pages back to every layer's pool.  Nothing is cleared."""
+        if self.mode != "block_fp":
+            raise NotImplementedError("DecodeState.release with mode='fp32': its rows have one common length")
+        if not 0 <= int(b) < self.batch:
+            raise ValueError(f"DecodeState.release: sequence {b} outside 0 .. {self.batch - 1}")
+        b = int(b)
+        if self.paged:
+            for c in self.kv:
+                heads = c.B // self.batch
+                c.release(range(b * heads, (b + 1) * heads))
+        self.lengths[b] = 0
+        self.length, self.ragged = max(self.lengths), True      # (from here on the rows differ in length: the ragged routes)
 
     def position_end(self, n: int) -> int:
         """rows of the rotary tables a call with n new tokens reads"""
@@ -555,6 +575,12 @@ class DecodeState:
             raise NotImplementedError(f"unequal counts {counts} behind non-empty rows: the decode kernel takes the same number of "
                                       "queries for every row that takes any")
         rows = lambda xs: torch.tensor(xs, dtype=torch.int32).repeat_interleave(self.heads)
+        if self.paged:      # pages for every layer, checked for all of them before any table changes (and before any cache is written)
+            need = rows(after).tolist()
+            for c in self.kv:
+                c.ensure(need, dry_run=True)
+            for c in self.kv:
+                c.ensure(need)
         self.rows_before.copy_(rows(before))
         self.rows_after.copy_(rows([a if c > 0 else 0 for a, c in zip(after, counts)]))      # (a row without a token: no decode work)
         self._rows_counts.copy_(rows(counts))
@@ -631,6 +657,36 @@ class DecodeState:
         return get_quantized_func(style, c1)(p, v, config=c1).view(B, nh, n, hd)
 
 
+class PagedDecodeState(DecodeState):
+    """DecodeState(model, batch, capacity, mode, extend) on paged caches: with `page_size` (a power of two >= 32; mode "block_fp" only)
+    every layer gets an ops.PagedKVCache of `num_pages` pages (default: enough for every row at `capacity`) with max_pages =
+    ceil(capacity / page_size) -- `num_pages` may be far below batch x capacity, a sequence holds pages for the keys it has.  Every
+    call runs through the ragged routes (a call without counts is the call with counts = [n] * batch); pages are handed out for ALL
+    layers before any cache is written (a call the pool cannot serve raises RuntimeError and leaves every layer as it was); and
+    `release(b)` gives sequence b's pages back, so that a new sequence can start in slot b on them.  The numbers are the contiguous
+    state's, bit for bit.  page_size=None builds exactly a DecodeState."""
+
+    def __init__(self, model, batch: int, capacity: int, mode: str = "block_fp", extend: bool = False, page_size: int = None,
+                 num_pages: int = None):
+        self.paged = page_size is not None
+        if self.paged and mode != "block_fp":
+            raise ValueError("PagedDecodeState: page_size belongs to mode 'block_fp' (the fp32 route is not paged)")
+        if num_pages is not None and not self.paged:
+            raise ValueError("PagedDecodeState: num_pages without page_size")
+        if self.paged and len({getattr(layer.self_attn, "nkv", layer.self_attn.nh) for layer in model.layers}) != 1:
+            # (a paged state runs every call through the ragged routes, whose per-row tensors are one set for all layers)
+            raise NotImplementedError("PagedDecodeState: paged caches for a model whose layers differ in their number of KV heads")
+        self.page_size, self.num_pages = page_size, num_pages
+        super().__init__(model, batch, capacity, mode, extend)
+
+    def _new_cache(self, rows, hd, qk, pv, dev):
+        if not self.paged:
+            return super()._new_cache(rows, hd, qk, pv, dev)
+        max_pages = -(-self.capacity // int(self.page_size))
+        return ops.PagedKVCache(rows, hd, qk, pv, dev, page_size=self.page_size, max_pages=max_pages,
+                                num_pages=rows * max_pages if self.num_pages is None else self.num_pages)
+
+
 def _forward_cached(model, input_ids, labels, state: DecodeState, counts=None):
     if labels is not None:
         raise ValueError("forward(cache=...): labels belong to the full forward")
@@ -677,20 +733,27 @@ def _forward_cached(model, input_ids, labels, state: DecodeState, counts=None):
     return fp32_linear(x, model.lm_head, model.mi355q_lm_head), None
 
 
+def _new_state(model, batch, capacity, mode, extend, page_size, num_pages):
+    if page_size is None and num_pages is None:
+        return DecodeState(model, batch, capacity, mode, extend=extend)
+    return PagedDecodeState(model, batch, capacity, mode, extend=extend, page_size=page_size, num_pages=num_pages)
+
+
 @torch.no_grad()
-def generate(model, prompt_ids, new_tokens: int, mode: str = "block_fp", chunk: int = None):
+def generate(model, prompt_ids, new_tokens: int, mode: str = "block_fp", chunk: int = None, page_size: int = None, num_pages: int = None):
     """greedy decoding: the prompt in one cached call, then one token a call.  Returns (ids [B, prompt + new_tokens], logits
     [B, new_tokens, vocab]: the logits each new token was picked from).
     `prompt_ids` may be a list of 1-D id tensors of DIFFERENT lengths (mode "block_fp"): one ragged prefill, then one token a row a
     call, every sequence decoded as if it were alone; returns (a list of id tensors [len_b + new_tokens], logits as above).
     `chunk`: chunked prefill -- the prompt goes in calls of at most `chunk` tokens through a state with extend=True; for a list of
-    prompts every call gives each row whatever it has left, up to `chunk`."""
+    prompts every call gives each row whatever it has left, up to `chunk`.
+    `page_size` / `num_pages`: paged caches (PagedDecodeState); the tokens and logits are those of the contiguous caches."""
     if chunk is not None and int(chunk) < 1:
         raise ValueError(f"generate: chunk = {chunk} < 1")
     if isinstance(prompt_ids, (list, tuple)):
         lens = [int(p.numel()) for p in prompt_ids]
         B, dev = len(lens), prompt_ids[0].device
-        state = DecodeState(model, B, max(lens) + new_tokens, mode, extend=chunk is not None)
+        state = _new_state(model, B, max(lens) + new_tokens, mode, chunk is not None, page_size, num_pages)
         if chunk is None:
             ids = torch.zeros(B, max(lens), dtype=prompt_ids[0].dtype, device=dev)
             for b, p in enumerate(prompt_ids):
@@ -719,7 +782,7 @@ def generate(model, prompt_ids, new_tokens: int, mode: str = "block_fp", chunk: 
                 logits = model(tok, cache=state, counts=[1] * B)[0][:, -1]
         return rows, torch.stack(steps, dim=1)
     B, T = prompt_ids.shape
-    state = DecodeState(model, B, T + new_tokens, mode, extend=chunk is not None)
+    state = _new_state(model, B, T + new_tokens, mode, chunk is not None, page_size, num_pages)
     ids, steps = prompt_ids, []
     step = int(chunk) if chunk is not None else max(T, 1)
     for t0 in range(0, max(T, 1), step):

@@ -1602,10 +1602,180 @@ class KVCache:
         return k, v
 
 
+class PagedKVCache:
+    """The block_fp KV cache in PAGES of `page_size` keys (a power of two >= 32) drawn from one pool: a row holds memory for the keys
+    it has, a finished row's pages serve the next sequence, and rows can share the pages of a common prefix.  Storage and kernels:
+    include/mi355q.h (paged cache), csrc/mi355q_decode.h; every value is the one `KVCache` holds, so append / dequantised /
+    bfp_attention_decode / bfp_attention_extend give the contiguous cache's bits.
+      kq, vq        the pools, `num_pages` pages (zeroed once; a recycled page is not cleared: finite values are all a V slot needs)
+      stage         [B][16][D] fp32, per ROW: the open 16-key tile belongs to a row, not to a page
+      block_table   int32 [B, max_pages] on the device: the page of row b's logical page i; `table` is its host mirror
+      free          the host free list (page ids; taken from its end), `held[b]` the pages of row b in logical order
+      capacity      max_pages * page_size: a row's logical capacity -- what `max_length` is checked against
+    Always addressed in the ragged form: `lengths` (int32 [B] on the device) and the host bound `max_length` are mandatory.  The
+    allocator is the host's: `ensure` before an append that needs new pages (the kernels never allocate, and look up only pages that
+    hold keys of the row).  Table entries behind a row's pages are never read; they hold `pad_page` (default 0).  With pad_page= given
+    that page is kept out of the free list for good -- a null page no row ever writes.
+    The interface is ensure / release / share_prefix / append / dequantised.  `assign`, `pad_page=`, `ensure(dry_run=)` and `pages_for`
+    are helpers: the tests and the timing tool place pages by hand with `assign` (out-of-order tables, a poison page), the harness asks
+    every layer with `dry_run` before it changes one.  `assign` filters the free list per call and is not meant for a hot loop."""
+
+    def __init__(self, B: int, D: int, qk_params, pv_params, device, *, page_size: int, num_pages: int, max_pages: int, pad_page: int = None):
+        import ctypes
+        B, D, P, num_pages, max_pages = int(B), int(D), int(page_size), int(num_pages), int(max_pages)
+        if not 1 <= B <= 65535:
+            raise ValueError(f"PagedKVCache: B = {B} outside 1 .. 65535")
+        if D < 32 or D % 32 != 0 or D > ATTENTION_MAX_HEAD_DIM:
+            raise ValueError(f"PagedKVCache: head_dim {D} is not a multiple of 32 up to {ATTENTION_MAX_HEAD_DIM}")
+        if P < 32 or P & (P - 1):
+            raise ValueError(f"PagedKVCache: page_size {P} is not a power of two >= 32 (a K tile, a V pair and an extend step stay in one page)")
+        if num_pages < 1 or max_pages < 1 or max_pages * P > 1 << 30:
+            raise ValueError(f"PagedKVCache: num_pages = {num_pages}, max_pages = {max_pages}: at least one each, max_pages * page_size <= 2^30")
+        if pad_page is not None and not 0 <= int(pad_page) < num_pages:
+            raise ValueError(f"PagedKVCache: pad_page {pad_page} outside 0 .. {num_pages - 1}")
+        self.qk_params = _decode_params(qk_params, "PagedKVCache qk_params")
+        self.pv_params = _decode_params(pv_params, "PagedKVCache pv_params")
+        self.B, self.D, self.device = B, D, torch.device(device)
+        self.page_size, self.num_pages, self.max_pages, self.capacity = P, num_pages, max_pages, max_pages * P
+        self.pad_page = 0 if pad_page is None else int(pad_page)
+        nb = [ctypes.c_int64(0) for _ in range(3)]
+        _lib.check(_lib.load_library().mi355q_bfp_kv_paged_bytes(num_pages, P, B, D, *[ctypes.addressof(n) for n in nb]), "mi355q_bfp_kv_paged_bytes")
+        self.kq, self.vq, self.stage = (torch.zeros(n.value, dtype=torch.uint8, device=self.device) for n in nb)
+        self.table = torch.full((B, max_pages), self.pad_page, dtype=torch.int32)
+        self.block_table = self.table.to(self.device)
+        self.free = [p for p in range(num_pages - 1, -1, -1) if pad_page is None or p != self.pad_page]
+        self.refs = [0] * num_pages                         # rows that hold a page (share_prefix: more than one)
+        self.held = [[] for _ in range(B)]
+        self._pa = (ctypes.c_int32 * 6)(*[_default_bias(p) if i % 3 == 2 else int(p) for i, p in enumerate(self.qk_params)])
+        self._pb = (ctypes.c_int32 * 6)(*[_default_bias(p) if i % 3 == 2 else int(p) for i, p in enumerate(self.pv_params)])
+
+    def pages_for(self, length: int) -> int:
+        return -(-int(length) // self.page_size)
+
+    def _upload(self) -> None:
+        self.block_table.copy_(self.table)
+
+    def ensure(self, lengths_after, dry_run: bool = False) -> None:
+        """every row b gets pages for lengths_after[b] keys (host ints, one per cache row; a row never loses pages here).  RuntimeError
+        naming the rows, the pages needed and the pages free when the pool does not have them -- raised BEFORE the table or the free
+        list changes.  The changed table goes to the device with one copy_.  dry_run: the checks only."""
+        want = [self.pages_for(n) for n in lengths_after]
+        if len(want) != self.B:
+            raise ValueError(f"PagedKVCache.ensure: {len(want)} lengths for {self.B} cache rows")
+        over = [b for b, w in enumerate(want) if w > self.max_pages]
+        if over:
+            raise ValueError(f"PagedKVCache.ensure: rows {over} ask for more than max_pages = {self.max_pages} pages "
+                             f"(lengths {[int(lengths_after[b]) for b in over]}, capacity {self.capacity})")
+        extra = {b: w - len(self.held[b]) for b, w in enumerate(want) if w > len(self.held[b])}
+        if sum(extra.values()) > len(self.free):
+            raise RuntimeError(f"PagedKVCache.ensure: rows {sorted(extra)} need {sum(extra.values())} more pages, {len(self.free)} of "
+                               f"{self.num_pages} are free")
+        if dry_run or not extra:
+            return
+        for b, e in extra.items():
+            self.assign(b, [self.free[-1 - i] for i in range(e)], upload=False)
+        self._upload()
+
+    def assign(self, row: int, pages, upload: bool = True) -> None:
+        """helper (tests, tools/time_decode_paged.py): the FREE pages `pages` become row's next logical pages, in this order"""
+        pages = [int(p) for p in pages]
+        taken = set(pages)
+        if len(taken) != len(pages) or not taken <= set(self.free):
+            raise ValueError(f"PagedKVCache.assign: pages {pages} are not distinct free pages")
+        if len(self.held[row]) + len(pages) > self.max_pages:
+            raise ValueError(f"PagedKVCache.assign: row {row} would hold more than max_pages = {self.max_pages} pages")
+        self.free = [p for p in self.free if p not in taken]
+        for p in pages:
+            self.refs[p] = 1
+            self.table[row, len(self.held[row])] = p
+            self.held[row].append(p)
+        if upload:
+            self._upload()
+
+    def release(self, rows) -> None:
+        """rows' pages back to the free list (a page shared with another row stays with that row); the rows then hold no keys"""
+        for b in ([rows] if isinstance(rows, int) else rows):
+            for p in self.held[b]:
+                self.refs[p] -= 1
+                if self.refs[p] == 0:
+                    self.free.append(p)
+            self.held[b] = []
+            self.table[b] = self.pad_page
+        self._upload()
+
+    def share_prefix(self, src: int, dst: int, pages: int) -> None:
+        """row dst, which holds no page, points at row src's first `pages` pages (reference-counted): dst then holds the first
+        pages * page_size keys of src -- set its length to that.  Whole, FULL pages only: the shared pages must lie wholly below both
+        rows' lengths from here on, since an append into a shared page would change the other row (there is no copy-on-write); K's
+        16-key blocks and V's blocks inside full pages are final, and the open tile of dst starts empty."""
+        pages = int(pages)
+        if src == dst or self.held[dst]:
+            raise ValueError(f"PagedKVCache.share_prefix: row {dst} holds {len(self.held[dst])} pages (only a row that holds none can share)")
+        if not 0 <= pages <= len(self.held[src]):
+            raise ValueError(f"PagedKVCache.share_prefix: {pages} pages, row {src} holds {len(self.held[src])}")
+        for i, p in enumerate(self.held[src][:pages]):
+            self.refs[p] += 1
+            self.table[dst, i] = p
+            self.held[dst].append(p)
+        self._upload()
+
+    def reset(self) -> None:
+        self.release(range(self.B))
+
+    _rows = KVCache._rows
+
+    def append(self, k: torch.Tensor, v: torch.Tensor, *, lengths: torch.Tensor, counts: torch.Tensor = None, max_length: int = None) -> None:
+        """KVCache.append in its ragged form (lengths: BEFORE the call; counts; max_length + n <= capacity).  The pages of the new keys
+        must be the rows' already (`ensure`): the kernel writes where the table points."""
+        import ctypes
+        k, v = self._rows(k, "k"), self._rows(v, "v")
+        n = k.shape[-2]
+        if v.shape[-2] != n or n < 1:
+            raise ValueError(f"PagedKVCache.append: {n} rows of k, {v.shape[-2]} of v (at least one, and as many of each)")
+        why = "lengths= is mandatory: a paged cache is always addressed in the ragged form" if lengths is None else \
+            _ragged_check(self, lengths, counts, max_length, n, "append")
+        if why is not None:
+            raise ValueError(f"PagedKVCache.append: {why}")
+        for t in (k, v):
+            if not t.is_cuda or t.dtype != torch.float32 or t.device != self.device:
+                raise ValueError(f"PagedKVCache.append: fp32 tensors on {self.device} only (got {t.dtype} on {t.device}); there is no CPU fallback")
+        k3, ksb, kst = _as_heads_view(k)
+        v3, vsb, vst = _as_heads_view(v)
+        strides = (ctypes.c_int64 * 4)(ksb, kst, vsb, vst)
+        with _on_device(self.device):
+            rc = _lib.load_library().mi355q_bfp_kv_append_paged(_ptr(self.kq), _ptr(self.vq), _ptr(self.stage), _ptr(k3), _ptr(v3), _ptr(lengths),
+                                                                _ptr(counts), _ptr(self.block_table), self.B, self.max_pages, self.num_pages,
+                                                                self.page_size, self.D, n, int(max_length), ctypes.addressof(self._pa),
+                                                                ctypes.addressof(self._pb), ctypes.addressof(strides), _stream_ptr(self.device))
+        _lib.check(rc, "mi355q_bfp_kv_append_paged")
+
+    def dequantised(self, lengths: torch.Tensor, max_length: int = None):
+        """the rows' quantised K and V as fp32 [B, max_length, D] through the page table, zeros behind each row's lengths[b]"""
+        why = "lengths= is mandatory: a paged cache is always addressed in the ragged form" if lengths is None else \
+            _ragged_check(self, lengths, None, max_length, 0, "dequantised")
+        if why is not None:
+            raise ValueError(f"PagedKVCache.dequantised: {why}")
+        if not self.kq.is_cuda:
+            raise ValueError("PagedKVCache.dequantised: the cache is not on a GPU; there is no CPU fallback")
+        k = torch.empty(self.B, int(max_length), self.D, dtype=torch.float32, device=self.device)
+        v = torch.empty_like(k)
+        with _on_device(self.device):
+            rc = _lib.load_library().mi355q_bfp_kv_decode_fp32_paged(_ptr(self.kq), _ptr(self.vq), _ptr(lengths), _ptr(self.block_table), _ptr(k),
+                                                                     _ptr(v), self.B, self.max_pages, self.num_pages, self.page_size, self.D,
+                                                                     int(max_length), _stream_ptr(self.device))
+        _lib.check(rc, "mi355q_bfp_kv_decode_fp32_paged")
+        return k, v
+
+
+_PAGED_NEEDS_LENGTHS = "a paged cache is always addressed in the ragged form: lengths= and max_length= (there is no uniform paged launch)"
+
+
 def _decode_check(q, cache, splits=None, lengths=None, max_length=None, group=1):
     """the reasons bfp_attention_decode declines (q, cache), None when it takes them; nothing here touches the device"""
-    if not isinstance(cache, KVCache):
+    if not isinstance(cache, (KVCache, PagedKVCache)):
         return "cache is not a KVCache"
+    if isinstance(cache, PagedKVCache) and lengths is None:
+        return _PAGED_NEEDS_LENGTHS
     if not isinstance(q, torch.Tensor) or q.ndim < 3:
         return "q must be a tensor [..., M, D]"
     M, D = q.shape[-2:]
@@ -1650,14 +1820,16 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     cache.B * G rows and query row r attends to cache row r // G (repeat_kv: query head j on KV head j // G).  `lengths` stays one
     entry per CACHE row.  decode_group_width(G, M) heads share one launch row's K / V loads; the default number of splits is that of
     cache.B * G // decode_group_width(G, M) rows.  Each query row gets the bits group=1 gives it on a cache of cache.B * G rows
-    holding the repeated K / V, with the same `splits`."""
+    holding the repeated K / V, with the same `splits`.
+    `cache` may be a PagedKVCache (always with `lengths`): the bits of the same call on a KVCache holding the same keys."""
     import ctypes
     why = _decode_check(q, cache, splits, lengths, max_length, group)
     if why is not None:
         raise ValueError(f"mi355q.bfp_attention_decode: {why}")
     M, D = q.shape[-2:]
     q3, qsb, qsm = _as_heads_view(q)
-    B, L, C = cache.B, cache.length, cache.capacity
+    paged = isinstance(cache, PagedKVCache)
+    B, L, C = cache.B, 0 if paged else cache.length, cache.capacity
     if token_major and q.ndim == 4 and q.shape[0] == 1:
         H = q.shape[1]
         out = torch.empty(1, M, H, D, dtype=torch.float32, device=q.device).permute(0, 2, 1, 3)
@@ -1676,6 +1848,15 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
         ws = _DECODE_WS.put(key, torch.empty(R * (C // 16) * 1024 + R * _DECODE_MAX_SPLITS * (128 + (D // 16) * 1024), dtype=torch.uint8,
                                              device=q.device))
     strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
+    if paged:
+        with _on_device(q.device):
+            rc = lib.mi355q_bfp_attention_decode_paged(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), group, _ptr(lengths), _ptr(cache.block_table),
+                                                       int(bool(causal)), float(q_scale) if q_scale else 0.0,
+                                                       float(scale_div) if scale_div else 0.0, _ptr(out), _ptr(ws), B, M, int(max_length),
+                                                       cache.max_pages, cache.num_pages, cache.page_size, D, ctypes.addressof(cache._pa),
+                                                       ctypes.addressof(cache._pb), ctypes.addressof(strides), int(splits or 0), sp)
+        _lib.check(rc, "mi355q_bfp_attention_decode_paged")
+        return out
     if group != 1:
         with _on_device(q.device):
             rc = lib.mi355q_bfp_attention_decode_grouped(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), group, _ptr(lengths), int(bool(causal)),
@@ -1704,8 +1885,10 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
 
 def _extend_check(q, cache, lengths=None, counts=None, max_length=None, group=1):
     """the reasons bfp_attention_extend declines (q, cache), None when it takes them; nothing here touches the device"""
-    if not isinstance(cache, KVCache):
+    if not isinstance(cache, (KVCache, PagedKVCache)):
         return "cache is not a KVCache"
+    if isinstance(cache, PagedKVCache) and lengths is None:
+        return _PAGED_NEEDS_LENGTHS
     if not isinstance(q, torch.Tensor) or q.ndim < 3:
         return "q must be a tensor [..., M, D]"
     M, D = q.shape[-2:]
@@ -1745,7 +1928,8 @@ def bfp_attention_extend(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     against ITS lengths[b] keys, as if the row were alone; output rows behind counts[b] are zeros, and a row with counts[b] == 0
     or counts[b] > lengths[b] (an empty slot) returns zeros.  cache.length is not used.
     Grouped queries (`group` = G > 1) as bfp_attention_decode: q folds to cache.B * G rows, query row r on cache row r // G, `lengths`
-    and `counts` one entry per CACHE row; each query row gets the bits group=1 gives it on a cache holding the repeated K / V."""
+    and `counts` one entry per CACHE row; each query row gets the bits group=1 gives it on a cache holding the repeated K / V.
+    `cache` may be a PagedKVCache (always with `lengths`): the bits of the same call on a KVCache holding the same keys."""
     import ctypes
     why = _extend_check(q, cache, lengths, counts, max_length, group)
     if why is not None:
@@ -1760,6 +1944,17 @@ def bfp_attention_extend(q: torch.Tensor, cache: KVCache, *, causal: bool = True
         out = torch.empty(*q.shape, dtype=torch.float32, device=q.device)
         osb, osm = M * D, D
     strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
+    if isinstance(cache, PagedKVCache):
+        with _on_device(q.device):
+            rc = _lib.load_library().mi355q_bfp_attention_extend_paged(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), group, _ptr(lengths), _ptr(counts),
+                                                                       _ptr(cache.block_table), int(bool(causal)),
+                                                                       float(q_scale) if q_scale else 0.0, float(scale_div) if scale_div else 0.0,
+                                                                       _ptr(out), cache.B, M, int(max_length), cache.max_pages, cache.num_pages,
+                                                                       cache.page_size, D, ctypes.addressof(cache._pa),
+                                                                       ctypes.addressof(cache._pb), ctypes.addressof(strides),
+                                                                       _stream_ptr(q.device))
+        _lib.check(rc, "mi355q_bfp_attention_extend_paged")
+        return out
     if group != 1:
         with _on_device(q.device):
             rc = _lib.load_library().mi355q_bfp_attention_extend_grouped(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), group, _ptr(lengths),
