@@ -724,6 +724,31 @@ int mi355q_bfp_attention_extend_paged(const float* q, const void* kq_pool, const
                                       int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
                                       void* stream);
 
+/* Sliding window: decode and extend with every query bound to its last `window` = W >= 1 keys, its own included -- a query at absolute
+ * position p (decode: L_b - M + i; extend: L_b - m_b + i) sees keys max(0, p - W + 1) .. p.  That is the `past_key_value` call with an
+ * additive mask that is finfo.min below the window as well as above the horizon: the cache is unchanged, K^T's and P's 16-key blocks
+ * stay aligned to absolute key index, probabilities of keys outside the window are exact zeros inside their blocks.  Key tiles wholly
+ * below the window of every query are not read, so a step costs O(W) whatever L_b is (csrc/mi355q_decode.h).
+ * Arguments are those of the *_paged calls plus `window`; always the ragged form (`lengths` mandatory), always causal (causal == 0 or
+ * window < 1: MI355Q_E_BADARG, before any launch).  block_table == NULL: the CONTIGUOUS cache, kq / vq as in the *_ragged calls with
+ * capacity C = max_pages * P keys a row (any P with C % 16 == 0; num_pages is not used).  The decode partition, the default number of
+ * splits and the workspace are those of span = min(max_length, W + M - 1 + 31) keys: mi355q_bfp_attention_decode_window_span, and
+ * mi355q_bfp_attention_decode_window_workspace_bytes in place of mi355q_bfp_attention_decode_workspace_bytes (B: launch rows).
+ * window >= max_length gives the bits of the unwindowed call.  A paged call looks up only pages that hold a key some query of the row
+ * sees: table entries wholly below the window may name any page. */
+int64_t mi355q_bfp_attention_decode_window_span(int64_t M, int64_t max_length, int64_t window);
+size_t mi355q_bfp_attention_decode_window_workspace_bytes(int64_t B, int64_t M, int64_t max_length, int64_t window, int64_t D, int32_t splits);
+int mi355q_bfp_attention_decode_window(const float* q, const void* kq, const void* vq, int32_t G, const int32_t* lengths,
+                                       const int32_t* block_table, int32_t causal, int64_t window, float q_scale, float scale_div,
+                                       float* out, void* workspace, int64_t B, int64_t M, int64_t max_length, int64_t max_pages,
+                                       int64_t num_pages, int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
+                                       const int64_t* strides, int32_t splits, void* stream);
+int mi355q_bfp_attention_extend_window(const float* q, const void* kq, const void* vq, int32_t G, const int32_t* lengths,
+                                       const int32_t* counts, const int32_t* block_table, int32_t causal, int64_t window, float q_scale,
+                                       float scale_div, float* out, int64_t B, int64_t M, int64_t max_length, int64_t max_pages,
+                                       int64_t num_pages, int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
+                                       const int64_t* strides, void* stream);
+
 /* ---- the un-blocked quantisers -------------------------------------------------------------------------------------
  * replaces: quantizers/minifloat.py:134-196 (minifloat_ieee_quantizer: implicit leading one, subnormals at the lowest
  *           exponent), :21-86 (minifloat_denorm_quantizer: no implicit one, exponent ceil(log2(|x| + 1e-9)) per element)

@@ -1375,6 +1375,100 @@ int mi355q_bfp_attention_extend_paged(const float* q, const void* kq_pool, const
                                        lengths, counts, static_cast<hipStream_t>(stream), G, &pg);
 }
 
+// ---- sliding window: a query sees its last `window` keys (mi355q_decode.h); always the ragged form, paged or contiguous ------------
+namespace {
+// the cache behind a *_window call: block_table != NULL the paged pools (paged_shape); NULL the contiguous cache of capacity
+// C = max_pages * P keys a row (decode_cache_shape; num_pages is not used).  -> C through `cap`, the kernels' page view through `pg`
+int window_cache_shape(int64_t B, int64_t max_pages, int64_t num_pages, int64_t P, int64_t D, const int32_t* block_table, KvPages* pg,
+                       int64_t* cap) {
+    if (block_table) {
+        const int rc = paged_shape(B, max_pages, num_pages, P, D, block_table, pg);
+        if (rc) return rc;
+    } else {
+        if (max_pages < 1 || P < 1 || max_pages > (1LL << 30) / P) return MI355Q_E_BADARG;
+        const int rc = decode_cache_shape(B, max_pages * P, D);
+        if (rc) return rc;
+    }
+    *cap = max_pages * P;
+    return 0;
+}
+}  // namespace
+
+int64_t mi355q_bfp_attention_decode_window_span(int64_t M, int64_t max_length, int64_t window) {
+    if (M < 1 || max_length < 1 || window < 1) return 0;
+    return decode_window_span(M, max_length, window);
+}
+
+size_t mi355q_bfp_attention_decode_window_workspace_bytes(int64_t B, int64_t M, int64_t max_length, int64_t window, int64_t D, int32_t splits) {
+    if (B <= 0 || M < 1 || M > 16 || max_length < M || window < 1 || D <= 0 || D % 32 != 0 || D > 128) return 0;
+    return decode_workspace_bytes(B, decode_window_span(M, max_length, window), D, splits);
+}
+
+int mi355q_bfp_attention_decode_window(const float* q, const void* kq, const void* vq, int32_t G, const int32_t* lengths,
+                                       const int32_t* block_table, int32_t causal, int64_t window, float q_scale, float scale_div,
+                                       float* out, void* workspace, int64_t B, int64_t M, int64_t max_length, int64_t max_pages,
+                                       int64_t num_pages, int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
+                                       const int64_t* strides, int32_t splits, void* stream) {
+    if (M < 0 || max_length < 0 || splits < 0 || G < 0 || window < 1 || !causal) return MI355Q_E_BADARG;
+    KvPages pg{};
+    int64_t C = 0;
+    int rc = window_cache_shape(B, max_pages, num_pages, P, D, block_table, &pg, &C);
+    if (rc) return rc;
+    if (max_length > C) return MI355Q_E_BADARG;
+    if (M < 1 || M > 16 || max_length < M) return MI355Q_E_UNSUPPORTED;
+    if (G <= 1) G = 0;                                        // (0 or 1: ungrouped)
+    if (G && B * (G / decode_group_width(G, M)) > 65535) return MI355Q_E_UNSUPPORTED;
+    if (!q || !kq || !vq || !lengths || !out || !workspace || !qk_params || !pv_params) return MI355Q_E_BADARG;
+    QuantArgs aq{}, ap{};
+    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) |
+         reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) % 16 ||
+        (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(block_table)) % 4)
+        return MI355Q_E_ALIGN;
+    long long st4[4];
+    if (strides)
+        for (int i = 0; i < 4; ++i) {
+            if (strides[i] % 4) return MI355Q_E_ALIGN;
+            st4[i] = strides[i];
+        }
+    if (window > max_length) window = max_length;             // (a window over every key the call can hold: the same mask)
+    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
+    return launch_bfp_attention_decode(aq, ap, c, q, out, workspace, M, max_length, 1, q_scale, scale_div, strides ? st4 : nullptr, splits,
+                                       static_cast<hipStream_t>(stream), lengths, G, block_table ? &pg : nullptr, window);
+}
+
+int mi355q_bfp_attention_extend_window(const float* q, const void* kq, const void* vq, int32_t G, const int32_t* lengths,
+                                       const int32_t* counts, const int32_t* block_table, int32_t causal, int64_t window, float q_scale,
+                                       float scale_div, float* out, int64_t B, int64_t M, int64_t max_length, int64_t max_pages,
+                                       int64_t num_pages, int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
+                                       const int64_t* strides, void* stream) {
+    if (M < 0 || max_length < 0 || G < 0 || window < 1 || !causal) return MI355Q_E_BADARG;
+    KvPages pg{};
+    int64_t C = 0;
+    int rc = window_cache_shape(B, max_pages, num_pages, P, D, block_table, &pg, &C);
+    if (rc) return rc;
+    if (max_length > C) return MI355Q_E_BADARG;
+    if (M < 1 || max_length < M) return MI355Q_E_UNSUPPORTED;
+    if (G <= 1) G = 0;
+    if (!q || !kq || !vq || !lengths || !out || !qk_params || !pv_params) return MI355Q_E_BADARG;
+    QuantArgs aq{}, ap{};
+    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) |
+         reinterpret_cast<uintptr_t>(out)) % 16 ||
+        (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(block_table)) % 4)
+        return MI355Q_E_ALIGN;
+    long long st4[4];
+    if (strides)
+        for (int i = 0; i < 4; ++i) {
+            if (strides[i] % 4) return MI355Q_E_ALIGN;
+            st4[i] = strides[i];
+        }
+    if (window > max_length) window = max_length;
+    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
+    return launch_bfp_attention_extend(aq, ap, c, q, out, M, max_length, 1, q_scale, scale_div, strides ? st4 : nullptr, lengths, counts,
+                                       static_cast<hipStream_t>(stream), G, block_table ? &pg : nullptr, window);
+}
+
 // block_minifloat (fmt 1) / block_log (fmt 2) products: the same two kernels with the other quantisers' block parameters
 static int values_matmul_impl(int fmt, bool softmax, const float* mask, long long causal_off, const float* x, const float* y,
                               float* out, void* workspace, int64_t B, int64_t M, int64_t K, int64_t N, int32_t x_width,

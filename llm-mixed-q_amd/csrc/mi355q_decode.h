@@ -53,6 +53,24 @@
 // never read.  stage stays [B][16][D] (the open tile belongs to a row), the scores workspace stays indexed by LOGICAL tile, and
 // every value is the one the contiguous cache holds: the paged kernels give its bits.  Pages start out zeroed; a recycled page holds
 // older quantised values, finite, which is all a V slot behind a row's length needs (above).
+//
+// Sliding window (WN = true kernels, always with RG = true and causal; window = W >= 1): a query at absolute position p sees keys
+// max(0, p - W + 1) .. p, W keys with its own -- the reference's call with an additive mask that is finfo.min below the window as well as
+// above the horizon.  The cache does not change: K^T's 16-key blocks and the [1,16] P blocks stay aligned to ABSOLUTE key index; a P
+// block that straddles the lower edge is quantised with exact zeros, outside the block maximum, for the keys below it.  Decode query i
+// is at p = L_b - M + i, so the row's first visible key is lo_b = max(0, L_b - M - W + 1), and the partition is RELATIVE to its pair:
+//   p0_b = lo_b / 32 (scalar, from lengths[b])      split s covers pairs p0_b + s pps .., wave w takes p0_b + p_lo + w, + 4, ...
+//   span = min(max_length, W + M - 1 + 31)          the keys 32 p0_b .. L_b - 1 a row can touch: the host sizes the partition (pps), the
+//                                                   default splits and the workspace stride NT from span, not from max_length
+//   scores workspace                                tile t of row b at index t - 2 p0_b
+// Tiles below tile lo_b / 16 are not read (no K fragment, paged no table look-up; the V pair of a visible pair is read whole): their
+// probabilities are exact zeros.  That is every tile below 2 p0_b, and tile 2 p0_b itself when lo_b lies in the pair's second tile.
+// Splits behind the row's last pair keep the (-inf, 0) / zero-partial paths.  With M > 1 the columns' lower bounds differ: a column may
+// see no key of the first split(s) -- e.g. lo_b % 32 >= 17 with one pair a split -- and gets (-inf, 0) there, which the combination skips;
+// every column sees its own key, so its row maximum is finite.  W < M: the later columns' windows begin behind lo_b, nothing else.
+// W = 1: each column sees its own key alone.  With W + M - 1 >= max_length, p0_b = 0 and span = max_length: the unwindowed partition and,
+// the lower bound being 0, the unwindowed bits.  A paged windowed kernel looks up only pages that hold a key some query of the row sees
+// (P >= 32: the page of pair p0_b is the page of key lo_b), so table entries wholly below the window may be stale (PagedKVCache.trim).
 #ifndef MI355Q_DECODE_H
 #define MI355Q_DECODE_H
 #include <hip/hip_runtime.h>
@@ -95,6 +113,8 @@ int launch_kv_decode_fp32(const KvCache& c, float* k_out, float* v_out, long lon
 // that no split is empty).  1 <= S <= ceil(L / 32).
 int decode_splits(long long B, long long L, long long D, int override);
 size_t decode_workspace_bytes(long long B, long long L, long long D, int splits);
+// the keys one row of a windowed decode can touch, min(L, window + M - 1 + 31) (window <= 0: L): what sizes partition and workspace
+long long decode_window_span(long long M, long long L, long long window);
 
 struct DecodeArgs {
     const float* q;           // [B, M, D] by strides
@@ -112,6 +132,7 @@ struct DecodeArgs {
     const int32_t* lengths;   // ragged: [B] on the device, L / NT / NP above are those of max_length (partition, strides); else NULL
     int gw, rpc;              // grouped queries (GQ): heads a launch row serves, launch rows a cache row; gw * rpc = G.  Else 1, 1
     KvPages pg;               // paged cache (PG): kq / vq are the pools; else zeros (behind every field the other kernels read)
+    long long W;              // sliding window (WN): NT / NP / S / pps are those of decode_window_span; else 0 (behind every other field)
 };
 // q's and out's element strides of batch and row from the wrapper's {q batch, q row, out batch, out row}; NULL: contiguous [B, M, D]
 // (DecodeArgs, and ExtendArgs of mi355q_extend.h)
@@ -124,10 +145,11 @@ inline void fill_qo_strides(Args& g, const long long* strides, long long M, long
 int decode_group_width(long long G, long long M);
 // lengths != NULL: the ragged form, L = max_length.  G >= 1: the grouped form (q / out hold c.B * G rows, the workspace is that of
 // c.B * G / decode_group_width(G, M) launch rows); G == 0: one query row a cache row.  pages != NULL (with lengths): the paged cache
+// window >= 1 (with lengths and causal): the sliding window; the workspace is that of decode_window_span keys
 int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out,
                                 void* workspace, long long M, long long L, int causal, float q_scale, float scale_div,
                                 const long long* strides, int splits, hipStream_t st, const int32_t* lengths = nullptr, int G = 0,
-                                const KvPages* pages = nullptr);
+                                const KvPages* pages = nullptr, long long window = 0);
 
 }  // namespace mi355q
 #endif

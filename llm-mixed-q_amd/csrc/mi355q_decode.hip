@@ -25,6 +25,9 @@
 // Paged cache (PG = true, with RG = true only; layout and address rules: mi355q_decode.h): a tile's or pair's place goes through the
 // row's page table.  In the decode loops the index is wave-uniform, so the entry is one 4-byte load kept scalar like lengths[b], asked
 // for one iteration AHEAD of the fragment loads it addresses; the score workspace keeps logical indices.
+// Sliding window (WN = true, with RG = true only; semantics and the relative partition: mi355q_decode.h): a query at position p sees keys
+// max(0, p - W + 1) .. p.  A lane keeps a lower bound klo next to its horizon; the row's first visible pair p0 -- scalar, from lengths[b] --
+// is where the split partition and the score workspace begin, so work, workspace traffic and splits follow W, not the row's length.
 // MFMA roles as in mi355q_attention.hip (v_mfma_f32_16x16x32_bf16, the queries are the 16 columns): a lane's own values of the score
 // tiles 2 s, 2 s + 1 are the slots of its P fragment, and vq is stored with the same slot order.
 #include <hip/hip_runtime.h>
@@ -274,6 +277,11 @@ int decode_splits(long long B, long long L, long long D, int override) {
     return (int)((NP + pps - 1) / pps);
 }
 
+long long decode_window_span(long long M, long long L, long long window) {
+    // keys 32 p0 .. L_b - 1 with 32 p0 > L_b - M - W + 1 - 32: fewer than W + M - 1 + 32 of them, and never more than the row has
+    return window > 0 && window < L && window + M - 1 + 31 < L ? window + M - 1 + 31 : L;
+}
+
 size_t decode_workspace_bytes(long long B, long long L, long long D, int splits) {
     if (B <= 0 || L <= 0 || D <= 0) return 0;
     const long long S = decode_splits(B, L, D, splits), NT = (L + 15) / 16;
@@ -284,6 +292,11 @@ size_t decode_workspace_bytes(long long B, long long L, long long D, int splits)
 __device__ __forceinline__ long long dec_horizon(const DecodeArgs& g, long long L, long long qrow) {
     return g.causal ? L - g.M + qrow : L - 1;
 }
+
+// Sliding window: the first key this lane's query sees (kvis its horizon), and the row's first visible pair and tile -- the first key
+// ANY of the row's M queries sees is max(0, L - M - W + 1), that of query 0 (scalar: L is).  An empty row (L = 0) gives 0.
+__device__ __forceinline__ long long dec_window_lo(const DecodeArgs& g, long long kvis) { return max(kvis - g.W + 1, 0ll); }
+__device__ __forceinline__ long long dec_window_first(const DecodeArgs& g, long long L) { return max(L - g.M - g.W + 1, 0ll); }
 
 // the keys row b holds.  Ragged: its own length, one scalar load a workgroup, never above max_length (= g.L: the partition and the
 // workspace strides are made for that); a row shorter than its M queries -- an empty slot, a finished sequence -- counts as 0
@@ -335,15 +348,24 @@ __device__ __forceinline__ long long dec_cache_row(const DecodeArgs& g, long lon
     else return y;
 }
 
-template <int DC, bool RG, bool GQ, bool PG>
+template <int DC, bool RG, bool GQ, bool PG, bool WN = false>
 __global__ __launch_bounds__(256) void decode_scores_kernel(const QuantArgs aq, const DecodeArgs g) {
+    static_assert(RG || !WN, "windowed launches exist in the ragged form only");
     __shared__ float sm_[4][64], sl_[4][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c16 = lane & 15, lg = lane >> 4;
     const long long b = blockIdx.y, s = blockIdx.x, cb = dec_cache_row<GQ>(g, b);   // b: launch row (workspace), cb: cache row
     const long long L = dec_length<RG>(g, cb), NT = RG ? (L + 15) >> 4 : g.NT;
+    // windowed: the partition starts at the row's first visible pair p0 (t0 = 2 p0 its first tile; the workspace holds tile t at t - t0),
+    // and the tiles below t_first, the tile of the first visible key -- tile t0 when the lower edge lies in the pair's second tile -- are
+    // not read: no query of the row sees a key of theirs
+    long long t0 = 0, t_first = 0;
+    if constexpr (WN) {
+        t_first = dec_window_first(g, L) >> 4;
+        t0 = t_first & ~1ll;
+    }
     if constexpr (RG) {
-        if (2 * g.pps * s >= NT) {      // a split wholly behind the row's last tile: the empty statistics, no kq read
+        if (t0 + 2 * g.pps * s >= NT) { // a split wholly behind the row's last tile: the empty statistics, no kq read
             if (tid < 16) {
                 float* st = g.stats + ((b * g.S + s) * 16 + tid) * 2;
                 st[0] = -INFINITY;
@@ -357,18 +379,35 @@ __global__ __launch_bounds__(256) void decode_scores_kernel(const QuantArgs aq, 
     bf16x8 qf[DC];                      // quantised in registers
     at_quant_q_frag(qf, g.q + row * g.qsb + qrow * g.qsm, g.q_scale, lg, aq, at_block_exponent_mem);
     const long long kvis = dec_horizon(g, L, qrow);
+    // windowed: key k is visible when klo <= k <= kvis -- one unsigned compare of k - klo against kvis - klo, in 32 bits (keys < 2^31);
+    // a column whose window begins behind this split leaves it with (-inf, 0)
+    int lane_rel = 0;
+    unsigned wd = 0;
+    if constexpr (WN) {
+        const long long klo = dec_window_lo(g, kvis);
+        lane_rel = (int)(4 * lg - klo);
+        wd = (unsigned)(kvis - klo);
+    }
+    auto visible = [&](long long t, long long key0, int e) -> bool {
+        if constexpr (WN) return (unsigned)((int)(t << 4) + lane_rel + e) <= wd;
+        else return key0 + e <= kvis;
+    };
     const float scale_inv = g.scale_div != 0.f ? 1.0f / g.scale_div : 0.f;
-    const long long t_lo = 2 * g.pps * s, t_hi = min(NT, t_lo + 2 * g.pps);
+    const long long t_lo = t0 + 2 * g.pps * s, t_hi = min(NT, t_lo + 2 * g.pps);
     const uint16_t* __restrict__ kfb = g.kq + (PG ? 0 : cb * g.NTC * DC * 512) + lane * 8;
-    float* __restrict__ sc = g.scores + b * g.NT * 256 + lane * 4;
+    float* __restrict__ sc = g.scores + b * g.NT * 256 + lane * 4 - t0 * 256;
+    long long t_begin = t_lo + wave;    // (windowed: the wave that would take a tile below t_first -- only tile t0 can be one -- moves on)
+    if constexpr (WN) {
+        if (t_begin < t_first) t_begin += 4;
+    }
     // running (max, sum of exp(x - max)) of this lane's visible scores, re-based when the maximum moves
     float m_run = -INFINITY, l_run = 0.f;
     // paged: the table entry of the NEXT tile this wave takes is asked for while this one's fragments are loaded (t < t_hi <= NT)
     int raw = 0;
     if constexpr (PG) {
-        if (t_lo + wave < t_hi) raw = pg_raw(g.pg, cb, (t_lo + wave) >> (g.pg.lg_p - 4));
+        if (t_begin < t_hi) raw = pg_raw(g.pg, cb, t_begin >> (g.pg.lg_p - 4));
     }
-    for (long long t = t_lo + wave; t < t_hi; t += 4) {
+    for (long long t = t_begin; t < t_hi; t += 4) {
         long long pt = t;                                   // the tile's place in kq; the workspace keeps t
         if constexpr (PG) {
             pt = pg_place(g.pg, __builtin_amdgcn_readfirstlane(raw), t, g.pg.lg_p - 4);
@@ -387,14 +426,14 @@ __global__ __launch_bounds__(256) void decode_scores_kernel(const QuantArgs aq, 
         float tm = -INFINITY;
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-            if (key0 + e <= kvis) tm = fmaxf(tm, acc[e]);
+            if (visible(t, key0, e)) tm = fmaxf(tm, acc[e]);
         if (tm > m_run) {
             l_run = m_run == -INFINITY ? 0.f : l_run * at_exp_neg(m_run - tm);
             m_run = tm;
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-            if (key0 + e <= kvis) l_run += at_exp_neg(acc[e] - m_run);
+            if (visible(t, key0, e)) l_run += at_exp_neg(acc[e] - m_run);
     }
     sm_[wave][lane] = m_run;
     sl_[wave][lane] = l_run;
@@ -416,15 +455,19 @@ __global__ __launch_bounds__(256) void decode_scores_kernel(const QuantArgs aq, 
     }
 }
 
-template <int DC, bool RG, bool GQ, bool PG>
+template <int DC, bool RG, bool GQ, bool PG, bool WN = false>
 __global__ __launch_bounds__(256) void decode_pv_kernel(const QuantArgs ap, const DecodeArgs g) {
+    static_assert(RG || !WN, "windowed launches exist in the ragged form only");
     constexpr int DT = DC * 2;
     __shared__ f32x4 red[4][DT][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c16 = lane & 15, lg = lane >> 4;
     const long long b = blockIdx.y, s = blockIdx.x, cb = dec_cache_row<GQ>(g, b);
     const long long L = dec_length<RG>(g, cb), NT = RG ? (L + 15) >> 4 : g.NT, NP = RG ? (L + 31) >> 5 : g.NP;
-    const long long p_lo = g.pps * s, p_hi = min(NP, p_lo + g.pps);
+    long long t_first = 0;              // windowed: the tile of the row's first visible key, p0 = t_first / 2 its pair (decode_scores_kernel)
+    if constexpr (WN) t_first = dec_window_first(g, L) >> 4;
+    const long long p0 = t_first >> 1;
+    const long long p_lo = p0 + g.pps * s, p_hi = min(NP, p_lo + g.pps);
     if constexpr (RG) {
         if (p_lo >= p_hi) {             // an empty split (every split of an empty row): a zero partial output, no vq read
             const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -441,8 +484,20 @@ __global__ __launch_bounds__(256) void decode_pv_kernel(const QuantArgs ap, cons
     long long row, qrow;
     dec_column<GQ>(g, b, c16, row, qrow);
     const long long kvis = dec_horizon(g, L, qrow);
-    // the row's statistics over all L keys: the S splits in split order (every query sees key 0: the first split's max is finite;
-    // splits behind a ragged row's last tile hold (-inf, 0) and are skipped like any split without a visible key)
+    int lane_rel = 0;                   // (windowed: the visibility test of decode_scores_kernel)
+    unsigned wd = 0;
+    if constexpr (WN) {
+        const long long klo = dec_window_lo(g, kvis);
+        lane_rel = (int)(4 * lg - klo);
+        wd = (unsigned)(kvis - klo);
+    }
+    auto visible = [&](long long t, long long key0, int e) -> bool {
+        if constexpr (WN) return (unsigned)((int)(t << 4) + lane_rel + e) <= wd;
+        else return key0 + e <= kvis;
+    };
+    // the row's statistics over all L keys: the S splits in split order (every query sees its own key: some split's max is finite.
+    // Unwindowed that is the first split, which holds key 0; windowed a column's window can begin behind the first split, which then
+    // holds (-inf, 0) for it.  Such a split, like those behind a ragged row's last tile, is skipped)
     const float* __restrict__ stp = g.stats + (b * g.S * 16 + c16) * 2;
     float row_max = -INFINITY;
     for (int i = 0; i < g.S; ++i) row_max = fmaxf(row_max, stp[i * 32]);
@@ -454,7 +509,7 @@ __global__ __launch_bounds__(256) void decode_pv_kernel(const QuantArgs ap, cons
     const float row_inv = 1.0f / row_sum;
     const int mbp = (int)__builtin_log2f(ap.shift);
     const uint16_t* __restrict__ vfb = g.vq + (PG ? 0 : cb * g.NPC * DT * 512) + lane * 8;
-    const float* __restrict__ sc = g.scores + b * g.NT * 256 + lane * 4;
+    const float* __restrict__ sc = g.scores + b * g.NT * 256 + lane * 4 - 2 * p0 * 256;
     f32x4 o[DT];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -476,12 +531,12 @@ __global__ __launch_bounds__(256) void decode_pv_kernel(const QuantArgs ap, cons
         for (int h = 0; h < 2; ++h) {
             const long long t = 2 * pr_i + h;                  // (uniform over the wave; the last pair's second tile may not exist)
             float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (t < NT) x = *reinterpret_cast<const float4*>(sc + t * 256);
+            if (t < NT && (!WN || t >= t_first)) x = *reinterpret_cast<const float4*>(sc + t * 256);   // (a tile below t_first has no scores)
             const float xs[4] = {x.x, x.y, x.z, x.w};
             const long long key0 = t * 16 + 4 * lg;
             float pr[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) pr[e] = (t < NT && key0 + e <= kvis) ? at_div(at_exp_neg(xs[e] - row_max), row_sum, row_inv) : 0.f;
+            for (int e = 0; e < 4; ++e) pr[e] = (t < NT && visible(t, key0, e)) ? at_div(at_exp_neg(xs[e] - row_max), row_sum, row_inv) : 0.f;
             at_quant_p_block(pr, pq + 4 * h, mbp, ap, at_block_exponent_mem);
         }
         const bf16x8 pf = at_pack_p(pq);
@@ -532,19 +587,24 @@ int decode_group_width(long long G, long long M) {
 // G == 0: one query row a cache row, the GQ = false kernels.  G >= 1: the grouped kernels over c.B * rpc launch rows.
 int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out,
                                 void* workspace, long long M, long long L, int causal, float q_scale, float scale_div,
-                                const long long* strides, int splits, hipStream_t st, const int32_t* lengths, int G, const KvPages* pages) {
-    if (pages && !lengths) return MI355Q_E_BADARG;          // (no uniform paged launch)
+                                const long long* strides, int splits, hipStream_t st, const int32_t* lengths, int G, const KvPages* pages,
+                                long long window) {
+    if ((pages || window) && !lengths) return MI355Q_E_BADARG;      // (no uniform paged or windowed launch)
+    if (window < 0 || (window && !causal)) return MI355Q_E_BADARG;
+    // windowed: partition, default splits and workspace strides are those of `span` keys, the most a row's queries can touch
+    const long long span = window ? decode_window_span(M, L, window) : L;
     DecodeArgs g{};
+    g.W = window;
     if (pages) g.pg = *pages;
     g.q = q; g.kq = c.kq; g.vq = c.vq; g.out = out; g.lengths = lengths;
     g.M = M; g.L = L; g.D = c.D;
-    g.NT = (L + 15) / 16; g.NP = (L + 31) / 32; g.NTC = c.C / 16; g.NPC = (c.C + 31) / 32;
+    g.NT = (span + 15) / 16; g.NP = (span + 31) / 32; g.NTC = c.C / 16; g.NPC = (c.C + 31) / 32;
     g.gw = G ? decode_group_width(G, M) : 1;
     if (g.gw < 1) return MI355Q_E_BADARG;
     g.rpc = G ? G / g.gw : 1;
     const long long rows = c.B * g.rpc;                     // launch rows: the workspace's and the grid's
     if (rows > 65535) return MI355Q_E_UNSUPPORTED;
-    g.S = decode_splits(rows, L, c.D, splits);
+    g.S = decode_splits(rows, span, c.D, splits);
     g.pps = (int)((g.NP + g.S - 1) / g.S);
     fill_qo_strides(g, strides, M, c.D);
     g.causal = causal; g.q_scale = q_scale; g.scale_div = scale_div;
@@ -552,11 +612,17 @@ int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const 
     g.stats = g.scores + rows * g.NT * 256;
     g.part = g.stats + rows * g.S * 32;
     const dim3 grid((unsigned)g.S, (unsigned)rows);
-#define MI355Q_DECODE_GO2(DC_, RG_, GQ_, PG_)                                                         \
-    hipLaunchKernelGGL((decode_scores_kernel<DC_, RG_, GQ_, PG_>), grid, dim3(256), 0, st, aq, g);    \
-    hipLaunchKernelGGL((decode_pv_kernel<DC_, RG_, GQ_, PG_>), grid, dim3(256), 0, st, ap, g);
+#define MI355Q_DECODE_GO2(DC_, RG_, GQ_, PG_, ...)                                                                  \
+    hipLaunchKernelGGL((decode_scores_kernel<DC_, RG_, GQ_, PG_, ##__VA_ARGS__>), grid, dim3(256), 0, st, aq, g);    \
+    hipLaunchKernelGGL((decode_pv_kernel<DC_, RG_, GQ_, PG_, ##__VA_ARGS__>), grid, dim3(256), 0, st, ap, g);
 #define MI355Q_DECODE_GO(DC_)                                                                         \
-    if (pages) {                                                                                      \
+    if (window) {                                                                                     \
+        if (pages) {                                                                                  \
+            if (G) { MI355Q_DECODE_GO2(DC_, true, true, true, true) } else { MI355Q_DECODE_GO2(DC_, true, false, true, true) }     \
+        } else {                                                                                      \
+            if (G) { MI355Q_DECODE_GO2(DC_, true, true, false, true) } else { MI355Q_DECODE_GO2(DC_, true, false, false, true) }   \
+        }                                                                                             \
+    } else if (pages) {                                                                                      \
         if (G) { MI355Q_DECODE_GO2(DC_, true, true, true) } else { MI355Q_DECODE_GO2(DC_, true, false, true) }             \
     } else if (G) {                                                                                   \
         if (lengths) { MI355Q_DECODE_GO2(DC_, true, true, false) } else { MI355Q_DECODE_GO2(DC_, false, true, false) }     \

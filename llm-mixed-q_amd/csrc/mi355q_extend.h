@@ -9,6 +9,8 @@
 // zeros.  The host's M and max_length size the grid only; nothing is addressed from them.  No workspace: the scores are formed twice.
 // Grouped queries (G >= 1): q / out hold B * G rows, query row r reads cache row r / G and lengths[r / G], counts[r / G].
 // Paged cache (pages != NULL, lengths != NULL): the step's pieces through the row's page table (mi355q_decode.h).
+// Sliding window (window >= 1, causal, lengths != NULL): query i sees keys max(0, p - window + 1) .. p, p = L_b - m_b + i; a workgroup's
+// walk begins at the 32-key step of its first query's lower bound (mi355q_extend.hip).
 #ifndef MI355Q_EXTEND_H
 #define MI355Q_EXTEND_H
 #include <hip/hip_runtime.h>
@@ -33,11 +35,13 @@ struct ExtendArgs {
     const int32_t* counts;    // [B] on the device or NULL
     int G;                    // grouped queries (GQ): query rows a cache row; nb = B * G, lengths / counts stay [B].  Else 0
     KvPages pg;               // paged cache (PG, mi355q_decode.h): kq / vq are the pools; else zeros
+    long long W;              // sliding window (WN, mi355q_decode.h); else 0 (behind every other field)
 };
 
 int launch_bfp_attention_extend(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out, long long M,
                                 long long max_length, int causal, float q_scale, float scale_div, const long long* strides,
-                                const int32_t* lengths, const int32_t* counts, hipStream_t st, int G = 0, const KvPages* pages = nullptr);
+                                const int32_t* lengths, const int32_t* counts, hipStream_t st, int G = 0, const KvPages* pages = nullptr,
+                                long long window = 0);
 
 }  // namespace mi355q
 #endif

@@ -26,6 +26,21 @@
 //                      holds an even number of tiles, so tile need would lie in the same page: the order decides which piece of the
 //                      page is read, not which table entry.)  The step's logical page holds key 32 st <= 16 (need - 1) <= L_b - 1: an
 //                      entry below ceil(L_b / P).  Entries are asked for two steps ahead of their DMA.
+//   sliding window     WN = true (semantics: mi355q_decode.h): query i at p = L_b - m_b + i sees keys max(0, p - W + 1) .. p.  The walk
+//                      begins at step st0 = lo / 32, lo the lower bound of the workgroup's FIRST real query (scalar): the later queries'
+//                      bounds are no smaller, so no query of the workgroup sees a key below step st0, and the steps below are not read
+//                      (no DMA, paged no table entry).  It ends where it ends today.  The three hazards above stay closed:
+//                        out-of-row reads    every step taken is st0 <= st < nsteps, a subset of today's steps; the clamp min(t, need - 1)
+//                                            and the V bound do not depend on where the walk starts.  lo <= the first query's horizon
+//                                            < 16 need, so st0 <= (need - 1) / 2 < nsteps: at least one step, the look-ahead guards
+//                                            (st + 1 < nsteps, pg_entry's st < nsteps) hold as they are.
+//                        divergent barriers  st0 is scalar like nsteps: all four waves make nsteps - st0 steps in both passes.  Buffers
+//                                            alternate by st & 1 from st0 on; the barrier between the passes still separates the last
+//                                            read of pass 1 from the first DMA of pass 2, whichever buffer that is.
+//                        paged cache         one entry a step as before, for steps st0 .. nsteps - 1 only: step st0 holds key lo, which
+//                                            the first query sees, so every page looked up holds a key some query of the row sees.
+//                      A lane's early steps can be wholly below ITS bound (a later wave, a lane group): scores of -inf, which the
+//                      running statistics take as "no key yet" -- as they do today above the horizon.  Every query sees its own key.
 //   missing V pieces   the last pair's second tile may not exist (t >= need): its probabilities are exact zeros, the stored V there
 //                      is finite (zeroed storage or older quantised values).
 #include <hip/hip_runtime.h>
@@ -42,7 +57,7 @@ namespace mi355q {
 // GQ = true (grouped queries): workgroup row b is a QUERY head -- q, out and the grid have B * G of them -- and reads cache row b / G:
 // its fragments, lengths[b / G], counts[b / G].  Nothing else differs, so a head's bits are those of GQ = false on a private copy of
 // the row.  The G workgroups of a group each read the row's fragments themselves (no sharing inside a workgroup).
-template <int DC, bool GQ, bool PG>
+template <int DC, bool GQ, bool PG, bool WN = false>
 __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantArgs aq, const QuantArgs ap, const ExtendArgs g) {
     constexpr int DT = DC * 2, KSTEP = 2 * DC * 1024, VSTEP = DT * 1024, STEP = KSTEP + VSTEP;      // bytes per 32 keys
     using gptr_t = const __attribute__((address_space(1))) void*;
@@ -77,6 +92,13 @@ __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantAr
     const long long kvis = g.causal ? L - m + qrow : L - 1;
     const long long need = (g.causal ? L - m + min(wg0 + 63, m - 1) : L - 1) / 16 + 1;
     const int nsteps = (int)((need + 1) / 2);
+    // windowed: this lane's lower bound, and the workgroup's first step (scalar) from that of its first real query
+    long long klo = 0;
+    int st0 = 0;
+    if constexpr (WN) {
+        klo = max(kvis - g.W + 1, 0ll);
+        st0 = (int)(max(L - m + wg0 - g.W + 1, 0ll) >> 5);
+    }
     const unsigned char* __restrict__ kfb = reinterpret_cast<const unsigned char*>(g.kq) + (PG ? 0 : cb * g.NTC * DC * 1024) + lane * 16;
     const unsigned char* __restrict__ vfb = reinterpret_cast<const unsigned char*>(g.vq) + (PG ? 0 : cb * g.NPC * DT * 1024) + lane * 16;
     const float scale_inv = g.scale_div != 0.f ? 1.0f / g.scale_div : 0.f;
@@ -123,16 +145,16 @@ __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantAr
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float x = g.scale_div != 0.f ? at_div(s[e], g.scale_div, scale_inv) : s[e];
-                sv[h][e] = (t < need && key0 + e <= kvis) ? x : -INFINITY;
+                sv[h][e] = (t < need && key0 + e <= kvis && (!WN || key0 + e >= klo)) ? x : -INFINITY;
             }
         }
     };
 
     // ---- pass 1: running maximum and sum of exponentials per lane
     float m_run = -INFINITY, l_run = 0.f;
-    int pg_next = pg_entry(1), pg_after = 0;                // entries of steps st + 1, st + 2 (the top-of-step wait covers their loads)
-    dma(0, 0, false, pg_entry(0));
-    for (int st = 0; st < nsteps; ++st) {
+    int pg_next = pg_entry(st0 + 1), pg_after = 0;          // entries of steps st + 1, st + 2 (the top-of-step wait covers their loads)
+    dma(st0, st0 & 1, false, pg_entry(st0));
+    for (int st = st0; st < nsteps; ++st) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if constexpr (PG) pg_after = pg_entry(st + 2);
@@ -142,7 +164,7 @@ __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantAr
         scores(st, st & 1, sv);
         at_softmax_step(sv, m_run, l_run);
     }
-    float row_max, row_sum, row_inv;                        // (every query sees key 0: the row maximum is finite)
+    float row_max, row_sum, row_inv;                        // (every query sees its own key: the row maximum is finite)
     at_softmax_finish(m_run, l_run, row_max, row_sum, row_inv);
     __syncthreads();                                        // (every wave is out of the last step's buffer)
 
@@ -151,9 +173,9 @@ __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantAr
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int mbp = (int)__builtin_log2f(ap.shift);
-    pg_next = pg_entry(1);
-    dma(0, 0, true, pg_entry(0));
-    for (int st = 0; st < nsteps; ++st) {
+    pg_next = pg_entry(st0 + 1);
+    dma(st0, st0 & 1, true, pg_entry(st0));
+    for (int st = st0; st < nsteps; ++st) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if constexpr (PG) pg_after = pg_entry(st + 2);
@@ -187,9 +209,12 @@ __global__ __launch_bounds__(256) void bfp_attention_extend_kernel(const QuantAr
 // G == 0: one query row a cache row (GQ = false).  G >= 1: q / out hold c.B * G rows, query row r on cache row r / G (GQ = true)
 int launch_bfp_attention_extend(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out, long long M,
                                 long long max_length, int causal, float q_scale, float scale_div, const long long* strides,
-                                const int32_t* lengths, const int32_t* counts, hipStream_t st, int G, const KvPages* pages) {
-    if (pages && !lengths) return MI355Q_E_BADARG;          // (no uniform paged launch)
+                                const int32_t* lengths, const int32_t* counts, hipStream_t st, int G, const KvPages* pages,
+                                long long window) {
+    if ((pages || window) && !lengths) return MI355Q_E_BADARG;      // (no uniform paged or windowed launch)
+    if (window < 0 || (window && !causal)) return MI355Q_E_BADARG;
     ExtendArgs g{};
+    g.W = window;
     if (pages) g.pg = *pages;
     g.q = q; g.kq = c.kq; g.vq = c.vq; g.out = out; g.lengths = lengths; g.counts = counts;
     g.M = M; g.L = max_length; g.NTC = c.C / 16; g.NPC = (c.C + 31) / 32;
@@ -200,7 +225,11 @@ int launch_bfp_attention_extend(const QuantArgs& aq, const QuantArgs& ap, const 
     g.nb = (int)rows; g.nxb = (int)nxb; g.G = G;
     const dim3 grid((unsigned)(rows * nxb));
 #define MI355Q_EXTEND_GO(DC_)                                                                                          \
-    if (pages && G) hipLaunchKernelGGL((bfp_attention_extend_kernel<DC_, true, true>), grid, dim3(256), 0, st, aq, ap, g);        \
+    if (window && pages && G) hipLaunchKernelGGL((bfp_attention_extend_kernel<DC_, true, true, true>), grid, dim3(256), 0, st, aq, ap, g);   \
+    else if (window && pages) hipLaunchKernelGGL((bfp_attention_extend_kernel<DC_, false, true, true>), grid, dim3(256), 0, st, aq, ap, g); \
+    else if (window && G) hipLaunchKernelGGL((bfp_attention_extend_kernel<DC_, true, false, true>), grid, dim3(256), 0, st, aq, ap, g);     \
+    else if (window) hipLaunchKernelGGL((bfp_attention_extend_kernel<DC_, false, false, true>), grid, dim3(256), 0, st, aq, ap, g);         \
+    else if (pages && G) hipLaunchKernelGGL((bfp_attention_extend_kernel<DC_, true, true>), grid, dim3(256), 0, st, aq, ap, g);        \
     else if (pages) hipLaunchKernelGGL((bfp_attention_extend_kernel<DC_, false, true>), grid, dim3(256), 0, st, aq, ap, g);      \
     else if (G) hipLaunchKernelGGL((bfp_attention_extend_kernel<DC_, true, false>), grid, dim3(256), 0, st, aq, ap, g);          \
     else hipLaunchKernelGGL((bfp_attention_extend_kernel<DC_, false, false>), grid, dim3(256), 0, st, aq, ap, g);

@@ -97,6 +97,12 @@ SIGNATURES = {
                                                     _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp]),
     "mi355q_bfp_attention_extend_paged": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, C.c_float, C.c_float, _vp, _i64, _i64, _i64,
                                                     _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "mi355q_bfp_attention_decode_window_span": (C.c_int64, [_i64, _i64, _i64]),
+    "mi355q_bfp_attention_decode_window_workspace_bytes": (C.c_size_t, [_i64, _i64, _i64, _i64, _i64, _i32]),
+    "mi355q_bfp_attention_decode_window": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i64, C.c_float, C.c_float, _vp, _vp, _i64, _i64,
+                                                     _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp]),
+    "mi355q_bfp_attention_extend_window": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i64, C.c_float, C.c_float, _vp, _i64, _i64,
+                                                     _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "mi355q_stream_capture_id": (C.c_uint64, [_vp]),
     "mi355q_rope_apply": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "mi355q_bfp_gemm_aligned": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),

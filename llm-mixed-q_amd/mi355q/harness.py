@@ -245,9 +245,13 @@ class TinyLlamaConfig:
     max_positions: int = 128
     rms_eps: float = 1e-6
     init_std: float = 0.02
+    sliding_window: int = None     # sliding-window attention (Mistral): a query sees its last `sliding_window` keys, its own included; None: all
     num_kv_heads: int = None       # grouped-query attention: K / V heads, each shared by num_heads // num_kv_heads query heads; None: num_heads
 
     def __post_init__(self):
+        w = self.sliding_window
+        if w is not None and (isinstance(w, bool) or not isinstance(w, int) or w < 1):
+            raise ValueError(f"TinyLlamaConfig: sliding_window = {w!r} is not an integer >= 1")
         if self.num_kv_heads is not None and (self.num_kv_heads < 1 or self.num_heads % self.num_kv_heads != 0):
             raise ValueError(f"TinyLlamaConfig: num_kv_heads = {self.num_kv_heads} does not divide num_heads = {self.num_heads}")
 
@@ -269,6 +273,15 @@ class _RMSNorm(nn.Module):
         return self.weight * (x * torch.rsqrt(v + self.eps)).to(x.dtype)
 
 
+def _causal_mask(n: int, L: int, window, dtype, device):
+    """the additive mask [n, L] of n queries at the last n of L positions (the offset of modeling_llama.py:53-79): finfo.min above the
+    horizon and, with a sliding window, below it -- query i at p = L - n + i sees keys max(0, p - window + 1) .. p"""
+    mask = torch.full((n, L), torch.finfo(dtype).min, device=device).triu(1 + L - n)
+    if window is not None:
+        mask = mask + torch.full((n, L), torch.finfo(dtype).min, device=device).tril(L - n - int(window))
+    return mask
+
+
 def _repeat_kv(t, G: int):
     """[B, nkv, n, hd] -> [B, nkv * G, n, hd], head j a copy of KV head j // G (HF Llama's repeat_kv: expand + reshape)"""
     B, nkv, n, hd = t.shape
@@ -287,6 +300,7 @@ class _LlamaAttention(nn.Module):
         super().__init__()
         self.h, self.nh, self.hd = cfg.hidden_size, cfg.num_heads, cfg.hidden_size // cfg.num_heads
         self.nkv = cfg.num_heads if cfg.num_kv_heads is None else cfg.num_kv_heads
+        self.window = cfg.sliding_window
         self.qc = qc
         for name in ("q_proj", "k_proj", "v_proj", "o_proj"):
             out = self.nkv * self.hd if name in ("k_proj", "v_proj") else self.h
@@ -322,7 +336,9 @@ class _LlamaAttention(nn.Module):
             k, v = _repeat_kv(k, self.nh // self.nkv), _repeat_kv(v, self.nh // self.nkv)
         rc = self.qc["rotary_positional_encoding"]
         c1 = self.qc["matmul_1"]
-        fused = c1["name"] == "block_fp" and c1.get("mi355q_fused_attention", False)
+        # (sliding window: the fused causal paths take no additive mask, so a windowed model with T > W takes the mask route below)
+        windowed = self.window is not None and T > self.window
+        fused = c1["name"] == "block_fp" and c1.get("mi355q_fused_attention", False) and not windowed
         if fused and c1.get("mi355q_fused_rotary", False):
             # (the rotary embedding applied where the attention pass loads q and k: attention_block_fp(rope=...))
             o = get_quantized_func("attention", c1)(q, k, v, self.qc["matmul_0"], c1, causal=True, scale_div=math.sqrt(self.hd),
@@ -336,7 +352,7 @@ class _LlamaAttention(nn.Module):
                                                     consumer=_attention_consumer(c1, self.o_proj, hs, B))
             return _project_attention_output(o, self.o_proj, out, B, T, nh * self.hd, residual)
         w = get_quantized_func("matmul", self.qc["matmul_0"])(q, k.transpose(2, 3), config=self.qc["matmul_0"])
-        if c1["name"] in ("block_fp", "block_minifloat") and c1.get("mi355q_fused_softmax", False):
+        if c1["name"] in ("block_fp", "block_minifloat") and c1.get("mi355q_fused_softmax", False) and not windowed:
             o = get_quantized_func("softmax_matmul", c1)(w / math.sqrt(self.hd), v, config=c1, causal=True)
         else:
             w = w / math.sqrt(self.hd) + mask
@@ -449,7 +465,7 @@ class TinyLlamaForCausalLM(nn.Module):
         B, T = input_ids.shape
         position_ids = torch.arange(T, device=input_ids.device)[None].expand(B, T)
         x = self.embed_tokens(input_ids)
-        mask = torch.full((T, T), torch.finfo(x.dtype).min, device=x.device).triu(1)[None, None]
+        mask = _causal_mask(T, T, self.cfg.sliding_window, x.dtype, x.device)[None, None]
         for layer in self.layers:
             x = layer(x, mask, position_ids)
         # (unquantised, modeling_llama.py:772,866: fp32-equivalent on the bf16 MFMA -- quantized_modules.linear.fp32_linear; "vendor" = F.linear)
@@ -480,6 +496,10 @@ class DecodeState:
     Grouped-query attention (k, v with fewer heads than q): the caches and the per-row tensors have batch x KV heads rows, the decode
     and extend functions get group = heads // KV heads; the prefill routes and mode "fp32" repeat k / v to the query heads at use
     (mode "fp32" concatenates them un-repeated).
+    Sliding window (model.cfg.sliding_window = W; TinyLlama only): every route bounds a query to its last W keys.  Mode "block_fp" passes
+    window= to the decode and extend functions; a prompt (or a ragged prefill with a row) longer than W runs on the windowed extend
+    kernel behind its own append, whatever `extend` says -- the prefill attention function has no window; mode "fp32" adds the window to
+    its additive mask.  A paged state gives back, after every call, the pages no later query can see (PagedKVCache.trim).
     Paged caches: PagedDecodeState below (this constructor's parameters stay as they are)."""
     paged = False
 
@@ -491,6 +511,7 @@ class DecodeState:
         if any(getattr(a, "mi355q_head_shard", None) is not None for a in attns):
             raise NotImplementedError("incremental decoding of head-sharded models")
         self.mode, self.batch, self.length = mode, int(batch), 0
+        self.window = getattr(model.cfg, "sliding_window", None)
         self.extend = bool(extend) and mode == "block_fp"
         self.lengths, self.ragged, self._call = [0] * self.batch, self.paged, None
         self.capacity = (int(capacity) + 15) // 16 * 16
@@ -591,22 +612,30 @@ class DecodeState:
     def end_ragged(self) -> None:
         self.lengths, self._call = self._call["after"], None
         self.length = max(self.lengths)
+        if self.paged and self.window is not None:
+            # sliding window: the pages wholly behind every later query's window go back to the pool, in every layer
+            for c in self.kv:
+                heads = c.B // self.batch
+                c.trim([l for l in self.lengths for _ in range(heads)], self.window)
 
     def _attend_ragged(self, idx, q, k, v, c0, c1, scale_div):
         B, nh, n, hd = q.shape
         call, cache = self._call, self.kv[idx]
         gq = {} if k.shape[1] == nh else dict(group=nh // k.shape[1])      # (grouped queries: k, v have the KV heads only)
+        if self.window is not None:
+            gq["window"] = self.window
         full = all(c == n for c in call["counts"])
         cache.append(k, v, lengths=self.rows_before, counts=None if full else self._rows_counts, max_length=call["max_before"])
         if call["route"] == "decode":
             return get_quantized_func("attention_decode", c1)(q, cache, c0, c1, causal=True, scale_div=scale_div, lengths=self.rows_after,
                                                               max_length=call["max_after"], **gq).reshape(B, nh, n, hd)
-        if call["route"] == "extend":
-            # (max_length bounds the lengths and must hold the n query columns, which may all be padding behind the largest count)
+        if call["route"] == "extend" or (call["route"] == "prefill" and self.window is not None and max(call["counts"]) > self.window):
+            # (a windowed prefill with a row longer than the window: the extend kernel behind the append -- a row that starts at 0 is the
+            #  row whose queries are all its keys; max_length bounds the lengths and must hold the n query columns, which may all be padding behind the largest count)
             return get_quantized_func("attention_extend", c1)(q, cache, c0, c1, causal=True, scale_div=scale_div, lengths=self.rows_after,
                                                               counts=self._rows_counts, max_length=max(call["max_after"], n), **gq
                                                               ).reshape(B, nh, n, hd)
-        if gq:
+        if "group" in gq:
             k, v = _repeat_kv(k, gq["group"]), _repeat_kv(v, gq["group"])
         # ragged prefill: every sequence's own queries against its own keys, one call of the existing attention function each (what
         # the sequence alone runs); prefill is not the hot path here
@@ -632,9 +661,12 @@ class DecodeState:
                 raise NotImplementedError(f"{n} new tokens behind a non-empty block_fp cache (at most {ops.DECODE_MAX_QUERIES} a call)")
             cache.append(k, v)
             gq = {} if k.shape[1] == nh else dict(group=nh // k.shape[1])  # (grouped queries: k, v have the KV heads only)
-            if self.length == 0:
+            if self.window is not None:
+                gq["window"] = self.window
+                wide = wide or (self.length == 0 and n > self.window)      # (a prompt longer than the window: the windowed extend kernel)
+            if self.length == 0 and not wide:
                 # the prompt's own queries against the prompt: the existing attention function (M = n)
-                if gq:
+                if "group" in gq:
                     k, v = _repeat_kv(k, gq["group"]), _repeat_kv(v, gq["group"])
                 return get_quantized_func("attention", c1)(q, k, v, c0, c1, causal=True, scale_div=scale_div).reshape(B, nh, n, hd)
             return get_quantized_func("attention_extend" if wide else "attention_decode", c1)(q, cache, c0, c1, causal=True,
@@ -651,7 +683,7 @@ class DecodeState:
         w = get_quantized_func(style, c0)(q, k.transpose(-1, -2), config=c0)
         if scale_div:
             w = w / scale_div
-        mask = torch.full((n, L), torch.finfo(w.dtype).min, device=w.device).triu(1 + L - n)
+        mask = _causal_mask(n, L, self.window, w.dtype, w.device)
         w = torch.max(w + mask, w.new_full((), torch.finfo(w.dtype).min))
         p = F.softmax(w, dim=-1, dtype=torch.float32).to(q.dtype)
         return get_quantized_func(style, c1)(p, v, config=c1).view(B, nh, n, hd)

@@ -1610,13 +1610,15 @@ class PagedKVCache:
       kq, vq        the pools, `num_pages` pages (zeroed once; a recycled page is not cleared: finite values are all a V slot needs)
       stage         [B][16][D] fp32, per ROW: the open 16-key tile belongs to a row, not to a page
       block_table   int32 [B, max_pages] on the device: the page of row b's logical page i; `table` is its host mirror
-      free          the host free list (page ids; taken from its end), `held[b]` the pages of row b in logical order
+      free          the host free list (page ids; taken from its end), `held[b]` the pages of row b in logical order -- None for a
+                    logical page `trim` has given back (the row keeps its logical index: `ensure` counts it and never refills it)
       capacity      max_pages * page_size: a row's logical capacity -- what `max_length` is checked against
     Always addressed in the ragged form: `lengths` (int32 [B] on the device) and the host bound `max_length` are mandatory.  The
     allocator is the host's: `ensure` before an append that needs new pages (the kernels never allocate, and look up only pages that
     hold keys of the row).  Table entries behind a row's pages are never read; they hold `pad_page` (default 0).  With pad_page= given
     that page is kept out of the free list for good -- a null page no row ever writes.
-    The interface is ensure / release / share_prefix / append / dequantised.  `assign`, `pad_page=`, `ensure(dry_run=)` and `pages_for`
+    Sliding window: `trim(lengths, window)` gives back the pages wholly behind the window, so a windowed row holds O(window) pages.
+    The interface is ensure / trim / release / share_prefix / append / dequantised.  `assign`, `pad_page=`, `ensure(dry_run=)` and `pages_for`
     are helpers: the tests and the timing tool place pages by hand with `assign` (out-of-order tables, a poison page), the harness asks
     every layer with `dry_run` before it changes one.  `assign` filters the free list per call and is not meant for a hot loop."""
 
@@ -1692,10 +1694,39 @@ class PagedKVCache:
         if upload:
             self._upload()
 
+    def trim(self, lengths, window: int) -> None:
+        """sliding-window attention: row b (lengths[b] keys, host ints, one per cache row) gives back every logical page i with
+        (i + 1) * page_size <= lengths[b] - window + 1 -- keys no query at a position >= lengths[b] sees, so no later windowed call reads
+        them (the windowed kernels look up only pages that hold a visible key).  Their table entries become `pad_page`, `held` keeps
+        None in their place; a page another row still holds (share_prefix) stays with that row.  One copy_ of the table when anything
+        changed.  Only for rows that are from here on read with this window (or a smaller one)."""
+        if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+            raise ValueError(f"PagedKVCache.trim: window = {window!r} is not an integer >= 1")
+        lengths = [int(n) for n in lengths]
+        if len(lengths) != self.B:
+            raise ValueError(f"PagedKVCache.trim: {len(lengths)} lengths for {self.B} cache rows")
+        changed = False
+        for b, n in enumerate(lengths):
+            held = self.held[b]
+            for i in range(min(max(n - window + 1, 0) // self.page_size, len(held))):
+                p = held[i]
+                if p is None:
+                    continue
+                self.refs[p] -= 1
+                if self.refs[p] == 0:
+                    self.free.append(p)
+                held[i] = None
+                self.table[b, i] = self.pad_page
+                changed = True
+        if changed:
+            self._upload()
+
     def release(self, rows) -> None:
         """rows' pages back to the free list (a page shared with another row stays with that row); the rows then hold no keys"""
         for b in ([rows] if isinstance(rows, int) else rows):
             for p in self.held[b]:
+                if p is None:                               # (a trimmed page went back when it was trimmed)
+                    continue
                 self.refs[p] -= 1
                 if self.refs[p] == 0:
                     self.free.append(p)
@@ -1713,6 +1744,8 @@ class PagedKVCache:
             raise ValueError(f"PagedKVCache.share_prefix: row {dst} holds {len(self.held[dst])} pages (only a row that holds none can share)")
         if not 0 <= pages <= len(self.held[src]):
             raise ValueError(f"PagedKVCache.share_prefix: {pages} pages, row {src} holds {len(self.held[src])}")
+        if any(p is None for p in self.held[src][:pages]):
+            raise ValueError(f"PagedKVCache.share_prefix: row {src} has trimmed pages among its first {pages} (a trimmed prefix cannot be shared)")
         for i, p in enumerate(self.held[src][:pages]):
             self.refs[p] += 1
             self.table[dst, i] = p
@@ -1750,7 +1783,8 @@ class PagedKVCache:
         _lib.check(rc, "mi355q_bfp_kv_append_paged")
 
     def dequantised(self, lengths: torch.Tensor, max_length: int = None):
-        """the rows' quantised K and V as fp32 [B, max_length, D] through the page table, zeros behind each row's lengths[b]"""
+        """the rows' quantised K and V as fp32 [B, max_length, D] through the page table, zeros behind each row's lengths[b].  Keys in
+        pages `trim` has given back are unspecified (their entries name `pad_page`)."""
         why = "lengths= is mandatory: a paged cache is always addressed in the ragged form" if lengths is None else \
             _ragged_check(self, lengths, None, max_length, 0, "dequantised")
         if why is not None:
@@ -1770,10 +1804,35 @@ class PagedKVCache:
 _PAGED_NEEDS_LENGTHS = "a paged cache is always addressed in the ragged form: lengths= and max_length= (there is no uniform paged launch)"
 
 
-def _decode_check(q, cache, splits=None, lengths=None, max_length=None, group=1):
+def _window_check(window, causal):
+    """the reasons a call declines `window`, None when it takes it (None: no window)"""
+    if window is None:
+        return None
+    if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+        return f"window = {window!r} is not an integer >= 1 (the keys a query sees, its own included)"
+    if not causal:
+        return "window with causal=False: a sliding window bounds a causal query to its last `window` keys"
+    return None
+
+
+def _window_lengths(cache, lengths, max_length):
+    """(lengths, max_length) of a windowed call: the windowed kernels exist in the ragged form only, so the uniform call brings every
+    row's cache.length as a device tensor (kept per cache and length: one fill when the length moves)"""
+    if lengths is not None:
+        return lengths, int(max_length)
+    kept = getattr(cache, "_uniform_lengths", None)
+    if kept is None or kept[0] != cache.length:
+        kept = cache._uniform_lengths = (cache.length, torch.full((cache.B,), cache.length, dtype=torch.int32, device=cache.device))
+    return kept[1], cache.length
+
+
+def _decode_check(q, cache, splits=None, lengths=None, max_length=None, group=1, *, causal=True, window=None):
     """the reasons bfp_attention_decode declines (q, cache), None when it takes them; nothing here touches the device"""
     if not isinstance(cache, (KVCache, PagedKVCache)):
         return "cache is not a KVCache"
+    why = _window_check(window, causal)
+    if why is not None:
+        return why
     if isinstance(cache, PagedKVCache) and lengths is None:
         return _PAGED_NEEDS_LENGTHS
     if not isinstance(q, torch.Tensor) or q.ndim < 3:
@@ -1808,7 +1867,7 @@ def bfp_attention_decode_supported(q, cache) -> bool:
 
 def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True, scale_div: float = None, q_scale: float = None,
                          token_major: bool = False, splits: int = None, lengths: torch.Tensor = None, max_length: int = None,
-                         group: int = 1):
+                         group: int = 1, window: int = None):
     """The attention core (modeling_llama.py:309-344) for the LAST M <= 16 positions of a sequence whose L = cache.length keys are in
     `cache` (their own keys included: append first): q [..., M, D] fp32; causal: query i sees keys 0 .. L - M + i, else all L.
     scale_div / q_scale / token_major as bfp_attention.  Keys are split over `splits` workgroups per head (default: decode_splits);
@@ -1821,9 +1880,16 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     entry per CACHE row.  decode_group_width(G, M) heads share one launch row's K / V loads; the default number of splits is that of
     cache.B * G // decode_group_width(G, M) rows.  Each query row gets the bits group=1 gives it on a cache of cache.B * G rows
     holding the repeated K / V, with the same `splits`.
-    `cache` may be a PagedKVCache (always with `lengths`): the bits of the same call on a KVCache holding the same keys."""
+    `cache` may be a PagedKVCache (always with `lengths`): the bits of the same call on a KVCache holding the same keys.
+    Sliding window (`window` = W >= 1, causal only): the query at absolute position p (row b's query i: lengths[b] - M + i) sees keys
+    max(0, p - W + 1) .. p, W keys with its own (HF Mistral's rule) -- the reference's call with an additive mask that is finfo.min
+    below the window too.  The cache is unchanged and the 16-key blocks of K^T and P stay aligned to absolute key index; key tiles
+    below every query's window are not read, and the splits cover span = min(max_length, W + M - 1 + 31) keys from each row's first
+    visible key pair on: the default is decode_splits(rows, span, D), and work and workspace follow W, not the length.
+    W >= max_length (cache.length) gives the bits of window=None.  A paged cache may have trimmed the pages behind the window
+    (PagedKVCache.trim)."""
     import ctypes
-    why = _decode_check(q, cache, splits, lengths, max_length, group)
+    why = _decode_check(q, cache, splits, lengths, max_length, group, causal=causal, window=window)
     if why is not None:
         raise ValueError(f"mi355q.bfp_attention_decode: {why}")
     M, D = q.shape[-2:]
@@ -1848,6 +1914,18 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
         ws = _DECODE_WS.put(key, torch.empty(R * (C // 16) * 1024 + R * _DECODE_MAX_SPLITS * (128 + (D // 16) * 1024), dtype=torch.uint8,
                                              device=q.device))
     strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
+    if window is not None:
+        wl, wmax = _window_lengths(cache, lengths, max_length)
+        with _on_device(q.device):
+            rc = lib.mi355q_bfp_attention_decode_window(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), group, _ptr(wl),
+                                                        _ptr(cache.block_table) if paged else None, 1, int(window),
+                                                        float(q_scale) if q_scale else 0.0, float(scale_div) if scale_div else 0.0,
+                                                        _ptr(out), _ptr(ws), B, M, wmax, cache.max_pages if paged else 1,
+                                                        cache.num_pages if paged else 1, cache.page_size if paged else C, D,
+                                                        ctypes.addressof(cache._pa), ctypes.addressof(cache._pb), ctypes.addressof(strides),
+                                                        int(splits or 0), sp)
+        _lib.check(rc, "mi355q_bfp_attention_decode_window")
+        return out
     if paged:
         with _on_device(q.device):
             rc = lib.mi355q_bfp_attention_decode_paged(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), group, _ptr(lengths), _ptr(cache.block_table),
@@ -1883,10 +1961,13 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     return out
 
 
-def _extend_check(q, cache, lengths=None, counts=None, max_length=None, group=1):
+def _extend_check(q, cache, lengths=None, counts=None, max_length=None, group=1, *, causal=True, window=None):
     """the reasons bfp_attention_extend declines (q, cache), None when it takes them; nothing here touches the device"""
     if not isinstance(cache, (KVCache, PagedKVCache)):
         return "cache is not a KVCache"
+    why = _window_check(window, causal)
+    if why is not None:
+        return why
     if isinstance(cache, PagedKVCache) and lengths is None:
         return _PAGED_NEEDS_LENGTHS
     if not isinstance(q, torch.Tensor) or q.ndim < 3:
@@ -1917,7 +1998,7 @@ def _extend_check(q, cache, lengths=None, counts=None, max_length=None, group=1)
 
 def bfp_attention_extend(q: torch.Tensor, cache: KVCache, *, causal: bool = True, scale_div: float = None, q_scale: float = None,
                          token_major: bool = False, lengths: torch.Tensor = None, counts: torch.Tensor = None, max_length: int = None,
-                         group: int = 1):
+                         group: int = 1, window: int = None):
     """Chunked prefill: the attention core (modeling_llama.py:309-344) for the LAST M positions -- any M >= 1 -- of a sequence whose
     L = cache.length keys are in `cache` (their own keys included: append first), the reference's `past_key_value` call with M new
     tokens behind a past of L - M.  q [..., M, D] fp32; causal: query i sees keys 0 .. L - M + i, else all L.  scale_div / q_scale /
@@ -1929,9 +2010,11 @@ def bfp_attention_extend(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     or counts[b] > lengths[b] (an empty slot) returns zeros.  cache.length is not used.
     Grouped queries (`group` = G > 1) as bfp_attention_decode: q folds to cache.B * G rows, query row r on cache row r // G, `lengths`
     and `counts` one entry per CACHE row; each query row gets the bits group=1 gives it on a cache holding the repeated K / V.
-    `cache` may be a PagedKVCache (always with `lengths`): the bits of the same call on a KVCache holding the same keys."""
+    `cache` may be a PagedKVCache (always with `lengths`): the bits of the same call on a KVCache holding the same keys.
+    Sliding window (`window` = W >= 1, causal only) as bfp_attention_decode: row b's query i, at p = lengths[b] - counts[b] + i, sees
+    keys max(0, p - W + 1) .. p; a block of 64 queries walks the keys from the 32-key step of its first query's lower bound on."""
     import ctypes
-    why = _extend_check(q, cache, lengths, counts, max_length, group)
+    why = _extend_check(q, cache, lengths, counts, max_length, group, causal=causal, window=window)
     if why is not None:
         raise ValueError(f"mi355q.bfp_attention_extend: {why}")
     M, D = q.shape[-2:]
@@ -1944,6 +2027,20 @@ def bfp_attention_extend(q: torch.Tensor, cache: KVCache, *, causal: bool = True
         out = torch.empty(*q.shape, dtype=torch.float32, device=q.device)
         osb, osm = M * D, D
     strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
+    if window is not None:
+        paged = isinstance(cache, PagedKVCache)
+        wl, wmax = _window_lengths(cache, lengths, max_length)
+        with _on_device(q.device):
+            rc = _lib.load_library().mi355q_bfp_attention_extend_window(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), group, _ptr(wl), _ptr(counts),
+                                                                        _ptr(cache.block_table) if paged else None, 1, int(window),
+                                                                        float(q_scale) if q_scale else 0.0,
+                                                                        float(scale_div) if scale_div else 0.0, _ptr(out), cache.B, M, wmax,
+                                                                        cache.max_pages if paged else 1, cache.num_pages if paged else 1,
+                                                                        cache.page_size if paged else cache.capacity, D,
+                                                                        ctypes.addressof(cache._pa), ctypes.addressof(cache._pb),
+                                                                        ctypes.addressof(strides), _stream_ptr(q.device))
+        _lib.check(rc, "mi355q_bfp_attention_extend_window")
+        return out
     if isinstance(cache, PagedKVCache):
         with _on_device(q.device):
             rc = _lib.load_library().mi355q_bfp_attention_extend_paged(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), group, _ptr(lengths), _ptr(counts),
