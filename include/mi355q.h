@@ -724,6 +724,28 @@ int mi355q_bfp_attention_extend_paged(const float* q, const void* kq_pool, const
                                       int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
                                       void* stream);
 
+/* Int8-mantissa cache: the contiguous cache above with every quantised value stored as a signed mantissa BYTE plus one shared-exponent
+ * byte per 16-value block -- 1 + 1/16 bytes a value, exactly 17/32 of mi355q_bfp_kv_cache_bytes' K and V bytes (the stage is the
+ * same) and of a decode step's K / V traffic.  Layout: csrc/mi355q_kv8.h.  The kernels rebuild the bf16 MFMA fragments in registers,
+ * pack_bf16(ldexp(mantissa, exponent - mantissa bits)), which is the halfword the bf16 cache stores: append, decode_fp32 and decode
+ * give the bits of their *_ragged / *_grouped counterparts on a bf16 cache holding the same keys (decode: with the same number of
+ * splits), with ONE exception: an input 0 < |x| <= 1e-8, which the bf16 cache passes through unquantised, is stored as 0.
+ * The CACHED operands -- the y side of qk_params and of pv_params -- must have width <= 8 (|mantissa| <= 127), else
+ * MI355Q_E_UNSUPPORTED; the x sides (Q, P) stay 2 .. 9.  v8 must be zeroed once before the first append, as vq above.
+ * Always the ragged form (`lengths` mandatory, `counts` / max_length as in the *_ragged calls); G = 0 or 1 is the ungrouped form,
+ * G > 1 as in mi355q_bfp_attention_decode_grouped (q / out hold B * G rows; workspace and splits those of the launch rows).  The
+ * workspace is mi355q_bfp_attention_decode_workspace_bytes'.  No paged, windowed or extend form reads this cache. */
+int mi355q_bfp_kv8_cache_bytes(int64_t B, int64_t C, int64_t D, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_bytes);
+int mi355q_bfp_kv8_append(void* k8, void* v8, float* stage, const float* k, const float* v, const int32_t* lengths,
+                          const int32_t* counts, int64_t B, int64_t C, int64_t D, int64_t n, int64_t max_length,
+                          const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides, void* stream);
+int mi355q_bfp_kv8_decode_fp32(const void* k8, const void* v8, const int32_t* lengths, float* k_out, float* v_out, int64_t B, int64_t C,
+                               int64_t D, int64_t max_length, const int32_t* qk_params, const int32_t* pv_params, void* stream);
+int mi355q_bfp_attention_decode_kv8(const float* q, const void* k8, const void* v8, int32_t G, const int32_t* lengths, int32_t causal,
+                                    float q_scale, float scale_div, float* out, void* workspace, int64_t B, int64_t M,
+                                    int64_t max_length, int64_t C, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
+                                    const int64_t* strides, int32_t splits, void* stream);
+
 /* Sliding window: decode and extend with every query bound to its last `window` = W >= 1 keys, its own included -- a query at absolute
  * position p (decode: L_b - M + i; extend: L_b - m_b + i) sees keys max(0, p - W + 1) .. p.  That is the `past_key_value` call with an
  * additive mask that is finfo.min below the window as well as above the horizon: the cache is unchanged, K^T's and P's 16-key blocks

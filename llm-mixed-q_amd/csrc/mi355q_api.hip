@@ -13,6 +13,7 @@
 #include "mi355q_internal.h"
 #include "mi355q_gemv.h"
 #include "mi355q_decode.h"
+#include "mi355q_kv8.h"
 #include "mi355q_extend.h"
 #include "mi355q_align_row.h"
 
@@ -1373,6 +1374,93 @@ int mi355q_bfp_attention_extend_paged(const float* q, const void* kq_pool, const
                     max_pages * P, (int)D};
     return launch_bfp_attention_extend(aq, ap, c, q, out, M, max_length, causal != 0, q_scale, scale_div, strides ? st4 : nullptr,
                                        lengths, counts, static_cast<hipStream_t>(stream), G, &pg);
+}
+
+// ---- int8-mantissa cache: mantissa bytes and one exponent byte a block (mi355q_kv8.h); always the ragged form, contiguous -------
+namespace {
+// the quantisers of the CACHED operands (the y side): a mantissa must fit int8
+int kv8_quant_args(const int32_t* qk_params, const int32_t* pv_params, QuantArgs& ak, QuantArgs& av) {
+    int rc;
+    if ((rc = decode_quant_args(qk_params + 3, ak)) != 0 || (rc = decode_quant_args(pv_params + 3, av)) != 0) return rc;
+    return qk_params[3] > 8 || pv_params[3] > 8 ? MI355Q_E_UNSUPPORTED : 0;
+}
+}  // namespace
+
+int mi355q_bfp_kv8_cache_bytes(int64_t B, int64_t C, int64_t D, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_bytes) {
+    if (!k_bytes || !v_bytes || !stage_bytes) return MI355Q_E_BADARG;
+    const int rc = decode_cache_shape(B, C, D);
+    if (rc) return rc;
+    *k_bytes = kv8_k_bytes(B, C, D);
+    *v_bytes = kv8_v_bytes(B, C, D);
+    *stage_bytes = kv_stage_bytes(B, D);
+    return 0;
+}
+
+int mi355q_bfp_kv8_append(void* k8, void* v8, float* stage, const float* k, const float* v, const int32_t* lengths,
+                          const int32_t* counts, int64_t B, int64_t C, int64_t D, int64_t n, int64_t max_length,
+                          const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides, void* stream) {
+    int rc = decode_cache_shape(B, C, D);
+    if (rc) return rc;
+    if (max_length < 0 || n < 0 || !qk_params || !pv_params) return MI355Q_E_BADARG;
+    if (max_length + n > C) return MI355Q_E_UNSUPPORTED;      // (nothing is written)
+    QuantArgs ak{}, av{};
+    if ((rc = kv8_quant_args(qk_params, pv_params, ak, av)) != 0) return rc;
+    if (n == 0) return 0;
+    if (!k8 || !v8 || !stage || !k || !v || !lengths) return MI355Q_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(k8) | reinterpret_cast<uintptr_t>(v8) | reinterpret_cast<uintptr_t>(stage) |
+         reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v)) % 16 ||
+        (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(counts)) % 4)
+        return MI355Q_E_ALIGN;
+    long long st4[4] = {n * D, D, n * D, D};
+    if (strides)
+        for (int i = 0; i < 4; ++i) {
+            if (strides[i] % 4) return MI355Q_E_ALIGN;
+            st4[i] = strides[i];
+        }
+    const Kv8Cache c{static_cast<uint8_t*>(k8), static_cast<uint8_t*>(v8), stage, B, C, (int)D};
+    return launch_kv8_append(c, ak, av, k, v, st4[0], st4[1], st4[2], st4[3], lengths, counts, n, static_cast<hipStream_t>(stream));
+}
+
+int mi355q_bfp_kv8_decode_fp32(const void* k8, const void* v8, const int32_t* lengths, float* k_out, float* v_out, int64_t B, int64_t C,
+                               int64_t D, int64_t max_length, const int32_t* qk_params, const int32_t* pv_params, void* stream) {
+    int rc = decode_cache_shape(B, C, D);
+    if (rc) return rc;
+    if (max_length < 0 || max_length > C || !qk_params || !pv_params) return MI355Q_E_BADARG;
+    QuantArgs ak{}, av{};
+    if ((rc = kv8_quant_args(qk_params, pv_params, ak, av)) != 0) return rc;
+    if (max_length == 0) return 0;
+    if (!k8 || !v8 || !k_out || !v_out || !lengths) return MI355Q_E_BADARG;
+    const Kv8Cache c{static_cast<uint8_t*>(const_cast<void*>(k8)), static_cast<uint8_t*>(const_cast<void*>(v8)), nullptr, B, C, (int)D};
+    return launch_kv8_decode_fp32(c, ak, av, k_out, v_out, max_length, lengths, static_cast<hipStream_t>(stream));
+}
+
+int mi355q_bfp_attention_decode_kv8(const float* q, const void* k8, const void* v8, int32_t G, const int32_t* lengths, int32_t causal,
+                                    float q_scale, float scale_div, float* out, void* workspace, int64_t B, int64_t M,
+                                    int64_t max_length, int64_t C, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
+                                    const int64_t* strides, int32_t splits, void* stream) {
+    if (M < 0 || max_length < 0 || splits < 0 || G < 0) return MI355Q_E_BADARG;
+    int rc = decode_cache_shape(B, C, D);
+    if (rc) return rc;
+    if (M < 1 || M > 16 || max_length < M) return MI355Q_E_UNSUPPORTED;
+    const int group = G > 1 ? G : 0;                          // (0 or 1: one query row a cache row)
+    if (group && B * (group / decode_group_width(group, M)) > 65535) return MI355Q_E_UNSUPPORTED;
+    if (max_length > C || !q || !k8 || !v8 || !lengths || !out || !workspace || !qk_params || !pv_params) return MI355Q_E_BADARG;
+    QuantArgs aq{}, ap{}, ak{}, av{};
+    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0 ||
+        (rc = kv8_quant_args(qk_params, pv_params, ak, av)) != 0)
+        return rc;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k8) | reinterpret_cast<uintptr_t>(v8) |
+         reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) % 16 || reinterpret_cast<uintptr_t>(lengths) % 4)
+        return MI355Q_E_ALIGN;
+    long long st4[4];
+    if (strides)
+        for (int i = 0; i < 4; ++i) {
+            if (strides[i] % 4) return MI355Q_E_ALIGN;
+            st4[i] = strides[i];
+        }
+    const Kv8Cache c{static_cast<uint8_t*>(const_cast<void*>(k8)), static_cast<uint8_t*>(const_cast<void*>(v8)), nullptr, B, C, (int)D};
+    return launch_bfp_attention_decode_kv8(aq, ap, ak, av, c, q, out, workspace, M, max_length, causal != 0, q_scale, scale_div,
+                                           strides ? st4 : nullptr, splits, static_cast<hipStream_t>(stream), lengths, group);
 }
 
 // ---- sliding window: a query sees its last `window` keys (mi355q_decode.h); always the ragged form, paged or contiguous ------------

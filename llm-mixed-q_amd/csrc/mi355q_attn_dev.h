@@ -26,6 +26,12 @@ __device__ __forceinline__ float at_quant(float x, int up, int down, float mant_
     const float q = __builtin_copysignf(__builtin_ldexpf(m, down), x);
     return fabsf(x) <= ATOL ? x : q;
 }
+// the signed integer mantissa at_quant scales back down -- at_quant(x) = ldexp(at_quant_mant(x), down) for |x| > 1e-8 -- and 0 where
+// at_quant passes x through (|x| <= 1e-8): what a cache of mantissas and block exponents stores (mi355q_kv8.h)
+__device__ __forceinline__ float at_quant_mant(float x, int up, float mant_max) {
+    const float m = fminf(__builtin_rintf(__builtin_ldexpf(fabsf(x) + EPS9, up)), mant_max);
+    return fabsf(x) <= ATOL ? 0.f : __builtin_copysignf(m, x);
+}
 __device__ __forceinline__ float at_exp_neg(float x) {
     x = fmaxf(x, -104.0f);
     constexpr float L2E_HI = 1.44269502162933349609375f, L2E_LO = 1.925963033500011e-08f, LN2 = 0.693147182464599609375f;

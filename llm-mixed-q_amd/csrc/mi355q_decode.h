@@ -16,6 +16,8 @@
 // Values are those of attn_pack_k / attn_pack_v (|x| <= 1e-8 passes through, rounded to bf16) with ONE difference: a zero is
 // always stored as +0.  A negative value whose mantissa rounds to 0 is -0 in the prefill fragments (copysign) and +0 in the
 // oracle's block_fp_quantize (its mantissas are integers); the products cannot tell, the bit-for-bit cache tests can.
+// (mi355q_kv8.h: the same cache with each value as a mantissa byte plus one exponent byte a block, 17/32 of these bytes; its one
+// further difference -- 0 < |x| <= 1e-8, stored here rounded to bf16, is stored there as 0 -- is noted next to its layout.)
 // The length L lives on the host: an append at L writes keys L .. L + n - 1, a decode at L reads keys 0 .. L - 1.
 //
 // Ragged batches (the *_ragged launches): every cache row b has its own length, lengths[b] in a DEVICE int32 array [B] that the
@@ -104,6 +106,10 @@ int launch_kv_append(const KvCache& c, const QuantArgs& ak, const QuantArgs& av,
 int launch_kv_append_ragged(const KvCache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
                             long long kst, long long vsb, long long vst, const int32_t* lengths, const int32_t* counts, long long n,
                             hipStream_t st, const KvPages* pages = nullptr);
+// the staging pass of launch_kv_append_ragged alone (n > 1: the new open tile's fp32 rows, behind the append kernel that read the old
+// ones): for the int8-mantissa cache of mi355q_kv8.h, whose stage is this one.  Reads c.stage, c.B, c.C and c.D only
+void launch_kv_stage_ragged(const KvCache& c, const float* k, long long ksb, long long kst, const int32_t* lengths, const int32_t* counts,
+                            long long n, hipStream_t st);
 // the cache's quantised values back as fp32 [B, L, D] (tests, debugging); lengths != NULL: zeros behind row b's lengths[b]
 // pages != NULL (with lengths): the paged cache
 int launch_kv_decode_fp32(const KvCache& c, float* k_out, float* v_out, long long L, hipStream_t st, const int32_t* lengths = nullptr,
@@ -150,6 +156,10 @@ int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const 
                                 void* workspace, long long M, long long L, int causal, float q_scale, float scale_div,
                                 const long long* strides, int splits, hipStream_t st, const int32_t* lengths = nullptr, int G = 0,
                                 const KvPages* pages = nullptr, long long window = 0);
+
+// phase C alone (nothing to do with one split): the partial outputs of `rows` launch rows summed in split order.  It reads no K / V,
+// so the int8-mantissa decode of mi355q_kv8.hip ends in it too
+void launch_decode_sum(const DecodeArgs& g, bool grouped, long long rows, hipStream_t st);
 
 }  // namespace mi355q
 #endif

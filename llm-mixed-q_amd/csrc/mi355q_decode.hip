@@ -38,6 +38,7 @@
 #include "mi355q_quant_dev.h"
 #include "mi355q_attn_dev.h"
 #include "mi355q_decode.h"
+#include "mi355q_decode_dev.h"
 
 namespace mi355q {
 
@@ -60,13 +61,6 @@ __device__ __forceinline__ int pg_raw(const KvPages& p, long long b, long long i
 __device__ __forceinline__ long long pg_place(const KvPages& p, int raw, long long t, int sh) {
     const long long page = min(max(raw, 0), p.num_pages - 1);
     return (page << sh) + (t & ((1ll << sh) - 1));
-}
-
-// row b's (L, n) of a ragged append, scalar; false: nothing to do (negative values are taken as 0, a count above n as n)
-__device__ __forceinline__ bool append_row(const AppendArgs& a, long long b, long long& L, long long& n) {
-    L = max(__builtin_amdgcn_readfirstlane(a.lengths[b]), 0);
-    if (a.counts) n = min((long long)max(__builtin_amdgcn_readfirstlane(a.counts[b]), 0), a.n);
-    return n > 0;
 }
 
 // one block of 16 values x with maximum bmax, quantised: value e is the low halfword of a lane's slot, 8 halfwords apart in kq
@@ -203,8 +197,17 @@ int launch_kv_append_ragged(const KvCache& c, const QuantArgs& ak, const QuantAr
     } else {
         hipLaunchKernelGGL((kv_append_kernel<true, false>), grid, dim3(256), 0, st, ak, av, a);
     }
-    if (n > 1) hipLaunchKernelGGL(kv_stage_kernel<true>, dim3((unsigned)(n - 1 < 15 ? n - 1 : 15), (unsigned)c.B), dim3(c.D), 0, st, a);
+    launch_kv_stage_ragged(c, k, ksb, kst, lengths, counts, n, st);
     return (int)hipGetLastError();
+}
+
+// the staging pass alone, for a cache that keeps its quantised values elsewhere (mi355q_kv8.hip): stage, B, C and D are all it reads of c
+void launch_kv_stage_ragged(const KvCache& c, const float* k, long long ksb, long long kst, const int32_t* lengths, const int32_t* counts,
+                            long long n, hipStream_t st) {
+    AppendArgs a{};
+    a.c = c; a.k = k; a.ksb = ksb; a.kst = kst;
+    a.n = n; a.lengths = lengths; a.counts = counts;
+    if (n > 1) hipLaunchKernelGGL(kv_stage_kernel<true>, dim3((unsigned)(n - 1 < 15 ? n - 1 : 15), (unsigned)c.B), dim3(c.D), 0, st, a);
 }
 
 template <bool RG, bool PG>
@@ -288,65 +291,10 @@ size_t decode_workspace_bytes(long long B, long long L, long long D, int splits)
     return (size_t)(B * NT * 256 + B * S * 32 + B * S * (D / 16) * 256) * 4;
 }
 
-// this lane's horizon: the last key its query (column c16 of the MFMA tiles) sees
-__device__ __forceinline__ long long dec_horizon(const DecodeArgs& g, long long L, long long qrow) {
-    return g.causal ? L - g.M + qrow : L - 1;
-}
-
 // Sliding window: the first key this lane's query sees (kvis its horizon), and the row's first visible pair and tile -- the first key
 // ANY of the row's M queries sees is max(0, L - M - W + 1), that of query 0 (scalar: L is).  An empty row (L = 0) gives 0.
 __device__ __forceinline__ long long dec_window_lo(const DecodeArgs& g, long long kvis) { return max(kvis - g.W + 1, 0ll); }
 __device__ __forceinline__ long long dec_window_first(const DecodeArgs& g, long long L) { return max(L - g.M - g.W + 1, 0ll); }
-
-// the keys row b holds.  Ragged: its own length, one scalar load a workgroup, never above max_length (= g.L: the partition and the
-// workspace strides are made for that); a row shorter than its M queries -- an empty slot, a finished sequence -- counts as 0
-// keys: every split of it is empty and its output is zeros.
-template <bool RG>
-__device__ __forceinline__ long long dec_length(const DecodeArgs& g, long long b) {
-    if constexpr (RG) {
-        const long long L = min((long long)max(__builtin_amdgcn_readfirstlane(g.lengths[b]), 0), g.L);
-        return L < g.M ? 0 : L;
-    } else {
-        return g.L;
-    }
-}
-
-// Column c16 of the MFMA tiles -> (query row of q / out, query).  GQ = false: row y, query min(c16, M - 1).  GQ = true: launch row y
-// serves the gw query rows y gw .. y gw + gw - 1, column c16 < gw M is head c16 / M, query c16 % M; the columns behind repeat the
-// last real one (and store nothing: dec_real).
-template <bool GQ>
-__device__ __forceinline__ void dec_column(const DecodeArgs& g, long long y, int c16, long long& row, long long& qrow) {
-    if constexpr (GQ) {
-        const int M = (int)g.M, col = min(c16, g.gw * M - 1), h = col / M;
-        row = y * g.gw + h;
-        qrow = col - h * M;
-    } else {
-        row = y;
-        qrow = min((long long)c16, g.M - 1);
-    }
-}
-template <bool GQ>
-__device__ __forceinline__ bool dec_real(const DecodeArgs& g, int c16) {
-    if constexpr (GQ) return c16 < g.gw * (int)g.M;
-    else return c16 < g.M;
-}
-// where a REAL column c16 of launch row y stores its output row
-template <bool GQ>
-__device__ __forceinline__ float* dec_out(const DecodeArgs& g, long long y, int c16) {
-    if constexpr (GQ) {
-        long long row, qrow;
-        dec_column<true>(g, y, c16, row, qrow);
-        return g.out + row * g.osb + qrow * g.osm;
-    } else {
-        return g.out + y * g.osb + c16 * g.osm;
-    }
-}
-// the cache row of launch row y (scalar)
-template <bool GQ>
-__device__ __forceinline__ long long dec_cache_row(const DecodeArgs& g, long long y) {
-    if constexpr (GQ) return (long long)((unsigned)y / (unsigned)g.rpc);
-    else return y;
-}
 
 template <int DC, bool RG, bool GQ, bool PG, bool WN = false>
 __global__ __launch_bounds__(256) void decode_scores_kernel(const QuantArgs aq, const DecodeArgs g) {
@@ -638,11 +586,14 @@ int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const 
     }
 #undef MI355Q_DECODE_GO
 #undef MI355Q_DECODE_GO2
-    if (g.S > 1) {
-        if (G) hipLaunchKernelGGL(decode_sum_kernel<true>, dim3((unsigned)rows), dim3(256), 0, st, g);
-        else hipLaunchKernelGGL(decode_sum_kernel<false>, dim3((unsigned)rows), dim3(256), 0, st, g);
-    }
+    launch_decode_sum(g, G != 0, rows, st);
     return (int)hipGetLastError();
+}
+
+void launch_decode_sum(const DecodeArgs& g, bool grouped, long long rows, hipStream_t st) {
+    if (g.S <= 1) return;
+    if (grouped) hipLaunchKernelGGL(decode_sum_kernel<true>, dim3((unsigned)rows), dim3(256), 0, st, g);
+    else hipLaunchKernelGGL(decode_sum_kernel<false>, dim3((unsigned)rows), dim3(256), 0, st, g);
 }
 
 }  // namespace mi355q

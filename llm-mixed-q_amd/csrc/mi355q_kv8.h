@@ -1,0 +1,73 @@
+// The int8-mantissa block_fp KV cache (mi355q_kv8.hip): the cache of mi355q_decode.h with every quantised value stored as what it is
+// -- a signed mantissa of at most 8 bits and a power of two that the 16 values of its block share -- instead of as bf16: 1 + 1/16
+// bytes a value, 17/32 of the bf16 cache's K and V bytes and decode traffic.  No arithmetic changes: the kernels rebuild the bf16
+// fragment the MFMA consumes in registers, and every fragment halfword is the bf16 cache's, bit for bit (one stated deviation below).
+//
+// Layout, per b = batch x head, capacity C keys (C % 16 == 0), head_dim D (D % 32 == 0, D <= 128).  A PIECE is 544 bytes: the 512
+// mantissa bytes of one MFMA operand -- lane l's 8 slots at bytes 8 l .. 8 l + 7, the lane and slot order of mi355q_decode.h -- and
+// behind them the 32 shared-exponent bytes of the piece's 32 blocks, as biased codes p + exponent_bias (what QuantArgs.code holds):
+//   k8  [B][C / 16][D / 32][544]     piece (b, key tile t, chunk c): lane (key 16 t + lane % 16, g = lane / 16) holds d = 32 c + 8 g + j
+//                                    in slot j.  A block is the tile's 16 keys at one d; the exponent of d = 32 c + i is byte 512 + i,
+//                                    so the 8 exponents a lane needs (8 different d) are ONE 8-byte load at 512 + 8 g, the same
+//                                    address for the 16 lanes of a group.  Keys the cache does not hold yet: mantissa 0.
+//   v8  [B][ceil(C / 32)][D / 16][544]   piece (b, key pair s, dt): lane (d = 16 dt + lane % 16, g = lane / 16) holds key
+//                                    32 s + 16 (j / 4) + 4 g + (j & 3) in slot j.  A block is 16 d of one key; the exponent of the key
+//                                    in slot j of group g is byte 512 + 8 g + j -- slot order, not key order -- so a lane's 8
+//                                    exponents (8 keys) are again ONE 8-byte load at 512 + 8 g.  The storage starts out ZEROED: a
+//                                    slot no key has reached is mantissa 0 under any exponent byte, a finite 0 for the probability
+//                                    of exactly 0 it meets; stale bytes of an earlier sequence rebuild to finite values as well.
+//   stage [B][16][D] fp32            the open key tile's rows, exactly as in mi355q_decode.h (shared code: launch_kv_stage_ragged)
+// Pieces are 32-byte aligned, a lane's mantissa load 8-byte aligned.  Every address is formed from (b, t < C / 16, c) or
+// (b, s < ceil(C / 32), dt): keys at or behind C are dropped by the append as in the bf16 cache.
+//
+// The rebuild: fragment halfword = pack_bf16(ldexpf((float)m, code - exponent_bias - mbits)), mbits = width - 1.  kv_store_block of
+// mi355q_decode.hip packs copysign(ldexp(|m|, p - mbits), x) + 0 of the SAME integer |m| <= 2^mbits - 1 and the same p: the same fp32
+// value, hence the same halfword -- also where p sits at a clamp end of the exponent range, and where the product is subnormal or
+// rounds in bf16 (both go through the one conversion).  A mantissa that rounds to 0 is +0 on both sides.  Widths: |m| <= 127 needs
+// width <= 8 of the CACHED operands (the y side of qk_params and of pv_params); Q and P, which are not stored, keep 2 .. 9.
+// ONE DEVIATION: at_quant passes 0 < |x| <= 1e-8 through unquantised (the bf16 cache stores it rounded to bf16); a mantissa and a block
+// exponent cannot hold that, and this cache stores 0 there -- a stored value moves by at most 1e-8.  An all-zero block stores zero
+// mantissas and the exponent code of the lowest exponent.
+//
+// Kernels: ragged forms only (a device lengths array; the Python layer supplies one for the uniform call), no pages, no window, no
+// extend.  Pages of whole pieces would carry over unchanged (P >= 32 keeps a piece inside a page).  The decode kernels are the
+// RG = true, PG = false, WN = false kernels of mi355q_decode.hip with another way of getting a K or V fragment into registers; split
+// partition, workspace, Q / P quantisers, softmax, (-inf, 0) paths and the grouped column map are theirs, phase C is theirs unchanged.
+#ifndef MI355Q_KV8_H
+#define MI355Q_KV8_H
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mi355q_decode.h"
+#include "mi355q_internal.h"
+
+namespace mi355q {
+
+constexpr int KV8_PIECE = 544;            // 512 mantissa bytes + 32 exponent bytes
+
+struct Kv8Cache {
+    uint8_t* k8;
+    uint8_t* v8;
+    float* stage;
+    long long B, C;
+    int D;
+};
+inline long long kv8_k_bytes(long long B, long long C, long long D) { return B * (C / 16) * (D / 32) * KV8_PIECE; }
+inline long long kv8_v_bytes(long long B, long long C, long long D) { return B * ((C + 31) / 32) * (D / 16) * KV8_PIECE; }
+
+// row b's first counts[b] (NULL: n) input rows behind ITS length lengths[b]: launch_kv_append_ragged on the packed storage
+// (ak / av: the quantisers of the cached operands, width <= 8)
+int launch_kv8_append(const Kv8Cache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
+                      long long kst, long long vsb, long long vst, const int32_t* lengths, const int32_t* counts, long long n,
+                      hipStream_t st);
+// the cache's values, as the decode kernels rebuild them, back as fp32 [B, L, D]; zeros behind row b's lengths[b]
+int launch_kv8_decode_fp32(const Kv8Cache& c, const QuantArgs& ak, const QuantArgs& av, float* k_out, float* v_out, long long L,
+                           const int32_t* lengths, hipStream_t st);
+// launch_bfp_attention_decode's ragged forms on the packed cache: L = max_length, G >= 1 the grouped form, G == 0 one query row a
+// cache row; workspace and splits as there
+int launch_bfp_attention_decode_kv8(const QuantArgs& aq, const QuantArgs& ap, const QuantArgs& ak, const QuantArgs& av, const Kv8Cache& c,
+                                    const float* q, float* out, void* workspace, long long M, long long L, int causal, float q_scale,
+                                    float scale_div, const long long* strides, int splits, hipStream_t st, const int32_t* lengths, int G);
+
+}  // namespace mi355q
+#endif

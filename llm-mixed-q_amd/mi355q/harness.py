@@ -719,6 +719,29 @@ class PagedDecodeState(DecodeState):
                                 num_pages=rows * max_pages if self.num_pages is None else self.num_pages)
 
 
+class PackedDecodeState(DecodeState):
+    """DecodeState(model, batch, capacity, mode) on ops.PackedKVCache: every layer's K and V as int8 mantissas with one exponent byte
+    per block of 16, 17/32 of the cache bytes and of a decode step's K / V traffic.  The numbers are DecodeState's, bit for bit
+    (ops.PackedKVCache names the one exception, inputs of magnitude <= 1e-8).  What the packed cache has no kernel for is refused
+    here, by name: extend=True (chunked prefill), a sliding-window model, and mode "fp32", which has no quantised cache at all.  A
+    prompt runs the prefill attention function on its fp32 K / V, as in DecodeState: it reads no cache."""
+
+    def __init__(self, model, batch: int, capacity: int, mode: str = "block_fp", extend: bool = False):
+        if mode != "block_fp":
+            raise ValueError(f"PackedDecodeState: mode {mode!r}: the int8-mantissa cache is a block_fp cache (mode 'fp32' keeps fp32 K / V)")
+        if extend:
+            raise NotImplementedError("PackedDecodeState: extend=True: no extend (chunked prefill) kernel reads the int8-mantissa cache")
+        if getattr(model.cfg, "sliding_window", None) is not None:
+            raise NotImplementedError("PackedDecodeState: a sliding-window model: no windowed kernel reads the int8-mantissa cache")
+        super().__init__(model, batch, capacity, mode, extend)
+
+    def _new_cache(self, rows, hd, qk, pv, dev):
+        try:
+            return ops.PackedKVCache(rows, self.capacity, hd, qk, pv, dev)
+        except ValueError as e:
+            raise ValueError(f"PackedDecodeState: {e}") from None
+
+
 def _forward_cached(model, input_ids, labels, state: DecodeState, counts=None):
     if labels is not None:
         raise ValueError("forward(cache=...): labels belong to the full forward")
@@ -765,27 +788,36 @@ def _forward_cached(model, input_ids, labels, state: DecodeState, counts=None):
     return fp32_linear(x, model.lm_head, model.mi355q_lm_head), None
 
 
-def _new_state(model, batch, capacity, mode, extend, page_size, num_pages):
+def _new_state(model, batch, capacity, mode, extend, page_size, num_pages, kv_storage=None):
+    if kv_storage is not None:
+        if kv_storage != "int8":
+            raise ValueError(f"generate: kv_storage = {kv_storage!r} is neither None (bf16 values) nor 'int8' (mantissa bytes)")
+        if page_size is not None or num_pages is not None:
+            raise NotImplementedError("generate: kv_storage='int8' with page_size / num_pages: the int8-mantissa cache is not paged")
+        return PackedDecodeState(model, batch, capacity, mode, extend=extend)
     if page_size is None and num_pages is None:
         return DecodeState(model, batch, capacity, mode, extend=extend)
     return PagedDecodeState(model, batch, capacity, mode, extend=extend, page_size=page_size, num_pages=num_pages)
 
 
 @torch.no_grad()
-def generate(model, prompt_ids, new_tokens: int, mode: str = "block_fp", chunk: int = None, page_size: int = None, num_pages: int = None):
+def generate(model, prompt_ids, new_tokens: int, mode: str = "block_fp", chunk: int = None, page_size: int = None, num_pages: int = None,
+             kv_storage: str = None):
     """greedy decoding: the prompt in one cached call, then one token a call.  Returns (ids [B, prompt + new_tokens], logits
     [B, new_tokens, vocab]: the logits each new token was picked from).
     `prompt_ids` may be a list of 1-D id tensors of DIFFERENT lengths (mode "block_fp"): one ragged prefill, then one token a row a
     call, every sequence decoded as if it were alone; returns (a list of id tensors [len_b + new_tokens], logits as above).
     `chunk`: chunked prefill -- the prompt goes in calls of at most `chunk` tokens through a state with extend=True; for a list of
     prompts every call gives each row whatever it has left, up to `chunk`.
-    `page_size` / `num_pages`: paged caches (PagedDecodeState); the tokens and logits are those of the contiguous caches."""
+    `page_size` / `num_pages`: paged caches (PagedDecodeState); the tokens and logits are those of the contiguous caches.
+    `kv_storage`: None keeps the caches' values as bf16; "int8" stores mantissa bytes (PackedDecodeState: 17/32 of the cache bytes, the
+    same tokens and logits; not with `chunk`, pages or a sliding-window model)."""
     if chunk is not None and int(chunk) < 1:
         raise ValueError(f"generate: chunk = {chunk} < 1")
     if isinstance(prompt_ids, (list, tuple)):
         lens = [int(p.numel()) for p in prompt_ids]
         B, dev = len(lens), prompt_ids[0].device
-        state = _new_state(model, B, max(lens) + new_tokens, mode, chunk is not None, page_size, num_pages)
+        state = _new_state(model, B, max(lens) + new_tokens, mode, chunk is not None, page_size, num_pages, kv_storage)
         if chunk is None:
             ids = torch.zeros(B, max(lens), dtype=prompt_ids[0].dtype, device=dev)
             for b, p in enumerate(prompt_ids):
@@ -814,7 +846,7 @@ def generate(model, prompt_ids, new_tokens: int, mode: str = "block_fp", chunk: 
                 logits = model(tok, cache=state, counts=[1] * B)[0][:, -1]
         return rows, torch.stack(steps, dim=1)
     B, T = prompt_ids.shape
-    state = _new_state(model, B, T + new_tokens, mode, chunk is not None, page_size, num_pages)
+    state = _new_state(model, B, T + new_tokens, mode, chunk is not None, page_size, num_pages, kv_storage)
     ids, steps = prompt_ids, []
     step = int(chunk) if chunk is not None else max(T, 1)
     for t0 in range(0, max(T, 1), step):

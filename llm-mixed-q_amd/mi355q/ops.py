@@ -1801,6 +1801,107 @@ class PagedKVCache:
         return k, v
 
 
+class PackedKVCache:
+    """`KVCache` with every quantised value stored as what it is -- a signed mantissa byte, and one shared-exponent byte per block of
+    16 -- instead of as bf16: 1 + 1/16 bytes a value, 17/32 of KVCache's K and V bytes and of a decode step's K / V traffic (layout:
+    csrc/mi355q_kv8.h).  Same constructor arguments and the same append / reset / dequantised / length / lengths= / counts= /
+    max_length= contract; a class of its own, NOT a KVCache: only bfp_attention_decode's packed route reads it (no window, no pages,
+    no bfp_attention_extend).  The decode kernels rebuild the bf16 fragments in registers, so dequantised() and
+    bfp_attention_decode give KVCache's bits for the same keys (decode: with the same `splits`), with one exception: an input
+    0 < |x| <= 1e-8, which KVCache passes through unquantised, is stored as 0.
+    The CACHED operands -- the y side of qk_params and of pv_params -- must have width <= 8, so that |mantissa| <= 127 fits a byte;
+    Q and P (the x sides), which are not stored, keep 2 .. 9.  The kernels exist in the ragged form only: a call without `lengths`
+    brings every row's `length` as a device tensor."""
+
+    def __init__(self, B: int, capacity: int, D: int, qk_params, pv_params, device):
+        import ctypes
+        B, capacity, D = int(B), int(capacity), int(D)
+        if not 1 <= B <= 65535:
+            raise ValueError(f"PackedKVCache: B = {B} outside 1 .. 65535")
+        if D < 32 or D % 32 != 0 or D > ATTENTION_MAX_HEAD_DIM:
+            raise ValueError(f"PackedKVCache: head_dim {D} is not a multiple of 32 up to {ATTENTION_MAX_HEAD_DIM}")
+        if capacity < 16 or capacity % 16 != 0:
+            raise ValueError(f"PackedKVCache: capacity {capacity} is not a positive multiple of 16")
+        self.qk_params = _decode_params(qk_params, "PackedKVCache qk_params")
+        self.pv_params = _decode_params(pv_params, "PackedKVCache pv_params")
+        for name, p in (("qk_params (K)", self.qk_params), ("pv_params (V)", self.pv_params)):
+            if int(p[3]) > 8:
+                raise ValueError(f"PackedKVCache {name}: cached operand of width {p[3]} > 8: its mantissa, up to 2^{int(p[3]) - 1} - 1 in "
+                                 "magnitude, does not fit the int8 the cache stores (KVCache takes width 9)")
+        self.B, self.capacity, self.D, self.device = B, capacity, D, torch.device(device)
+        self.length = 0
+        nb = [ctypes.c_int64(0) for _ in range(3)]
+        _lib.check(_lib.load_library().mi355q_bfp_kv8_cache_bytes(B, capacity, D, *[ctypes.addressof(n) for n in nb]), "mi355q_bfp_kv8_cache_bytes")
+        # (zeroed: a V slot no key has reached is mantissa 0, a finite 0 under any exponent byte, for the probability of exactly 0 it meets)
+        self.k8, self.v8, self.stage = (torch.zeros(n.value, dtype=torch.uint8, device=self.device) for n in nb)
+        self._pa = (ctypes.c_int32 * 6)(*[_default_bias(p) if i % 3 == 2 else int(p) for i, p in enumerate(self.qk_params)])
+        self._pb = (ctypes.c_int32 * 6)(*[_default_bias(p) if i % 3 == 2 else int(p) for i, p in enumerate(self.pv_params)])
+
+    def reset(self) -> None:
+        # nothing to clear, as in KVCache.reset: stale mantissa and exponent bytes rebuild to finite values
+        self.length = 0
+
+    _rows = KVCache._rows
+
+    def append(self, k: torch.Tensor, v: torch.Tensor, *, lengths: torch.Tensor = None, counts: torch.Tensor = None,
+               max_length: int = None) -> None:
+        """KVCache.append on the packed storage: n >= 1 new fp32 rows k, v [B, n, D] (or [1, H, n, D] head views) become keys
+        length .. length + n - 1, or -- ragged -- row b's first counts[b] rows become its keys lengths[b] .. (lengths BEFORE the call)."""
+        import ctypes
+        k, v = self._rows(k, "k"), self._rows(v, "v")
+        n = k.shape[-2]
+        if v.shape[-2] != n or n < 1:
+            raise ValueError(f"PackedKVCache.append: {n} rows of k, {v.shape[-2]} of v (at least one, and as many of each)")
+        ragged = lengths is not None
+        if ragged:
+            why = _ragged_check(self, lengths, counts, max_length, n, "append")
+            if why is not None:
+                raise ValueError(f"PackedKVCache.append: {why}")
+        elif counts is not None or max_length is not None:
+            raise ValueError("PackedKVCache.append: counts / max_length belong to a ragged append (lengths=)")
+        elif self.length + n > self.capacity:
+            raise ValueError(f"PackedKVCache.append: {self.length} + {n} keys exceed the capacity {self.capacity}")
+        for t in (k, v):
+            if not t.is_cuda or t.dtype != torch.float32 or t.device != self.device:
+                raise ValueError(f"PackedKVCache.append: fp32 tensors on {self.device} only (got {t.dtype} on {t.device}); there is no CPU fallback")
+        k3, ksb, kst = _as_heads_view(k)
+        v3, vsb, vst = _as_heads_view(v)
+        strides = (ctypes.c_int64 * 4)(ksb, kst, vsb, vst)
+        if not ragged:      # (the kernels read lengths from the device: every row at `length`)
+            lengths, max_length = _window_lengths(self, None, None)
+        with _on_device(self.device):
+            rc = _lib.load_library().mi355q_bfp_kv8_append(_ptr(self.k8), _ptr(self.v8), _ptr(self.stage), _ptr(k3), _ptr(v3), _ptr(lengths),
+                                                           _ptr(counts), self.B, self.capacity, self.D, n, int(max_length),
+                                                           ctypes.addressof(self._pa), ctypes.addressof(self._pb), ctypes.addressof(strides),
+                                                           _stream_ptr(self.device))
+        _lib.check(rc, "mi355q_bfp_kv8_append")
+        if not ragged:
+            self.length += n
+
+    def dequantised(self, lengths: torch.Tensor = None, max_length: int = None):
+        """the cache's K and V as the decode kernels rebuild them, fp32 [B, length, D] (tests, debugging); ragged: [B, max_length, D],
+        zeros behind each row's lengths[b]"""
+        import ctypes
+        if lengths is not None:
+            why = _ragged_check(self, lengths, None, max_length, 0, "dequantised")
+            if why is not None:
+                raise ValueError(f"PackedKVCache.dequantised: {why}")
+        elif max_length is not None:
+            raise ValueError("PackedKVCache.dequantised: max_length belongs to a ragged call (lengths=)")
+        if not self.k8.is_cuda:
+            raise ValueError("PackedKVCache.dequantised: the cache is not on a GPU; there is no CPU fallback")
+        if lengths is None:
+            lengths, max_length = _window_lengths(self, None, None)
+        k = torch.empty(self.B, int(max_length), self.D, dtype=torch.float32, device=self.device)
+        v = torch.empty_like(k)
+        with _on_device(self.device):
+            rc = _lib.load_library().mi355q_bfp_kv8_decode_fp32(_ptr(self.k8), _ptr(self.v8), _ptr(lengths), _ptr(k), _ptr(v), self.B,
+                                                                self.capacity, self.D, int(max_length), ctypes.addressof(self._pa),
+                                                                ctypes.addressof(self._pb), _stream_ptr(self.device))
+        _lib.check(rc, "mi355q_bfp_kv8_decode_fp32")
+        return k, v
+
+
 _PAGED_NEEDS_LENGTHS = "a paged cache is always addressed in the ragged form: lengths= and max_length= (there is no uniform paged launch)"
 
 
@@ -1835,6 +1936,11 @@ def _decode_check(q, cache, splits=None, lengths=None, max_length=None, group=1,
         return why
     if isinstance(cache, PagedKVCache) and lengths is None:
         return _PAGED_NEEDS_LENGTHS
+    return _decode_call_check(q, cache, splits, lengths, max_length, group)
+
+
+def _decode_call_check(q, cache, splits, lengths, max_length, group):
+    """_decode_check behind the cache's kind: q against the cache's shape, the group, the ragged arguments, splits, the device"""
     if not isinstance(q, torch.Tensor) or q.ndim < 3:
         return "q must be a tensor [..., M, D]"
     M, D = q.shape[-2:]
@@ -1887,8 +1993,12 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     below every query's window are not read, and the splits cover span = min(max_length, W + M - 1 + 31) keys from each row's first
     visible key pair on: the default is decode_splits(rows, span, D), and work and workspace follow W, not the length.
     W >= max_length (cache.length) gives the bits of window=None.  A paged cache may have trimmed the pages behind the window
-    (PagedKVCache.trim)."""
+    (PagedKVCache.trim).
+    `cache` may be a PackedKVCache (int8 mantissas, 17/32 of the K / V bytes): the same keywords with the same meaning and the bits
+    of the same call on a KVCache holding the same keys; `window` is refused (NotImplementedError), and there is no paged form."""
     import ctypes
+    if isinstance(cache, PackedKVCache):
+        return _decode_packed(q, cache, causal, scale_div, q_scale, token_major, splits, lengths, max_length, group, window)
     why = _decode_check(q, cache, splits, lengths, max_length, group, causal=causal, window=window)
     if why is not None:
         raise ValueError(f"mi355q.bfp_attention_decode: {why}")
@@ -1961,6 +2071,48 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     return out
 
 
+def _decode_packed(q, cache, causal, scale_div, q_scale, token_major, splits, lengths, max_length, group, window):
+    """bfp_attention_decode on a PackedKVCache: one entry point for every form it has -- ragged (the uniform call brings the cache's
+    length as a device tensor), grouped or not"""
+    import ctypes
+    if window is not None:
+        raise NotImplementedError("mi355q.bfp_attention_decode: no sliding-window kernel reads a PackedKVCache (int8 mantissas); "
+                                  "window= needs a KVCache or a PagedKVCache")
+    why = _decode_call_check(q, cache, splits, lengths, max_length, group)
+    if why is not None:
+        raise ValueError(f"mi355q.bfp_attention_decode: {why}")
+    M, D = q.shape[-2:]
+    q3, qsb, qsm = _as_heads_view(q)
+    B, C = cache.B, cache.capacity
+    if token_major and q.ndim == 4 and q.shape[0] == 1:
+        H = q.shape[1]
+        out = torch.empty(1, M, H, D, dtype=torch.float32, device=q.device).permute(0, 2, 1, 3)
+        osb, osm = D, H * D
+    else:
+        out = torch.empty(*q.shape, dtype=torch.float32, device=q.device)
+        osb, osm = M * D, D
+    sp = _stream_ptr(q.device)
+    R = B if group == 1 else B * group // decode_group_width(group, M)       # launch rows: the workspace is theirs
+    if R > 65535:
+        raise ValueError(f"mi355q.bfp_attention_decode: {R} launch rows (cache.B * group / decode_group_width) exceed 65535")
+    key = (q.device.index, sp, R, C, D)
+    ws = _DECODE_WS.get(key)
+    if ws is None:      # (the bf16 decode's workspace: it holds scores, statistics and partial outputs, no K / V)
+        ws = _DECODE_WS.put(key, torch.empty(R * (C // 16) * 1024 + R * _DECODE_MAX_SPLITS * (128 + (D // 16) * 1024), dtype=torch.uint8,
+                                             device=q.device))
+    strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
+    if lengths is None:
+        lengths, max_length = _window_lengths(cache, None, None)
+    with _on_device(q.device):
+        rc = _lib.load_library().mi355q_bfp_attention_decode_kv8(_ptr(q3), _ptr(cache.k8), _ptr(cache.v8), group, _ptr(lengths),
+                                                                 int(bool(causal)), float(q_scale) if q_scale else 0.0,
+                                                                 float(scale_div) if scale_div else 0.0, _ptr(out), _ptr(ws), B, M,
+                                                                 int(max_length), C, D, ctypes.addressof(cache._pa),
+                                                                 ctypes.addressof(cache._pb), ctypes.addressof(strides), int(splits or 0), sp)
+    _lib.check(rc, "mi355q_bfp_attention_decode_kv8")
+    return out
+
+
 def _extend_check(q, cache, lengths=None, counts=None, max_length=None, group=1, *, causal=True, window=None):
     """the reasons bfp_attention_extend declines (q, cache), None when it takes them; nothing here touches the device"""
     if not isinstance(cache, (KVCache, PagedKVCache)):
@@ -2014,6 +2166,9 @@ def bfp_attention_extend(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     Sliding window (`window` = W >= 1, causal only) as bfp_attention_decode: row b's query i, at p = lengths[b] - counts[b] + i, sees
     keys max(0, p - W + 1) .. p; a block of 64 queries walks the keys from the 32-key step of its first query's lower bound on."""
     import ctypes
+    if isinstance(cache, PackedKVCache):
+        raise NotImplementedError("mi355q.bfp_attention_extend: no extend kernel reads a PackedKVCache (int8 mantissas); chunked prefill "
+                                  "needs a KVCache or a PagedKVCache")
     why = _extend_check(q, cache, lengths, counts, max_length, group, causal=causal, window=window)
     if why is not None:
         raise ValueError(f"mi355q.bfp_attention_extend: {why}")

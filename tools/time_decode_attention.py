@@ -16,6 +16,13 @@ sized for the SMALLEST reader of a case, so every route's window reads more than
 second build of libmi355q.so (an earlier commit's) whose uniform route is replayed in the same interleaving, through the C ABI.
 
     python tools/time_decode_attention.py --ragged [--baseline-lib PATH] --out profiles/decode_ragged.jsonl
+
+--packed: the same step (append of one key a row + decode, D = 128, M = 1) on ops.PackedKVCache -- int8 mantissas, 17/32 of the K / V
+bytes -- against ops.KVCache holding the same keys, at the shapes of profiles/decode_gqa.jsonl: 8 KV heads, batch 1 / 8 / 32 at
+L = 512 / 2048 / 8192, and 4 query heads a KV head at batch 8.  Both routes run their ragged form on the same device lengths (the
+packed kernels have no other); the sets are sized for the packed cache, the smaller reader.
+
+    python tools/time_decode_attention.py --packed --out profiles/decode_kv8.jsonl
 """
 import argparse
 import json
@@ -140,6 +147,70 @@ def ragged(args):
         Path(args.out).write_text("".join(json.dumps(l) + "\n" for l in lines))
 
 
+def packed(args):
+    import torch
+    from mi355q import ops
+    dev, D, HKV = "cuda:0", 128, 8
+    lines = []
+    stream = torch.cuda.Stream()
+    for batch, G in ((1, 1), (8, 1), (32, 1), (8, 4)):
+        B = batch * HKV
+        for L in (512, 2048, 8192):
+            made = {"packed": ops.PackedKVCache(B, L, D, PAR, PAR, dev), "bf16": ops.KVCache(B, L, D, PAR, PAR, dev)}
+            nbytes = {r: c.kq.numel() + c.vq.numel() if r == "bf16" else c.k8.numel() + c.v8.numel() for r, c in made.items()}
+            n_sets = int(CACHE_BYTES // nbytes["packed"]) + 2
+            calls = max(args.calls, n_sets)
+            g = torch.Generator(device=dev).manual_seed(L + B + G)
+            before, after = (torch.full((B,), n, dtype=torch.int32, device=dev) for n in (L - 1, L))
+            zero = torch.zeros(B, dtype=torch.int32, device=dev)
+            sets = []
+            for i in range(n_sets):
+                k, v = (torch.randn(B, L, D, device=dev, generator=g) for _ in range(2))
+                caches = made if i == 0 else {"packed": ops.PackedKVCache(B, L, D, PAR, PAR, dev), "bf16": ops.KVCache(B, L, D, PAR, PAR, dev)}
+                for c in caches.values():
+                    c.append(k, v, lengths=zero, max_length=0)
+                sets.append((k[:, L - 1:].clone(), v[:, L - 1:].clone(), caches))     # (the step's own row goes in again on every step)
+                del k, v
+            q = torch.randn(B * G, 1, D, device=dev, generator=g)
+            gq = dict(group=G) if G > 1 else {}
+
+            def step(route, i):
+                kn, vn, caches = sets[i % n_sets]
+                caches[route].append(kn, vn, lengths=before, max_length=L - 1)
+                return ops.bfp_attention_decode(q, caches[route], causal=True, scale_div=math.sqrt(D), lengths=after, max_length=L, **gq)
+
+            same = all(torch.equal(step("packed", i), step("bf16", i)) for i in range(min(n_sets, 2)))
+            graphs = {}
+            for route in ("bf16", "packed"):
+                stream.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(stream):
+                    for i in range(n_sets):
+                        step(route, i)
+                torch.cuda.current_stream().wait_stream(stream)
+                torch.cuda.synchronize()
+                gr = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gr, stream=stream):
+                    for i in range(calls):
+                        step(route, i)
+                graphs[route] = gr
+            times = _replay(graphs, args.repeats, calls)
+            R = B if G == 1 else B * G // ops.decode_group_width(G, 1)
+            line = dict(kernel="decode", form="ragged", Hkv=HKV, batch=batch, G=G, D=D, M=1, L=L, splits=ops.decode_splits(R, L, D),
+                        cache_MiB_bf16=round(nbytes["bf16"] / 2 ** 20, 2), cache_MiB_packed=round(nbytes["packed"] / 2 ** 20, 2),
+                        sets=n_sets, calls=calls, repeats=args.repeats, same_bits=bool(same),
+                        bf16_us=round(statistics.median(times["bf16"]), 2), bf16_spread_us=round(max(times["bf16"]) - min(times["bf16"]), 2),
+                        packed_us=round(statistics.median(times["packed"]), 2),
+                        packed_spread_us=round(max(times["packed"]) - min(times["packed"]), 2))
+            line["bf16_over_packed"] = round(line["bf16_us"] / line["packed_us"], 2)
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+            del graphs, sets, made
+            torch.cuda.empty_cache()
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text("".join(json.dumps(l) + "\n" for l in lines))
+
+
 def main():
     import torch
     from mi355q import ops
@@ -149,9 +220,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--ragged", action="store_true", help="per-row lengths against the uniform route (module docstring)")
     ap.add_argument("--baseline-lib", default=None, help="--ragged: another build of libmi355q.so whose uniform route is timed alongside")
+    ap.add_argument("--packed", action="store_true", help="ops.PackedKVCache against ops.KVCache at the grouped-query shapes (module docstring)")
     args = ap.parse_args()
     if args.ragged:
         return ragged(args)
+    if args.packed:
+        return packed(args)
     dev, B = "cuda:0", 32
     lines = []
     stream = torch.cuda.Stream()
