@@ -15,6 +15,7 @@
 #include "mi355q_decode.h"
 #include "mi355q_kv8.h"
 #include "mi355q_extend.h"
+#include "mi355q_kv_call.h"
 #include "mi355q_align_row.h"
 
 using namespace mi355q;
@@ -79,11 +80,6 @@ int fill_common(QuantArgs& a, const float* x, float* y, void* workspace, int64_t
     if (x == nullptr) return MI355Q_E_BADARG;
     if ((flags & MI355Q_ZERO_BLOCK_FAST) == 0u && workspace == nullptr) return MI355Q_E_BADARG;
     return 0;
-}
-void set_mantissa(QuantArgs& a, int mbits) {
-    a.shift = std::ldexp(1.0f, mbits);
-    a.inv_shift = std::ldexp(1.0f, -mbits);
-    a.mant_max = a.shift - 1.0f;
 }
 }  // namespace
 
@@ -1006,71 +1002,73 @@ int mi355q_bfp_attention_fused(const float* q, const float* k, const float* v, c
                                 out_bf16_tiled ? &ao : nullptr, q_scale);
 }
 
-// ---- incremental decoding: block_fp KV cache + split-key decode attention (mi355q_decode.hip) ----------------------------
+// ---- the KV cache and the attention that reads it (mi355q_decode.h, mi355q_extend.h, mi355q_kv8.h) ------------------------------
+// Every export below fills a KvCall, has kv_call_check (mi355q_kv_call.h) refuse it or fill what the launchers take, and launches.
+// Uniform, ragged (per-row lengths on the device), grouped (G query rows a cache row), paged (pools of pages and a page table per row),
+// int8 mantissas (kv8) and the sliding window differ in the KV_EXPORTS entry they start from and in the arguments they have.
 namespace {
-// the block_fp quantiser of one operand: {width, exponent width, exponent bias} at pr
-int decode_quant_args(const int32_t* pr, QuantArgs& a) {
-    if (pr[0] < 2 || pr[1] < 1 || pr[1] > 8) return MI355Q_E_BADARG;
-    if (pr[0] > 9) return MI355Q_E_UNSUPPORTED;               // a quantised value must fit bf16's 8 significant bits
-    int bias = pr[2];
-    if (bias == MI355Q_BIAS_DEFAULT) bias = (1 << (pr[1] - 1)) - 1;
-    a.b0 = 1; a.b1 = 16;
-    a.code_bias = bias;
-    a.e_min = -bias;
-    a.e_max = (1 << pr[1]) - 1 - bias;
-    set_mantissa(a, pr[0] - 1);
+hipStream_t hs(void* stream) { return static_cast<hipStream_t>(stream); }
+int sizes(const KvCall& d, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_bytes) {
+    KvChecked c;
+    int rc;
+    if (!kv_call_check(d, c, rc)) return rc;
+    const int64_t rows = d.storage == KV_PAGED ? d.num_pages : d.B, keys = d.storage == KV_PAGED ? d.P : d.C;      // (a page is a cache row of P keys)
+    *k_bytes = d.storage == KV_INT8 ? kv8_k_bytes(rows, keys, d.D) : kv_k_bytes(rows, keys, d.D);
+    *v_bytes = d.storage == KV_INT8 ? kv8_v_bytes(rows, keys, d.D) : kv_v_bytes(rows, keys, d.D);
+    *stage_bytes = kv_stage_bytes(d.B, d.D);
     return 0;
 }
-int decode_cache_shape(int64_t B, int64_t C, int64_t D) {
-    if (B < 1 || C < 1 || D < 1 || B > 65535) return MI355Q_E_BADARG;
-    if (C % 16 != 0 || D % 32 != 0 || D > 128 || C > (1LL << 30)) return MI355Q_E_UNSUPPORTED;
-    return 0;
+int append(const KvCall& d, const float* k, const float* v, void* stream) {
+    KvChecked c;
+    int rc;
+    if (!kv_call_check(d, c, rc)) return rc;
+    if (d.storage == KV_INT8)
+        return launch_kv8_append(c.c8, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.lengths, d.counts, d.n, hs(stream));
+    if (!(d.form & KV_LENGTHS)) return launch_kv_append(c.c, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.L, d.n, hs(stream));
+    return launch_kv_append_ragged(c.c, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.lengths, d.counts, d.n, hs(stream), c.pages);
+}
+int dequantise(const KvCall& d, float* k_out, float* v_out, void* stream) {
+    KvChecked c;
+    int rc;
+    if (!kv_call_check(d, c, rc)) return rc;
+    if (d.storage == KV_INT8) return launch_kv8_decode_fp32(c.c8, c.ak, c.av, k_out, v_out, d.L, d.lengths, hs(stream));
+    return launch_kv_decode_fp32(c.c, k_out, v_out, d.L, hs(stream), d.lengths, c.pages);
+}
+int decode(const KvCall& d, const float* q, float* out, void* workspace, float q_scale, float scale_div, void* stream) {
+    KvChecked c;
+    int rc;
+    if (!kv_call_check(d, c, rc)) return rc;
+    if (d.storage == KV_INT8)
+        return launch_bfp_attention_decode_kv8(c.aq, c.ap, c.ak, c.av, c.c8, q, out, workspace, d.M, d.L, c.causal, q_scale, scale_div, c.strides,
+                                               d.splits, hs(stream), d.lengths, c.G);
+    return launch_bfp_attention_decode(c.aq, c.ap, c.c, q, out, workspace, d.M, d.L, c.causal, q_scale, scale_div, c.strides, d.splits, hs(stream),
+                                       d.lengths, c.G, c.pages, c.window);
+}
+int extend(const KvCall& d, const float* q, float* out, float q_scale, float scale_div, void* stream) {
+    KvChecked c;
+    int rc;
+    if (!kv_call_check(d, c, rc)) return rc;
+    return launch_bfp_attention_extend(c.aq, c.ap, c.c, q, out, d.M, d.L, c.causal, q_scale, scale_div, c.strides, d.lengths, d.counts, hs(stream),
+                                       c.G, c.pages, c.window);
 }
 }  // namespace
 
 int mi355q_bfp_kv_cache_bytes(int64_t B, int64_t C, int64_t D, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_bytes) {
-    if (!k_bytes || !v_bytes || !stage_bytes) return MI355Q_E_BADARG;
-    const int rc = decode_cache_shape(B, C, D);
-    if (rc) return rc;
-    *k_bytes = kv_k_bytes(B, C, D);
-    *v_bytes = kv_v_bytes(B, C, D);
-    *stage_bytes = kv_stage_bytes(B, D);
-    return 0;
+    return sizes(KvCall(KV_EXPORTS[KVX_CACHE_BYTES]).cache(nullptr, nullptr, nullptr, B, C, D).sizes(k_bytes, v_bytes, stage_bytes), k_bytes, v_bytes,
+                 stage_bytes);
 }
 
 int mi355q_bfp_kv_append(void* kq, void* vq, float* stage, const float* k, const float* v, int64_t B, int64_t C, int64_t D,
                          int64_t L, int64_t n, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
                          void* stream) {
-    int rc = decode_cache_shape(B, C, D);
-    if (rc) return rc;
-    if (L < 0 || n < 0 || !qk_params || !pv_params) return MI355Q_E_BADARG;
-    if (L + n > C) return MI355Q_E_UNSUPPORTED;               // (nothing is written)
-    if (n == 0) return 0;
-    if (!kq || !vq || !stage || !k || !v) return MI355Q_E_BADARG;
-    QuantArgs ak{}, av{};
-    if ((rc = decode_quant_args(qk_params + 3, ak)) != 0 || (rc = decode_quant_args(pv_params + 3, av)) != 0) return rc;
-    if ((reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) | reinterpret_cast<uintptr_t>(stage) |
-         reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v)) % 16)
-        return MI355Q_E_ALIGN;
-    long long st4[4] = {n * D, D, n * D, D};
-    if (strides)
-        for (int i = 0; i < 4; ++i) {
-            if (strides[i] % 4) return MI355Q_E_ALIGN;
-            st4[i] = strides[i];
-        }
-    const KvCache c{static_cast<uint16_t*>(kq), static_cast<uint16_t*>(vq), stage, B, C, (int)D};
-    return launch_kv_append(c, ak, av, k, v, st4[0], st4[1], st4[2], st4[3], L, n, static_cast<hipStream_t>(stream));
+    return append(KvCall(KV_EXPORTS[KVX_APPEND]).cache(kq, vq, stage, B, C, D).rows(k, v, n).lens(nullptr, nullptr, L).quant(qk_params, pv_params, strides),
+                  k, v, stream);
 }
 
 int mi355q_bfp_kv_decode_fp32(const void* kq, const void* vq, float* k_out, float* v_out, int64_t B, int64_t C, int64_t D, int64_t L,
                               void* stream) {
-    const int rc = decode_cache_shape(B, C, D);
-    if (rc) return rc;
-    if (L < 0 || L > C) return MI355Q_E_BADARG;
-    if (L == 0) return 0;
-    if (!kq || !vq || !k_out || !v_out) return MI355Q_E_BADARG;
-    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
-    return launch_kv_decode_fp32(c, k_out, v_out, L, static_cast<hipStream_t>(stream));
+    return dequantise(KvCall(KV_EXPORTS[KVX_DECODE_FP32]).cache(kq, vq, nullptr, B, C, D).rows(k_out, v_out, 0).lens(nullptr, nullptr, L), k_out, v_out,
+                      stream);
 }
 
 int mi355q_bfp_attention_decode_splits(int64_t B, int64_t L, int64_t D, int32_t splits) { return decode_splits(B, L, D, splits); }
@@ -1084,233 +1082,79 @@ int mi355q_bfp_attention_decode(const float* q, const void* kq, const void* vq, 
                                 float* out, void* workspace, int64_t B, int64_t M, int64_t L, int64_t C, int64_t D,
                                 const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides, int32_t splits,
                                 void* stream) {
-    if (M < 0 || L < 0 || splits < 0) return MI355Q_E_BADARG;
-    int rc = decode_cache_shape(B, C, D);
-    if (rc) return rc;
-    if (M < 1 || M > 16 || L < M) return MI355Q_E_UNSUPPORTED;      // (the last M <= 16 positions against all L keys)
-    if (L > C || !q || !kq || !vq || !out || !workspace || !qk_params || !pv_params) return MI355Q_E_BADARG;
-    QuantArgs aq{}, ap{};
-    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) |
-         reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) % 16)
-        return MI355Q_E_ALIGN;
-    long long st4[4];
-    if (strides)
-        for (int i = 0; i < 4; ++i) {
-            if (strides[i] % 4) return MI355Q_E_ALIGN;
-            st4[i] = strides[i];
-        }
-    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
-    return launch_bfp_attention_decode(aq, ap, c, q, out, workspace, M, L, causal != 0, q_scale, scale_div, strides ? st4 : nullptr,
-                                       splits, static_cast<hipStream_t>(stream));
+    return decode(KvCall(KV_EXPORTS[KVX_DECODE]).cache(kq, vq, nullptr, B, C, D).lens(nullptr, nullptr, L).query(q, out, workspace, M, 0, causal, 0, splits)
+                      .quant(qk_params, pv_params, strides), q, out, workspace, q_scale, scale_div, stream);
 }
 
-// ---- ragged batches: the same three with per-row lengths on the device (mi355q_decode.h) ---------------------------------
+// ragged batches: per-row lengths on the device
 int mi355q_bfp_kv_append_ragged(void* kq, void* vq, float* stage, const float* k, const float* v, const int32_t* lengths,
                                 const int32_t* counts, int64_t B, int64_t C, int64_t D, int64_t n, int64_t max_length,
                                 const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides, void* stream) {
-    int rc = decode_cache_shape(B, C, D);
-    if (rc) return rc;
-    if (max_length < 0 || n < 0 || !qk_params || !pv_params) return MI355Q_E_BADARG;
-    if (max_length + n > C) return MI355Q_E_UNSUPPORTED;      // (nothing is written)
-    if (n == 0) return 0;
-    if (!kq || !vq || !stage || !k || !v || !lengths) return MI355Q_E_BADARG;
-    QuantArgs ak{}, av{};
-    if ((rc = decode_quant_args(qk_params + 3, ak)) != 0 || (rc = decode_quant_args(pv_params + 3, av)) != 0) return rc;
-    if ((reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) | reinterpret_cast<uintptr_t>(stage) |
-         reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v)) % 16 ||
-        (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(counts)) % 4)
-        return MI355Q_E_ALIGN;
-    long long st4[4] = {n * D, D, n * D, D};
-    if (strides)
-        for (int i = 0; i < 4; ++i) {
-            if (strides[i] % 4) return MI355Q_E_ALIGN;
-            st4[i] = strides[i];
-        }
-    const KvCache c{static_cast<uint16_t*>(kq), static_cast<uint16_t*>(vq), stage, B, C, (int)D};
-    return launch_kv_append_ragged(c, ak, av, k, v, st4[0], st4[1], st4[2], st4[3], lengths, counts, n, static_cast<hipStream_t>(stream));
+    return append(KvCall(KV_EXPORTS[KVX_APPEND_RAGGED]).cache(kq, vq, stage, B, C, D).rows(k, v, n).lens(lengths, counts, max_length)
+                      .quant(qk_params, pv_params, strides), k, v, stream);
 }
 
 int mi355q_bfp_kv_decode_fp32_ragged(const void* kq, const void* vq, const int32_t* lengths, float* k_out, float* v_out, int64_t B,
                                      int64_t C, int64_t D, int64_t max_length, void* stream) {
-    const int rc = decode_cache_shape(B, C, D);
-    if (rc) return rc;
-    if (max_length < 0 || max_length > C) return MI355Q_E_BADARG;
-    if (max_length == 0) return 0;
-    if (!kq || !vq || !k_out || !v_out || !lengths) return MI355Q_E_BADARG;
-    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
-    return launch_kv_decode_fp32(c, k_out, v_out, max_length, static_cast<hipStream_t>(stream), lengths);
+    return dequantise(KvCall(KV_EXPORTS[KVX_DECODE_FP32_RAGGED]).cache(kq, vq, nullptr, B, C, D).rows(k_out, v_out, 0).lens(lengths, nullptr, max_length),
+                      k_out, v_out, stream);
 }
 
 int mi355q_bfp_attention_decode_ragged(const float* q, const void* kq, const void* vq, const int32_t* lengths, int32_t causal,
                                        float q_scale, float scale_div, float* out, void* workspace, int64_t B, int64_t M,
                                        int64_t max_length, int64_t C, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
                                        const int64_t* strides, int32_t splits, void* stream) {
-    if (M < 0 || max_length < 0 || splits < 0) return MI355Q_E_BADARG;
-    int rc = decode_cache_shape(B, C, D);
-    if (rc) return rc;
-    if (M < 1 || M > 16 || max_length < M) return MI355Q_E_UNSUPPORTED;
-    if (max_length > C || !q || !kq || !vq || !lengths || !out || !workspace || !qk_params || !pv_params) return MI355Q_E_BADARG;
-    QuantArgs aq{}, ap{};
-    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) |
-         reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) % 16 || reinterpret_cast<uintptr_t>(lengths) % 4)
-        return MI355Q_E_ALIGN;
-    long long st4[4];
-    if (strides)
-        for (int i = 0; i < 4; ++i) {
-            if (strides[i] % 4) return MI355Q_E_ALIGN;
-            st4[i] = strides[i];
-        }
-    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
-    return launch_bfp_attention_decode(aq, ap, c, q, out, workspace, M, max_length, causal != 0, q_scale, scale_div,
-                                       strides ? st4 : nullptr, splits, static_cast<hipStream_t>(stream), lengths);
+    return decode(KvCall(KV_EXPORTS[KVX_DECODE_RAGGED]).cache(kq, vq, nullptr, B, C, D).lens(lengths, nullptr, max_length)
+                      .query(q, out, workspace, M, 0, causal, 0, splits).quant(qk_params, pv_params, strides), q, out, workspace, q_scale, scale_div, stream);
 }
 
-// ---- chunked prefill: any number of queries per row behind the cache (mi355q_extend.h) ------------------------------------
+// chunked prefill: any number of queries per row behind the cache; lengths == NULL is the uniform form
 int mi355q_bfp_attention_extend(const float* q, const void* kq, const void* vq, const int32_t* lengths, const int32_t* counts,
                                 int32_t causal, float q_scale, float scale_div, float* out, int64_t B, int64_t M, int64_t max_length,
                                 int64_t C, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
                                 void* stream) {
-    if (M < 0 || max_length < 0) return MI355Q_E_BADARG;
-    int rc = decode_cache_shape(B, C, D);
-    if (rc) return rc;
-    if (M < 1 || max_length < M) return MI355Q_E_UNSUPPORTED;
-    if (max_length > C || !q || !kq || !vq || !out || !qk_params || !pv_params || (counts && !lengths)) return MI355Q_E_BADARG;
-    QuantArgs aq{}, ap{};
-    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) |
-         reinterpret_cast<uintptr_t>(out)) % 16 || (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(counts)) % 4)
-        return MI355Q_E_ALIGN;
-    long long st4[4];
-    if (strides)
-        for (int i = 0; i < 4; ++i) {
-            if (strides[i] % 4) return MI355Q_E_ALIGN;
-            st4[i] = strides[i];
-        }
-    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
-    return launch_bfp_attention_extend(aq, ap, c, q, out, M, max_length, causal != 0, q_scale, scale_div, strides ? st4 : nullptr,
-                                       lengths, counts, static_cast<hipStream_t>(stream));
+    return extend(KvCall(KV_EXPORTS[KVX_EXTEND]).cache(kq, vq, nullptr, B, C, D).lens(lengths, counts, max_length).query(q, out, nullptr, M, 0, causal, 0, 0)
+                      .quant(qk_params, pv_params, strides), q, out, q_scale, scale_div, stream);
 }
 
-// ---- grouped queries: G query rows a cache row, query row r on cache row r / G (mi355q_decode.h, mi355q_extend.h) -----------
+// grouped queries: G query rows a cache row, query row r on cache row r / G
 int mi355q_bfp_attention_decode_group_width(int64_t G, int64_t M) { return decode_group_width(G, M); }
 
 int mi355q_bfp_attention_decode_grouped(const float* q, const void* kq, const void* vq, int32_t G, const int32_t* lengths,
                                         int32_t causal, float q_scale, float scale_div, float* out, void* workspace, int64_t B,
                                         int64_t M, int64_t max_length, int64_t C, int64_t D, const int32_t* qk_params,
                                         const int32_t* pv_params, const int64_t* strides, int32_t splits, void* stream) {
-    if (M < 0 || max_length < 0 || splits < 0 || G < 1) return MI355Q_E_BADARG;
-    int rc = decode_cache_shape(B, C, D);
-    if (rc) return rc;
-    if (M < 1 || M > 16 || max_length < M) return MI355Q_E_UNSUPPORTED;
-    if (B * (G / decode_group_width(G, M)) > 65535) return MI355Q_E_UNSUPPORTED;     // (launch rows: the grid's second dimension)
-    if (max_length > C || !q || !kq || !vq || !out || !workspace || !qk_params || !pv_params) return MI355Q_E_BADARG;
-    QuantArgs aq{}, ap{};
-    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) |
-         reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) % 16 || reinterpret_cast<uintptr_t>(lengths) % 4)
-        return MI355Q_E_ALIGN;
-    long long st4[4];
-    if (strides)
-        for (int i = 0; i < 4; ++i) {
-            if (strides[i] % 4) return MI355Q_E_ALIGN;
-            st4[i] = strides[i];
-        }
-    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
-    return launch_bfp_attention_decode(aq, ap, c, q, out, workspace, M, max_length, causal != 0, q_scale, scale_div,
-                                       strides ? st4 : nullptr, splits, static_cast<hipStream_t>(stream), lengths, G);
+    return decode(KvCall(KV_EXPORTS[KVX_DECODE_GROUPED]).cache(kq, vq, nullptr, B, C, D).lens(lengths, nullptr, max_length)
+                      .query(q, out, workspace, M, G, causal, 0, splits).quant(qk_params, pv_params, strides), q, out, workspace, q_scale, scale_div, stream);
 }
 
 int mi355q_bfp_attention_extend_grouped(const float* q, const void* kq, const void* vq, int32_t G, const int32_t* lengths,
                                         const int32_t* counts, int32_t causal, float q_scale, float scale_div, float* out, int64_t B,
                                         int64_t M, int64_t max_length, int64_t C, int64_t D, const int32_t* qk_params,
                                         const int32_t* pv_params, const int64_t* strides, void* stream) {
-    if (M < 0 || max_length < 0 || G < 1) return MI355Q_E_BADARG;
-    int rc = decode_cache_shape(B, C, D);
-    if (rc) return rc;
-    if (M < 1 || max_length < M) return MI355Q_E_UNSUPPORTED;
-    if (max_length > C || !q || !kq || !vq || !out || !qk_params || !pv_params || (counts && !lengths)) return MI355Q_E_BADARG;
-    QuantArgs aq{}, ap{};
-    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) |
-         reinterpret_cast<uintptr_t>(out)) % 16 || (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(counts)) % 4)
-        return MI355Q_E_ALIGN;
-    long long st4[4];
-    if (strides)
-        for (int i = 0; i < 4; ++i) {
-            if (strides[i] % 4) return MI355Q_E_ALIGN;
-            st4[i] = strides[i];
-        }
-    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
-    return launch_bfp_attention_extend(aq, ap, c, q, out, M, max_length, causal != 0, q_scale, scale_div, strides ? st4 : nullptr,
-                                       lengths, counts, static_cast<hipStream_t>(stream), G);
+    return extend(KvCall(KV_EXPORTS[KVX_EXTEND_GROUPED]).cache(kq, vq, nullptr, B, C, D).lens(lengths, counts, max_length)
+                      .query(q, out, nullptr, M, G, causal, 0, 0).quant(qk_params, pv_params, strides), q, out, q_scale, scale_div, stream);
 }
 
-// ---- paged cache: pools of pages and a page table per row (mi355q_decode.h); always the ragged form ---------------------------
-namespace {
-// the pools' shape and the rows' table: BADARG for a page size that is no power of two >= 32; `pg` gets the kernels' view
-int paged_shape(int64_t B, int64_t max_pages, int64_t num_pages, int64_t P, int64_t D, const int32_t* block_table, KvPages* pg) {
-    if (P < 32 || (P & (P - 1)) != 0 || B < 1 || B > 65535 || D < 1 || max_pages < 1 || num_pages < 1) return MI355Q_E_BADARG;
-    if (D % 32 != 0 || D > 128 || P > (1LL << 30) || max_pages > (1LL << 30) / P || num_pages > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
-    if (pg) {
-        int lg = 5;
-        while ((1LL << lg) < P) ++lg;
-        *pg = KvPages{block_table, (int)max_pages, (int)num_pages, lg};
-    }
-    return 0;
-}
-}  // namespace
-
+// paged cache: pools of pages and a page table per row; always the ragged form
 int mi355q_bfp_kv_paged_bytes(int64_t num_pages, int64_t P, int64_t B, int64_t D, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_bytes) {
-    if (!k_bytes || !v_bytes || !stage_bytes) return MI355Q_E_BADARG;
-    const int rc = paged_shape(B, 1, num_pages, P, D, nullptr, nullptr);
-    if (rc) return rc;
-    *k_bytes = kv_k_bytes(num_pages, P, D);                   // (a page is a cache row of P keys; P % 32 == 0: no rounding in V)
-    *v_bytes = kv_v_bytes(num_pages, P, D);
-    *stage_bytes = kv_stage_bytes(B, D);
-    return 0;
+    return sizes(KvCall(KV_EXPORTS[KVX_PAGED_BYTES]).pools(nullptr, nullptr, nullptr, nullptr, B, 0, num_pages, P, D).sizes(k_bytes, v_bytes, stage_bytes),
+                 k_bytes, v_bytes, stage_bytes);
 }
 
 int mi355q_bfp_kv_append_paged(void* kq_pool, void* vq_pool, float* stage, const float* k, const float* v, const int32_t* lengths,
                                const int32_t* counts, const int32_t* block_table, int64_t B, int64_t max_pages, int64_t num_pages,
                                int64_t P, int64_t D, int64_t n, int64_t max_length, const int32_t* qk_params, const int32_t* pv_params,
                                const int64_t* strides, void* stream) {
-    KvPages pg{};
-    int rc = paged_shape(B, max_pages, num_pages, P, D, block_table, &pg);
-    if (rc) return rc;
-    if (max_length < 0 || n < 0 || !qk_params || !pv_params) return MI355Q_E_BADARG;
-    if (max_length + n > max_pages * P) return MI355Q_E_BADARG;  // (nothing is written)
-    if (n == 0) return 0;
-    if (!kq_pool || !vq_pool || !stage || !k || !v || !lengths || !block_table) return MI355Q_E_BADARG;
-    QuantArgs ak{}, av{};
-    if ((rc = decode_quant_args(qk_params + 3, ak)) != 0 || (rc = decode_quant_args(pv_params + 3, av)) != 0) return rc;
-    if ((reinterpret_cast<uintptr_t>(kq_pool) | reinterpret_cast<uintptr_t>(vq_pool) | reinterpret_cast<uintptr_t>(stage) |
-         reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v)) % 16 ||
-        (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(block_table)) % 4)
-        return MI355Q_E_ALIGN;
-    long long st4[4] = {n * D, D, n * D, D};
-    if (strides)
-        for (int i = 0; i < 4; ++i) {
-            if (strides[i] % 4) return MI355Q_E_ALIGN;
-            st4[i] = strides[i];
-        }
-    const KvCache c{static_cast<uint16_t*>(kq_pool), static_cast<uint16_t*>(vq_pool), stage, B, max_pages * P, (int)D};
-    return launch_kv_append_ragged(c, ak, av, k, v, st4[0], st4[1], st4[2], st4[3], lengths, counts, n, static_cast<hipStream_t>(stream), &pg);
+    return append(KvCall(KV_EXPORTS[KVX_APPEND_PAGED]).pools(kq_pool, vq_pool, stage, block_table, B, max_pages, num_pages, P, D).rows(k, v, n)
+                      .lens(lengths, counts, max_length).quant(qk_params, pv_params, strides), k, v, stream);
 }
 
 int mi355q_bfp_kv_decode_fp32_paged(const void* kq_pool, const void* vq_pool, const int32_t* lengths, const int32_t* block_table,
                                     float* k_out, float* v_out, int64_t B, int64_t max_pages, int64_t num_pages, int64_t P, int64_t D,
                                     int64_t max_length, void* stream) {
-    KvPages pg{};
-    const int rc = paged_shape(B, max_pages, num_pages, P, D, block_table, &pg);
-    if (rc) return rc;
-    if (max_length < 0 || max_length > max_pages * P) return MI355Q_E_BADARG;
-    if (max_length == 0) return 0;
-    if (!kq_pool || !vq_pool || !k_out || !v_out || !lengths || !block_table) return MI355Q_E_BADARG;
-    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq_pool)), static_cast<uint16_t*>(const_cast<void*>(vq_pool)), nullptr, B,
-                    max_pages * P, (int)D};
-    return launch_kv_decode_fp32(c, k_out, v_out, max_length, static_cast<hipStream_t>(stream), lengths, &pg);
+    return dequantise(KvCall(KV_EXPORTS[KVX_DECODE_FP32_PAGED]).pools(kq_pool, vq_pool, nullptr, block_table, B, max_pages, num_pages, P, D)
+                          .rows(k_out, v_out, 0).lens(lengths, nullptr, max_length), k_out, v_out, stream);
 }
 
 int mi355q_bfp_attention_decode_paged(const float* q, const void* kq_pool, const void* vq_pool, int32_t G, const int32_t* lengths,
@@ -1318,31 +1162,9 @@ int mi355q_bfp_attention_decode_paged(const float* q, const void* kq_pool, const
                                       void* workspace, int64_t B, int64_t M, int64_t max_length, int64_t max_pages, int64_t num_pages,
                                       int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
                                       int32_t splits, void* stream) {
-    if (M < 0 || max_length < 0 || splits < 0 || G < 0) return MI355Q_E_BADARG;
-    KvPages pg{};
-    int rc = paged_shape(B, max_pages, num_pages, P, D, block_table, &pg);
-    if (rc) return rc;
-    if (max_length > max_pages * P) return MI355Q_E_BADARG;
-    if (M < 1 || M > 16 || max_length < M) return MI355Q_E_UNSUPPORTED;
-    if (G <= 1) G = 0;                                        // (0 or 1: ungrouped)
-    if (G && B * (G / decode_group_width(G, M)) > 65535) return MI355Q_E_UNSUPPORTED;
-    if (!q || !kq_pool || !vq_pool || !lengths || !block_table || !out || !workspace || !qk_params || !pv_params) return MI355Q_E_BADARG;
-    QuantArgs aq{}, ap{};
-    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq_pool) | reinterpret_cast<uintptr_t>(vq_pool) |
-         reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) % 16 ||
-        (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(block_table)) % 4)
-        return MI355Q_E_ALIGN;
-    long long st4[4];
-    if (strides)
-        for (int i = 0; i < 4; ++i) {
-            if (strides[i] % 4) return MI355Q_E_ALIGN;
-            st4[i] = strides[i];
-        }
-    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq_pool)), static_cast<uint16_t*>(const_cast<void*>(vq_pool)), nullptr, B,
-                    max_pages * P, (int)D};
-    return launch_bfp_attention_decode(aq, ap, c, q, out, workspace, M, max_length, causal != 0, q_scale, scale_div,
-                                       strides ? st4 : nullptr, splits, static_cast<hipStream_t>(stream), lengths, G, &pg);
+    return decode(KvCall(KV_EXPORTS[KVX_DECODE_PAGED]).pools(kq_pool, vq_pool, nullptr, block_table, B, max_pages, num_pages, P, D)
+                      .lens(lengths, nullptr, max_length).query(q, out, workspace, M, G, causal, 0, splits).quant(qk_params, pv_params, strides),
+                  q, out, workspace, q_scale, scale_div, stream);
 }
 
 int mi355q_bfp_attention_extend_paged(const float* q, const void* kq_pool, const void* vq_pool, int32_t G, const int32_t* lengths,
@@ -1350,138 +1172,39 @@ int mi355q_bfp_attention_extend_paged(const float* q, const void* kq_pool, const
                                       float* out, int64_t B, int64_t M, int64_t max_length, int64_t max_pages, int64_t num_pages,
                                       int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
                                       void* stream) {
-    if (M < 0 || max_length < 0 || G < 0) return MI355Q_E_BADARG;
-    KvPages pg{};
-    int rc = paged_shape(B, max_pages, num_pages, P, D, block_table, &pg);
-    if (rc) return rc;
-    if (max_length > max_pages * P) return MI355Q_E_BADARG;
-    if (M < 1 || max_length < M) return MI355Q_E_UNSUPPORTED;
-    if (G <= 1) G = 0;
-    if (!q || !kq_pool || !vq_pool || !lengths || !block_table || !out || !qk_params || !pv_params) return MI355Q_E_BADARG;
-    QuantArgs aq{}, ap{};
-    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq_pool) | reinterpret_cast<uintptr_t>(vq_pool) |
-         reinterpret_cast<uintptr_t>(out)) % 16 ||
-        (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(block_table)) % 4)
-        return MI355Q_E_ALIGN;
-    long long st4[4];
-    if (strides)
-        for (int i = 0; i < 4; ++i) {
-            if (strides[i] % 4) return MI355Q_E_ALIGN;
-            st4[i] = strides[i];
-        }
-    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq_pool)), static_cast<uint16_t*>(const_cast<void*>(vq_pool)), nullptr, B,
-                    max_pages * P, (int)D};
-    return launch_bfp_attention_extend(aq, ap, c, q, out, M, max_length, causal != 0, q_scale, scale_div, strides ? st4 : nullptr,
-                                       lengths, counts, static_cast<hipStream_t>(stream), G, &pg);
+    return extend(KvCall(KV_EXPORTS[KVX_EXTEND_PAGED]).pools(kq_pool, vq_pool, nullptr, block_table, B, max_pages, num_pages, P, D)
+                      .lens(lengths, counts, max_length).query(q, out, nullptr, M, G, causal, 0, 0).quant(qk_params, pv_params, strides),
+                  q, out, q_scale, scale_div, stream);
 }
 
-// ---- int8-mantissa cache: mantissa bytes and one exponent byte a block (mi355q_kv8.h); always the ragged form, contiguous -------
-namespace {
-// the quantisers of the CACHED operands (the y side): a mantissa must fit int8
-int kv8_quant_args(const int32_t* qk_params, const int32_t* pv_params, QuantArgs& ak, QuantArgs& av) {
-    int rc;
-    if ((rc = decode_quant_args(qk_params + 3, ak)) != 0 || (rc = decode_quant_args(pv_params + 3, av)) != 0) return rc;
-    return qk_params[3] > 8 || pv_params[3] > 8 ? MI355Q_E_UNSUPPORTED : 0;
-}
-}  // namespace
-
+// int8-mantissa cache: mantissa bytes and one exponent byte a block; always the ragged form, contiguous
 int mi355q_bfp_kv8_cache_bytes(int64_t B, int64_t C, int64_t D, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_bytes) {
-    if (!k_bytes || !v_bytes || !stage_bytes) return MI355Q_E_BADARG;
-    const int rc = decode_cache_shape(B, C, D);
-    if (rc) return rc;
-    *k_bytes = kv8_k_bytes(B, C, D);
-    *v_bytes = kv8_v_bytes(B, C, D);
-    *stage_bytes = kv_stage_bytes(B, D);
-    return 0;
+    return sizes(KvCall(KV_EXPORTS[KVX_KV8_CACHE_BYTES]).cache(nullptr, nullptr, nullptr, B, C, D).sizes(k_bytes, v_bytes, stage_bytes), k_bytes, v_bytes,
+                 stage_bytes);
 }
 
 int mi355q_bfp_kv8_append(void* k8, void* v8, float* stage, const float* k, const float* v, const int32_t* lengths,
                           const int32_t* counts, int64_t B, int64_t C, int64_t D, int64_t n, int64_t max_length,
                           const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides, void* stream) {
-    int rc = decode_cache_shape(B, C, D);
-    if (rc) return rc;
-    if (max_length < 0 || n < 0 || !qk_params || !pv_params) return MI355Q_E_BADARG;
-    if (max_length + n > C) return MI355Q_E_UNSUPPORTED;      // (nothing is written)
-    QuantArgs ak{}, av{};
-    if ((rc = kv8_quant_args(qk_params, pv_params, ak, av)) != 0) return rc;
-    if (n == 0) return 0;
-    if (!k8 || !v8 || !stage || !k || !v || !lengths) return MI355Q_E_BADARG;
-    if ((reinterpret_cast<uintptr_t>(k8) | reinterpret_cast<uintptr_t>(v8) | reinterpret_cast<uintptr_t>(stage) |
-         reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v)) % 16 ||
-        (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(counts)) % 4)
-        return MI355Q_E_ALIGN;
-    long long st4[4] = {n * D, D, n * D, D};
-    if (strides)
-        for (int i = 0; i < 4; ++i) {
-            if (strides[i] % 4) return MI355Q_E_ALIGN;
-            st4[i] = strides[i];
-        }
-    const Kv8Cache c{static_cast<uint8_t*>(k8), static_cast<uint8_t*>(v8), stage, B, C, (int)D};
-    return launch_kv8_append(c, ak, av, k, v, st4[0], st4[1], st4[2], st4[3], lengths, counts, n, static_cast<hipStream_t>(stream));
+    return append(KvCall(KV_EXPORTS[KVX_KV8_APPEND]).cache(k8, v8, stage, B, C, D).rows(k, v, n).lens(lengths, counts, max_length)
+                      .quant(qk_params, pv_params, strides), k, v, stream);
 }
 
 int mi355q_bfp_kv8_decode_fp32(const void* k8, const void* v8, const int32_t* lengths, float* k_out, float* v_out, int64_t B, int64_t C,
                                int64_t D, int64_t max_length, const int32_t* qk_params, const int32_t* pv_params, void* stream) {
-    int rc = decode_cache_shape(B, C, D);
-    if (rc) return rc;
-    if (max_length < 0 || max_length > C || !qk_params || !pv_params) return MI355Q_E_BADARG;
-    QuantArgs ak{}, av{};
-    if ((rc = kv8_quant_args(qk_params, pv_params, ak, av)) != 0) return rc;
-    if (max_length == 0) return 0;
-    if (!k8 || !v8 || !k_out || !v_out || !lengths) return MI355Q_E_BADARG;
-    const Kv8Cache c{static_cast<uint8_t*>(const_cast<void*>(k8)), static_cast<uint8_t*>(const_cast<void*>(v8)), nullptr, B, C, (int)D};
-    return launch_kv8_decode_fp32(c, ak, av, k_out, v_out, max_length, lengths, static_cast<hipStream_t>(stream));
+    return dequantise(KvCall(KV_EXPORTS[KVX_KV8_DECODE_FP32]).cache(k8, v8, nullptr, B, C, D).rows(k_out, v_out, 0).lens(lengths, nullptr, max_length)
+                          .quant(qk_params, pv_params, nullptr), k_out, v_out, stream);
 }
 
 int mi355q_bfp_attention_decode_kv8(const float* q, const void* k8, const void* v8, int32_t G, const int32_t* lengths, int32_t causal,
                                     float q_scale, float scale_div, float* out, void* workspace, int64_t B, int64_t M,
                                     int64_t max_length, int64_t C, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
                                     const int64_t* strides, int32_t splits, void* stream) {
-    if (M < 0 || max_length < 0 || splits < 0 || G < 0) return MI355Q_E_BADARG;
-    int rc = decode_cache_shape(B, C, D);
-    if (rc) return rc;
-    if (M < 1 || M > 16 || max_length < M) return MI355Q_E_UNSUPPORTED;
-    const int group = G > 1 ? G : 0;                          // (0 or 1: one query row a cache row)
-    if (group && B * (group / decode_group_width(group, M)) > 65535) return MI355Q_E_UNSUPPORTED;
-    if (max_length > C || !q || !k8 || !v8 || !lengths || !out || !workspace || !qk_params || !pv_params) return MI355Q_E_BADARG;
-    QuantArgs aq{}, ap{}, ak{}, av{};
-    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0 ||
-        (rc = kv8_quant_args(qk_params, pv_params, ak, av)) != 0)
-        return rc;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k8) | reinterpret_cast<uintptr_t>(v8) |
-         reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) % 16 || reinterpret_cast<uintptr_t>(lengths) % 4)
-        return MI355Q_E_ALIGN;
-    long long st4[4];
-    if (strides)
-        for (int i = 0; i < 4; ++i) {
-            if (strides[i] % 4) return MI355Q_E_ALIGN;
-            st4[i] = strides[i];
-        }
-    const Kv8Cache c{static_cast<uint8_t*>(const_cast<void*>(k8)), static_cast<uint8_t*>(const_cast<void*>(v8)), nullptr, B, C, (int)D};
-    return launch_bfp_attention_decode_kv8(aq, ap, ak, av, c, q, out, workspace, M, max_length, causal != 0, q_scale, scale_div,
-                                           strides ? st4 : nullptr, splits, static_cast<hipStream_t>(stream), lengths, group);
+    return decode(KvCall(KV_EXPORTS[KVX_DECODE_KV8]).cache(k8, v8, nullptr, B, C, D).lens(lengths, nullptr, max_length)
+                      .query(q, out, workspace, M, G, causal, 0, splits).quant(qk_params, pv_params, strides), q, out, workspace, q_scale, scale_div, stream);
 }
 
-// ---- sliding window: a query sees its last `window` keys (mi355q_decode.h); always the ragged form, paged or contiguous ------------
-namespace {
-// the cache behind a *_window call: block_table != NULL the paged pools (paged_shape); NULL the contiguous cache of capacity
-// C = max_pages * P keys a row (decode_cache_shape; num_pages is not used).  -> C through `cap`, the kernels' page view through `pg`
-int window_cache_shape(int64_t B, int64_t max_pages, int64_t num_pages, int64_t P, int64_t D, const int32_t* block_table, KvPages* pg,
-                       int64_t* cap) {
-    if (block_table) {
-        const int rc = paged_shape(B, max_pages, num_pages, P, D, block_table, pg);
-        if (rc) return rc;
-    } else {
-        if (max_pages < 1 || P < 1 || max_pages > (1LL << 30) / P) return MI355Q_E_BADARG;
-        const int rc = decode_cache_shape(B, max_pages * P, D);
-        if (rc) return rc;
-    }
-    *cap = max_pages * P;
-    return 0;
-}
-}  // namespace
-
+// sliding window: a query sees its last `window` keys; always the ragged form, paged or (block_table == NULL) contiguous
 int64_t mi355q_bfp_attention_decode_window_span(int64_t M, int64_t max_length, int64_t window) {
     if (M < 1 || max_length < 1 || window < 1) return 0;
     return decode_window_span(M, max_length, window);
@@ -1497,32 +1220,9 @@ int mi355q_bfp_attention_decode_window(const float* q, const void* kq, const voi
                                        float* out, void* workspace, int64_t B, int64_t M, int64_t max_length, int64_t max_pages,
                                        int64_t num_pages, int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
                                        const int64_t* strides, int32_t splits, void* stream) {
-    if (M < 0 || max_length < 0 || splits < 0 || G < 0 || window < 1 || !causal) return MI355Q_E_BADARG;
-    KvPages pg{};
-    int64_t C = 0;
-    int rc = window_cache_shape(B, max_pages, num_pages, P, D, block_table, &pg, &C);
-    if (rc) return rc;
-    if (max_length > C) return MI355Q_E_BADARG;
-    if (M < 1 || M > 16 || max_length < M) return MI355Q_E_UNSUPPORTED;
-    if (G <= 1) G = 0;                                        // (0 or 1: ungrouped)
-    if (G && B * (G / decode_group_width(G, M)) > 65535) return MI355Q_E_UNSUPPORTED;
-    if (!q || !kq || !vq || !lengths || !out || !workspace || !qk_params || !pv_params) return MI355Q_E_BADARG;
-    QuantArgs aq{}, ap{};
-    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) |
-         reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) % 16 ||
-        (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(block_table)) % 4)
-        return MI355Q_E_ALIGN;
-    long long st4[4];
-    if (strides)
-        for (int i = 0; i < 4; ++i) {
-            if (strides[i] % 4) return MI355Q_E_ALIGN;
-            st4[i] = strides[i];
-        }
-    if (window > max_length) window = max_length;             // (a window over every key the call can hold: the same mask)
-    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
-    return launch_bfp_attention_decode(aq, ap, c, q, out, workspace, M, max_length, 1, q_scale, scale_div, strides ? st4 : nullptr, splits,
-                                       static_cast<hipStream_t>(stream), lengths, G, block_table ? &pg : nullptr, window);
+    return decode(KvCall(KV_EXPORTS[KVX_DECODE_WINDOW]).pools(kq, vq, nullptr, block_table, B, max_pages, num_pages, P, D)
+                      .lens(lengths, nullptr, max_length).query(q, out, workspace, M, G, causal, window, splits).quant(qk_params, pv_params, strides),
+                  q, out, workspace, q_scale, scale_div, stream);
 }
 
 int mi355q_bfp_attention_extend_window(const float* q, const void* kq, const void* vq, int32_t G, const int32_t* lengths,
@@ -1530,31 +1230,35 @@ int mi355q_bfp_attention_extend_window(const float* q, const void* kq, const voi
                                        float scale_div, float* out, int64_t B, int64_t M, int64_t max_length, int64_t max_pages,
                                        int64_t num_pages, int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
                                        const int64_t* strides, void* stream) {
-    if (M < 0 || max_length < 0 || G < 0 || window < 1 || !causal) return MI355Q_E_BADARG;
-    KvPages pg{};
-    int64_t C = 0;
-    int rc = window_cache_shape(B, max_pages, num_pages, P, D, block_table, &pg, &C);
-    if (rc) return rc;
-    if (max_length > C) return MI355Q_E_BADARG;
-    if (M < 1 || max_length < M) return MI355Q_E_UNSUPPORTED;
-    if (G <= 1) G = 0;
-    if (!q || !kq || !vq || !lengths || !out || !qk_params || !pv_params) return MI355Q_E_BADARG;
-    QuantArgs aq{}, ap{};
-    if ((rc = decode_quant_args(qk_params, aq)) != 0 || (rc = decode_quant_args(pv_params, ap)) != 0) return rc;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(kq) | reinterpret_cast<uintptr_t>(vq) |
-         reinterpret_cast<uintptr_t>(out)) % 16 ||
-        (reinterpret_cast<uintptr_t>(lengths) | reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(block_table)) % 4)
-        return MI355Q_E_ALIGN;
-    long long st4[4];
-    if (strides)
-        for (int i = 0; i < 4; ++i) {
-            if (strides[i] % 4) return MI355Q_E_ALIGN;
-            st4[i] = strides[i];
-        }
-    if (window > max_length) window = max_length;
-    const KvCache c{static_cast<uint16_t*>(const_cast<void*>(kq)), static_cast<uint16_t*>(const_cast<void*>(vq)), nullptr, B, C, (int)D};
-    return launch_bfp_attention_extend(aq, ap, c, q, out, M, max_length, 1, q_scale, scale_div, strides ? st4 : nullptr, lengths, counts,
-                                       static_cast<hipStream_t>(stream), G, block_table ? &pg : nullptr, window);
+    return extend(KvCall(KV_EXPORTS[KVX_EXTEND_WINDOW]).pools(kq, vq, nullptr, block_table, B, max_pages, num_pages, P, D)
+                      .lens(lengths, counts, max_length).query(q, out, nullptr, M, G, causal, window, 0).quant(qk_params, pv_params, strides),
+                  q, out, q_scale, scale_div, stream);
+}
+
+// diagnostic hook, not part of include/mi355q.h: what kv_call_check -- the function every export above calls -- makes of a call,
+// without launching (no HIP call: works without a GPU).  id: a KvExport; a: 14 addresses, never dereferenced (kq, vq, stage, k, v, q,
+// out, workspace, lengths, counts, block_table, k_bytes, v_bytes, stage_bytes), then B, C, max_pages, num_pages, P, D, M, L, n, G,
+// causal, window, splits; qk_params / pv_params / strides as the exports take them.  out: the code, 1 where the export would go on
+// to launch (or to write its sizes), then the normalised call: B, capacity, D, M, L, n, G, window, lg_p, pages set, causal, strides set,
+// the four strides.
+__attribute__((visibility("default"))) int mi355q_debug_kv_call(int32_t id, const int64_t a[27], const int32_t* qk_params, const int32_t* pv_params,
+                                                                 const int64_t* strides, int64_t out[18]) {
+    if (id < 0 || id >= KVX_COUNT || !a || !out) return MI355Q_E_BADARG;
+    const auto p = [a](int i) { return reinterpret_cast<const void*>(static_cast<uintptr_t>(a[i])); };
+    const auto p32 = [a](int i) { return reinterpret_cast<const int32_t*>(static_cast<uintptr_t>(a[i])); };
+    const auto p64 = [a](int i) { return reinterpret_cast<const int64_t*>(static_cast<uintptr_t>(a[i])); };
+    KvCall d = KV_EXPORTS[id];
+    d.cache(p(0), p(1), p(2), a[14], a[15], a[19]).pools(p(0), p(1), p(2), p32(10), a[14], a[16], a[17], a[18], a[19]).sizes(p64(11), p64(12), p64(13))
+        .rows(p(3), p(4), a[22]).lens(p32(8), p32(9), a[21]).query(p(5), p(6), p(7), a[20], (int32_t)a[23], (int32_t)a[24], a[25], (int32_t)a[26])
+        .quant(qk_params, pv_params, strides);
+    KvChecked c;
+    int rc;
+    const bool go = kv_call_check(d, c, rc);
+    const int64_t cap = d.storage == KV_INT8 ? c.c8.C : c.c.C;
+    const int64_t words[18] = {rc, go, d.B, cap, d.D, d.M, d.L, d.n, c.G, c.window, c.pg.lg_p, c.pages != nullptr, c.causal, c.strides != nullptr,
+                               c.st[0], c.st[1], c.st[2], c.st[3]};
+    for (int i = 0; i < 18; ++i) out[i] = words[i];
+    return 0;
 }
 
 // block_minifloat (fmt 1) / block_log (fmt 2) products: the same two kernels with the other quantisers' block parameters

@@ -1491,7 +1491,90 @@ def _ragged_check(cache, lengths, counts, max_length, rows, what):
     return None
 
 
-class KVCache:
+def _kv_call(device, export, args):
+    """THE call of a KV-cache export (csrc/mi355q_api.hip: each checks its arguments through csrc/mi355q_kv_call.h): every cache method and
+    both cached-attention functions end here"""
+    with _on_device(device):
+        rc = getattr(_lib.load_library(), export)(*args)
+    _lib.check(rc, export)
+
+
+class _KVCacheBase:
+    """What KVCache, PagedKVCache and PackedKVCache share: the constructor's checks, the quantiser parameter words (`_pa`, `_pb`), the
+    zeroed storage, and the checks of append / dequantised.  A subclass adds its storage's names, its exports' arguments and -- the paged
+    one -- its allocator.  Messages carry the subclass's name."""
+    RAGGED_ONLY = False         # PagedKVCache: lengths= is mandatory
+
+    def _init_rows(self, B, D, qk_params, pv_params, device, capacity=None):
+        import ctypes
+        name = type(self).__name__
+        if not 1 <= B <= 65535:
+            raise ValueError(f"{name}: B = {B} outside 1 .. 65535")
+        if D < 32 or D % 32 != 0 or D > ATTENTION_MAX_HEAD_DIM:
+            raise ValueError(f"{name}: head_dim {D} is not a multiple of 32 up to {ATTENTION_MAX_HEAD_DIM}")
+        if capacity is None:
+            self._check_pages()
+        elif capacity < 16 or capacity % 16 != 0:
+            raise ValueError(f"{name}: capacity {capacity} is not a positive multiple of 16")
+        self.qk_params = _decode_params(qk_params, f"{name} qk_params")
+        self.pv_params = _decode_params(pv_params, f"{name} pv_params")
+        self.B, self.D, self.device = B, D, torch.device(device)
+        self._pa = (ctypes.c_int32 * 6)(*[_default_bias(p) if i % 3 == 2 else int(p) for i, p in enumerate(self.qk_params)])
+        self._pb = (ctypes.c_int32 * 6)(*[_default_bias(p) if i % 3 == 2 else int(p) for i, p in enumerate(self.pv_params)])
+
+    def _zeroed(self, export, *dims):
+        """the three zeroed byte tensors (K, V, stage) of the sizes `export` gives for `dims`"""
+        import ctypes
+        nb = [ctypes.c_int64(0) for _ in range(3)]
+        _lib.check(getattr(_lib.load_library(), export)(*dims, *[ctypes.addressof(n) for n in nb]), export)
+        return tuple(torch.zeros(n.value, dtype=torch.uint8, device=self.device) for n in nb)
+
+    def _rows(self, t, what):
+        if not isinstance(t, torch.Tensor) or t.ndim < 3:       # (every cache has always said "KVCache.append" here)
+            raise ValueError(f"KVCache.append: {what} must be a tensor [..., n, D]")
+        if t.shape[-1] != self.D or t.shape[:-2].numel() != self.B:
+            raise ValueError(f"KVCache.append: {what} {tuple(t.shape)} does not match B = {self.B}, D = {self.D}")
+        return t
+
+    def _append_args(self, k, v, lengths, counts, max_length):
+        """append's checks -> (k and v as [rows, n, D] views, n, their strides for the export)"""
+        import ctypes
+        k, v = self._rows(k, "k"), self._rows(v, "v")
+        n = k.shape[-2]
+        if v.shape[-2] != n or n < 1:
+            raise ValueError(f"{type(self).__name__}.append: {n} rows of k, {v.shape[-2]} of v (at least one, and as many of each)")
+        if lengths is not None or self.RAGGED_ONLY:
+            why = "lengths= is mandatory: a paged cache is always addressed in the ragged form" if lengths is None else \
+                _ragged_check(self, lengths, counts, max_length, n, "append")
+            if why is not None:
+                raise ValueError(f"{type(self).__name__}.append: {why}")
+        elif counts is not None or max_length is not None:
+            raise ValueError(f"{type(self).__name__}.append: counts / max_length belong to a ragged append (lengths=)")
+        elif self.length + n > self.capacity:
+            raise ValueError(f"{type(self).__name__}.append: {self.length} + {n} keys exceed the capacity {self.capacity}")
+        for t in (k, v):
+            if not t.is_cuda or t.dtype != torch.float32 or t.device != self.device:
+                raise ValueError(f"{type(self).__name__}.append: fp32 tensors on {self.device} only (got {t.dtype} on {t.device}); there is no CPU fallback")
+        k3, ksb, kst = _as_heads_view(k)
+        v3, vsb, vst = _as_heads_view(v)
+        return k3, v3, n, (ctypes.c_int64 * 4)(ksb, kst, vsb, vst)
+
+    def _dequantised_out(self, lengths, max_length):
+        """dequantised's checks -> the empty fp32 outputs k, v [B, max_length (uniform: length), D]"""
+        if lengths is not None or self.RAGGED_ONLY:
+            why = "lengths= is mandatory: a paged cache is always addressed in the ragged form" if lengths is None else \
+                _ragged_check(self, lengths, None, max_length, 0, "dequantised")
+            if why is not None:
+                raise ValueError(f"{type(self).__name__}.dequantised: {why}")
+        elif max_length is not None:
+            raise ValueError(f"{type(self).__name__}.dequantised: max_length belongs to a ragged call (lengths=)")
+        if not self.stage.is_cuda:
+            raise ValueError(f"{type(self).__name__}.dequantised: the cache is not on a GPU; there is no CPU fallback")
+        k = torch.empty(self.B, self.length if lengths is None else int(max_length), self.D, dtype=torch.float32, device=self.device)
+        return k, torch.empty_like(k)
+
+
+class KVCache(_KVCacheBase):
     """What the reference's `past_key_value` (torch.cat of fp32 K / V, modeling_llama.py:301-306) becomes under the block_fp [1,16]
     quantisers of bmm_0 / bmm_1: per b = batch x head, quantised K and V as bf16 in the decode kernel's fragment order, plus the
     fp32 rows of the open 16-key block of K^T, which is quantised again on every append until it is full (include/mi355q.h).
@@ -1502,36 +1585,15 @@ class KVCache:
     advanced -- the caller owns the lengths -- and each row holds exactly what a cache of its own would."""
 
     def __init__(self, B: int, capacity: int, D: int, qk_params, pv_params, device):
-        import ctypes
-        B, capacity, D = int(B), int(capacity), int(D)
-        if not 1 <= B <= 65535:
-            raise ValueError(f"KVCache: B = {B} outside 1 .. 65535")
-        if D < 32 or D % 32 != 0 or D > ATTENTION_MAX_HEAD_DIM:
-            raise ValueError(f"KVCache: head_dim {D} is not a multiple of 32 up to {ATTENTION_MAX_HEAD_DIM}")
-        if capacity < 16 or capacity % 16 != 0:
-            raise ValueError(f"KVCache: capacity {capacity} is not a positive multiple of 16")
-        self.qk_params = _decode_params(qk_params, "KVCache qk_params")
-        self.pv_params = _decode_params(pv_params, "KVCache pv_params")
-        self.B, self.capacity, self.D, self.device = B, capacity, D, torch.device(device)
-        self.length = 0
-        nb = [ctypes.c_int64(0) for _ in range(3)]
-        _lib.check(_lib.load_library().mi355q_bfp_kv_cache_bytes(B, capacity, D, *[ctypes.addressof(n) for n in nb]), "mi355q_bfp_kv_cache_bytes")
+        self._init_rows(int(B), int(D), qk_params, pv_params, device, int(capacity))
+        self.capacity, self.length = int(capacity), 0
         # (zeroed: a V slot no key has reached meets a probability of exactly 0 and must be finite)
-        self.kq, self.vq, self.stage = (torch.zeros(n.value, dtype=torch.uint8, device=self.device) for n in nb)
-        self._pa = (ctypes.c_int32 * 6)(*[_default_bias(p) if i % 3 == 2 else int(p) for i, p in enumerate(self.qk_params)])
-        self._pb = (ctypes.c_int32 * 6)(*[_default_bias(p) if i % 3 == 2 else int(p) for i, p in enumerate(self.pv_params)])
+        self.kq, self.vq, self.stage = self._zeroed("mi355q_bfp_kv_cache_bytes", self.B, self.capacity, self.D)
 
     def reset(self) -> None:
         # nothing to clear: append rewrites every K tile it touches in full, and a V slot behind `length` only ever meets a
         # probability of exactly 0 -- what it needs is to be finite, which zeroed storage and older quantised values both are
         self.length = 0
-
-    def _rows(self, t, what):
-        if not isinstance(t, torch.Tensor) or t.ndim < 3:
-            raise ValueError(f"KVCache.append: {what} must be a tensor [..., n, D]")
-        if t.shape[-1] != self.D or t.shape[:-2].numel() != self.B:
-            raise ValueError(f"KVCache.append: {what} {tuple(t.shape)} does not match B = {self.B}, D = {self.D}")
-        return t
 
     def append(self, k: torch.Tensor, v: torch.Tensor, *, lengths: torch.Tensor = None, counts: torch.Tensor = None,
                max_length: int = None) -> None:
@@ -1540,69 +1602,31 @@ class KVCache:
         [B]; None: all n; the rest is padding, never read) as keys lengths[b] .. lengths[b] + counts[b] - 1; counts[b] == 0 leaves
         the row untouched.  `max_length`: the caller's upper bound on `lengths`, max_length + n <= capacity.  `length` stays."""
         import ctypes
-        k, v = self._rows(k, "k"), self._rows(v, "v")
-        n = k.shape[-2]
-        if v.shape[-2] != n or n < 1:
-            raise ValueError(f"KVCache.append: {n} rows of k, {v.shape[-2]} of v (at least one, and as many of each)")
-        ragged = lengths is not None
-        if ragged:
-            why = _ragged_check(self, lengths, counts, max_length, n, "append")
-            if why is not None:
-                raise ValueError(f"KVCache.append: {why}")
-        elif counts is not None or max_length is not None:
-            raise ValueError("KVCache.append: counts / max_length belong to a ragged append (lengths=)")
-        elif self.length + n > self.capacity:
-            raise ValueError(f"KVCache.append: {self.length} + {n} keys exceed the capacity {self.capacity}")
-        for t in (k, v):
-            if not t.is_cuda or t.dtype != torch.float32 or t.device != self.device:
-                raise ValueError(f"KVCache.append: fp32 tensors on {self.device} only (got {t.dtype} on {t.device}); there is no CPU fallback")
-        k3, ksb, kst = _as_heads_view(k)
-        v3, vsb, vst = _as_heads_view(v)
-        strides = (ctypes.c_int64 * 4)(ksb, kst, vsb, vst)
-        if ragged:
-            with _on_device(self.device):
-                rc = _lib.load_library().mi355q_bfp_kv_append_ragged(_ptr(self.kq), _ptr(self.vq), _ptr(self.stage), _ptr(k3), _ptr(v3),
-                                                                     _ptr(lengths), _ptr(counts), self.B, self.capacity, self.D, n,
-                                                                     int(max_length), ctypes.addressof(self._pa), ctypes.addressof(self._pb),
-                                                                     ctypes.addressof(strides), _stream_ptr(self.device))
-            _lib.check(rc, "mi355q_bfp_kv_append_ragged")
+        k3, v3, n, strides = self._append_args(k, v, lengths, counts, max_length)
+        if lengths is not None:
+            _kv_call(self.device, "mi355q_bfp_kv_append_ragged", (
+                _ptr(self.kq), _ptr(self.vq), _ptr(self.stage), _ptr(k3), _ptr(v3), _ptr(lengths), _ptr(counts), self.B, self.capacity, self.D, n,
+                int(max_length), ctypes.addressof(self._pa), ctypes.addressof(self._pb), ctypes.addressof(strides), _stream_ptr(self.device)))
             return
-        with _on_device(self.device):
-            rc = _lib.load_library().mi355q_bfp_kv_append(_ptr(self.kq), _ptr(self.vq), _ptr(self.stage), _ptr(k3), _ptr(v3), self.B, self.capacity,
-                                                          self.D, self.length, n, ctypes.addressof(self._pa), ctypes.addressof(self._pb),
-                                                          ctypes.addressof(strides), _stream_ptr(self.device))
-        _lib.check(rc, "mi355q_bfp_kv_append")
+        _kv_call(self.device, "mi355q_bfp_kv_append", (
+            _ptr(self.kq), _ptr(self.vq), _ptr(self.stage), _ptr(k3), _ptr(v3), self.B, self.capacity, self.D, self.length, n,
+            ctypes.addressof(self._pa), ctypes.addressof(self._pb), ctypes.addressof(strides), _stream_ptr(self.device)))
         self.length += n
 
     def dequantised(self, lengths: torch.Tensor = None, max_length: int = None):
         """the cache's quantised K and V as fp32 [B, length, D] (tests, debugging); ragged: [B, max_length, D], zeros behind each
         row's lengths[b]"""
+        k, v = self._dequantised_out(lengths, max_length)
         if lengths is not None:
-            why = _ragged_check(self, lengths, None, max_length, 0, "dequantised")
-            if why is not None:
-                raise ValueError(f"KVCache.dequantised: {why}")
-        elif max_length is not None:
-            raise ValueError("KVCache.dequantised: max_length belongs to a ragged call (lengths=)")
-        if not self.kq.is_cuda:
-            raise ValueError("KVCache.dequantised: the cache is not on a GPU; there is no CPU fallback")
-        if lengths is not None:
-            k = torch.empty(self.B, int(max_length), self.D, dtype=torch.float32, device=self.device)
-            v = torch.empty_like(k)
-            with _on_device(self.device):
-                rc = _lib.load_library().mi355q_bfp_kv_decode_fp32_ragged(_ptr(self.kq), _ptr(self.vq), _ptr(lengths), _ptr(k), _ptr(v), self.B,
-                                                                          self.capacity, self.D, int(max_length), _stream_ptr(self.device))
-            _lib.check(rc, "mi355q_bfp_kv_decode_fp32_ragged")
-            return k, v
-        k = torch.empty(self.B, self.length, self.D, dtype=torch.float32, device=self.device)
-        v = torch.empty_like(k)
-        with _on_device(self.device):
-            rc = _lib.load_library().mi355q_bfp_kv_decode_fp32(_ptr(self.kq), _ptr(self.vq), _ptr(k), _ptr(v), self.B, self.capacity, self.D,
-                                                               self.length, _stream_ptr(self.device))
-        _lib.check(rc, "mi355q_bfp_kv_decode_fp32")
+            _kv_call(self.device, "mi355q_bfp_kv_decode_fp32_ragged", (_ptr(self.kq), _ptr(self.vq), _ptr(lengths), _ptr(k), _ptr(v), self.B,
+                                                                         self.capacity, self.D, int(max_length), _stream_ptr(self.device)))
+        else:
+            _kv_call(self.device, "mi355q_bfp_kv_decode_fp32", (_ptr(self.kq), _ptr(self.vq), _ptr(k), _ptr(v), self.B, self.capacity, self.D,
+                                                                  self.length, _stream_ptr(self.device)))
         return k, v
 
 
-class PagedKVCache:
+class PagedKVCache(_KVCacheBase):
     """The block_fp KV cache in PAGES of `page_size` keys (a power of two >= 32) drawn from one pool: a row holds memory for the keys
     it has, a finished row's pages serve the next sequence, and rows can share the pages of a common prefix.  Storage and kernels:
     include/mi355q.h (paged cache), csrc/mi355q_decode.h; every value is the one `KVCache` holds, so append / dequantised /
@@ -1622,34 +1646,28 @@ class PagedKVCache:
     are helpers: the tests and the timing tool place pages by hand with `assign` (out-of-order tables, a poison page), the harness asks
     every layer with `dry_run` before it changes one.  `assign` filters the free list per call and is not meant for a hot loop."""
 
+    RAGGED_ONLY = True
+
     def __init__(self, B: int, D: int, qk_params, pv_params, device, *, page_size: int, num_pages: int, max_pages: int, pad_page: int = None):
-        import ctypes
-        B, D, P, num_pages, max_pages = int(B), int(D), int(page_size), int(num_pages), int(max_pages)
-        if not 1 <= B <= 65535:
-            raise ValueError(f"PagedKVCache: B = {B} outside 1 .. 65535")
-        if D < 32 or D % 32 != 0 or D > ATTENTION_MAX_HEAD_DIM:
-            raise ValueError(f"PagedKVCache: head_dim {D} is not a multiple of 32 up to {ATTENTION_MAX_HEAD_DIM}")
+        self.page_size, self.num_pages, self.max_pages, self.capacity = int(page_size), int(num_pages), int(max_pages), int(max_pages) * int(page_size)
+        self.pad_page = pad_page
+        self._init_rows(int(B), int(D), qk_params, pv_params, device)
+        self.pad_page = 0 if pad_page is None else int(pad_page)
+        self.kq, self.vq, self.stage = self._zeroed("mi355q_bfp_kv_paged_bytes", self.num_pages, self.page_size, self.B, self.D)
+        self.table = torch.full((self.B, self.max_pages), self.pad_page, dtype=torch.int32)
+        self.block_table = self.table.to(self.device)
+        self.free = [p for p in range(self.num_pages - 1, -1, -1) if pad_page is None or p != self.pad_page]
+        self.refs = [0] * self.num_pages                    # rows that hold a page (share_prefix: more than one)
+        self.held = [[] for _ in range(self.B)]
+
+    def _check_pages(self):
+        P, num_pages, max_pages, pad_page = self.page_size, self.num_pages, self.max_pages, self.pad_page
         if P < 32 or P & (P - 1):
             raise ValueError(f"PagedKVCache: page_size {P} is not a power of two >= 32 (a K tile, a V pair and an extend step stay in one page)")
         if num_pages < 1 or max_pages < 1 or max_pages * P > 1 << 30:
             raise ValueError(f"PagedKVCache: num_pages = {num_pages}, max_pages = {max_pages}: at least one each, max_pages * page_size <= 2^30")
         if pad_page is not None and not 0 <= int(pad_page) < num_pages:
             raise ValueError(f"PagedKVCache: pad_page {pad_page} outside 0 .. {num_pages - 1}")
-        self.qk_params = _decode_params(qk_params, "PagedKVCache qk_params")
-        self.pv_params = _decode_params(pv_params, "PagedKVCache pv_params")
-        self.B, self.D, self.device = B, D, torch.device(device)
-        self.page_size, self.num_pages, self.max_pages, self.capacity = P, num_pages, max_pages, max_pages * P
-        self.pad_page = 0 if pad_page is None else int(pad_page)
-        nb = [ctypes.c_int64(0) for _ in range(3)]
-        _lib.check(_lib.load_library().mi355q_bfp_kv_paged_bytes(num_pages, P, B, D, *[ctypes.addressof(n) for n in nb]), "mi355q_bfp_kv_paged_bytes")
-        self.kq, self.vq, self.stage = (torch.zeros(n.value, dtype=torch.uint8, device=self.device) for n in nb)
-        self.table = torch.full((B, max_pages), self.pad_page, dtype=torch.int32)
-        self.block_table = self.table.to(self.device)
-        self.free = [p for p in range(num_pages - 1, -1, -1) if pad_page is None or p != self.pad_page]
-        self.refs = [0] * num_pages                         # rows that hold a page (share_prefix: more than one)
-        self.held = [[] for _ in range(B)]
-        self._pa = (ctypes.c_int32 * 6)(*[_default_bias(p) if i % 3 == 2 else int(p) for i, p in enumerate(self.qk_params)])
-        self._pb = (ctypes.c_int32 * 6)(*[_default_bias(p) if i % 3 == 2 else int(p) for i, p in enumerate(self.pv_params)])
 
     def pages_for(self, length: int) -> int:
         return -(-int(length) // self.page_size)
@@ -1755,53 +1773,27 @@ class PagedKVCache:
     def reset(self) -> None:
         self.release(range(self.B))
 
-    _rows = KVCache._rows
-
     def append(self, k: torch.Tensor, v: torch.Tensor, *, lengths: torch.Tensor, counts: torch.Tensor = None, max_length: int = None) -> None:
         """KVCache.append in its ragged form (lengths: BEFORE the call; counts; max_length + n <= capacity).  The pages of the new keys
         must be the rows' already (`ensure`): the kernel writes where the table points."""
         import ctypes
-        k, v = self._rows(k, "k"), self._rows(v, "v")
-        n = k.shape[-2]
-        if v.shape[-2] != n or n < 1:
-            raise ValueError(f"PagedKVCache.append: {n} rows of k, {v.shape[-2]} of v (at least one, and as many of each)")
-        why = "lengths= is mandatory: a paged cache is always addressed in the ragged form" if lengths is None else \
-            _ragged_check(self, lengths, counts, max_length, n, "append")
-        if why is not None:
-            raise ValueError(f"PagedKVCache.append: {why}")
-        for t in (k, v):
-            if not t.is_cuda or t.dtype != torch.float32 or t.device != self.device:
-                raise ValueError(f"PagedKVCache.append: fp32 tensors on {self.device} only (got {t.dtype} on {t.device}); there is no CPU fallback")
-        k3, ksb, kst = _as_heads_view(k)
-        v3, vsb, vst = _as_heads_view(v)
-        strides = (ctypes.c_int64 * 4)(ksb, kst, vsb, vst)
-        with _on_device(self.device):
-            rc = _lib.load_library().mi355q_bfp_kv_append_paged(_ptr(self.kq), _ptr(self.vq), _ptr(self.stage), _ptr(k3), _ptr(v3), _ptr(lengths),
-                                                                _ptr(counts), _ptr(self.block_table), self.B, self.max_pages, self.num_pages,
-                                                                self.page_size, self.D, n, int(max_length), ctypes.addressof(self._pa),
-                                                                ctypes.addressof(self._pb), ctypes.addressof(strides), _stream_ptr(self.device))
-        _lib.check(rc, "mi355q_bfp_kv_append_paged")
+        k3, v3, n, strides = self._append_args(k, v, lengths, counts, max_length)
+        _kv_call(self.device, "mi355q_bfp_kv_append_paged", (
+            _ptr(self.kq), _ptr(self.vq), _ptr(self.stage), _ptr(k3), _ptr(v3), _ptr(lengths), _ptr(counts), _ptr(self.block_table), self.B,
+            self.max_pages, self.num_pages, self.page_size, self.D, n, int(max_length), ctypes.addressof(self._pa), ctypes.addressof(self._pb),
+            ctypes.addressof(strides), _stream_ptr(self.device)))
 
     def dequantised(self, lengths: torch.Tensor, max_length: int = None):
         """the rows' quantised K and V as fp32 [B, max_length, D] through the page table, zeros behind each row's lengths[b].  Keys in
         pages `trim` has given back are unspecified (their entries name `pad_page`)."""
-        why = "lengths= is mandatory: a paged cache is always addressed in the ragged form" if lengths is None else \
-            _ragged_check(self, lengths, None, max_length, 0, "dequantised")
-        if why is not None:
-            raise ValueError(f"PagedKVCache.dequantised: {why}")
-        if not self.kq.is_cuda:
-            raise ValueError("PagedKVCache.dequantised: the cache is not on a GPU; there is no CPU fallback")
-        k = torch.empty(self.B, int(max_length), self.D, dtype=torch.float32, device=self.device)
-        v = torch.empty_like(k)
-        with _on_device(self.device):
-            rc = _lib.load_library().mi355q_bfp_kv_decode_fp32_paged(_ptr(self.kq), _ptr(self.vq), _ptr(lengths), _ptr(self.block_table), _ptr(k),
-                                                                     _ptr(v), self.B, self.max_pages, self.num_pages, self.page_size, self.D,
-                                                                     int(max_length), _stream_ptr(self.device))
-        _lib.check(rc, "mi355q_bfp_kv_decode_fp32_paged")
+        k, v = self._dequantised_out(lengths, max_length)
+        _kv_call(self.device, "mi355q_bfp_kv_decode_fp32_paged", (
+            _ptr(self.kq), _ptr(self.vq), _ptr(lengths), _ptr(self.block_table), _ptr(k), _ptr(v), self.B, self.max_pages, self.num_pages,
+            self.page_size, self.D, int(max_length), _stream_ptr(self.device)))
         return k, v
 
 
-class PackedKVCache:
+class PackedKVCache(_KVCacheBase):
     """`KVCache` with every quantised value stored as what it is -- a signed mantissa byte, and one shared-exponent byte per block of
     16 -- instead of as bf16: 1 + 1/16 bytes a value, 17/32 of KVCache's K and V bytes and of a decode step's K / V traffic (layout:
     csrc/mi355q_kv8.h).  Same constructor arguments and the same append / reset / dequantised / length / lengths= / counts= /
@@ -1814,67 +1806,31 @@ class PackedKVCache:
     brings every row's `length` as a device tensor."""
 
     def __init__(self, B: int, capacity: int, D: int, qk_params, pv_params, device):
-        import ctypes
-        B, capacity, D = int(B), int(capacity), int(D)
-        if not 1 <= B <= 65535:
-            raise ValueError(f"PackedKVCache: B = {B} outside 1 .. 65535")
-        if D < 32 or D % 32 != 0 or D > ATTENTION_MAX_HEAD_DIM:
-            raise ValueError(f"PackedKVCache: head_dim {D} is not a multiple of 32 up to {ATTENTION_MAX_HEAD_DIM}")
-        if capacity < 16 or capacity % 16 != 0:
-            raise ValueError(f"PackedKVCache: capacity {capacity} is not a positive multiple of 16")
-        self.qk_params = _decode_params(qk_params, "PackedKVCache qk_params")
-        self.pv_params = _decode_params(pv_params, "PackedKVCache pv_params")
+        self._init_rows(int(B), int(D), qk_params, pv_params, device, int(capacity))
         for name, p in (("qk_params (K)", self.qk_params), ("pv_params (V)", self.pv_params)):
             if int(p[3]) > 8:
                 raise ValueError(f"PackedKVCache {name}: cached operand of width {p[3]} > 8: its mantissa, up to 2^{int(p[3]) - 1} - 1 in "
                                  "magnitude, does not fit the int8 the cache stores (KVCache takes width 9)")
-        self.B, self.capacity, self.D, self.device = B, capacity, D, torch.device(device)
-        self.length = 0
-        nb = [ctypes.c_int64(0) for _ in range(3)]
-        _lib.check(_lib.load_library().mi355q_bfp_kv8_cache_bytes(B, capacity, D, *[ctypes.addressof(n) for n in nb]), "mi355q_bfp_kv8_cache_bytes")
+        self.capacity, self.length = int(capacity), 0
         # (zeroed: a V slot no key has reached is mantissa 0, a finite 0 under any exponent byte, for the probability of exactly 0 it meets)
-        self.k8, self.v8, self.stage = (torch.zeros(n.value, dtype=torch.uint8, device=self.device) for n in nb)
-        self._pa = (ctypes.c_int32 * 6)(*[_default_bias(p) if i % 3 == 2 else int(p) for i, p in enumerate(self.qk_params)])
-        self._pb = (ctypes.c_int32 * 6)(*[_default_bias(p) if i % 3 == 2 else int(p) for i, p in enumerate(self.pv_params)])
+        self.k8, self.v8, self.stage = self._zeroed("mi355q_bfp_kv8_cache_bytes", self.B, self.capacity, self.D)
 
     def reset(self) -> None:
         # nothing to clear, as in KVCache.reset: stale mantissa and exponent bytes rebuild to finite values
         self.length = 0
-
-    _rows = KVCache._rows
 
     def append(self, k: torch.Tensor, v: torch.Tensor, *, lengths: torch.Tensor = None, counts: torch.Tensor = None,
                max_length: int = None) -> None:
         """KVCache.append on the packed storage: n >= 1 new fp32 rows k, v [B, n, D] (or [1, H, n, D] head views) become keys
         length .. length + n - 1, or -- ragged -- row b's first counts[b] rows become its keys lengths[b] .. (lengths BEFORE the call)."""
         import ctypes
-        k, v = self._rows(k, "k"), self._rows(v, "v")
-        n = k.shape[-2]
-        if v.shape[-2] != n or n < 1:
-            raise ValueError(f"PackedKVCache.append: {n} rows of k, {v.shape[-2]} of v (at least one, and as many of each)")
+        k3, v3, n, strides = self._append_args(k, v, lengths, counts, max_length)
         ragged = lengths is not None
-        if ragged:
-            why = _ragged_check(self, lengths, counts, max_length, n, "append")
-            if why is not None:
-                raise ValueError(f"PackedKVCache.append: {why}")
-        elif counts is not None or max_length is not None:
-            raise ValueError("PackedKVCache.append: counts / max_length belong to a ragged append (lengths=)")
-        elif self.length + n > self.capacity:
-            raise ValueError(f"PackedKVCache.append: {self.length} + {n} keys exceed the capacity {self.capacity}")
-        for t in (k, v):
-            if not t.is_cuda or t.dtype != torch.float32 or t.device != self.device:
-                raise ValueError(f"PackedKVCache.append: fp32 tensors on {self.device} only (got {t.dtype} on {t.device}); there is no CPU fallback")
-        k3, ksb, kst = _as_heads_view(k)
-        v3, vsb, vst = _as_heads_view(v)
-        strides = (ctypes.c_int64 * 4)(ksb, kst, vsb, vst)
         if not ragged:      # (the kernels read lengths from the device: every row at `length`)
             lengths, max_length = _window_lengths(self, None, None)
-        with _on_device(self.device):
-            rc = _lib.load_library().mi355q_bfp_kv8_append(_ptr(self.k8), _ptr(self.v8), _ptr(self.stage), _ptr(k3), _ptr(v3), _ptr(lengths),
-                                                           _ptr(counts), self.B, self.capacity, self.D, n, int(max_length),
-                                                           ctypes.addressof(self._pa), ctypes.addressof(self._pb), ctypes.addressof(strides),
-                                                           _stream_ptr(self.device))
-        _lib.check(rc, "mi355q_bfp_kv8_append")
+        _kv_call(self.device, "mi355q_bfp_kv8_append", (
+            _ptr(self.k8), _ptr(self.v8), _ptr(self.stage), _ptr(k3), _ptr(v3), _ptr(lengths), _ptr(counts), self.B, self.capacity, self.D, n,
+            int(max_length), ctypes.addressof(self._pa), ctypes.addressof(self._pb), ctypes.addressof(strides), _stream_ptr(self.device)))
         if not ragged:
             self.length += n
 
@@ -1882,24 +1838,14 @@ class PackedKVCache:
         """the cache's K and V as the decode kernels rebuild them, fp32 [B, length, D] (tests, debugging); ragged: [B, max_length, D],
         zeros behind each row's lengths[b]"""
         import ctypes
-        if lengths is not None:
-            why = _ragged_check(self, lengths, None, max_length, 0, "dequantised")
-            if why is not None:
-                raise ValueError(f"PackedKVCache.dequantised: {why}")
-        elif max_length is not None:
-            raise ValueError("PackedKVCache.dequantised: max_length belongs to a ragged call (lengths=)")
-        if not self.k8.is_cuda:
-            raise ValueError("PackedKVCache.dequantised: the cache is not on a GPU; there is no CPU fallback")
+        k, v = self._dequantised_out(lengths, max_length)
         if lengths is None:
             lengths, max_length = _window_lengths(self, None, None)
-        k = torch.empty(self.B, int(max_length), self.D, dtype=torch.float32, device=self.device)
-        v = torch.empty_like(k)
-        with _on_device(self.device):
-            rc = _lib.load_library().mi355q_bfp_kv8_decode_fp32(_ptr(self.k8), _ptr(self.v8), _ptr(lengths), _ptr(k), _ptr(v), self.B,
-                                                                self.capacity, self.D, int(max_length), ctypes.addressof(self._pa),
-                                                                ctypes.addressof(self._pb), _stream_ptr(self.device))
-        _lib.check(rc, "mi355q_bfp_kv8_decode_fp32")
+        _kv_call(self.device, "mi355q_bfp_kv8_decode_fp32", (
+            _ptr(self.k8), _ptr(self.v8), _ptr(lengths), _ptr(k), _ptr(v), self.B, self.capacity, self.D, int(max_length),
+            ctypes.addressof(self._pa), ctypes.addressof(self._pb), _stream_ptr(self.device)))
         return k, v
+
 
 
 _PAGED_NEEDS_LENGTHS = "a paged cache is always addressed in the ragged form: lengths= and max_length= (there is no uniform paged launch)"
@@ -1971,6 +1917,74 @@ def bfp_attention_decode_supported(q, cache) -> bool:
     return _decode_check(q, cache) is None
 
 
+def _attention_out(q, M, D, token_major):
+    """the empty output of a cached-attention call and its element strides of batch and row: q's shape, or -- token_major, q [1, H, M, D]
+    -- the [1, M, H, D] tensor seen as [1, H, M, D]"""
+    if token_major and q.ndim == 4 and q.shape[0] == 1:
+        H = q.shape[1]
+        return torch.empty(1, M, H, D, dtype=torch.float32, device=q.device).permute(0, 2, 1, 3), D, H * D
+    return torch.empty(*q.shape, dtype=torch.float32, device=q.device), M * D, D
+
+
+def _decode_workspace(q, cache, M, D, group, sp):
+    """the decode kernels' workspace, kept per (device, stream, launch rows, capacity, D): score tiles + statistics + partial outputs for
+    any L <= capacity and any number of splits (it holds no K / V: the same for every kind of cache)"""
+    R = cache.B if group == 1 else cache.B * group // decode_group_width(group, M)       # launch rows: the workspace is theirs
+    if R > 65535:
+        raise ValueError(f"mi355q.bfp_attention_decode: {R} launch rows (cache.B * group / decode_group_width) exceed 65535")
+    key = (q.device.index, sp, R, cache.capacity, D)
+    ws = _DECODE_WS.get(key)
+    if ws is None:
+        ws = _DECODE_WS.put(key, torch.empty(R * (cache.capacity // 16) * 1024 + R * _DECODE_MAX_SPLITS * (128 + (D // 16) * 1024),
+                                             dtype=torch.uint8, device=q.device))
+    return ws
+
+
+def _cached_attention(op, q, cache, causal, scale_div, q_scale, token_major, splits, lengths, counts, max_length, group, window):
+    """bfp_attention_decode (op "decode") and bfp_attention_extend ("extend") behind their checks: the ROUTE -- the export
+    mi355q_bfp_attention_<op><form> and its arguments, from the cache's kind, lengths, group and window -- and the call.
+      form       chosen when                                      takes, next to what every export takes
+      _window    window is given (any bf16 cache)                 G, lengths (the uniform call brings cache.length as a device tensor),
+                                                                  the block table or NULL, causal = 1, window, the paged dimensions
+                                                                  (a contiguous cache: 1 page of `capacity` keys)
+      _paged     a PagedKVCache                                   G, lengths, the block table, the paged dimensions
+      _kv8       a PackedKVCache (decode only)                    G, lengths (as _window), k8 / v8 for kq / vq
+      _grouped   group != 1                                       G, lengths or NULL
+      _ragged    lengths are given (decode only)                  lengths
+      (none)     else                                             decode: L = cache.length; extend: lengths or NULL
+    extend exports take `counts` behind `lengths` and have no workspace and no splits."""
+    import ctypes
+    decode = op == "decode"
+    M, D = q.shape[-2:]
+    q3, qsb, qsm = _as_heads_view(q)
+    out, osb, osm = _attention_out(q, M, D, token_major)
+    sp = _stream_ptr(q.device)
+    strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
+    paged, packed, windowed = isinstance(cache, PagedKVCache), isinstance(cache, PackedKVCache), window is not None
+    form = "_window" if windowed else "_paged" if paged else "_kv8" if packed else "_grouped" if group != 1 else \
+        "_ragged" if decode and lengths is not None else ""
+    if windowed or packed:
+        lengths, L = _window_lengths(cache, lengths, max_length)
+    else:
+        L = int(max_length) if lengths is not None else cache.length
+    which = (group,) if form not in ("", "_ragged") else ()
+    if form or not decode:
+        which += (_ptr(lengths),)
+    if not decode:
+        which += (_ptr(counts),)
+    if windowed or paged:
+        which += (_ptr(cache.block_table) if paged else None,)
+        capacity = (cache.max_pages, cache.num_pages, cache.page_size) if paged else (1, 1, cache.capacity)
+    else:
+        capacity = (cache.capacity,)
+    _kv_call(q.device, f"mi355q_bfp_attention_{op}{form}", (
+        _ptr(q3), *((_ptr(cache.k8), _ptr(cache.v8)) if packed else (_ptr(cache.kq), _ptr(cache.vq))), *which,
+        *((1, int(window)) if windowed else (int(bool(causal)),)), float(q_scale) if q_scale else 0.0, float(scale_div) if scale_div else 0.0,
+        _ptr(out), *((_ptr(_decode_workspace(q, cache, M, D, group, sp)),) if decode else ()), cache.B, M, L, *capacity, D,
+        ctypes.addressof(cache._pa), ctypes.addressof(cache._pb), ctypes.addressof(strides), *((int(splits or 0),) if decode else ()), sp))
+    return out
+
+
 def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True, scale_div: float = None, q_scale: float = None,
                          token_major: bool = False, splits: int = None, lengths: torch.Tensor = None, max_length: int = None,
                          group: int = 1, window: int = None):
@@ -1996,121 +2010,17 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     (PagedKVCache.trim).
     `cache` may be a PackedKVCache (int8 mantissas, 17/32 of the K / V bytes): the same keywords with the same meaning and the bits
     of the same call on a KVCache holding the same keys; `window` is refused (NotImplementedError), and there is no paged form."""
-    import ctypes
     if isinstance(cache, PackedKVCache):
-        return _decode_packed(q, cache, causal, scale_div, q_scale, token_major, splits, lengths, max_length, group, window)
-    why = _decode_check(q, cache, splits, lengths, max_length, group, causal=causal, window=window)
+        if window is not None:
+            raise NotImplementedError("mi355q.bfp_attention_decode: no sliding-window kernel reads a PackedKVCache (int8 mantissas); "
+                                      "window= needs a KVCache or a PagedKVCache")
+        why = _decode_call_check(q, cache, splits, lengths, max_length, group)
+    else:
+        why = _decode_check(q, cache, splits, lengths, max_length, group, causal=causal, window=window)
     if why is not None:
         raise ValueError(f"mi355q.bfp_attention_decode: {why}")
-    M, D = q.shape[-2:]
-    q3, qsb, qsm = _as_heads_view(q)
-    paged = isinstance(cache, PagedKVCache)
-    B, L, C = cache.B, 0 if paged else cache.length, cache.capacity
-    if token_major and q.ndim == 4 and q.shape[0] == 1:
-        H = q.shape[1]
-        out = torch.empty(1, M, H, D, dtype=torch.float32, device=q.device).permute(0, 2, 1, 3)
-        osb, osm = D, H * D
-    else:
-        out = torch.empty(*q.shape, dtype=torch.float32, device=q.device)
-        osb, osm = M * D, D
-    lib = _lib.load_library()
-    sp = _stream_ptr(q.device)
-    R = B if group == 1 else B * group // decode_group_width(group, M)       # launch rows: the workspace is theirs
-    if R > 65535:
-        raise ValueError(f"mi355q.bfp_attention_decode: {R} launch rows (cache.B * group / decode_group_width) exceed 65535")
-    key = (q.device.index, sp, R, C, D)
-    ws = _DECODE_WS.get(key)
-    if ws is None:      # (any L <= C, any number of splits: score tiles + statistics + partial outputs)
-        ws = _DECODE_WS.put(key, torch.empty(R * (C // 16) * 1024 + R * _DECODE_MAX_SPLITS * (128 + (D // 16) * 1024), dtype=torch.uint8,
-                                             device=q.device))
-    strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
-    if window is not None:
-        wl, wmax = _window_lengths(cache, lengths, max_length)
-        with _on_device(q.device):
-            rc = lib.mi355q_bfp_attention_decode_window(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), group, _ptr(wl),
-                                                        _ptr(cache.block_table) if paged else None, 1, int(window),
-                                                        float(q_scale) if q_scale else 0.0, float(scale_div) if scale_div else 0.0,
-                                                        _ptr(out), _ptr(ws), B, M, wmax, cache.max_pages if paged else 1,
-                                                        cache.num_pages if paged else 1, cache.page_size if paged else C, D,
-                                                        ctypes.addressof(cache._pa), ctypes.addressof(cache._pb), ctypes.addressof(strides),
-                                                        int(splits or 0), sp)
-        _lib.check(rc, "mi355q_bfp_attention_decode_window")
-        return out
-    if paged:
-        with _on_device(q.device):
-            rc = lib.mi355q_bfp_attention_decode_paged(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), group, _ptr(lengths), _ptr(cache.block_table),
-                                                       int(bool(causal)), float(q_scale) if q_scale else 0.0,
-                                                       float(scale_div) if scale_div else 0.0, _ptr(out), _ptr(ws), B, M, int(max_length),
-                                                       cache.max_pages, cache.num_pages, cache.page_size, D, ctypes.addressof(cache._pa),
-                                                       ctypes.addressof(cache._pb), ctypes.addressof(strides), int(splits or 0), sp)
-        _lib.check(rc, "mi355q_bfp_attention_decode_paged")
-        return out
-    if group != 1:
-        with _on_device(q.device):
-            rc = lib.mi355q_bfp_attention_decode_grouped(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), group, _ptr(lengths), int(bool(causal)),
-                                                         float(q_scale) if q_scale else 0.0, float(scale_div) if scale_div else 0.0,
-                                                         _ptr(out), _ptr(ws), B, M, int(max_length) if lengths is not None else L, C, D,
-                                                         ctypes.addressof(cache._pa), ctypes.addressof(cache._pb),
-                                                         ctypes.addressof(strides), int(splits or 0), sp)
-        _lib.check(rc, "mi355q_bfp_attention_decode_grouped")
-        return out
-    if lengths is not None:
-        with _on_device(q.device):
-            rc = lib.mi355q_bfp_attention_decode_ragged(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), _ptr(lengths), int(bool(causal)),
-                                                        float(q_scale) if q_scale else 0.0, float(scale_div) if scale_div else 0.0,
-                                                        _ptr(out), _ptr(ws), B, M, int(max_length), C, D, ctypes.addressof(cache._pa),
-                                                        ctypes.addressof(cache._pb), ctypes.addressof(strides), int(splits or 0), sp)
-        _lib.check(rc, "mi355q_bfp_attention_decode_ragged")
-        return out
-    with _on_device(q.device):
-        rc = lib.mi355q_bfp_attention_decode(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), int(bool(causal)), float(q_scale) if q_scale else 0.0,
-                                             float(scale_div) if scale_div else 0.0, _ptr(out), _ptr(ws), B, M, L, C, D,
-                                             ctypes.addressof(cache._pa), ctypes.addressof(cache._pb), ctypes.addressof(strides),
-                                             int(splits or 0), sp)
-    _lib.check(rc, "mi355q_bfp_attention_decode")
-    return out
+    return _cached_attention("decode", q, cache, causal, scale_div, q_scale, token_major, splits, lengths, None, max_length, group, window)
 
-
-def _decode_packed(q, cache, causal, scale_div, q_scale, token_major, splits, lengths, max_length, group, window):
-    """bfp_attention_decode on a PackedKVCache: one entry point for every form it has -- ragged (the uniform call brings the cache's
-    length as a device tensor), grouped or not"""
-    import ctypes
-    if window is not None:
-        raise NotImplementedError("mi355q.bfp_attention_decode: no sliding-window kernel reads a PackedKVCache (int8 mantissas); "
-                                  "window= needs a KVCache or a PagedKVCache")
-    why = _decode_call_check(q, cache, splits, lengths, max_length, group)
-    if why is not None:
-        raise ValueError(f"mi355q.bfp_attention_decode: {why}")
-    M, D = q.shape[-2:]
-    q3, qsb, qsm = _as_heads_view(q)
-    B, C = cache.B, cache.capacity
-    if token_major and q.ndim == 4 and q.shape[0] == 1:
-        H = q.shape[1]
-        out = torch.empty(1, M, H, D, dtype=torch.float32, device=q.device).permute(0, 2, 1, 3)
-        osb, osm = D, H * D
-    else:
-        out = torch.empty(*q.shape, dtype=torch.float32, device=q.device)
-        osb, osm = M * D, D
-    sp = _stream_ptr(q.device)
-    R = B if group == 1 else B * group // decode_group_width(group, M)       # launch rows: the workspace is theirs
-    if R > 65535:
-        raise ValueError(f"mi355q.bfp_attention_decode: {R} launch rows (cache.B * group / decode_group_width) exceed 65535")
-    key = (q.device.index, sp, R, C, D)
-    ws = _DECODE_WS.get(key)
-    if ws is None:      # (the bf16 decode's workspace: it holds scores, statistics and partial outputs, no K / V)
-        ws = _DECODE_WS.put(key, torch.empty(R * (C // 16) * 1024 + R * _DECODE_MAX_SPLITS * (128 + (D // 16) * 1024), dtype=torch.uint8,
-                                             device=q.device))
-    strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
-    if lengths is None:
-        lengths, max_length = _window_lengths(cache, None, None)
-    with _on_device(q.device):
-        rc = _lib.load_library().mi355q_bfp_attention_decode_kv8(_ptr(q3), _ptr(cache.k8), _ptr(cache.v8), group, _ptr(lengths),
-                                                                 int(bool(causal)), float(q_scale) if q_scale else 0.0,
-                                                                 float(scale_div) if scale_div else 0.0, _ptr(out), _ptr(ws), B, M,
-                                                                 int(max_length), C, D, ctypes.addressof(cache._pa),
-                                                                 ctypes.addressof(cache._pb), ctypes.addressof(strides), int(splits or 0), sp)
-    _lib.check(rc, "mi355q_bfp_attention_decode_kv8")
-    return out
 
 
 def _extend_check(q, cache, lengths=None, counts=None, max_length=None, group=1, *, causal=True, window=None):
@@ -2165,68 +2075,13 @@ def bfp_attention_extend(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     `cache` may be a PagedKVCache (always with `lengths`): the bits of the same call on a KVCache holding the same keys.
     Sliding window (`window` = W >= 1, causal only) as bfp_attention_decode: row b's query i, at p = lengths[b] - counts[b] + i, sees
     keys max(0, p - W + 1) .. p; a block of 64 queries walks the keys from the 32-key step of its first query's lower bound on."""
-    import ctypes
     if isinstance(cache, PackedKVCache):
         raise NotImplementedError("mi355q.bfp_attention_extend: no extend kernel reads a PackedKVCache (int8 mantissas); chunked prefill "
                                   "needs a KVCache or a PagedKVCache")
     why = _extend_check(q, cache, lengths, counts, max_length, group, causal=causal, window=window)
     if why is not None:
         raise ValueError(f"mi355q.bfp_attention_extend: {why}")
-    M, D = q.shape[-2:]
-    q3, qsb, qsm = _as_heads_view(q)
-    if token_major and q.ndim == 4 and q.shape[0] == 1:
-        H = q.shape[1]
-        out = torch.empty(1, M, H, D, dtype=torch.float32, device=q.device).permute(0, 2, 1, 3)
-        osb, osm = D, H * D
-    else:
-        out = torch.empty(*q.shape, dtype=torch.float32, device=q.device)
-        osb, osm = M * D, D
-    strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
-    if window is not None:
-        paged = isinstance(cache, PagedKVCache)
-        wl, wmax = _window_lengths(cache, lengths, max_length)
-        with _on_device(q.device):
-            rc = _lib.load_library().mi355q_bfp_attention_extend_window(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), group, _ptr(wl), _ptr(counts),
-                                                                        _ptr(cache.block_table) if paged else None, 1, int(window),
-                                                                        float(q_scale) if q_scale else 0.0,
-                                                                        float(scale_div) if scale_div else 0.0, _ptr(out), cache.B, M, wmax,
-                                                                        cache.max_pages if paged else 1, cache.num_pages if paged else 1,
-                                                                        cache.page_size if paged else cache.capacity, D,
-                                                                        ctypes.addressof(cache._pa), ctypes.addressof(cache._pb),
-                                                                        ctypes.addressof(strides), _stream_ptr(q.device))
-        _lib.check(rc, "mi355q_bfp_attention_extend_window")
-        return out
-    if isinstance(cache, PagedKVCache):
-        with _on_device(q.device):
-            rc = _lib.load_library().mi355q_bfp_attention_extend_paged(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), group, _ptr(lengths), _ptr(counts),
-                                                                       _ptr(cache.block_table), int(bool(causal)),
-                                                                       float(q_scale) if q_scale else 0.0, float(scale_div) if scale_div else 0.0,
-                                                                       _ptr(out), cache.B, M, int(max_length), cache.max_pages, cache.num_pages,
-                                                                       cache.page_size, D, ctypes.addressof(cache._pa),
-                                                                       ctypes.addressof(cache._pb), ctypes.addressof(strides),
-                                                                       _stream_ptr(q.device))
-        _lib.check(rc, "mi355q_bfp_attention_extend_paged")
-        return out
-    if group != 1:
-        with _on_device(q.device):
-            rc = _lib.load_library().mi355q_bfp_attention_extend_grouped(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), group, _ptr(lengths),
-                                                                         _ptr(counts), int(bool(causal)), float(q_scale) if q_scale else 0.0,
-                                                                         float(scale_div) if scale_div else 0.0, _ptr(out), cache.B, M,
-                                                                         int(max_length) if lengths is not None else cache.length,
-                                                                         cache.capacity, D, ctypes.addressof(cache._pa),
-                                                                         ctypes.addressof(cache._pb), ctypes.addressof(strides),
-                                                                         _stream_ptr(q.device))
-        _lib.check(rc, "mi355q_bfp_attention_extend_grouped")
-        return out
-    with _on_device(q.device):
-        rc = _lib.load_library().mi355q_bfp_attention_extend(_ptr(q3), _ptr(cache.kq), _ptr(cache.vq), _ptr(lengths), _ptr(counts),
-                                                             int(bool(causal)), float(q_scale) if q_scale else 0.0,
-                                                             float(scale_div) if scale_div else 0.0, _ptr(out), cache.B, M,
-                                                             int(max_length) if lengths is not None else cache.length, cache.capacity, D,
-                                                             ctypes.addressof(cache._pa), ctypes.addressof(cache._pb),
-                                                             ctypes.addressof(strides), _stream_ptr(q.device))
-    _lib.check(rc, "mi355q_bfp_attention_extend")
-    return out
+    return _cached_attention("extend", q, cache, causal, scale_div, q_scale, token_major, None, lengths, counts, max_length, group, window)
 
 
 class TiledBf16:

@@ -92,18 +92,21 @@ def test_form_of():
 
 
 def test_form_of_follows_ops():
-    """the two facts form_of takes from ops.py, read there: group == 1 never reaches a grouped entry point with G = 1 (the *_grouped call
-    sits behind `group != 1`, the paged and windowed entry points turn G <= 1 into 0), and a windowed call always brings lengths"""
+    """the two facts form_of takes from ops.py, read there: group == 1 never reaches a grouped entry point with G = 1 (the *_grouped route
+    sits behind `group != 1` and behind the windowed and paged routes, whose entry points turn G <= 1 into 0 -- one line of the exports'
+    shared check, which spares only the *_grouped exports), and a windowed call always brings lengths"""
     import inspect
     import torch
     from mi355q import ops
+    src = inspect.getsource(ops._cached_attention)
+    assert src.index('"_window" if windowed') < src.index('"_paged" if paged') < src.index('"_grouped" if group != 1')
+    assert "_window_lengths(cache, lengths, max_length)" in src
     for fn in (ops.bfp_attention_decode, ops.bfp_attention_extend):
-        src = inspect.getsource(fn)
-        assert src.index("if window is not None:") < src.index("if paged:" if fn is ops.bfp_attention_decode else "if isinstance(cache, PagedKVCache):") \
-            < src.index("if group != 1:")
-        assert "_window_lengths(cache, lengths, max_length)" in src
+        assert "_cached_attention(" in inspect.getsource(fn)
+    check = (CSRC / "mi355q_kv_call.h").read_text()
+    assert len(re.findall(r"k\.G = \(d\.form & KV_GROUPED\) \|\| d\.G > 1 \? d\.G : 0;", check)) == 1       # decode / extend x paged / window / kv8
     api = (CSRC / "mi355q_api.hip").read_text()
-    assert len(re.findall(r"if \(G <= 1\) G = 0;", api)) == 4           # decode / extend x paged / window
+    assert len(re.findall(r"KV_EXPORTS\[KVX_(?:DECODE|EXTEND)_(?:PAGED|WINDOW)\]", api)) == 4 and "G = 0" not in api
     cache = ops.KVCache(2, 64, 64, U.par(6), U.par(6), "cpu")
     cache.length = 40
     lengths, max_length = ops._window_lengths(cache, None, None)
