@@ -724,6 +724,21 @@ int mi355q_bfp_attention_extend_paged(const float* q, const void* kq_pool, const
                                       int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
                                       void* stream);
 
+/* Copy-on-write for the paged cache: what a fork of a row at an arbitrary length, or a reorder of the rows (the reference's
+ * `_reorder_cache`: index_select over the batch), has to COPY -- full pages are shared through the table, by reference.
+ *   jobs: int32 [n_jobs][4] on the device, 16-byte aligned: (src_page, dst_page, src_row, dst_row) each.
+ *     src_page, dst_page >= 0: the whole page src_page of kq_pool and of vq_pool (P * D * 2 bytes each) becomes page dst_page; either
+ *       negative: no page copy.  Page ids are clamped into 0 .. num_pages - 1.
+ *     src_row, dst_row >= 0: the [16][D] fp32 stage rows of src_row in stage_src become those of dst_row in stage_dst; either negative:
+ *       no stage copy.  Rows are clamped into 0 .. B - 1.  stage_dst is a SECOND buffer of stage's shape, never stage_src itself (a
+ *       permutation of rows cannot be done in place): the caller passes stage_dst as `stage` from here on.
+ *   The jobs of one call must not name a page as the destination of one job and the source or destination of another, nor a row as
+ *   dst_row twice.  One launch, at most 65535 jobs (more: MI355Q_E_UNSUPPORTED); n_jobs == 0 returns 0 and launches nothing.
+ * MI355Q_E_BADARG: n_jobs < 0; B, num_pages < 1; P no power of two >= 32; D % 32 != 0 or D > 128; with n_jobs > 0 a NULL pool, stage
+ * or jobs pointer, or stage_src == stage_dst.  MI355Q_E_ALIGN: a pointer that is not 16-byte aligned. */
+int mi355q_bfp_kv_paged_copy(void* kq_pool, void* vq_pool, const float* stage_src, float* stage_dst, const int32_t* jobs, int64_t n_jobs,
+                             int64_t B, int64_t num_pages, int64_t P, int64_t D, void* stream);
+
 /* Int8-mantissa cache: the contiguous cache above with every quantised value stored as a signed mantissa BYTE plus one shared-exponent
  * byte per 16-value block -- 1 + 1/16 bytes a value, exactly 17/32 of mi355q_bfp_kv_cache_bytes' K and V bytes (the stage is the
  * same) and of a decode step's K / V traffic.  Layout: csrc/mi355q_kv8.h.  The kernels rebuild the bf16 MFMA fragments in registers,

@@ -16,6 +16,7 @@
 #include "mi355q_kv8.h"
 #include "mi355q_extend.h"
 #include "mi355q_kv_call.h"
+#include "mi355q_kv_copy.h"
 #include "mi355q_align_row.h"
 
 using namespace mi355q;
@@ -1175,6 +1176,15 @@ int mi355q_bfp_attention_extend_paged(const float* q, const void* kq_pool, const
     return extend(KvCall(KV_EXPORTS[KVX_EXTEND_PAGED]).pools(kq_pool, vq_pool, nullptr, block_table, B, max_pages, num_pages, P, D)
                       .lens(lengths, counts, max_length).query(q, out, nullptr, M, G, causal, 0, 0).quant(qk_params, pv_params, strides),
                   q, out, q_scale, scale_div, stream);
+}
+
+// copy-on-write (fork, reorder): whole pages and stage rows by a device list of jobs, one launch; its check is mi355q_kv_copy.h's
+int mi355q_bfp_kv_paged_copy(void* kq_pool, void* vq_pool, const float* stage_src, float* stage_dst, const int32_t* jobs, int64_t n_jobs,
+                             int64_t B, int64_t num_pages, int64_t P, int64_t D, void* stream) {
+    KvCopyArgs g;
+    int rc;
+    if (!kv_copy_check(kq_pool, vq_pool, stage_src, stage_dst, jobs, n_jobs, B, num_pages, P, D, g, rc)) return rc;
+    return launch_kv_paged_copy(g, stream);
 }
 
 // int8-mantissa cache: mantissa bytes and one exponent byte a block; always the ragged form, contiguous

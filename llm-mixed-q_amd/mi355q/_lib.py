@@ -97,6 +97,7 @@ SIGNATURES = {
                                                     _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp]),
     "mi355q_bfp_attention_extend_paged": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, C.c_float, C.c_float, _vp, _i64, _i64, _i64,
                                                     _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "mi355q_bfp_kv_paged_copy": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
     "mi355q_bfp_attention_decode_window_span": (C.c_int64, [_i64, _i64, _i64]),
     "mi355q_bfp_attention_decode_window_workspace_bytes": (C.c_size_t, [_i64, _i64, _i64, _i64, _i64, _i32]),
     "mi355q_bfp_attention_decode_window": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i64, C.c_float, C.c_float, _vp, _vp, _i64, _i64,

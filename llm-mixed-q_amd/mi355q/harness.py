@@ -559,6 +559,49 @@ class DecodeState:
         self.lengths[b] = 0
         self.length, self.ragged = max(self.lengths), True      # (from here on the rows differ in length: the ragged routes)
 
+    def _copy_check(self, what: str, seqs) -> list:
+        if not self.paged:
+            raise NotImplementedError(f"DecodeState.{what}: only a paged state can fork or reorder its sequences (page_size=...: full pages are "
+                                      "shared by reference, the contiguous caches would copy every row)")
+        if self._call is not None:
+            raise RuntimeError(f"DecodeState.{what} inside a cached call")
+        seqs = [int(b) for b in seqs]
+        if any(not 0 <= b < self.batch for b in seqs):
+            raise ValueError(f"DecodeState.{what}: sequences {seqs} outside 0 .. {self.batch - 1}")
+        return seqs
+
+    def fork(self, src, dst) -> None:
+        """sequence dst, which is empty, becomes a copy of sequence src where it stands (PagedKVCache.fork on the sequence's cache rows --
+        its KV heads -- in every layer; src, dst may be equal-length lists: one launch a layer).  Every layer is checked before any
+        changes: a fork the pools cannot serve raises RuntimeError and leaves the state as it was."""
+        one = isinstance(dst, int)
+        src, dst = self._copy_check("fork", [src] if one else src), self._copy_check("fork", [dst] if one else dst)
+        if len(src) != len(dst) or any(self.lengths[d] for d in dst):
+            raise ValueError(f"DecodeState.fork: {len(src)} sources for {len(dst)} sequences, which must be empty (lengths "
+                             f"{[self.lengths[d] for d in dst]})")
+        for dry in (True, False):
+            for c in self.kv:
+                heads = c.B // self.batch
+                rows = lambda seqs: [b * heads + h for b in seqs for h in range(heads)]
+                c.fork(rows(src), rows(dst), [self.lengths[b] for b in src for _ in range(heads)], dry_run=dry)
+        for s_, d in zip(src, dst):
+            self.lengths[d] = self.lengths[s_]
+        self.length, self.ragged = max(self.lengths), True
+
+    def reorder(self, beam_idx) -> None:
+        """sequence b becomes what sequence beam_idx[b] was -- the reference's `_reorder_cache(past_key_values, beam_idx)` -- in every layer
+        (PagedKVCache.reorder: one launch a layer), the host lengths with it.  Every layer is checked before any changes.  A
+        sliding-window state works unchanged: the partial page is the newest and never trimmed, trimmed pages stay trimmed."""
+        beam_idx = self._copy_check("reorder", beam_idx.tolist() if isinstance(beam_idx, torch.Tensor) else beam_idx)
+        if len(beam_idx) != self.batch:
+            raise ValueError(f"DecodeState.reorder: {len(beam_idx)} indices for a batch of {self.batch}")
+        for dry in (True, False):
+            for c in self.kv:
+                heads = c.B // self.batch
+                c.reorder([b * heads + h for b in beam_idx for h in range(heads)], [l for l in self.lengths for _ in range(heads)], dry_run=dry)
+        self.lengths = [self.lengths[b] for b in beam_idx]
+        self.length, self.ragged = max(self.lengths), True
+
     def position_end(self, n: int) -> int:
         """rows of the rotary tables a call with n new tokens reads"""
         return (max(self.lengths) if self._call is not None else self.length) + n
@@ -858,6 +901,64 @@ def generate(model, prompt_ids, new_tokens: int, mode: str = "block_fp", chunk: 
         if i + 1 < new_tokens:
             logits = model(tok, cache=state)[0][:, -1]
     return ids, torch.stack(steps, dim=1)
+
+
+@torch.no_grad()
+def beam_search(model, prompt_ids, new_tokens: int, num_beams: int, page_size: int = 32, num_pages: int = None, chunk: int = None):
+    """beam search on paged caches: ONE prefill of the B prompts, each then forked into its `num_beams` slots (PagedDecodeState.fork: the
+    prompt's full pages by reference, its partial page and open tile copied), and per step one cached call over B * num_beams rows,
+    log_softmax, the top num_beams of num_beams * vocab candidates per prompt, and `reorder(beam_idx)` -- the reference's
+    `_reorder_cache`, which here copies one partial page a row instead of every row's K and V.  Scores are sums of log-probabilities; no
+    length penalty and no EOS (the harness has none).  -> (ids [B, num_beams, T + new_tokens], scores [B, num_beams]), best beam first.
+    `prompt_ids` may be a list of 1-D id tensors of different lengths: ids is then a list of [num_beams, len_b + new_tokens].
+    `num_pages` (per layer) defaults to every cache row at its capacity plus the one page a row a reorder draws before it gives any back;
+    `chunk`: chunked prefill, as in generate."""
+    if page_size is None:
+        raise NotImplementedError("beam_search: page_size=None: only a paged state can fork or reorder its sequences")
+    if chunk is not None and int(chunk) < 1:
+        raise ValueError(f"beam_search: chunk = {chunk} < 1")
+    ragged = isinstance(prompt_ids, (list, tuple))
+    prompts = [p.reshape(-1) for p in prompt_ids]
+    lens, B, nb, dev = [int(p.numel()) for p in prompts], len(prompts), int(num_beams), prompts[0].device
+    if not 1 <= nb <= model.cfg.vocab_size or new_tokens < 1 or min(lens) < 1:
+        raise ValueError(f"beam_search: num_beams = {num_beams} outside 1 .. the vocabulary's {model.cfg.vocab_size}, new_tokens = {new_tokens} "
+                         f"< 1 or an empty prompt (lengths {lens})")
+    N, capacity = B * nb, max(lens) + new_tokens
+    if num_pages is None:
+        a = model.layers[0].self_attn
+        num_pages = N * getattr(a, "nkv", a.nh) * (-(-((capacity + 15) // 16 * 16) // int(page_size)) + 1)
+    state = PagedDecodeState(model, N, capacity, "block_fp", extend=chunk is not None, page_size=page_size, num_pages=num_pages)
+    # the prompts in slots 0, nb, 2 nb, ...; the other slots take no token
+    done, last, step = [0] * B, [None] * B, max(lens) if chunk is None else int(chunk)
+    while any(d < l for d, l in zip(done, lens)):
+        counts = [min(step, l - d) for d, l in zip(done, lens)]
+        ids = torch.zeros(N, max(counts), dtype=prompts[0].dtype, device=dev)
+        for b, p in enumerate(prompts):
+            ids[b * nb, :counts[b]] = p[done[b]:done[b] + counts[b]]
+        out = model(ids, cache=state, counts=[counts[s // nb] if s % nb == 0 else 0 for s in range(N)])[0]
+        for b, c in enumerate(counts):
+            done[b] += c
+            if c and done[b] == lens[b]:
+                last[b] = out[b * nb, c - 1]                   # (the prompt's last REAL position, in the call that ends it)
+    if nb > 1:
+        state.fork([b * nb for b in range(B) for _ in range(nb - 1)], [b * nb + j for b in range(B) for j in range(1, nb)])
+    logits = torch.stack(last)[:, None].expand(B, nb, -1)      # every beam of a prompt starts as the prompt
+    scores = torch.full((B, nb), float("-inf"), device=dev)
+    scores[:, 0] = 0.0                                         # (so the first step's candidates are beam 0's num_beams best tokens)
+    seqs, base = [p[None].expand(nb, -1) for p in prompts], torch.arange(B, device=dev)[:, None] * nb
+    for i in range(new_tokens):
+        V = logits.shape[-1]
+        cand = (F.log_softmax(logits.float(), dim=-1) + scores[..., None]).reshape(B, nb * V)
+        scores, idx = cand.topk(nb, dim=-1)                     # (sorted: best first)
+        beam, tok = idx // V, idx % V
+        seqs = [torch.cat([s_[beam[b]], tok[b][:, None].to(s_.dtype)], dim=1) for b, s_ in enumerate(seqs)]
+        if i + 1 < new_tokens:
+            if i:                                              # (after the first step the slots of a prompt still hold the same keys)
+                state.reorder((base + beam).reshape(-1))
+            logits = model(tok.reshape(N, 1).to(prompts[0].dtype), cache=state)[0][:, -1].reshape(B, nb, V)
+    for s in range(N):
+        state.release(s)
+    return (seqs if ragged else torch.stack(seqs)), scores
 
 
 @torch.no_grad()

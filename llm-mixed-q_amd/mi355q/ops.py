@@ -1642,7 +1642,13 @@ class PagedKVCache(_KVCacheBase):
     hold keys of the row).  Table entries behind a row's pages are never read; they hold `pad_page` (default 0).  With pad_page= given
     that page is kept out of the free list for good -- a null page no row ever writes.
     Sliding window: `trim(lengths, window)` gives back the pages wholly behind the window, so a windowed row holds O(window) pages.
-    The interface is ensure / trim / release / share_prefix / append / dequantised.  `assign`, `pad_page=`, `ensure(dry_run=)` and `pages_for`
+    Copy-on-write: `fork(src, dst, length)` gives row dst what row src holds at ANY length, `reorder(src_rows, lengths)` makes row b what
+    row src_rows[b] was (the reference's `_reorder_cache`: index_select over the batch).  Full pages move by reference; the row's last,
+    partially filled page and its stage rows are copied by ONE launch (csrc/mi355q_kv_copy.h) that writes the stage rows into
+    `stage_alt`, a second buffer of stage's shape, after which the two swap names: `stage` is always the one the kernels are given.
+    Both are eager calls between steps, not to be captured in a graph (the stage pointer alternates).  A reorder draws every private
+    page before any page returns to the free list: the pool needs up to one page a row beyond what the rows hold.
+    The interface is ensure / trim / release / share_prefix / fork / reorder / append / dequantised.  `assign`, `pad_page=`, `ensure(dry_run=)` and `pages_for`
     are helpers: the tests and the timing tool place pages by hand with `assign` (out-of-order tables, a poison page), the harness asks
     every layer with `dry_run` before it changes one.  `assign` filters the free list per call and is not meant for a hot loop."""
 
@@ -1654,6 +1660,8 @@ class PagedKVCache(_KVCacheBase):
         self._init_rows(int(B), int(D), qk_params, pv_params, device)
         self.pad_page = 0 if pad_page is None else int(pad_page)
         self.kq, self.vq, self.stage = self._zeroed("mi355q_bfp_kv_paged_bytes", self.num_pages, self.page_size, self.B, self.D)
+        self.stage_alt = torch.zeros_like(self.stage)       # fork / reorder write the stage rows here, then the two swap
+        self._jobs = torch.zeros(self.B, 4, dtype=torch.int32, device=self.device)
         self.table = torch.full((self.B, self.max_pages), self.pad_page, dtype=torch.int32)
         self.block_table = self.table.to(self.device)
         self.free = [p for p in range(self.num_pages - 1, -1, -1) if pad_page is None or p != self.pad_page]
@@ -1755,7 +1763,8 @@ class PagedKVCache(_KVCacheBase):
     def share_prefix(self, src: int, dst: int, pages: int) -> None:
         """row dst, which holds no page, points at row src's first `pages` pages (reference-counted): dst then holds the first
         pages * page_size keys of src -- set its length to that.  Whole, FULL pages only: the shared pages must lie wholly below both
-        rows' lengths from here on, since an append into a shared page would change the other row (there is no copy-on-write); K's
+        rows' lengths from here on, since an append into a shared page would change the other row (no copy is made here: `fork` is
+        the call that forks a row at any length); K's
         16-key blocks and V's blocks inside full pages are final, and the open tile of dst starts empty."""
         pages = int(pages)
         if src == dst or self.held[dst]:
@@ -1769,6 +1778,124 @@ class PagedKVCache(_KVCacheBase):
             self.table[dst, i] = p
             self.held[dst].append(p)
         self._upload()
+
+    def _plan_copy(self, pairs, what: str = "reorder"):
+        """The host half of fork / reorder, pure: reads no GPU and changes nothing.  pairs: (dst row, src row, length of src) -- every dst
+        becomes what src holds at `length` keys; rows that are no dst stay as they are.  -> a plan:
+          held   {dst: its new pages in logical order}: src's full pages below `length` by reference (None, a trimmed page, stays None),
+                 then -- length % page_size != 0 -- a private page DRAWN from the free list for a copy of src's partial page (dst == src
+                 keeps its own when no other row holds it).  Pages a dst held behind that are given up
+          refs   the reference counts after the call          drawn   the pages taken from the free list, in the order of the draws
+          freed  the pages whose count drops to 0, to be appended to the free list BEHIND the queued copy
+          jobs   (src_page, dst_page, src_row, dst_row) per dst with length > 0; (-1, -1, ...): no page to copy.  No dst_page is any job's
+                 src_page: every one is drawn from the free list as it stands before `freed` returns
+        ValueError for rows or lengths that do not fit; RuntimeError, naming the rows, the pages needed and the pages free, when the pool
+        is short."""
+        import types
+        name, P = f"PagedKVCache.{what}", self.page_size
+        pairs = [(int(d), int(s), int(n)) for d, s, n in pairs]
+        dsts = [d for d, _, _ in pairs]
+        if len(set(dsts)) != len(dsts) or any(not 0 <= r < self.B for d, s, _ in pairs for r in (d, s)):
+            raise ValueError(f"{name}: rows {[(d, s) for d, s, _ in pairs]} (dst, src) are not distinct dst rows inside 0 .. {self.B - 1}")
+        held, jobs, want = {}, [], {}
+        for d, s, n in pairs:
+            full, part = divmod(n, P)
+            if n < 0 or self.pages_for(n) > len(self.held[s]):
+                raise ValueError(f"{name}: row {s} holds {len(self.held[s])} pages, not the {self.pages_for(n)} of {n} keys")
+            row, page_job = list(self.held[s][:full]), (-1, -1)
+            if part:
+                sp = self.held[s][full]
+                if sp is None:
+                    raise ValueError(f"{name}: row {s}'s partial page (logical page {full}) is trimmed")
+                if d == s and self.refs[sp] == 1:
+                    row.append(sp)
+                else:
+                    want[d] = len(want)
+                    row.append(None)                        # (placed below, once the pool is known to have them all)
+                    page_job = (sp, d)
+            held[d] = row
+            if n > 0:
+                jobs.append((page_job, s, d))
+        if len(want) > len(self.free):
+            raise RuntimeError(f"{name}: rows {sorted(want)} need {len(want)} more pages, {len(self.free)} of {self.num_pages} are free")
+        drawn = [self.free[-1 - i] for i in range(len(want))]
+        for d, i in want.items():
+            held[d][-1] = drawn[i]
+        jobs = [(pj[0], -1 if pj[0] < 0 else drawn[want[pj[1]]], s, d) for pj, s, d in jobs]
+        refs = list(self.refs)
+        moved = [d for d in dsts if held[d] != self.held[d]]  # (a row that keeps its pages -- an identity with a private page -- counts nothing)
+        for d in moved:
+            for p in self.held[d]:
+                if p is not None:
+                    refs[p] -= 1
+        for d in moved:
+            for p in held[d]:
+                if p is not None:
+                    refs[p] += 1
+        old = dict.fromkeys(p for d in moved for p in self.held[d] if p is not None)
+        return types.SimpleNamespace(held=held, refs=refs, drawn=drawn, freed=[p for p in old if refs[p] == 0], jobs=jobs)
+
+    def _commit_plan(self, plan, free_now: bool = True) -> None:
+        """the host half of a plan: table rows, held lists, reference counts, free list (free_now=False: plan.freed stays out, for the
+        caller to append behind the queued copy).  No GPU call but the table's copy_."""
+        for d, row in plan.held.items():
+            if row != self.held[d]:
+                self.held[d] = list(row)
+                self.table[d] = torch.tensor([self.pad_page if p is None else p for p in row] + [self.pad_page] * (self.max_pages - len(row)),
+                                             dtype=torch.int32)
+        self.refs = list(plan.refs)
+        taken = set(plan.drawn)
+        self.free = [p for p in self.free if p not in taken] + (list(plan.freed) if free_now else [])
+        self._upload()
+
+    def _copy(self, plan, what: str, dry_run: bool) -> None:
+        """commit a plan and queue its ONE launch: the jobs with one copy_, the kernel, the stage buffers' swap, then plan.freed"""
+        if dry_run:
+            return
+        if not self.stage.is_cuda:
+            raise ValueError(f"PagedKVCache.{what}: the cache is not on a GPU; there is no CPU fallback")
+        self._commit_plan(plan, free_now=False)
+        if plan.jobs:
+            n = len(plan.jobs)
+            self._jobs[:n].copy_(torch.tensor(plan.jobs, dtype=torch.int32))
+            _kv_call(self.device, "mi355q_bfp_kv_paged_copy", (_ptr(self.kq), _ptr(self.vq), _ptr(self.stage), _ptr(self.stage_alt), _ptr(self._jobs),
+                                                               n, self.B, self.num_pages, self.page_size, self.D, _stream_ptr(self.device)))
+            self.stage, self.stage_alt = self.stage_alt, self.stage
+        self.free += plan.freed                             # (behind the copy in stream order: the next writer of such a page is a later launch)
+
+    def fork(self, src, dst, length, dry_run: bool = False) -> None:
+        """row dst, which holds no page, becomes a copy of row src at its `length` keys (a host int: the caller owns the lengths) -- set
+        dst's length to it.  dst refers to src's full pages below `length` (their counts go up; a trimmed one stays trimmed), gets a
+        freshly drawn page with a copy of src's partial page if length % page_size != 0, and src's stage rows: an append to either row
+        never shows in the other.  src is unchanged.  src, dst, length may be equal-length sequences -- several forks, still one launch.
+        Everything is checked before anything changes (ValueError; RuntimeError when the pool is short).  The stage buffers swap, so every
+        other row's stage rows travel with the same launch.  dry_run: the checks only."""
+        one = isinstance(dst, int)
+        src, dst, length = ([src], [dst], [length]) if one else (list(src), list(dst), list(length))
+        if not len(src) == len(dst) == len(length):
+            raise ValueError(f"PagedKVCache.fork: {len(src)} src rows, {len(dst)} dst rows, {len(length)} lengths")
+        busy = [int(d) for d in dst if 0 <= int(d) < self.B and self.held[int(d)]]
+        if busy or set(map(int, src)) & set(map(int, dst)):
+            raise ValueError(f"PagedKVCache.fork: rows {busy or sorted(set(map(int, src)) & set(map(int, dst)))} hold pages or are their own "
+                             "source (only a row that holds none can become a fork)")
+        plan = self._plan_copy(zip(dst, src, length), "fork")
+        rest = set(range(self.B)) - set(plan.held)
+        plan.jobs += [(-1, -1, b, b) for b in sorted(rest)]  # (the other rows' open tiles: into the buffer that is `stage` from here on)
+        self._copy(plan, "fork", dry_run)
+
+    def reorder(self, src_rows, lengths, dry_run: bool = False) -> None:
+        """row b becomes what row src_rows[b] was -- the reference's `_reorder_cache`, index_select(0, beam_idx), without moving K or V:
+        full pages change hands in the table, every new row gets a private copy of its source's partial page (a row that stays itself
+        keeps its own) and its stage rows, by ONE launch.  lengths: the rows' CURRENT lengths (host ints, one per cache row, BEFORE the
+        reorder; permute them as the rows).  Pages nobody holds afterwards return to the free list behind the copy.  Every private page is
+        drawn before that, so the pool needs up to one free page per row with a partial page; RuntimeError, before anything changes,
+        when it has not.  Afterwards `stage` is the buffer just written.  dry_run: the checks only."""
+        src_rows, lengths = [int(s) for s in src_rows], [int(n) for n in lengths]
+        if len(src_rows) != self.B or len(lengths) != self.B:
+            raise ValueError(f"PagedKVCache.reorder: {len(src_rows)} source rows and {len(lengths)} lengths for {self.B} cache rows")
+        if any(not 0 <= s < self.B for s in src_rows):
+            raise ValueError(f"PagedKVCache.reorder: source rows {src_rows} outside 0 .. {self.B - 1}")
+        self._copy(self._plan_copy([(b, s, lengths[s]) for b, s in enumerate(src_rows)]), "reorder", dry_run)
 
     def reset(self) -> None:
         self.release(range(self.B))
