@@ -749,7 +749,7 @@ int mi355q_bfp_kv_paged_copy(void* kq_pool, void* vq_pool, const float* stage_sr
  * MI355Q_E_UNSUPPORTED; the x sides (Q, P) stay 2 .. 9.  v8 must be zeroed once before the first append, as vq above.
  * Always the ragged form (`lengths` mandatory, `counts` / max_length as in the *_ragged calls); G = 0 or 1 is the ungrouped form,
  * G > 1 as in mi355q_bfp_attention_decode_grouped (q / out hold B * G rows; workspace and splits those of the launch rows).  The
- * workspace is mi355q_bfp_attention_decode_workspace_bytes'.  No paged, windowed or extend form reads this cache. */
+ * workspace is mi355q_bfp_attention_decode_workspace_bytes'.  No windowed or extend form reads this cache; its paged form is below. */
 int mi355q_bfp_kv8_cache_bytes(int64_t B, int64_t C, int64_t D, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_bytes);
 int mi355q_bfp_kv8_append(void* k8, void* v8, float* stage, const float* k, const float* v, const int32_t* lengths,
                           const int32_t* counts, int64_t B, int64_t C, int64_t D, int64_t n, int64_t max_length,
@@ -760,6 +760,33 @@ int mi355q_bfp_attention_decode_kv8(const float* q, const void* k8, const void* 
                                     float q_scale, float scale_div, float* out, void* workspace, int64_t B, int64_t M,
                                     int64_t max_length, int64_t C, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
                                     const int64_t* strides, int32_t splits, void* stream);
+
+/* Int8-mantissa cache in PAGES: the pools of the paged cache above, in the same page order, holding the 544-byte pieces of the int8-mantissa
+ * cache (csrc/mi355q_kv8.h):  k8_pool [num_pages][P / 16][D / 32][544],  v8_pool [num_pages][P / 32][D / 16][544]  -- a page of either pool
+ * is P * D * 17 / 16 bytes (mi355q_bfp_kv8_paged_bytes; exactly 17/32 of mi355q_bfp_kv_paged_bytes' K and V bytes), stage stays
+ * [B][16][D] fp32 per row, block_table is the paged cache's int32 [B][max_pages].  Only a piece's place goes through the table, page ids
+ * are clamped into 0 .. num_pages - 1 (a wrong table gives wrong numbers, never an address outside the pools), and only logical pages
+ * that hold keys of the row are looked up.  Arguments are those of the *_paged calls plus, for decode_fp32, the quantiser words the
+ * kv8 call takes; codes are theirs (MI355Q_E_BADARG for a bad page size or max_length (+ n) > max_pages * P) and MI355Q_E_UNSUPPORTED
+ * for a cached operand of width 9, before the "nothing to do" return of 0.  append / decode_fp32 / decode give the bits of the
+ * contiguous int8-mantissa calls -- and with them those of the bf16 caches -- on the same keys (decode: same number of splits).
+ * mi355q_bfp_kv8_paged_copy is mi355q_bfp_kv_paged_copy on these pools: same jobs, same codes in the same order, pages of
+ * P * D * 17 / 16 bytes.  There is NO extend and NO windowed form on these pools. */
+int mi355q_bfp_kv8_paged_bytes(int64_t num_pages, int64_t P, int64_t B, int64_t D, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_bytes);
+int mi355q_bfp_kv8_append_paged(void* k8_pool, void* v8_pool, float* stage, const float* k, const float* v, const int32_t* lengths,
+                                const int32_t* counts, const int32_t* block_table, int64_t B, int64_t max_pages, int64_t num_pages,
+                                int64_t P, int64_t D, int64_t n, int64_t max_length, const int32_t* qk_params, const int32_t* pv_params,
+                                const int64_t* strides, void* stream);
+int mi355q_bfp_kv8_decode_fp32_paged(const void* k8_pool, const void* v8_pool, const int32_t* lengths, const int32_t* block_table,
+                                     float* k_out, float* v_out, int64_t B, int64_t max_pages, int64_t num_pages, int64_t P, int64_t D,
+                                     int64_t max_length, const int32_t* qk_params, const int32_t* pv_params, void* stream);
+int mi355q_bfp_attention_decode_kv8_paged(const float* q, const void* k8_pool, const void* v8_pool, int32_t G, const int32_t* lengths,
+                                          const int32_t* block_table, int32_t causal, float q_scale, float scale_div, float* out,
+                                          void* workspace, int64_t B, int64_t M, int64_t max_length, int64_t max_pages, int64_t num_pages,
+                                          int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
+                                          int32_t splits, void* stream);
+int mi355q_bfp_kv8_paged_copy(void* k8_pool, void* v8_pool, const float* stage_src, float* stage_dst, const int32_t* jobs, int64_t n_jobs,
+                              int64_t B, int64_t num_pages, int64_t P, int64_t D, void* stream);
 
 /* Sliding window: decode and extend with every query bound to its last `window` = W >= 1 keys, its own included -- a query at absolute
  * position p (decode: L_b - M + i; extend: L_b - m_b + i) sees keys max(0, p - W + 1) .. p.  That is the `past_key_value` call with an

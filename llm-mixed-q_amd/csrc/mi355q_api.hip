@@ -1013,9 +1013,9 @@ int sizes(const KvCall& d, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_by
     KvChecked c;
     int rc;
     if (!kv_call_check(d, c, rc)) return rc;
-    const int64_t rows = d.storage == KV_PAGED ? d.num_pages : d.B, keys = d.storage == KV_PAGED ? d.P : d.C;      // (a page is a cache row of P keys)
-    *k_bytes = d.storage == KV_INT8 ? kv8_k_bytes(rows, keys, d.D) : kv_k_bytes(rows, keys, d.D);
-    *v_bytes = d.storage == KV_INT8 ? kv8_v_bytes(rows, keys, d.D) : kv_v_bytes(rows, keys, d.D);
+    const int64_t rows = kv_paged(d.storage) ? d.num_pages : d.B, keys = kv_paged(d.storage) ? d.P : d.C;      // (a page is a cache row of P keys)
+    *k_bytes = kv_int8(d.storage) ? kv8_k_bytes(rows, keys, d.D) : kv_k_bytes(rows, keys, d.D);
+    *v_bytes = kv_int8(d.storage) ? kv8_v_bytes(rows, keys, d.D) : kv_v_bytes(rows, keys, d.D);
     *stage_bytes = kv_stage_bytes(d.B, d.D);
     return 0;
 }
@@ -1023,8 +1023,8 @@ int append(const KvCall& d, const float* k, const float* v, void* stream) {
     KvChecked c;
     int rc;
     if (!kv_call_check(d, c, rc)) return rc;
-    if (d.storage == KV_INT8)
-        return launch_kv8_append(c.c8, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.lengths, d.counts, d.n, hs(stream));
+    if (kv_int8(d.storage))
+        return launch_kv8_append(c.c8, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.lengths, d.counts, d.n, hs(stream), c.pages);
     if (!(d.form & KV_LENGTHS)) return launch_kv_append(c.c, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.L, d.n, hs(stream));
     return launch_kv_append_ragged(c.c, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.lengths, d.counts, d.n, hs(stream), c.pages);
 }
@@ -1032,16 +1032,16 @@ int dequantise(const KvCall& d, float* k_out, float* v_out, void* stream) {
     KvChecked c;
     int rc;
     if (!kv_call_check(d, c, rc)) return rc;
-    if (d.storage == KV_INT8) return launch_kv8_decode_fp32(c.c8, c.ak, c.av, k_out, v_out, d.L, d.lengths, hs(stream));
+    if (kv_int8(d.storage)) return launch_kv8_decode_fp32(c.c8, c.ak, c.av, k_out, v_out, d.L, d.lengths, hs(stream), c.pages);
     return launch_kv_decode_fp32(c.c, k_out, v_out, d.L, hs(stream), d.lengths, c.pages);
 }
 int decode(const KvCall& d, const float* q, float* out, void* workspace, float q_scale, float scale_div, void* stream) {
     KvChecked c;
     int rc;
     if (!kv_call_check(d, c, rc)) return rc;
-    if (d.storage == KV_INT8)
+    if (kv_int8(d.storage))
         return launch_bfp_attention_decode_kv8(c.aq, c.ap, c.ak, c.av, c.c8, q, out, workspace, d.M, d.L, c.causal, q_scale, scale_div, c.strides,
-                                               d.splits, hs(stream), d.lengths, c.G);
+                                               d.splits, hs(stream), d.lengths, c.G, c.pages);
     return launch_bfp_attention_decode(c.aq, c.ap, c.c, q, out, workspace, d.M, d.L, c.causal, q_scale, scale_div, c.strides, d.splits, hs(stream),
                                        d.lengths, c.G, c.pages, c.window);
 }
@@ -1183,7 +1183,7 @@ int mi355q_bfp_kv_paged_copy(void* kq_pool, void* vq_pool, const float* stage_sr
                              int64_t B, int64_t num_pages, int64_t P, int64_t D, void* stream) {
     KvCopyArgs g;
     int rc;
-    if (!kv_copy_check(kq_pool, vq_pool, stage_src, stage_dst, jobs, n_jobs, B, num_pages, P, D, g, rc)) return rc;
+    if (!kv_copy_check(kq_pool, vq_pool, stage_src, stage_dst, jobs, n_jobs, B, num_pages, P, D, false, g, rc)) return rc;
     return launch_kv_paged_copy(g, stream);
 }
 
@@ -1212,6 +1212,46 @@ int mi355q_bfp_attention_decode_kv8(const float* q, const void* k8, const void* 
                                     const int64_t* strides, int32_t splits, void* stream) {
     return decode(KvCall(KV_EXPORTS[KVX_DECODE_KV8]).cache(k8, v8, nullptr, B, C, D).lens(lengths, nullptr, max_length)
                       .query(q, out, workspace, M, G, causal, 0, splits).quant(qk_params, pv_params, strides), q, out, workspace, q_scale, scale_div, stream);
+}
+
+// int8-mantissa cache in pages: the pools of the paged cache holding the 544-byte pieces above; always the ragged form, no extend, no window
+int mi355q_bfp_kv8_paged_bytes(int64_t num_pages, int64_t P, int64_t B, int64_t D, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_bytes) {
+    return sizes(KvCall(KV_EXPORTS[KVX_KV8P_BYTES]).pools(nullptr, nullptr, nullptr, nullptr, B, 0, num_pages, P, D).sizes(k_bytes, v_bytes, stage_bytes),
+                 k_bytes, v_bytes, stage_bytes);
+}
+
+int mi355q_bfp_kv8_append_paged(void* k8_pool, void* v8_pool, float* stage, const float* k, const float* v, const int32_t* lengths,
+                                const int32_t* counts, const int32_t* block_table, int64_t B, int64_t max_pages, int64_t num_pages,
+                                int64_t P, int64_t D, int64_t n, int64_t max_length, const int32_t* qk_params, const int32_t* pv_params,
+                                const int64_t* strides, void* stream) {
+    return append(KvCall(KV_EXPORTS[KVX_KV8P_APPEND]).pools(k8_pool, v8_pool, stage, block_table, B, max_pages, num_pages, P, D).rows(k, v, n)
+                      .lens(lengths, counts, max_length).quant(qk_params, pv_params, strides), k, v, stream);
+}
+
+int mi355q_bfp_kv8_decode_fp32_paged(const void* k8_pool, const void* v8_pool, const int32_t* lengths, const int32_t* block_table,
+                                     float* k_out, float* v_out, int64_t B, int64_t max_pages, int64_t num_pages, int64_t P, int64_t D,
+                                     int64_t max_length, const int32_t* qk_params, const int32_t* pv_params, void* stream) {
+    return dequantise(KvCall(KV_EXPORTS[KVX_KV8P_DECODE_FP32]).pools(k8_pool, v8_pool, nullptr, block_table, B, max_pages, num_pages, P, D)
+                          .rows(k_out, v_out, 0).lens(lengths, nullptr, max_length).quant(qk_params, pv_params, nullptr), k_out, v_out, stream);
+}
+
+int mi355q_bfp_attention_decode_kv8_paged(const float* q, const void* k8_pool, const void* v8_pool, int32_t G, const int32_t* lengths,
+                                          const int32_t* block_table, int32_t causal, float q_scale, float scale_div, float* out,
+                                          void* workspace, int64_t B, int64_t M, int64_t max_length, int64_t max_pages, int64_t num_pages,
+                                          int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
+                                          int32_t splits, void* stream) {
+    return decode(KvCall(KV_EXPORTS[KVX_KV8P_DECODE]).pools(k8_pool, v8_pool, nullptr, block_table, B, max_pages, num_pages, P, D)
+                      .lens(lengths, nullptr, max_length).query(q, out, workspace, M, G, causal, 0, splits).quant(qk_params, pv_params, strides),
+                  q, out, workspace, q_scale, scale_div, stream);
+}
+
+// its copy-on-write: mi355q_bfp_kv_paged_copy's kernel and check on pages of P * D * 17 / 16 bytes
+int mi355q_bfp_kv8_paged_copy(void* k8_pool, void* v8_pool, const float* stage_src, float* stage_dst, const int32_t* jobs, int64_t n_jobs,
+                              int64_t B, int64_t num_pages, int64_t P, int64_t D, void* stream) {
+    KvCopyArgs g;
+    int rc;
+    if (!kv_copy_check(k8_pool, v8_pool, stage_src, stage_dst, jobs, n_jobs, B, num_pages, P, D, true, g, rc)) return rc;
+    return launch_kv_paged_copy(g, stream);
 }
 
 // sliding window: a query sees its last `window` keys; always the ragged form, paged or (block_table == NULL) contiguous
@@ -1264,7 +1304,7 @@ __attribute__((visibility("default"))) int mi355q_debug_kv_call(int32_t id, cons
     KvChecked c;
     int rc;
     const bool go = kv_call_check(d, c, rc);
-    const int64_t cap = d.storage == KV_INT8 ? c.c8.C : c.c.C;
+    const int64_t cap = kv_int8(d.storage) ? c.c8.C : c.c.C;
     const int64_t words[18] = {rc, go, d.B, cap, d.D, d.M, d.L, d.n, c.G, c.window, c.pg.lg_p, c.pages != nullptr, c.causal, c.strides != nullptr,
                                c.st[0], c.st[1], c.st[2], c.st[3]};
     for (int i = 0; i < 18; ++i) out[i] = words[i];

@@ -55,14 +55,6 @@ struct AppendArgs {
     KvPages pg;                 // paged cache (PG): c.kq / c.vq are the pools, c.C = max_pages * P; else zeros
 };
 
-// Paged cache: the table entry of row b's logical page i as loaded (pg_raw: i must be a page that holds keys of the row), and the
-// physical tile (sh = lg_p - 4) or pair (sh = lg_p - 5) of logical tile / pair t from it -- the page id clamped into the pool first.
-__device__ __forceinline__ int pg_raw(const KvPages& p, long long b, long long i) { return p.table[b * p.max_pages + i]; }
-__device__ __forceinline__ long long pg_place(const KvPages& p, int raw, long long t, int sh) {
-    const long long page = min(max(raw, 0), p.num_pages - 1);
-    return (page << sh) + (t & ((1ll << sh) - 1));
-}
-
 // one block of 16 values x with maximum bmax, quantised: value e is the low halfword of a lane's slot, 8 halfwords apart in kq
 // (the 16 keys of a tile at one d) and in vq (the 16 d of one key) alike
 __device__ __forceinline__ void kv_store_block(uint16_t* __restrict__ dst, const float (&x)[16], float bmax, const QuantArgs& a) {

@@ -1,5 +1,5 @@
 // Device helpers the decode kernels of mi355q_decode.hip (bf16 cache) and mi355q_kv8.hip (int8-mantissa cache) share: a ragged row's
-// (length, count) of an append, and what a lane of the split-key decode kernels knows of its column -- horizon, length, the grouped
+// (length, count) of an append, a paged cache's table lookup, and what a lane of the split-key decode kernels knows of its column -- horizon, length, the grouped
 // column map.  Layout notes: mi355q_decode.h.
 #ifndef MI355Q_DECODE_DEV_H
 #define MI355Q_DECODE_DEV_H
@@ -17,6 +17,14 @@ __device__ __forceinline__ bool append_row(const Args& a, long long b, long long
     L = max(__builtin_amdgcn_readfirstlane(a.lengths[b]), 0);
     if (a.counts) n = min((long long)max(__builtin_amdgcn_readfirstlane(a.counts[b]), 0), a.n);
     return n > 0;
+}
+
+// Paged cache: the table entry of row b's logical page i as loaded (pg_raw: i must be a page that holds keys of the row), and the
+// physical tile (sh = lg_p - 4) or pair (sh = lg_p - 5) of logical tile / pair t from it -- the page id clamped into the pool first.
+__device__ __forceinline__ int pg_raw(const KvPages& p, long long b, long long i) { return p.table[b * p.max_pages + i]; }
+__device__ __forceinline__ long long pg_place(const KvPages& p, int raw, long long t, int sh) {
+    const long long page = min(max(raw, 0), p.num_pages - 1);
+    return (page << sh) + (t & ((1ll << sh) - 1));
 }
 
 // this lane's horizon: the last key its query (column c16 of the MFMA tiles) sees

@@ -29,9 +29,24 @@
 // exponent cannot hold that, and this cache stores 0 there -- a stored value moves by at most 1e-8.  An all-zero block stores zero
 // mantissas and the exponent code of the lowest exponent.
 //
-// Kernels: ragged forms only (a device lengths array; the Python layer supplies one for the uniform call), no pages, no window, no
-// extend.  Pages of whole pieces would carry over unchanged (P >= 32 keeps a piece inside a page).  The decode kernels are the
-// RG = true, PG = false, WN = false kernels of mi355q_decode.hip with another way of getting a K or V fragment into registers; split
+// Paged pools (PG = true kernels; `pages` of the launchers): the pools of mi355q_decode.h's paged cache in the same page order, of these
+// pieces -- num_pages pages of P keys, P a power of two >= 32, so a piece (16 keys of K, 32 keys of V) never straddles a page:
+//   k8_pool [num_pages][P / 16][D / 32][544]     v8_pool [num_pages][P / 32][D / 16][544]     table int32 [B][max_pages]
+// A page of either pool is P D 17 / 16 bytes, P D 17 / 256 units of 16 bytes (a whole number: P D is a multiple of 1024; 68 at
+// P = D = 32), the unit of the copy-on-write launch (mi355q_kv_copy.h).  Only a piece's PLACE changes: logical K tile t sits at tile
+// pg_place(pg, pg_raw(pg, b, t >> (lg_p - 4)), t, lg_p - 4), logical V pair s the same with lg_p - 5 (mi355q_decode_dev.h); the page id is
+// clamped into the pool, so a wrong table gives wrong numbers and never an address outside the pools.  A kernel looks up only logical
+// pages that hold keys of the row (the append: the pages of its new keys, which the host has given the row before); Kv8Cache.C is
+// max_pages * P there.  stage stays per row, the scores workspace stays indexed by LOGICAL tile, and nothing else of a kernel changes:
+// split partition, statistics and the order of every sum are the contiguous kernels', so the paged decode gives their bits -- and with
+// them those of the bf16 caches -- by construction.  A recycled page pairs stale mantissas with stale exponent bytes: any such pair
+// rebuilds to a finite value, which is all a slot behind a row's length needs.  The append stores single BYTES into pieces that
+// neighbouring threads of the same launch write too (16 keys of a tile share a piece with the other d): byte stores never read, so no
+// thread's store can undo another's -- do not widen them into read-modify-write words.
+//
+// Kernels: ragged forms only (a device lengths array; the Python layer supplies one for the uniform call), no window, no
+// extend.  The decode kernels are the
+// RG = true, WN = false kernels of mi355q_decode.hip with another way of getting a K or V fragment into registers; split
 // partition, workspace, Q / P quantisers, softmax, (-inf, 0) paths and the grouped column map are theirs, phase C is theirs unchanged.
 #ifndef MI355Q_KV8_H
 #define MI355Q_KV8_H
@@ -59,15 +74,16 @@ inline long long kv8_v_bytes(long long B, long long C, long long D) { return B *
 // (ak / av: the quantisers of the cached operands, width <= 8)
 int launch_kv8_append(const Kv8Cache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
                       long long kst, long long vsb, long long vst, const int32_t* lengths, const int32_t* counts, long long n,
-                      hipStream_t st);
+                      hipStream_t st, const KvPages* pages = nullptr);
 // the cache's values, as the decode kernels rebuild them, back as fp32 [B, L, D]; zeros behind row b's lengths[b]
 int launch_kv8_decode_fp32(const Kv8Cache& c, const QuantArgs& ak, const QuantArgs& av, float* k_out, float* v_out, long long L,
-                           const int32_t* lengths, hipStream_t st);
+                           const int32_t* lengths, hipStream_t st, const KvPages* pages = nullptr);
 // launch_bfp_attention_decode's ragged forms on the packed cache: L = max_length, G >= 1 the grouped form, G == 0 one query row a
-// cache row; workspace and splits as there
+// cache row; workspace and splits as there.  pages != NULL: c.k8 / c.v8 are the paged pools, c.C = max_pages * P
 int launch_bfp_attention_decode_kv8(const QuantArgs& aq, const QuantArgs& ap, const QuantArgs& ak, const QuantArgs& av, const Kv8Cache& c,
                                     const float* q, float* out, void* workspace, long long M, long long L, int causal, float q_scale,
-                                    float scale_div, const long long* strides, int splits, hipStream_t st, const int32_t* lengths, int G);
+                                    float scale_div, const long long* strides, int splits, hipStream_t st, const int32_t* lengths, int G,
+                                    const KvPages* pages = nullptr);
 
 }  // namespace mi355q
 #endif

@@ -12,6 +12,10 @@
 //                            piece.  Phase C is decode_sum_kernel itself (launch_decode_sum): it reads no K / V.
 // Workspace, split partition, statistics and the order of every sum are those of mi355q_decode.hip, so a decode gives the bits of the
 // bf16 cache's decode with the same number of splits.
+// Paged pools (PG = true; layout and address rules: mi355q_kv8.h): every kernel here takes the flag, and with it only a piece's PLACE
+// changes -- pg_place of the row's table entry (mi355q_decode_dev.h), the page id clamped into the pool -- exactly as PG does in
+// mi355q_decode.hip: the decode loops ask for the NEXT tile's (pair's) entry while this one's two 8-byte loads are in flight and keep
+// it scalar.  PG = false is the code this file had before there were pages (profiles/decode_kv8_paged_isa.txt).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -35,6 +39,7 @@ struct Append8Args {
     int kblocks;
     const int32_t* lengths;     // row b's L = lengths[b], its n = counts[b] (NULL: n) <= n
     const int32_t* counts;
+    KvPages pg;                 // paged pools (PG): c.k8 / c.v8 are the pools, c.C = max_pages * P; else zeros (behind every other field)
 };
 
 // one block of 16 values x with maximum bmax: mantissa e is the byte of a lane's slot, 8 bytes apart in k8 (the 16 keys of a tile at
@@ -51,6 +56,7 @@ __device__ __forceinline__ void kv8_store_block(uint8_t* __restrict__ dst, uint8
     *code = (uint8_t)(p + a.code_bias);                                                        // (e_min = -bias: 0 .. 2^exponent width - 1)
 }
 
+template <bool PG>
 __global__ __launch_bounds__(256) void kv8_append_kernel(const QuantArgs ak, const QuantArgs av, const Append8Args a) {
     const int tid = threadIdx.x, D = a.c.D;
     const long long b = blockIdx.y, NTC = a.c.C >> 4, NPC = (a.c.C + 31) >> 5;
@@ -84,7 +90,9 @@ __global__ __launch_bounds__(256) void kv8_append_kernel(const QuantArgs ak, con
             }
         }
         const int c = d >> 5, g = (d >> 3) & 3, j = d & 7;
-        uint8_t* __restrict__ piece = a.c.k8 + ((b * NTC + t) * (D >> 5) + c) * KV8_PIECE;
+        long long pt = b * NTC + t;
+        if constexpr (PG) pt = pg_place(a.pg, pg_raw(a.pg, b, t >> (a.pg.lg_p - 4)), t, a.pg.lg_p - 4);     // (t < NTC: inside the table's row)
+        uint8_t* __restrict__ piece = a.c.k8 + (pt * (D >> 5) + c) * KV8_PIECE;
         kv8_store_block(piece + 16 * g * 8 + j, piece + 512 + (d & 31), x, bmax, ak);
     } else {
         // V: thread (new key, 16-d block) quantises one block
@@ -104,7 +112,9 @@ __global__ __launch_bounds__(256) void kv8_append_kernel(const QuantArgs ak, con
         }
         const long long s = key >> 5;
         const int h = (int)(key >> 4) & 1, g = (int)(key & 15) >> 2, j = 4 * h + (int)(key & 3);
-        uint8_t* __restrict__ piece = a.c.v8 + ((b * NPC + s) * DT + dt) * KV8_PIECE;
+        long long ps = b * NPC + s;
+        if constexpr (PG) ps = pg_place(a.pg, pg_raw(a.pg, b, s >> (a.pg.lg_p - 5)), s, a.pg.lg_p - 5);     // (key < C: inside the table's row)
+        uint8_t* __restrict__ piece = a.c.v8 + (ps * DT + dt) * KV8_PIECE;
         kv8_store_block(piece + 16 * g * 8 + j, piece + 512 + 8 * g + j, x, bmax, av);
     }
 }
@@ -112,7 +122,7 @@ __global__ __launch_bounds__(256) void kv8_append_kernel(const QuantArgs ak, con
 // Grids from n alone, as launch_kv_append_ragged's: n keys touch at most (n + 14) / 16 + 1 tiles wherever they start.
 int launch_kv8_append(const Kv8Cache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
                       long long kst, long long vsb, long long vst, const int32_t* lengths, const int32_t* counts, long long n,
-                      hipStream_t st) {
+                      hipStream_t st, const KvPages* pages) {
     Append8Args a{};
     a.c = c; a.k = k; a.v = v;
     a.ksb = ksb; a.kst = kst; a.vsb = vsb; a.vst = vst;
@@ -121,7 +131,13 @@ int launch_kv8_append(const Kv8Cache& c, const QuantArgs& ak, const QuantArgs& a
     const long long kblocks = ((n + 14) / 16 + 1 + per - 1) / per, vblocks = (n * (c.D / 16) + 255) / 256;
     if (kblocks + vblocks > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
     a.kblocks = (int)kblocks;
-    hipLaunchKernelGGL(kv8_append_kernel, dim3((unsigned)(kblocks + vblocks), (unsigned)c.B), dim3(256), 0, st, ak, av, a);
+    const dim3 grid((unsigned)(kblocks + vblocks), (unsigned)c.B);
+    if (pages) {
+        a.pg = *pages;
+        hipLaunchKernelGGL(kv8_append_kernel<true>, grid, dim3(256), 0, st, ak, av, a);
+    } else {
+        hipLaunchKernelGGL(kv8_append_kernel<false>, grid, dim3(256), 0, st, ak, av, a);
+    }
     launch_kv_stage_ragged(KvCache{nullptr, nullptr, c.stage, c.B, c.C, c.D}, k, ksb, kst, lengths, counts, n, st);
     return (int)hipGetLastError();
 }
@@ -148,8 +164,10 @@ __device__ __forceinline__ bf16x8 kv8_rebuild(uint2 m, uint2 e, int down) {
     return __builtin_bit_cast(bf16x8, pk);
 }
 
-__global__ __launch_bounds__(256) void kv8_decode_fp32_kernel(const Kv8Cache c, const int k_down, const int v_down, float* __restrict__ k_out,
-                                                              float* __restrict__ v_out, long long L, const int32_t* __restrict__ lengths) {
+template <bool PG>
+__device__ __forceinline__ void kv8_decode_fp32_body(const Kv8Cache& c, const int k_down, const int v_down, float* __restrict__ k_out,
+                                                     float* __restrict__ v_out, long long L, const int32_t* __restrict__ lengths,
+                                                     const KvPages& pg) {
     const int D = c.D;
     const long long b = blockIdx.y, NTC = c.C >> 4, NPC = (c.C + 31) >> 5;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -164,6 +182,11 @@ __global__ __launch_bounds__(256) void kv8_decode_fp32_kernel(const Kv8Cache c, 
     const uint8_t* __restrict__ kp = c.k8 + ((b * NTC + (key >> 4)) * (D >> 5) + (d >> 5)) * KV8_PIECE;
     const int h = (int)(key >> 4) & 1, g = (int)(key & 15) >> 2, j = 4 * h + (int)(key & 3);
     const uint8_t* __restrict__ vp = c.v8 + ((b * NPC + (key >> 5)) * (D >> 4) + (d >> 4)) * KV8_PIECE;
+    if constexpr (PG) {                                               // (key < lengths[b], key < L <= C: a page of the row's)
+        const int raw = pg_raw(pg, b, key >> pg.lg_p);
+        kp = c.k8 + (pg_place(pg, raw, key >> 4, pg.lg_p - 4) * (D >> 5) + (d >> 5)) * KV8_PIECE;
+        vp = c.v8 + (pg_place(pg, raw, key >> 5, pg.lg_p - 5) * (D >> 4) + (d >> 4)) * KV8_PIECE;
+    }
     const float kf = kv8_value(kp[((key & 15) + 16 * ((d >> 3) & 3)) * 8 + (d & 7)], kp[512 + (d & 31)], k_down);
     const float vf = kv8_value(vp[((d & 15) + 16 * g) * 8 + j], vp[512 + 8 * g + j], v_down);
     // through bf16, as the decode kernels' fragments are
@@ -171,25 +194,37 @@ __global__ __launch_bounds__(256) void kv8_decode_fp32_kernel(const Kv8Cache c, 
     v_out[(b * L + key) * D + d] = __uint_as_float(pack_bf16(vf, 0.f) << 16);
 }
 
+// (two entry points, one body, as kv_decode_fp32_kernel has: the unpaged kernel keeps its argument list and its code)
+__global__ __launch_bounds__(256) void kv8_decode_fp32_kernel(const Kv8Cache c, const int k_down, const int v_down, float* __restrict__ k_out,
+                                                              float* __restrict__ v_out, long long L, const int32_t* __restrict__ lengths) {
+    kv8_decode_fp32_body<false>(c, k_down, v_down, k_out, v_out, L, lengths, KvPages{});
+}
+__global__ __launch_bounds__(256) void kv8_decode_fp32_paged_kernel(const Kv8Cache c, const int k_down, const int v_down, float* __restrict__ k_out,
+                                                                    float* __restrict__ v_out, long long L, const int32_t* __restrict__ lengths,
+                                                                    const KvPages pg) {
+    kv8_decode_fp32_body<true>(c, k_down, v_down, k_out, v_out, L, lengths, pg);
+}
+
 int launch_kv8_decode_fp32(const Kv8Cache& c, const QuantArgs& ak, const QuantArgs& av, float* k_out, float* v_out, long long L,
-                           const int32_t* lengths, hipStream_t st) {
+                           const int32_t* lengths, hipStream_t st, const KvPages* pages) {
     const long long blocks = (L * c.D + 255) / 256;
     if (blocks > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
     if (!lengths) return MI355Q_E_BADARG;
-    hipLaunchKernelGGL(kv8_decode_fp32_kernel, dim3((unsigned)blocks, (unsigned)c.B), dim3(256), 0, st, c, kv8_down(ak), kv8_down(av), k_out,
-                       v_out, L, lengths);
+    const dim3 grid((unsigned)blocks, (unsigned)c.B);
+    if (pages) hipLaunchKernelGGL(kv8_decode_fp32_paged_kernel, grid, dim3(256), 0, st, c, kv8_down(ak), kv8_down(av), k_out, v_out, L, lengths, *pages);
+    else hipLaunchKernelGGL(kv8_decode_fp32_kernel, grid, dim3(256), 0, st, c, kv8_down(ak), kv8_down(av), k_out, v_out, L, lengths);
     return (int)hipGetLastError();
 }
 
 // ---- decode ---------------------------------------------------------------------------------------------------------------
 struct Decode8Args {
-    DecodeArgs g;               // as for the ragged launches of mi355q_decode.hip; kq / vq stay NULL
+    DecodeArgs g;               // as for the ragged launches of mi355q_decode.hip (PG: g.pg the page table); kq / vq stay NULL
     const uint8_t* k8;
     const uint8_t* v8;
     int k_down, v_down;         // kv8_down of the cached K / V operand's quantiser
 };
 
-template <int DC, bool GQ>
+template <int DC, bool GQ, bool PG>
 __global__ __launch_bounds__(256) void decode8_scores_kernel(const QuantArgs aq, const Decode8Args a) {
     __shared__ float sm_[4][64], sl_[4][64];
     const DecodeArgs& g = a.g;
@@ -213,17 +248,27 @@ __global__ __launch_bounds__(256) void decode8_scores_kernel(const QuantArgs aq,
     const float scale_inv = g.scale_div != 0.f ? 1.0f / g.scale_div : 0.f;
     const long long t_lo = 2 * g.pps * s, t_hi = min(NT, t_lo + 2 * g.pps);
     // a lane's mantissas at 8 lane, its 8 exponent codes (the d of its group) at 512 + 8 lg of the piece (t < NT <= NTC)
-    const uint8_t* __restrict__ kmb = a.k8 + cb * g.NTC * DC * KV8_PIECE + lane * 8;
-    const uint8_t* __restrict__ keb = a.k8 + cb * g.NTC * DC * KV8_PIECE + 512 + lg * 8;
+    const uint8_t* __restrict__ kmb = a.k8 + (PG ? 0 : cb * g.NTC * DC * KV8_PIECE) + lane * 8;
+    const uint8_t* __restrict__ keb = a.k8 + (PG ? 0 : cb * g.NTC * DC * KV8_PIECE) + 512 + lg * 8;
     float* __restrict__ sc = g.scores + b * g.NT * 256 + lane * 4;
     // running (max, sum of exp(x - max)) of this lane's visible scores, re-based when the maximum moves
     float m_run = -INFINITY, l_run = 0.f;
+    // paged: the table entry of the NEXT tile this wave takes is asked for while this one's pieces are loaded (t < t_hi <= NT)
+    int raw = 0;
+    if constexpr (PG) {
+        if (t_lo + wave < t_hi) raw = pg_raw(g.pg, cb, (t_lo + wave) >> (g.pg.lg_p - 4));
+    }
     for (long long t = t_lo + wave; t < t_hi; t += 4) {
+        long long pt = t;                                   // the tile's place in k8; the workspace keeps t
+        if constexpr (PG) pt = pg_place(g.pg, __builtin_amdgcn_readfirstlane(raw), t, g.pg.lg_p - 4);
         uint2 km[DC], ke[DC];           // both loads of every chunk in front of the first rebuild
 #pragma unroll
         for (int c = 0; c < DC; ++c) {
-            km[c] = *reinterpret_cast<const uint2*>(kmb + (t * DC + c) * KV8_PIECE);
-            ke[c] = *reinterpret_cast<const uint2*>(keb + (t * DC + c) * KV8_PIECE);
+            km[c] = *reinterpret_cast<const uint2*>(kmb + (pt * DC + c) * KV8_PIECE);
+            ke[c] = *reinterpret_cast<const uint2*>(keb + (pt * DC + c) * KV8_PIECE);
+        }
+        if constexpr (PG) {
+            if (t + 4 < t_hi) raw = pg_raw(g.pg, cb, (t + 4) >> (g.pg.lg_p - 4));
         }
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -267,7 +312,7 @@ __global__ __launch_bounds__(256) void decode8_scores_kernel(const QuantArgs aq,
     }
 }
 
-template <int DC, bool GQ>
+template <int DC, bool GQ, bool PG>
 __global__ __launch_bounds__(256) void decode8_pv_kernel(const QuantArgs ap, const Decode8Args a) {
     constexpr int DT = DC * 2;
     __shared__ f32x4 red[4][DT][64];
@@ -304,18 +349,27 @@ __global__ __launch_bounds__(256) void decode8_pv_kernel(const QuantArgs ap, con
     const float row_inv = 1.0f / row_sum;
     const int mbp = (int)__builtin_log2f(ap.shift);
     // a lane's mantissas at 8 lane, the 8 exponent codes of its 8 keys at 512 + 8 lg of the piece (pair < NP <= NPC)
-    const uint8_t* __restrict__ vmb = a.v8 + cb * g.NPC * DT * KV8_PIECE + lane * 8;
-    const uint8_t* __restrict__ veb = a.v8 + cb * g.NPC * DT * KV8_PIECE + 512 + lg * 8;
+    const uint8_t* __restrict__ vmb = a.v8 + (PG ? 0 : cb * g.NPC * DT * KV8_PIECE) + lane * 8;
+    const uint8_t* __restrict__ veb = a.v8 + (PG ? 0 : cb * g.NPC * DT * KV8_PIECE) + 512 + lg * 8;
     const float* __restrict__ sc = g.scores + b * g.NT * 256 + lane * 4;
     f32x4 o[DT];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    int raw = 0;                                            // (paged: one pair ahead, as in decode8_scores_kernel; pr_i < p_hi <= NP)
+    if constexpr (PG) {
+        if (p_lo + wave < p_hi) raw = pg_raw(g.pg, cb, (p_lo + wave) >> (g.pg.lg_p - 5));
+    }
     for (long long pr_i = p_lo + wave; pr_i < p_hi; pr_i += 4) {
+        long long pp = pr_i;                                // the pair's place in v8; scores and horizon keep pr_i
+        if constexpr (PG) pp = pg_place(g.pg, __builtin_amdgcn_readfirstlane(raw), pr_i, g.pg.lg_p - 5);
         uint2 vm[DT], ve[DT];           // both loads of every piece in front of the probabilities: in flight while those are made
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
-            vm[dt] = *reinterpret_cast<const uint2*>(vmb + (pr_i * DT + dt) * KV8_PIECE);
-            ve[dt] = *reinterpret_cast<const uint2*>(veb + (pr_i * DT + dt) * KV8_PIECE);
+            vm[dt] = *reinterpret_cast<const uint2*>(vmb + (pp * DT + dt) * KV8_PIECE);
+            ve[dt] = *reinterpret_cast<const uint2*>(veb + (pp * DT + dt) * KV8_PIECE);
+        }
+        if constexpr (PG) {
+            if (pr_i + 4 < p_hi) raw = pg_raw(g.pg, cb, (pr_i + 4) >> (g.pg.lg_p - 5));
         }
         float pq[8];
 #pragma unroll
@@ -352,14 +406,16 @@ __global__ __launch_bounds__(256) void decode8_pv_kernel(const QuantArgs ap, con
     }
 }
 
-// launch_bfp_attention_decode's arithmetic for its ragged, unpaged, unwindowed forms: the same launch rows, splits and workspace
+// launch_bfp_attention_decode's arithmetic for its ragged, unwindowed forms: the same launch rows, splits and workspace
 int launch_bfp_attention_decode_kv8(const QuantArgs& aq, const QuantArgs& ap, const QuantArgs& ak, const QuantArgs& av, const Kv8Cache& c,
                                     const float* q, float* out, void* workspace, long long M, long long L, int causal, float q_scale,
-                                    float scale_div, const long long* strides, int splits, hipStream_t st, const int32_t* lengths, int G) {
+                                    float scale_div, const long long* strides, int splits, hipStream_t st, const int32_t* lengths, int G,
+                                    const KvPages* pages) {
     if (!lengths) return MI355Q_E_BADARG;                   // (no uniform launch)
     Decode8Args a{};
     DecodeArgs& g = a.g;
     a.k8 = c.k8; a.v8 = c.v8;
+    if (pages) g.pg = *pages;
     a.k_down = kv8_down(ak); a.v_down = kv8_down(av);
     g.q = q; g.out = out; g.lengths = lengths;
     g.M = M; g.L = L; g.D = c.D;
@@ -377,13 +433,14 @@ int launch_bfp_attention_decode_kv8(const QuantArgs& aq, const QuantArgs& ap, co
     g.stats = g.scores + rows * g.NT * 256;
     g.part = g.stats + rows * g.S * 32;
     const dim3 grid((unsigned)g.S, (unsigned)rows);
+#define MI355Q_DECODE8_GO2(DC_, GQ_, PG_)                                                                            \
+    hipLaunchKernelGGL((decode8_scores_kernel<DC_, GQ_, PG_>), grid, dim3(256), 0, st, aq, a);                       \
+    hipLaunchKernelGGL((decode8_pv_kernel<DC_, GQ_, PG_>), grid, dim3(256), 0, st, ap, a);
 #define MI355Q_DECODE8_GO(DC_)                                                                                       \
-    if (G) {                                                                                                         \
-        hipLaunchKernelGGL((decode8_scores_kernel<DC_, true>), grid, dim3(256), 0, st, aq, a);                       \
-        hipLaunchKernelGGL((decode8_pv_kernel<DC_, true>), grid, dim3(256), 0, st, ap, a);                           \
+    if (pages) {                                                                                                     \
+        if (G) { MI355Q_DECODE8_GO2(DC_, true, true) } else { MI355Q_DECODE8_GO2(DC_, false, true) }                 \
     } else {                                                                                                         \
-        hipLaunchKernelGGL((decode8_scores_kernel<DC_, false>), grid, dim3(256), 0, st, aq, a);                      \
-        hipLaunchKernelGGL((decode8_pv_kernel<DC_, false>), grid, dim3(256), 0, st, ap, a);                          \
+        if (G) { MI355Q_DECODE8_GO2(DC_, true, false) } else { MI355Q_DECODE8_GO2(DC_, false, false) }               \
     }
     switch (c.D / 32) {
         case 1: MI355Q_DECODE8_GO(1); break;
@@ -393,6 +450,7 @@ int launch_bfp_attention_decode_kv8(const QuantArgs& aq, const QuantArgs& ap, co
         default: return MI355Q_E_UNSUPPORTED;
     }
 #undef MI355Q_DECODE8_GO
+#undef MI355Q_DECODE8_GO2
     launch_decode_sum(g, G != 0, rows, st);
     return (int)hipGetLastError();
 }

@@ -65,7 +65,10 @@ inline int window_cache_shape(int64_t B, int64_t max_pages, int64_t num_pages, i
     return decode_cache_shape(B, max_pages * P, D);
 }
 
-enum KvStorage { KV_BF16, KV_INT8, KV_PAGED };      // KV_PAGED: the cache comes as (max_pages, num_pages, P) and a block table
+enum KvStorage { KV_BF16, KV_INT8, KV_PAGED, KV_INT8_PAGED };   // KV_PAGED: the cache comes as (max_pages, num_pages, P) and a block table;
+                                                                // KV_INT8_PAGED: both -- int8-mantissa pieces in paged pools
+constexpr bool kv_int8(KvStorage s) { return s == KV_INT8 || s == KV_INT8_PAGED; }
+constexpr bool kv_paged(KvStorage s) { return s == KV_PAGED || s == KV_INT8_PAGED; }
 enum KvOp { KV_BYTES, KV_APPEND, KV_DEQUANT, KV_DECODE, KV_EXTEND };
 enum : unsigned {
     KV_LENGTHS = 1,     // `lengths` is mandatory (else: not taken, or optional -- NULL is the uniform form)
@@ -78,7 +81,8 @@ enum : unsigned {
 enum KvExport {
     KVX_CACHE_BYTES, KVX_APPEND, KVX_DECODE_FP32, KVX_DECODE, KVX_APPEND_RAGGED, KVX_DECODE_FP32_RAGGED, KVX_DECODE_RAGGED, KVX_EXTEND,
     KVX_DECODE_GROUPED, KVX_EXTEND_GROUPED, KVX_PAGED_BYTES, KVX_APPEND_PAGED, KVX_DECODE_FP32_PAGED, KVX_DECODE_PAGED, KVX_EXTEND_PAGED,
-    KVX_KV8_CACHE_BYTES, KVX_KV8_APPEND, KVX_KV8_DECODE_FP32, KVX_DECODE_KV8, KVX_DECODE_WINDOW, KVX_EXTEND_WINDOW, KVX_COUNT
+    KVX_KV8_CACHE_BYTES, KVX_KV8_APPEND, KVX_KV8_DECODE_FP32, KVX_DECODE_KV8, KVX_DECODE_WINDOW, KVX_EXTEND_WINDOW,
+    KVX_KV8P_BYTES, KVX_KV8P_APPEND, KVX_KV8P_DECODE_FP32, KVX_KV8P_DECODE, KVX_COUNT
 };
 
 // one call of a KV-cache export: the form (what KV_EXPORTS says of the export), then the raw arguments; what an export does not
@@ -137,12 +141,14 @@ constexpr KvCall KV_EXPORTS[KVX_COUNT] = {
     {KV_PAGED, KV_DECODE, KV_LENGTHS}, {KV_PAGED, KV_EXTEND, KV_LENGTHS},
     {KV_INT8, KV_BYTES, 0},           {KV_INT8, KV_APPEND, KV_LENGTHS}, {KV_INT8, KV_DEQUANT, KV_LENGTHS}, {KV_INT8, KV_DECODE, KV_LENGTHS},
     {KV_PAGED, KV_DECODE, KV_LENGTHS | KV_WINDOW}, {KV_PAGED, KV_EXTEND, KV_LENGTHS | KV_WINDOW},
+    {KV_INT8_PAGED, KV_BYTES, 0},     {KV_INT8_PAGED, KV_APPEND, KV_LENGTHS}, {KV_INT8_PAGED, KV_DEQUANT, KV_LENGTHS},
+    {KV_INT8_PAGED, KV_DECODE, KV_LENGTHS},
 };
 
 // what the launchers take of a call that passed
 struct KvChecked {
     KvCache c;                  // storage KV_BF16 / KV_PAGED (C: the row's logical capacity)
-    Kv8Cache c8;                // storage KV_INT8
+    Kv8Cache c8;                // storage KV_INT8 / KV_INT8_PAGED (C: the row's logical capacity)
     KvPages pg;
     const KvPages* pages;       // &pg with a block table, else NULL
     QuantArgs aq, ap, ak, av;   // Q and P (decode, extend); the cached K and V (append; int8: every operation)
@@ -154,7 +160,7 @@ struct KvChecked {
 
 // true: launch with `k`.  false: return rc (an MI355Q_E_* code, or 0 where there is nothing to do)
 inline bool kv_call_check(const KvCall& d, KvChecked& k, int& rc) {
-    const bool attn = d.op == KV_DECODE || d.op == KV_EXTEND, int8 = d.storage == KV_INT8, paged_form = d.storage == KV_PAGED;
+    const bool attn = d.op == KV_DECODE || d.op == KV_EXTEND, int8 = kv_int8(d.storage), paged_form = kv_paged(d.storage);
     const bool windowed = (d.form & KV_WINDOW) != 0;
     const auto stop = [&rc](int code) { rc = code; return false; };
     const auto misaligned = [](std::initializer_list<const void*> ptrs, uintptr_t to) {      // (an optional NULL passes)

@@ -4,7 +4,8 @@
 //
 // A JOB is int32 x 4 on the device, 16 bytes: (src_page, dst_page, src_row, dst_row).
 //   pages   src_page, dst_page >= 0: the WHOLE page src_page of both pools becomes page dst_page -- P / 16 tiles x D / 32 KiB of K^T and
-//           P / 32 pairs x D / 16 KiB of V (mi355q_decode.h: paged cache), P * D * 2 bytes each.  Whole pages: a recycled page may hold
+//           P / 32 pairs x D / 16 KiB of V (mi355q_decode.h: paged cache), P * D * 2 bytes each; of the int8-mantissa pools
+//           (mi355q_kv8.h, mi355q_bfp_kv8_paged_copy) the same pieces at 544 bytes, P * D * 17 / 16 bytes each.  Whole pages: a recycled page may hold
 //           anything behind the row's keys, and copying all of it keeps the kernel free of per-row lengths.  Either id negative: no page
 //           copy.  Ids are clamped into 0 .. num_pages - 1 like every paged kernel's: a wrong job gives wrong numbers, never an address
 //           outside the pools.
@@ -33,14 +34,15 @@ struct KvCopyArgs {
     const float* stage_src;   // [B][16][D] fp32
     float* stage_dst;
     const int32_t* jobs;      // [n_jobs][4] on the device
-    long long page_units;     // 16-byte units of one page of ONE pool: P * D / 8
+    long long page_units;     // 16-byte units of one page of ONE pool: P * D / 8 (bf16), P * D * 17 / 256 (int8 mantissas)
     int stage_units;          // 16-byte units of one row's stage: 4 * D
     int num_pages, B, n_jobs;
 };
 
 // true: launch with `g`.  false: return rc (an MI355Q_E_* code, or 0 where there is nothing to do).  The order of the checks is ABI.
+// int8: the pools hold the 544-byte pieces of mi355q_kv8.h -- only the size of a page differs (P * D is a multiple of 1024: whole units)
 inline bool kv_copy_check(const void* kq, const void* vq, const void* stage_src, const void* stage_dst, const void* jobs, int64_t n_jobs,
-                          int64_t B, int64_t num_pages, int64_t P, int64_t D, KvCopyArgs& g, int& rc) {
+                          int64_t B, int64_t num_pages, int64_t P, int64_t D, bool int8, KvCopyArgs& g, int& rc) {
     const auto stop = [&rc](int code) { rc = code; return false; };
     g = KvCopyArgs{};
     if (n_jobs < 0 || B < 1 || B > 65535 || num_pages < 1 || num_pages > 0x7FFFFFFFLL) return stop(MI355Q_E_BADARG);
@@ -54,13 +56,14 @@ inline bool kv_copy_check(const void* kq, const void* vq, const void* stage_src,
     g.kq = const_cast<void*>(kq); g.vq = const_cast<void*>(vq);
     g.stage_src = static_cast<const float*>(stage_src); g.stage_dst = static_cast<float*>(const_cast<void*>(stage_dst));
     g.jobs = static_cast<const int32_t*>(jobs);
-    g.page_units = P * D / 8;
+    g.page_units = int8 ? P * D / 256 * 17 : P * D / 8;
     g.stage_units = (int)(4 * D);
     g.num_pages = (int)num_pages; g.B = (int)B; g.n_jobs = (int)n_jobs;
     rc = 0;
     return true;
 }
-// blocks a job: both pools' pages and the stage rows, one unit a thread (every segment is a multiple of 64 units: a wave is in one)
+// blocks a job: both pools' pages and the stage rows, one unit a thread.  The kernel picks a unit's segment per THREAD: a bf16 page and
+// the stage rows are multiples of 64 units, an int8-mantissa page (68 units at P = D = 32) is not, and a wave may straddle two segments
 inline long long kv_copy_blocks(const KvCopyArgs& g) { return (2 * g.page_units + g.stage_units + KV_COPY_THREADS - 1) / KV_COPY_THREADS; }
 
 // mi355q_kv_copy.hip; `stream` is a hipStream_t

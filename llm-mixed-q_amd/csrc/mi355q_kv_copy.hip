@@ -1,7 +1,7 @@
 // kv_paged_copy_kernel: the private copies a fork or a reorder of the paged block_fp KV cache needs -- a row's last, partially filled
 // page and its open tile's fp32 stage rows -- for every row of one layer in ONE launch (layout of a job and the rules: mi355q_kv_copy.h).
-// One instantiation, generic in bytes: a page of either pool is P * D * 2 bytes whatever D / 32 is, and nothing here looks inside a
-// piece, so a template on D / 32 would only multiply code objects.  A fork moves at most 2 x 16 KiB + 8 KiB a row (P = 64, D = 128):
+// One instantiation, generic in bytes: a page of either pool is P * D * 2 bytes (int8 mantissas: P * D * 17 / 16) whatever D / 32 is,
+// and nothing here looks inside a piece, so a template on D / 32 would only multiply code objects.  A fork moves at most 2 x 16 KiB + 8 KiB a row (P = 64, D = 128):
 // latency, not bandwidth, so the work is spread one 16-byte unit a thread over as many waves as there are units.
 #include <hip/hip_runtime.h>
 

@@ -109,6 +109,13 @@ SIGNATURES = {
     "mi355q_bfp_kv8_decode_fp32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "mi355q_bfp_attention_decode_kv8": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, C.c_float, C.c_float, _vp, _vp, _i64, _i64, _i64,
                                                   _i64, _i64, _vp, _vp, _vp, _i32, _vp]),
+    "mi355q_bfp_kv8_paged_bytes": (C.c_int, [_i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "mi355q_bfp_kv8_append_paged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp,
+                                              _vp, _vp]),
+    "mi355q_bfp_kv8_decode_fp32_paged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "mi355q_bfp_attention_decode_kv8_paged": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, C.c_float, C.c_float, _vp, _vp, _i64, _i64, _i64,
+                                                        _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp]),
+    "mi355q_bfp_kv8_paged_copy": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
     "mi355q_stream_capture_id": (C.c_uint64, [_vp]),
     "mi355q_rope_apply": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "mi355q_bfp_gemm_aligned": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),

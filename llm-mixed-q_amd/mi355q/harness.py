@@ -624,8 +624,8 @@ class DecodeState:
             raise ValueError(f"forward(counts=...): lengths {before} + {n} tokens exceed the capacity {self.capacity} "
                              f"or the model's {max_positions} positions")
         active = [b for b, c in enumerate(counts) if c > 0]
-        if all(l == 0 for l in before):
-            route = "prefill"
+        if all(l == 0 for l in before) or (active and all(before[b] == 0 for b in active)):
+            route = "prefill"                                  # (also: sequences that start in released slots while NO other row takes a token)
         elif all(before[b] > 0 and counts[b] == n for b in active) and n <= ops.DECODE_MAX_QUERIES:
             route = "decode"
         elif self.extend:
@@ -785,6 +785,35 @@ class PackedDecodeState(DecodeState):
             raise ValueError(f"PackedDecodeState: {e}") from None
 
 
+class PagedPackedDecodeState(PagedDecodeState):
+    """PagedDecodeState(model, batch, capacity, mode, extend, page_size, num_pages) on ops.PagedPackedKVCache: paged caches of int8
+    mantissas, 17/32 of the paged state's K and V bytes and of a decode step's K / V traffic, with its release / fork / reorder and its
+    ragged prefill and decode routes as inherited -- the numbers are PagedDecodeState's, bit for bit (ops.PackedKVCache names the one
+    exception, inputs of magnitude <= 1e-8).  `page_size` is mandatory.  What this storage has no kernel for is refused here, by name:
+    extend=True (chunked prefill), a sliding-window model, and mode "fp32"; a mixed call and a call with more than 16 new tokens behind
+    a non-empty row therefore keep raising DecodeState's NotImplementedError."""
+
+    def __init__(self, model, batch: int, capacity: int, mode: str = "block_fp", extend: bool = False, page_size: int = None,
+                 num_pages: int = None):
+        if mode != "block_fp":
+            raise ValueError(f"PagedPackedDecodeState: mode {mode!r}: the int8-mantissa cache is a block_fp cache (mode 'fp32' keeps fp32 K / V)")
+        if page_size is None:
+            raise ValueError("PagedPackedDecodeState: page_size is mandatory (the contiguous int8-mantissa state is PackedDecodeState)")
+        if extend:
+            raise NotImplementedError("PagedPackedDecodeState: extend=True: no extend (chunked prefill) kernel reads the int8-mantissa cache")
+        if getattr(model.cfg, "sliding_window", None) is not None:
+            raise NotImplementedError("PagedPackedDecodeState: a sliding-window model: no windowed kernel reads the int8-mantissa cache")
+        super().__init__(model, batch, capacity, mode, extend, page_size, num_pages)
+
+    def _new_cache(self, rows, hd, qk, pv, dev):
+        max_pages = -(-self.capacity // int(self.page_size))
+        try:
+            return ops.PagedPackedKVCache(rows, hd, qk, pv, dev, page_size=self.page_size, max_pages=max_pages,
+                                          num_pages=rows * max_pages if self.num_pages is None else self.num_pages)
+        except ValueError as e:
+            raise ValueError(f"PagedPackedDecodeState: {e}") from None
+
+
 def _forward_cached(model, input_ids, labels, state: DecodeState, counts=None):
     if labels is not None:
         raise ValueError("forward(cache=...): labels belong to the full forward")
@@ -904,7 +933,8 @@ def generate(model, prompt_ids, new_tokens: int, mode: str = "block_fp", chunk: 
 
 
 @torch.no_grad()
-def beam_search(model, prompt_ids, new_tokens: int, num_beams: int, page_size: int = 32, num_pages: int = None, chunk: int = None):
+def beam_search(model, prompt_ids, new_tokens: int, num_beams: int, page_size: int = 32, num_pages: int = None, chunk: int = None,
+                kv_storage: str = None):
     """beam search on paged caches: ONE prefill of the B prompts, each then forked into its `num_beams` slots (PagedDecodeState.fork: the
     prompt's full pages by reference, its partial page and open tile copied), and per step one cached call over B * num_beams rows,
     log_softmax, the top num_beams of num_beams * vocab candidates per prompt, and `reorder(beam_idx)` -- the reference's
@@ -912,9 +942,15 @@ def beam_search(model, prompt_ids, new_tokens: int, num_beams: int, page_size: i
     length penalty and no EOS (the harness has none).  -> (ids [B, num_beams, T + new_tokens], scores [B, num_beams]), best beam first.
     `prompt_ids` may be a list of 1-D id tensors of different lengths: ids is then a list of [num_beams, len_b + new_tokens].
     `num_pages` (per layer) defaults to every cache row at its capacity plus the one page a row a reorder draws before it gives any back;
-    `chunk`: chunked prefill, as in generate."""
+    `chunk`: chunked prefill, as in generate.
+    `kv_storage`: None keeps the pages' values as bf16; "int8" stores mantissa bytes (PagedPackedDecodeState: 17/32 of the K / V bytes,
+    the same ids and scores; not with `chunk`, which needs the extend kernel, nor a sliding-window model)."""
     if page_size is None:
         raise NotImplementedError("beam_search: page_size=None: only a paged state can fork or reorder its sequences")
+    if kv_storage not in (None, "int8"):
+        raise ValueError(f"beam_search: kv_storage = {kv_storage!r} is neither None (bf16 values) nor 'int8' (mantissa bytes)")
+    if kv_storage is not None and chunk is not None:
+        raise NotImplementedError("beam_search: kv_storage='int8' with chunk: no extend (chunked prefill) kernel reads the int8-mantissa cache")
     if chunk is not None and int(chunk) < 1:
         raise ValueError(f"beam_search: chunk = {chunk} < 1")
     ragged = isinstance(prompt_ids, (list, tuple))
@@ -927,7 +963,8 @@ def beam_search(model, prompt_ids, new_tokens: int, num_beams: int, page_size: i
     if num_pages is None:
         a = model.layers[0].self_attn
         num_pages = N * getattr(a, "nkv", a.nh) * (-(-((capacity + 15) // 16 * 16) // int(page_size)) + 1)
-    state = PagedDecodeState(model, N, capacity, "block_fp", extend=chunk is not None, page_size=page_size, num_pages=num_pages)
+    state = (PagedDecodeState if kv_storage is None else PagedPackedDecodeState)(model, N, capacity, "block_fp", extend=chunk is not None,
+                                                                                 page_size=page_size, num_pages=num_pages)
     # the prompts in slots 0, nb, 2 nb, ...; the other slots take no token
     done, last, step = [0] * B, [None] * B, max(lens) if chunk is None else int(chunk)
     while any(d < l for d, l in zip(done, lens)):

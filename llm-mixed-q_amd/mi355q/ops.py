@@ -1500,7 +1500,7 @@ def _kv_call(device, export, args):
 
 
 class _KVCacheBase:
-    """What KVCache, PagedKVCache and PackedKVCache share: the constructor's checks, the quantiser parameter words (`_pa`, `_pb`), the
+    """What KVCache, PagedKVCache, PackedKVCache and PagedPackedKVCache share: the constructor's checks, the quantiser parameter words (`_pa`, `_pb`), the
     zeroed storage, and the checks of append / dequantised.  A subclass adds its storage's names, its exports' arguments and -- the paged
     one -- its allocator.  Messages carry the subclass's name."""
     RAGGED_ONLY = False         # PagedKVCache: lengths= is mandatory
@@ -1626,40 +1626,23 @@ class KVCache(_KVCacheBase):
         return k, v
 
 
-class PagedKVCache(_KVCacheBase):
-    """The block_fp KV cache in PAGES of `page_size` keys (a power of two >= 32) drawn from one pool: a row holds memory for the keys
-    it has, a finished row's pages serve the next sequence, and rows can share the pages of a common prefix.  Storage and kernels:
-    include/mi355q.h (paged cache), csrc/mi355q_decode.h; every value is the one `KVCache` holds, so append / dequantised /
-    bfp_attention_decode / bfp_attention_extend give the contiguous cache's bits.
-      kq, vq        the pools, `num_pages` pages (zeroed once; a recycled page is not cleared: finite values are all a V slot needs)
-      stage         [B][16][D] fp32, per ROW: the open 16-key tile belongs to a row, not to a page
-      block_table   int32 [B, max_pages] on the device: the page of row b's logical page i; `table` is its host mirror
-      free          the host free list (page ids; taken from its end), `held[b]` the pages of row b in logical order -- None for a
-                    logical page `trim` has given back (the row keeps its logical index: `ensure` counts it and never refills it)
-      capacity      max_pages * page_size: a row's logical capacity -- what `max_length` is checked against
-    Always addressed in the ragged form: `lengths` (int32 [B] on the device) and the host bound `max_length` are mandatory.  The
-    allocator is the host's: `ensure` before an append that needs new pages (the kernels never allocate, and look up only pages that
-    hold keys of the row).  Table entries behind a row's pages are never read; they hold `pad_page` (default 0).  With pad_page= given
-    that page is kept out of the free list for good -- a null page no row ever writes.
-    Sliding window: `trim(lengths, window)` gives back the pages wholly behind the window, so a windowed row holds O(window) pages.
-    Copy-on-write: `fork(src, dst, length)` gives row dst what row src holds at ANY length, `reorder(src_rows, lengths)` makes row b what
-    row src_rows[b] was (the reference's `_reorder_cache`: index_select over the batch).  Full pages move by reference; the row's last,
-    partially filled page and its stage rows are copied by ONE launch (csrc/mi355q_kv_copy.h) that writes the stage rows into
-    `stage_alt`, a second buffer of stage's shape, after which the two swap names: `stage` is always the one the kernels are given.
-    Both are eager calls between steps, not to be captured in a graph (the stage pointer alternates).  A reorder draws every private
-    page before any page returns to the free list: the pool needs up to one page a row beyond what the rows hold.
-    The interface is ensure / trim / release / share_prefix / fork / reorder / append / dequantised.  `assign`, `pad_page=`, `ensure(dry_run=)` and `pages_for`
-    are helpers: the tests and the timing tool place pages by hand with `assign` (out-of-order tables, a poison page), the harness asks
-    every layer with `dry_run` before it changes one.  `assign` filters the free list per call and is not meant for a hot loop."""
+class _PagedHost(_KVCacheBase):
+    """The host half of a paged cache, whatever its pools hold (PagedKVCache: bf16; PagedPackedKVCache: int8 mantissas): the page table
+    and its device copy, the free list, the reference counts, and the planner and the ONE launch of copy-on-write.  Nothing here looks
+    inside a page.  A subclass names its pools (POOLS), the export that copies whole pages of them (COPY_EXPORT), fills them in its
+    constructor between `_init_pages` and `_init_table`, and adds append / dequantised.  Messages carry the subclass's name."""
 
     RAGGED_ONLY = True
+    POOLS = ("kq", "vq")
+    COPY_EXPORT = "mi355q_bfp_kv_paged_copy"
 
-    def __init__(self, B: int, D: int, qk_params, pv_params, device, *, page_size: int, num_pages: int, max_pages: int, pad_page: int = None):
+    def _init_pages(self, B, D, qk_params, pv_params, device, page_size, num_pages, max_pages, pad_page):
         self.page_size, self.num_pages, self.max_pages, self.capacity = int(page_size), int(num_pages), int(max_pages), int(max_pages) * int(page_size)
         self.pad_page = pad_page
         self._init_rows(int(B), int(D), qk_params, pv_params, device)
         self.pad_page = 0 if pad_page is None else int(pad_page)
-        self.kq, self.vq, self.stage = self._zeroed("mi355q_bfp_kv_paged_bytes", self.num_pages, self.page_size, self.B, self.D)
+
+    def _init_table(self, pad_page):
         self.stage_alt = torch.zeros_like(self.stage)       # fork / reorder write the stage rows here, then the two swap
         self._jobs = torch.zeros(self.B, 4, dtype=torch.int32, device=self.device)
         self.table = torch.full((self.B, self.max_pages), self.pad_page, dtype=torch.int32)
@@ -1671,11 +1654,11 @@ class PagedKVCache(_KVCacheBase):
     def _check_pages(self):
         P, num_pages, max_pages, pad_page = self.page_size, self.num_pages, self.max_pages, self.pad_page
         if P < 32 or P & (P - 1):
-            raise ValueError(f"PagedKVCache: page_size {P} is not a power of two >= 32 (a K tile, a V pair and an extend step stay in one page)")
+            raise ValueError(f"{type(self).__name__}: page_size {P} is not a power of two >= 32 (a K tile, a V pair and an extend step stay in one page)")
         if num_pages < 1 or max_pages < 1 or max_pages * P > 1 << 30:
-            raise ValueError(f"PagedKVCache: num_pages = {num_pages}, max_pages = {max_pages}: at least one each, max_pages * page_size <= 2^30")
+            raise ValueError(f"{type(self).__name__}: num_pages = {num_pages}, max_pages = {max_pages}: at least one each, max_pages * page_size <= 2^30")
         if pad_page is not None and not 0 <= int(pad_page) < num_pages:
-            raise ValueError(f"PagedKVCache: pad_page {pad_page} outside 0 .. {num_pages - 1}")
+            raise ValueError(f"{type(self).__name__}: pad_page {pad_page} outside 0 .. {num_pages - 1}")
 
     def pages_for(self, length: int) -> int:
         return -(-int(length) // self.page_size)
@@ -1689,14 +1672,14 @@ class PagedKVCache(_KVCacheBase):
         list changes.  The changed table goes to the device with one copy_.  dry_run: the checks only."""
         want = [self.pages_for(n) for n in lengths_after]
         if len(want) != self.B:
-            raise ValueError(f"PagedKVCache.ensure: {len(want)} lengths for {self.B} cache rows")
+            raise ValueError(f"{type(self).__name__}.ensure: {len(want)} lengths for {self.B} cache rows")
         over = [b for b, w in enumerate(want) if w > self.max_pages]
         if over:
-            raise ValueError(f"PagedKVCache.ensure: rows {over} ask for more than max_pages = {self.max_pages} pages "
+            raise ValueError(f"{type(self).__name__}.ensure: rows {over} ask for more than max_pages = {self.max_pages} pages "
                              f"(lengths {[int(lengths_after[b]) for b in over]}, capacity {self.capacity})")
         extra = {b: w - len(self.held[b]) for b, w in enumerate(want) if w > len(self.held[b])}
         if sum(extra.values()) > len(self.free):
-            raise RuntimeError(f"PagedKVCache.ensure: rows {sorted(extra)} need {sum(extra.values())} more pages, {len(self.free)} of "
+            raise RuntimeError(f"{type(self).__name__}.ensure: rows {sorted(extra)} need {sum(extra.values())} more pages, {len(self.free)} of "
                                f"{self.num_pages} are free")
         if dry_run or not extra:
             return
@@ -1709,42 +1692,15 @@ class PagedKVCache(_KVCacheBase):
         pages = [int(p) for p in pages]
         taken = set(pages)
         if len(taken) != len(pages) or not taken <= set(self.free):
-            raise ValueError(f"PagedKVCache.assign: pages {pages} are not distinct free pages")
+            raise ValueError(f"{type(self).__name__}.assign: pages {pages} are not distinct free pages")
         if len(self.held[row]) + len(pages) > self.max_pages:
-            raise ValueError(f"PagedKVCache.assign: row {row} would hold more than max_pages = {self.max_pages} pages")
+            raise ValueError(f"{type(self).__name__}.assign: row {row} would hold more than max_pages = {self.max_pages} pages")
         self.free = [p for p in self.free if p not in taken]
         for p in pages:
             self.refs[p] = 1
             self.table[row, len(self.held[row])] = p
             self.held[row].append(p)
         if upload:
-            self._upload()
-
-    def trim(self, lengths, window: int) -> None:
-        """sliding-window attention: row b (lengths[b] keys, host ints, one per cache row) gives back every logical page i with
-        (i + 1) * page_size <= lengths[b] - window + 1 -- keys no query at a position >= lengths[b] sees, so no later windowed call reads
-        them (the windowed kernels look up only pages that hold a visible key).  Their table entries become `pad_page`, `held` keeps
-        None in their place; a page another row still holds (share_prefix) stays with that row.  One copy_ of the table when anything
-        changed.  Only for rows that are from here on read with this window (or a smaller one)."""
-        if isinstance(window, bool) or not isinstance(window, int) or window < 1:
-            raise ValueError(f"PagedKVCache.trim: window = {window!r} is not an integer >= 1")
-        lengths = [int(n) for n in lengths]
-        if len(lengths) != self.B:
-            raise ValueError(f"PagedKVCache.trim: {len(lengths)} lengths for {self.B} cache rows")
-        changed = False
-        for b, n in enumerate(lengths):
-            held = self.held[b]
-            for i in range(min(max(n - window + 1, 0) // self.page_size, len(held))):
-                p = held[i]
-                if p is None:
-                    continue
-                self.refs[p] -= 1
-                if self.refs[p] == 0:
-                    self.free.append(p)
-                held[i] = None
-                self.table[b, i] = self.pad_page
-                changed = True
-        if changed:
             self._upload()
 
     def release(self, rows) -> None:
@@ -1768,11 +1724,11 @@ class PagedKVCache(_KVCacheBase):
         16-key blocks and V's blocks inside full pages are final, and the open tile of dst starts empty."""
         pages = int(pages)
         if src == dst or self.held[dst]:
-            raise ValueError(f"PagedKVCache.share_prefix: row {dst} holds {len(self.held[dst])} pages (only a row that holds none can share)")
+            raise ValueError(f"{type(self).__name__}.share_prefix: row {dst} holds {len(self.held[dst])} pages (only a row that holds none can share)")
         if not 0 <= pages <= len(self.held[src]):
-            raise ValueError(f"PagedKVCache.share_prefix: {pages} pages, row {src} holds {len(self.held[src])}")
+            raise ValueError(f"{type(self).__name__}.share_prefix: {pages} pages, row {src} holds {len(self.held[src])}")
         if any(p is None for p in self.held[src][:pages]):
-            raise ValueError(f"PagedKVCache.share_prefix: row {src} has trimmed pages among its first {pages} (a trimmed prefix cannot be shared)")
+            raise ValueError(f"{type(self).__name__}.share_prefix: row {src} has trimmed pages among its first {pages} (a trimmed prefix cannot be shared)")
         for i, p in enumerate(self.held[src][:pages]):
             self.refs[p] += 1
             self.table[dst, i] = p
@@ -1792,7 +1748,7 @@ class PagedKVCache(_KVCacheBase):
         ValueError for rows or lengths that do not fit; RuntimeError, naming the rows, the pages needed and the pages free, when the pool
         is short."""
         import types
-        name, P = f"PagedKVCache.{what}", self.page_size
+        name, P = f"{type(self).__name__}.{what}", self.page_size
         pairs = [(int(d), int(s), int(n)) for d, s, n in pairs]
         dsts = [d for d, _, _ in pairs]
         if len(set(dsts)) != len(dsts) or any(not 0 <= r < self.B for d, s, _ in pairs for r in (d, s)):
@@ -1853,13 +1809,13 @@ class PagedKVCache(_KVCacheBase):
         if dry_run:
             return
         if not self.stage.is_cuda:
-            raise ValueError(f"PagedKVCache.{what}: the cache is not on a GPU; there is no CPU fallback")
+            raise ValueError(f"{type(self).__name__}.{what}: the cache is not on a GPU; there is no CPU fallback")
         self._commit_plan(plan, free_now=False)
         if plan.jobs:
             n = len(plan.jobs)
             self._jobs[:n].copy_(torch.tensor(plan.jobs, dtype=torch.int32))
-            _kv_call(self.device, "mi355q_bfp_kv_paged_copy", (_ptr(self.kq), _ptr(self.vq), _ptr(self.stage), _ptr(self.stage_alt), _ptr(self._jobs),
-                                                               n, self.B, self.num_pages, self.page_size, self.D, _stream_ptr(self.device)))
+            _kv_call(self.device, self.COPY_EXPORT, (*(_ptr(getattr(self, pool)) for pool in self.POOLS), _ptr(self.stage), _ptr(self.stage_alt),
+                                                     _ptr(self._jobs), n, self.B, self.num_pages, self.page_size, self.D, _stream_ptr(self.device)))
             self.stage, self.stage_alt = self.stage_alt, self.stage
         self.free += plan.freed                             # (behind the copy in stream order: the next writer of such a page is a later launch)
 
@@ -1873,10 +1829,10 @@ class PagedKVCache(_KVCacheBase):
         one = isinstance(dst, int)
         src, dst, length = ([src], [dst], [length]) if one else (list(src), list(dst), list(length))
         if not len(src) == len(dst) == len(length):
-            raise ValueError(f"PagedKVCache.fork: {len(src)} src rows, {len(dst)} dst rows, {len(length)} lengths")
+            raise ValueError(f"{type(self).__name__}.fork: {len(src)} src rows, {len(dst)} dst rows, {len(length)} lengths")
         busy = [int(d) for d in dst if 0 <= int(d) < self.B and self.held[int(d)]]
         if busy or set(map(int, src)) & set(map(int, dst)):
-            raise ValueError(f"PagedKVCache.fork: rows {busy or sorted(set(map(int, src)) & set(map(int, dst)))} hold pages or are their own "
+            raise ValueError(f"{type(self).__name__}.fork: rows {busy or sorted(set(map(int, src)) & set(map(int, dst)))} hold pages or are their own "
                              "source (only a row that holds none can become a fork)")
         plan = self._plan_copy(zip(dst, src, length), "fork")
         rest = set(range(self.B)) - set(plan.held)
@@ -1892,13 +1848,72 @@ class PagedKVCache(_KVCacheBase):
         when it has not.  Afterwards `stage` is the buffer just written.  dry_run: the checks only."""
         src_rows, lengths = [int(s) for s in src_rows], [int(n) for n in lengths]
         if len(src_rows) != self.B or len(lengths) != self.B:
-            raise ValueError(f"PagedKVCache.reorder: {len(src_rows)} source rows and {len(lengths)} lengths for {self.B} cache rows")
+            raise ValueError(f"{type(self).__name__}.reorder: {len(src_rows)} source rows and {len(lengths)} lengths for {self.B} cache rows")
         if any(not 0 <= s < self.B for s in src_rows):
-            raise ValueError(f"PagedKVCache.reorder: source rows {src_rows} outside 0 .. {self.B - 1}")
+            raise ValueError(f"{type(self).__name__}.reorder: source rows {src_rows} outside 0 .. {self.B - 1}")
         self._copy(self._plan_copy([(b, s, lengths[s]) for b, s in enumerate(src_rows)]), "reorder", dry_run)
 
     def reset(self) -> None:
         self.release(range(self.B))
+
+
+class PagedKVCache(_PagedHost):
+    """The block_fp KV cache in PAGES of `page_size` keys (a power of two >= 32) drawn from one pool: a row holds memory for the keys
+    it has, a finished row's pages serve the next sequence, and rows can share the pages of a common prefix.  Storage and kernels:
+    include/mi355q.h (paged cache), csrc/mi355q_decode.h; every value is the one `KVCache` holds, so append / dequantised /
+    bfp_attention_decode / bfp_attention_extend give the contiguous cache's bits.
+      kq, vq        the pools, `num_pages` pages (zeroed once; a recycled page is not cleared: finite values are all a V slot needs)
+      stage         [B][16][D] fp32, per ROW: the open 16-key tile belongs to a row, not to a page
+      block_table   int32 [B, max_pages] on the device: the page of row b's logical page i; `table` is its host mirror
+      free          the host free list (page ids; taken from its end), `held[b]` the pages of row b in logical order -- None for a
+                    logical page `trim` has given back (the row keeps its logical index: `ensure` counts it and never refills it)
+      capacity      max_pages * page_size: a row's logical capacity -- what `max_length` is checked against
+    Always addressed in the ragged form: `lengths` (int32 [B] on the device) and the host bound `max_length` are mandatory.  The
+    allocator is the host's: `ensure` before an append that needs new pages (the kernels never allocate, and look up only pages that
+    hold keys of the row).  Table entries behind a row's pages are never read; they hold `pad_page` (default 0).  With pad_page= given
+    that page is kept out of the free list for good -- a null page no row ever writes.
+    Sliding window: `trim(lengths, window)` gives back the pages wholly behind the window, so a windowed row holds O(window) pages.
+    Copy-on-write: `fork(src, dst, length)` gives row dst what row src holds at ANY length, `reorder(src_rows, lengths)` makes row b what
+    row src_rows[b] was (the reference's `_reorder_cache`: index_select over the batch).  Full pages move by reference; the row's last,
+    partially filled page and its stage rows are copied by ONE launch (csrc/mi355q_kv_copy.h) that writes the stage rows into
+    `stage_alt`, a second buffer of stage's shape, after which the two swap names: `stage` is always the one the kernels are given.
+    Both are eager calls between steps, not to be captured in a graph (the stage pointer alternates).  A reorder draws every private
+    page before any page returns to the free list: the pool needs up to one page a row beyond what the rows hold.
+    The interface is ensure / trim / release / share_prefix / fork / reorder / append / dequantised.  `assign`, `pad_page=`, `ensure(dry_run=)` and `pages_for`
+    are helpers: the tests and the timing tool place pages by hand with `assign` (out-of-order tables, a poison page), the harness asks
+    every layer with `dry_run` before it changes one.  `assign` filters the free list per call and is not meant for a hot loop."""
+
+    def __init__(self, B: int, D: int, qk_params, pv_params, device, *, page_size: int, num_pages: int, max_pages: int, pad_page: int = None):
+        self._init_pages(B, D, qk_params, pv_params, device, page_size, num_pages, max_pages, pad_page)
+        self.kq, self.vq, self.stage = self._zeroed("mi355q_bfp_kv_paged_bytes", self.num_pages, self.page_size, self.B, self.D)
+        self._init_table(pad_page)
+
+    def trim(self, lengths, window: int) -> None:
+        """sliding-window attention: row b (lengths[b] keys, host ints, one per cache row) gives back every logical page i with
+        (i + 1) * page_size <= lengths[b] - window + 1 -- keys no query at a position >= lengths[b] sees, so no later windowed call reads
+        them (the windowed kernels look up only pages that hold a visible key).  Their table entries become `pad_page`, `held` keeps
+        None in their place; a page another row still holds (share_prefix) stays with that row.  One copy_ of the table when anything
+        changed.  Only for rows that are from here on read with this window (or a smaller one)."""
+        if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+            raise ValueError(f"PagedKVCache.trim: window = {window!r} is not an integer >= 1")
+        lengths = [int(n) for n in lengths]
+        if len(lengths) != self.B:
+            raise ValueError(f"PagedKVCache.trim: {len(lengths)} lengths for {self.B} cache rows")
+        changed = False
+        for b, n in enumerate(lengths):
+            held = self.held[b]
+            for i in range(min(max(n - window + 1, 0) // self.page_size, len(held))):
+                p = held[i]
+                if p is None:
+                    continue
+                self.refs[p] -= 1
+                if self.refs[p] == 0:
+                    self.free.append(p)
+                held[i] = None
+                self.table[b, i] = self.pad_page
+                changed = True
+        if changed:
+            self._upload()
 
     def append(self, k: torch.Tensor, v: torch.Tensor, *, lengths: torch.Tensor, counts: torch.Tensor = None, max_length: int = None) -> None:
         """KVCache.append in its ragged form (lengths: BEFORE the call; counts; max_length + n <= capacity).  The pages of the new keys
@@ -1973,6 +1988,54 @@ class PackedKVCache(_KVCacheBase):
             ctypes.addressof(self._pa), ctypes.addressof(self._pb), _stream_ptr(self.device)))
         return k, v
 
+
+
+class PagedPackedKVCache(_PagedHost):
+    """`PagedKVCache` with the int8-mantissa storage of `PackedKVCache`: pools of pages whose pieces are 512 mantissa bytes and 32
+    shared-exponent bytes (csrc/mi355q_kv8.h, paged pools) -- 17/32 of PagedKVCache's K and V bytes and of a decode step's K / V traffic,
+    with its pages, prefix sharing, fork and reorder.  PagedKVCache's constructor and interface -- ensure / assign / release /
+    share_prefix / fork / reorder / reset / append / dequantised / pages_for, `stage_alt`, `block_table`, `free` / `refs` / `held`, all
+    of them the same code (_PagedHost) -- on the storage `k8`, `v8`, `stage`; always addressed in the ragged form.  The cached operands
+    need width <= 8, as in PackedKVCache.  A class of its own: NOT a PagedKVCache, a PackedKVCache or a KVCache, so that only
+    bfp_attention_decode's route for it (form `_kv8_paged`) ever reads its bytes.  dequantised() and bfp_attention_decode give the bits
+    of PackedKVCache -- and so of KVCache / PagedKVCache, but for an input 0 < |x| <= 1e-8, stored as 0 -- for the same keys (decode:
+    with the same `splits`).  A recycled page pairs stale mantissas with stale exponents: finite, all a slot behind a row's length needs.
+    There is no extend kernel and no sliding window on this storage: `trim`, `window=` and bfp_attention_extend raise
+    NotImplementedError."""
+
+    POOLS = ("k8", "v8")
+    COPY_EXPORT = "mi355q_bfp_kv8_paged_copy"
+
+    def __init__(self, B: int, D: int, qk_params, pv_params, device, *, page_size: int, num_pages: int, max_pages: int, pad_page: int = None):
+        self._init_pages(B, D, qk_params, pv_params, device, page_size, num_pages, max_pages, pad_page)
+        for name, p in (("qk_params (K)", self.qk_params), ("pv_params (V)", self.pv_params)):
+            if int(p[3]) > 8:
+                raise ValueError(f"PagedPackedKVCache {name}: cached operand of width {p[3]} > 8: its mantissa, up to 2^{int(p[3]) - 1} - 1 in "
+                                 "magnitude, does not fit the int8 the cache stores (PagedKVCache takes width 9)")
+        self.k8, self.v8, self.stage = self._zeroed("mi355q_bfp_kv8_paged_bytes", self.num_pages, self.page_size, self.B, self.D)
+        self._init_table(pad_page)
+
+    def trim(self, lengths, window: int) -> None:
+        raise NotImplementedError("PagedPackedKVCache.trim: no sliding-window kernel reads a PagedPackedKVCache (int8 mantissas), so there is "
+                                  "nothing to trim for; windows need a KVCache or a PagedKVCache")
+
+    def append(self, k: torch.Tensor, v: torch.Tensor, *, lengths: torch.Tensor, counts: torch.Tensor = None, max_length: int = None) -> None:
+        """PagedKVCache.append on the packed pools (lengths: BEFORE the call; counts; max_length + n <= capacity; `ensure` first)"""
+        import ctypes
+        k3, v3, n, strides = self._append_args(k, v, lengths, counts, max_length)
+        _kv_call(self.device, "mi355q_bfp_kv8_append_paged", (
+            _ptr(self.k8), _ptr(self.v8), _ptr(self.stage), _ptr(k3), _ptr(v3), _ptr(lengths), _ptr(counts), _ptr(self.block_table), self.B,
+            self.max_pages, self.num_pages, self.page_size, self.D, n, int(max_length), ctypes.addressof(self._pa), ctypes.addressof(self._pb),
+            ctypes.addressof(strides), _stream_ptr(self.device)))
+
+    def dequantised(self, lengths: torch.Tensor, max_length: int = None):
+        """the rows' K and V as the decode kernels rebuild them, fp32 [B, max_length, D] through the page table, zeros behind lengths[b]"""
+        import ctypes
+        k, v = self._dequantised_out(lengths, max_length)
+        _kv_call(self.device, "mi355q_bfp_kv8_decode_fp32_paged", (
+            _ptr(self.k8), _ptr(self.v8), _ptr(lengths), _ptr(self.block_table), _ptr(k), _ptr(v), self.B, self.max_pages, self.num_pages,
+            self.page_size, self.D, int(max_length), ctypes.addressof(self._pa), ctypes.addressof(self._pb), _stream_ptr(self.device)))
+        return k, v
 
 
 _PAGED_NEEDS_LENGTHS = "a paged cache is always addressed in the ragged form: lengths= and max_length= (there is no uniform paged launch)"
@@ -2076,6 +2139,7 @@ def _cached_attention(op, q, cache, causal, scale_div, q_scale, token_major, spl
                                                                   (a contiguous cache: 1 page of `capacity` keys)
       _paged     a PagedKVCache                                   G, lengths, the block table, the paged dimensions
       _kv8       a PackedKVCache (decode only)                    G, lengths (as _window), k8 / v8 for kq / vq
+      _kv8_paged a PagedPackedKVCache (decode only)               as _paged, k8 / v8 for kq / vq
       _grouped   group != 1                                       G, lengths or NULL
       _ragged    lengths are given (decode only)                  lengths
       (none)     else                                             decode: L = cache.length; extend: lengths or NULL
@@ -2087,8 +2151,8 @@ def _cached_attention(op, q, cache, causal, scale_div, q_scale, token_major, spl
     out, osb, osm = _attention_out(q, M, D, token_major)
     sp = _stream_ptr(q.device)
     strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
-    paged, packed, windowed = isinstance(cache, PagedKVCache), isinstance(cache, PackedKVCache), window is not None
-    form = "_window" if windowed else "_paged" if paged else "_kv8" if packed else "_grouped" if group != 1 else \
+    paged, packed, windowed = isinstance(cache, _PagedHost), isinstance(cache, (PackedKVCache, PagedPackedKVCache)), window is not None
+    form = "_window" if windowed else "_kv8_paged" if paged and packed else "_paged" if paged else "_kv8" if packed else "_grouped" if group != 1 else \
         "_ragged" if decode and lengths is not None else ""
     if windowed or packed:
         lengths, L = _window_lengths(cache, lengths, max_length)
@@ -2136,12 +2200,13 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     W >= max_length (cache.length) gives the bits of window=None.  A paged cache may have trimmed the pages behind the window
     (PagedKVCache.trim).
     `cache` may be a PackedKVCache (int8 mantissas, 17/32 of the K / V bytes): the same keywords with the same meaning and the bits
-    of the same call on a KVCache holding the same keys; `window` is refused (NotImplementedError), and there is no paged form."""
-    if isinstance(cache, PackedKVCache):
+    of the same call on a KVCache holding the same keys; `window` is refused (NotImplementedError).  Its paged form is a
+    PagedPackedKVCache (always with `lengths`), with the same bits and the same refusal."""
+    if isinstance(cache, (PackedKVCache, PagedPackedKVCache)):
         if window is not None:
-            raise NotImplementedError("mi355q.bfp_attention_decode: no sliding-window kernel reads a PackedKVCache (int8 mantissas); "
+            raise NotImplementedError(f"mi355q.bfp_attention_decode: no sliding-window kernel reads a {type(cache).__name__} (int8 mantissas); "
                                       "window= needs a KVCache or a PagedKVCache")
-        why = _decode_call_check(q, cache, splits, lengths, max_length, group)
+        why = _PAGED_NEEDS_LENGTHS if cache.RAGGED_ONLY and lengths is None else _decode_call_check(q, cache, splits, lengths, max_length, group)
     else:
         why = _decode_check(q, cache, splits, lengths, max_length, group, causal=causal, window=window)
     if why is not None:
@@ -2202,8 +2267,8 @@ def bfp_attention_extend(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     `cache` may be a PagedKVCache (always with `lengths`): the bits of the same call on a KVCache holding the same keys.
     Sliding window (`window` = W >= 1, causal only) as bfp_attention_decode: row b's query i, at p = lengths[b] - counts[b] + i, sees
     keys max(0, p - W + 1) .. p; a block of 64 queries walks the keys from the 32-key step of its first query's lower bound on."""
-    if isinstance(cache, PackedKVCache):
-        raise NotImplementedError("mi355q.bfp_attention_extend: no extend kernel reads a PackedKVCache (int8 mantissas); chunked prefill "
+    if isinstance(cache, (PackedKVCache, PagedPackedKVCache)):
+        raise NotImplementedError(f"mi355q.bfp_attention_extend: no extend kernel reads a {type(cache).__name__} (int8 mantissas); chunked prefill "
                                   "needs a KVCache or a PagedKVCache")
     why = _extend_check(q, cache, lengths, counts, max_length, group, causal=causal, window=window)
     if why is not None:

@@ -2,12 +2,70 @@
 // tests/golden/kv_api_codes.json / .npz, for a sanitizer build.  Reads the lines `python tools/record_kv_api_codes.py --dump N` writes:
 //   export id, recorded code, the 27 flat arguments of mi355q_debug_kv_call, then for qk_params, pv_params and strides a 0 / 1 "given"
 //   and their 6, 6 and 4 values
-// and exits 1 at the first row whose code differs or that would launch.  Build and run: see the Makefile next to this file.
+// and exits 1 at the first row whose code differs or that would launch.  Behind them: the rows below for the four ids of the paged
+// int8-mantissa cache (KVX_KV8P_*), which the recorded table does not hold -- a valid call of each, which must pass with the paged view
+// and the int8 cache filled, and its refusals with the code written next to them.  Build and run: see the Makefile next to this file.
 #include <cstdio>
+#include <string>
 
 #include "mi355q_kv_call.h"
 
 using namespace mi355q;
+
+// the paged int8-mantissa ids: {id, what differs from the valid call, expected code, expected "would launch"}
+struct NewRow {
+    KvExport id;
+    const char* what;
+    int code;
+    bool go;
+};
+
+static int new_rows() {
+    const int32_t good[6] = {6, 8, 127, 6, 8, 127}, w9[6] = {6, 8, 127, 9, 8, 127};
+    int64_t nb[3];
+    const void* a = reinterpret_cast<const void*>(static_cast<uintptr_t>(0x10000));
+    const int32_t* a32 = static_cast<const int32_t*>(a);
+    const NewRow rows[] = {
+        {KVX_KV8P_BYTES, "", 0, true},         {KVX_KV8P_BYTES, "P48", MI355Q_E_BADARG, false},
+        {KVX_KV8P_APPEND, "", 0, true},        {KVX_KV8P_APPEND, "P48", MI355Q_E_BADARG, false},
+        {KVX_KV8P_APPEND, "over", MI355Q_E_BADARG, false},          // L + n > max_pages * P: the paged form's code
+        {KVX_KV8P_APPEND, "w9 n0", MI355Q_E_UNSUPPORTED, false},    // the int8 check, before the early 0
+        {KVX_KV8P_APPEND, "n0", 0, false},     {KVX_KV8P_APPEND, "notable", MI355Q_E_BADARG, false},
+        {KVX_KV8P_APPEND, "odd", MI355Q_E_ALIGN, false},
+        {KVX_KV8P_DECODE_FP32, "", 0, true},   {KVX_KV8P_DECODE_FP32, "over", MI355Q_E_BADARG, false},
+        {KVX_KV8P_DECODE_FP32, "w9 n0", MI355Q_E_UNSUPPORTED, false}, {KVX_KV8P_DECODE_FP32, "n0", 0, false},
+        {KVX_KV8P_DECODE, "", 0, true},        {KVX_KV8P_DECODE, "over", MI355Q_E_BADARG, false},
+        {KVX_KV8P_DECODE, "w9", MI355Q_E_UNSUPPORTED, false},       {KVX_KV8P_DECODE, "M17", MI355Q_E_UNSUPPORTED, false},
+        {KVX_KV8P_DECODE, "notable", MI355Q_E_BADARG, false},       {KVX_KV8P_DECODE, "odd", MI355Q_E_ALIGN, false},
+    };
+    int n = 0;
+    for (const NewRow& r : rows) {
+        const std::string w = r.what;
+        const auto has = [&w](const char* s) { return w.find(s) != std::string::npos; };
+        const bool over = has("over"), n0 = has("n0");
+        const void* kq = has("odd") ? reinterpret_cast<const void*>(static_cast<uintptr_t>(0x10008)) : a;
+        KvCall d = KV_EXPORTS[r.id];
+        d.pools(kq, a, a, has("notable") ? nullptr : a32, 4, 3, 12, has("P48") ? 48 : 64, 32).sizes(nb, nb + 1, nb + 2)
+            .rows(a, a, n0 ? 0 : 5).lens(a32, a32, over ? 193 : n0 && r.id != KVX_KV8P_APPEND ? 0 : 40)
+            .query(a, a, a, has("M17") ? 17 : 4, 2, 1, 0, 0).quant(has("w9") ? w9 : good, good, nullptr);
+        if (r.id == KVX_KV8P_APPEND) d.counts = a32;
+        else d.counts = nullptr;
+        KvChecked c;
+        int rc = 99;
+        const bool go = kv_call_check(d, c, rc);
+        bool ok = go == r.go && rc == r.code;
+        if (go && r.id != KVX_KV8P_BYTES)      // what the launchers get: the int8 cache at the rows' logical capacity, and the page table
+            ok = ok && c.c8.C == 192 && c.c8.D == 32 && c.c8.B == 4 && c.pages == &c.pg && c.pg.lg_p == 6 && c.pg.num_pages == 12 && c.pg.max_pages == 3 &&
+                 c.c.kq == nullptr && (r.id != KVX_KV8P_DECODE || c.G == 2);
+        if (!ok) {
+            std::printf("new row %d (export %d, '%s'): code %d (launch %d), expected %d (launch %d)\n", n, (int)r.id, r.what, rc, (int)go, r.code,
+                        (int)r.go);
+            return -1;
+        }
+        ++n;
+    }
+    return n;
+}
 
 int main() {
     long long id, code, a[27], given[3], vals[3][6];
@@ -41,6 +99,8 @@ int main() {
         }
         ++rows;
     }
-    std::printf("kv_call_rows: %d rows, every code as recorded\n", rows);
+    const int added = new_rows();
+    if (added < 0) return 1;
+    std::printf("kv_call_rows: %d rows, every code as recorded; %d rows of the paged int8-mantissa ids, every code as written\n", rows, added);
     return rows ? 0 : 2;
 }
