@@ -106,6 +106,9 @@ int launch_kv_append(const KvCache& c, const QuantArgs& ak, const QuantArgs& av,
 int launch_kv_append_ragged(const KvCache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
                             long long kst, long long vsb, long long vst, const int32_t* lengths, const int32_t* counts, long long n,
                             hipStream_t st, const KvPages* pages = nullptr);
+// the grid of a ragged append of up to n keys a row, from n alone: K blocks (-> kblocks) in front of V blocks, by B rows; more than 2^31
+// - 1 blocks: MI355Q_E_UNSUPPORTED.  launch_kv_append_ragged's and, in mi355q_kv8.hip, launch_kv8_append's
+int append_ragged_grid(long long B, int D, long long n, int& kblocks, dim3& grid);
 // the staging pass of launch_kv_append_ragged alone (n > 1: the new open tile's fp32 rows, behind the append kernel that read the old
 // ones): for the int8-mantissa cache of mi355q_kv8.h, whose stage is this one.  Reads c.stage, c.B, c.C and c.D only
 void launch_kv_stage_ragged(const KvCache& c, const float* k, long long ksb, long long kst, const int32_t* lengths, const int32_t* counts,
@@ -149,6 +152,12 @@ inline void fill_qo_strides(Args& g, const long long* strides, long long M, long
 }
 // heads of a group one launch row serves: the largest divisor gw of G with gw * M <= 16 (0: G < 1 or M outside 1 .. 16)
 int decode_group_width(long long G, long long M);
+// What a decode launch derives from its shapes, for a cache of B rows, capacity C, head_dim D: tile and pair counts of `span` keys (L,
+// or decode_window_span), group width and launch rows (-> rows), splits, pps, q / out strides, the workspace carve-up, the page table.
+// The grid is (g.S, rows).  Pointers to q, out, lengths and K / V, the window and the softmax's scalars stay with the caller.  Returns an
+// error code (group width, more than 65535 rows).  launch_bfp_attention_decode's and, in mi355q_kv8.hip, launch_bfp_attention_decode_kv8's
+int decode_args_fill(DecodeArgs& g, long long B, long long C, int D, long long M, long long L, long long span, int G, int splits,
+                     const long long* strides, void* workspace, const KvPages* pages, long long& rows);
 // lengths != NULL: the ragged form, L = max_length.  G >= 1: the grouped form (q / out hold c.B * G rows, the workspace is that of
 // c.B * G / decode_group_width(G, M) launch rows); G == 0: one query row a cache row.  pages != NULL (with lengths): the paged cache
 // window >= 1 (with lengths and causal): the sliding window; the workspace is that of decode_window_span keys

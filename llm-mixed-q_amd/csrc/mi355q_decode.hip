@@ -121,13 +121,7 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const QuantArgs ak, cons
             if (kl >= n || key >= a.c.C) return;               // (input rows behind the row's count are padding: never read)
         }
         float x[16];
-        float bmax = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float4 f = *reinterpret_cast<const float4*>(a.v + b * a.vsb + kl * a.vst + dt * 16 + 4 * i);
-            x[4 * i] = f.x; x[4 * i + 1] = f.y; x[4 * i + 2] = f.z; x[4 * i + 3] = f.w;
-            bmax = fmaxf(bmax, fmaxf(fmaxf(fabsf(f.x), fabsf(f.y)), fmaxf(fabsf(f.z), fabsf(f.w))));
-        }
+        const float bmax = append_v_block(a, b, kl, dt, x);
         const long long s = key >> 5;
         const int h = (int)(key >> 4) & 1, g = (int)(key & 15) >> 2, j = 4 * h + (int)(key & 3);
         long long ps = b * NPC + s;
@@ -171,6 +165,15 @@ int launch_kv_append(const KvCache& c, const QuantArgs& ak, const QuantArgs& av,
 // Grids from n alone: n keys touch at most (n + 14) / 16 + 1 tiles wherever they start, and an append that crosses a tile edge
 // leaves at most min(n - 1, 15) rows open (one key at least lies in tile t0).  The staging pass stays a second launch: tile t1's
 // rows overwrite the staged rows that tile t0's threads of the same row read.  n == 1, the decode step, never crosses.
+int append_ragged_grid(long long B, int D, long long n, int& kblocks_out, dim3& grid) {
+    const int per = 256 / D;
+    const long long kblocks = ((n + 14) / 16 + 1 + per - 1) / per, vblocks = (n * (D / 16) + 255) / 256;
+    if (kblocks + vblocks > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
+    kblocks_out = (int)kblocks;
+    grid = dim3((unsigned)(kblocks + vblocks), (unsigned)B);
+    return 0;
+}
+
 int launch_kv_append_ragged(const KvCache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
                             long long kst, long long vsb, long long vst, const int32_t* lengths, const int32_t* counts, long long n,
                             hipStream_t st, const KvPages* pages) {
@@ -178,11 +181,8 @@ int launch_kv_append_ragged(const KvCache& c, const QuantArgs& ak, const QuantAr
     a.c = c; a.k = k; a.v = v;
     a.ksb = ksb; a.kst = kst; a.vsb = vsb; a.vst = vst;
     a.n = n; a.lengths = lengths; a.counts = counts;
-    const int per = 256 / c.D;
-    const long long kblocks = ((n + 14) / 16 + 1 + per - 1) / per, vblocks = (n * (c.D / 16) + 255) / 256;
-    if (kblocks + vblocks > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
-    a.kblocks = (int)kblocks;
-    const dim3 grid((unsigned)(kblocks + vblocks), (unsigned)c.B);
+    dim3 grid;
+    if (const int rc = append_ragged_grid(c.B, c.D, n, a.kblocks, grid)) return rc;
     if (pages) {
         a.pg = *pages;
         hipLaunchKernelGGL((kv_append_kernel<true, true>), grid, dim3(256), 0, st, ak, av, a);
@@ -306,11 +306,7 @@ __global__ __launch_bounds__(256) void decode_scores_kernel(const QuantArgs aq, 
     }
     if constexpr (RG) {
         if (t0 + 2 * g.pps * s >= NT) { // a split wholly behind the row's last tile: the empty statistics, no kq read
-            if (tid < 16) {
-                float* st = g.stats + ((b * g.S + s) * 16 + tid) * 2;
-                st[0] = -INFINITY;
-                st[1] = 0.f;
-            }
+            dec_stats_empty(g, b, s, tid);
             return;
         }
     }
@@ -524,6 +520,25 @@ int decode_group_width(long long G, long long M) {
     return 1;
 }
 
+int decode_args_fill(DecodeArgs& g, long long B, long long C, int D, long long M, long long L, long long span, int G, int splits,
+                     const long long* strides, void* workspace, const KvPages* pages, long long& rows) {
+    if (pages) g.pg = *pages;
+    g.M = M; g.L = L; g.D = D;
+    g.NT = (span + 15) / 16; g.NP = (span + 31) / 32; g.NTC = C / 16; g.NPC = (C + 31) / 32;
+    g.gw = G ? decode_group_width(G, M) : 1;
+    if (g.gw < 1) return MI355Q_E_BADARG;
+    g.rpc = G ? G / g.gw : 1;
+    rows = B * g.rpc;                                       // launch rows: the workspace's and the grid's
+    if (rows > 65535) return MI355Q_E_UNSUPPORTED;
+    g.S = decode_splits(rows, span, D, splits);
+    g.pps = (int)((g.NP + g.S - 1) / g.S);
+    fill_qo_strides(g, strides, M, D);
+    g.scores = static_cast<float*>(workspace);
+    g.stats = g.scores + rows * g.NT * 256;
+    g.part = g.stats + rows * g.S * 32;
+    return 0;
+}
+
 // G == 0: one query row a cache row, the GQ = false kernels.  G >= 1: the grouped kernels over c.B * rpc launch rows.
 int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const KvCache& c, const float* q, float* out,
                                 void* workspace, long long M, long long L, int causal, float q_scale, float scale_div,
@@ -534,23 +549,11 @@ int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const 
     // windowed: partition, default splits and workspace strides are those of `span` keys, the most a row's queries can touch
     const long long span = window ? decode_window_span(M, L, window) : L;
     DecodeArgs g{};
+    long long rows;
+    if (const int rc = decode_args_fill(g, c.B, c.C, c.D, M, L, span, G, splits, strides, workspace, pages, rows)) return rc;
     g.W = window;
-    if (pages) g.pg = *pages;
     g.q = q; g.kq = c.kq; g.vq = c.vq; g.out = out; g.lengths = lengths;
-    g.M = M; g.L = L; g.D = c.D;
-    g.NT = (span + 15) / 16; g.NP = (span + 31) / 32; g.NTC = c.C / 16; g.NPC = (c.C + 31) / 32;
-    g.gw = G ? decode_group_width(G, M) : 1;
-    if (g.gw < 1) return MI355Q_E_BADARG;
-    g.rpc = G ? G / g.gw : 1;
-    const long long rows = c.B * g.rpc;                     // launch rows: the workspace's and the grid's
-    if (rows > 65535) return MI355Q_E_UNSUPPORTED;
-    g.S = decode_splits(rows, span, c.D, splits);
-    g.pps = (int)((g.NP + g.S - 1) / g.S);
-    fill_qo_strides(g, strides, M, c.D);
     g.causal = causal; g.q_scale = q_scale; g.scale_div = scale_div;
-    g.scores = static_cast<float*>(workspace);
-    g.stats = g.scores + rows * g.NT * 256;
-    g.part = g.stats + rows * g.S * 32;
     const dim3 grid((unsigned)g.S, (unsigned)rows);
 #define MI355Q_DECODE_GO2(DC_, RG_, GQ_, PG_, ...)                                                                  \
     hipLaunchKernelGGL((decode_scores_kernel<DC_, RG_, GQ_, PG_, ##__VA_ARGS__>), grid, dim3(256), 0, st, aq, g);    \

@@ -1,6 +1,8 @@
-// Device helpers the decode kernels of mi355q_decode.hip (bf16 cache) and mi355q_kv8.hip (int8-mantissa cache) share: a ragged row's
-// (length, count) of an append, a paged cache's table lookup, and what a lane of the split-key decode kernels knows of its column -- horizon, length, the grouped
-// column map.  Layout notes: mi355q_decode.h.
+// Device code the kernels of mi355q_decode.hip (bf16 cache) and mi355q_kv8.hip (int8-mantissa cache) share, one copy of each: a ragged
+// row's (length, count) of an append and the V walk that gathers a block, a paged cache's table lookup, what a lane of the split-key
+// decode kernels knows of its column -- horizon, length, the grouped column map -- and the empty split's statistics.  All force-inlined,
+// and only what leaves every kernel's instruction text as it was with the code in place (profiles/decode_shared_isa.txt, which also
+// names the blocks the two files still hold twice because a helper moved the text).  Layout notes: mi355q_decode.h.
 #ifndef MI355Q_DECODE_DEV_H
 #define MI355Q_DECODE_DEV_H
 #include <hip/hip_runtime.h>
@@ -17,6 +19,19 @@ __device__ __forceinline__ bool append_row(const Args& a, long long b, long long
     L = max(__builtin_amdgcn_readfirstlane(a.lengths[b]), 0);
     if (a.counts) n = min((long long)max(__builtin_amdgcn_readfirstlane(a.counts[b]), 0), a.n);
     return n > 0;
+}
+
+// V of an append: thread (new key kl of the row, 16-d block dt) takes one block
+template <class Args>
+__device__ __forceinline__ float append_v_block(const Args& a, long long b, long long kl, int dt, float (&x)[16]) {
+    float bmax = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float4 f = *reinterpret_cast<const float4*>(a.v + b * a.vsb + kl * a.vst + dt * 16 + 4 * i);
+        x[4 * i] = f.x; x[4 * i + 1] = f.y; x[4 * i + 2] = f.z; x[4 * i + 3] = f.w;
+        bmax = fmaxf(bmax, fmaxf(fmaxf(fabsf(f.x), fabsf(f.y)), fmaxf(fabsf(f.z), fabsf(f.w))));
+    }
+    return bmax;
 }
 
 // Paged cache: the table entry of row b's logical page i as loaded (pg_raw: i must be a page that holds keys of the row), and the
@@ -80,6 +95,15 @@ template <bool GQ>
 __device__ __forceinline__ long long dec_cache_row(const DecodeArgs& g, long long y) {
     if constexpr (GQ) return (long long)((unsigned)y / (unsigned)g.rpc);
     else return y;
+}
+
+// phase A, a split wholly behind the row's last tile: the empty statistics
+__device__ __forceinline__ void dec_stats_empty(const DecodeArgs& g, long long b, long long s, int tid) {
+    if (tid < 16) {
+        float* st = g.stats + ((b * g.S + s) * 16 + tid) * 2;
+        st[0] = -INFINITY;
+        st[1] = 0.f;
+    }
 }
 
 }  // namespace mi355q

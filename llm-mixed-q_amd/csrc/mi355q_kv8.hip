@@ -1,21 +1,18 @@
 // mi355q_kv8.hip -- the block_fp KV cache with int8 mantissas and one shared-exponent byte per block (layout, the rebuild and its
 // one deviation: mi355q_kv8.h), and the split-key decode attention on it.
 //
-// Everything here is a twin of mi355q_decode.hip on the helpers of mi355q_attn_dev.h / mi355q_decode_dev.h, in the ragged form only:
-//   kv8_append_kernel        kv_append_kernel<true, false>'s K and V walks (staged rows, new rows, zeros behind L + n), ending in a
-//                            packed kv8_store_block; the staging pass behind it is mi355q_decode.hip's own (launch_kv_stage_ragged)
-//   kv8_decode_fp32_kernel   the test hook
-//   decode8_scores_kernel    decode_scores_kernel<DC, true, GQ, false> / decode_pv_kernel<DC, true, GQ, false> with ONE difference: a K
-//   decode8_pv_kernel        or V fragment is 8 mantissa bytes and 8 exponent bytes a lane -- two 8-byte loads issued together, in
-//                            front of the arithmetic that needs them -- and is rebuilt in registers (kv8_rebuild): int8 -> fp32,
-//                            ldexp by the block's exponent, packed to bf16 pairs.  About 3.5 VALU operations a value, 28 a lane and
-//                            piece.  Phase C is decode_sum_kernel itself (launch_decode_sum): it reads no K / V.
-// Workspace, split partition, statistics and the order of every sum are those of mi355q_decode.hip, so a decode gives the bits of the
-// bf16 cache's decode with the same number of splits.
-// Paged pools (PG = true; layout and address rules: mi355q_kv8.h): every kernel here takes the flag, and with it only a piece's PLACE
-// changes -- pg_place of the row's table entry (mi355q_decode_dev.h), the page id clamped into the pool -- exactly as PG does in
-// mi355q_decode.hip: the decode loops ask for the NEXT tile's (pair's) entry while this one's two 8-byte loads are in flight and keep
-// it scalar.  PG = false is the code this file had before there were pages (profiles/decode_kv8_paged_isa.txt).
+// What this file owns, in the ragged form only: the piece layout's store (kv8_store_block) and place arithmetic, the rebuild of a K or
+// V fragment in registers (kv8_rebuild: int8 -> fp32, ldexp by the block's exponent, packed to bf16 pairs; about 3.5 VALU operations a
+// value) and where its loads sit -- 8 mantissa bytes and 8 exponent bytes a lane, two 8-byte loads issued together in front of the
+// arithmetic that needs them, the paged look-ahead (PG: the NEXT tile's or pair's table entry, kept scalar) behind them.
+// What it takes from elsewhere: append_row, append_v_block, pg_raw / pg_place, the column helpers and dec_stats_empty
+// (mi355q_decode_dev.h), the quantiser and softmax arithmetic (mi355q_attn_dev.h), and from mi355q_decode.hip the staging pass
+// (launch_kv_stage_ragged), phase C (launch_decode_sum) and the host arithmetic of both launches (append_ragged_grid, decode_args_fill).
+// What it still holds a second time, typed like decode_scores_kernel / decode_pv_kernel<DC, true, GQ, PG> and kv_append_kernel<true, PG>
+// because a helper changed some kernel's instruction text (profiles/decode_shared_isa.txt): the K walk, the per-tile statistics and
+// their reduction, the zero partial output, the row statistics, the probability block, the wave reduction.  A change to one of these
+// is made in both files: workspace, split partition, statistics and the order of every sum must stay those of mi355q_decode.hip, so
+// that a decode gives the bits of the bf16 cache's decode with the same number of splits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -103,13 +100,7 @@ __global__ __launch_bounds__(256) void kv8_append_kernel(const QuantArgs ak, con
         const int dt = (int)(item - kl * DT);
         if (kl >= n || key >= a.c.C) return;                   // (input rows behind the row's count are padding: never read)
         float x[16];
-        float bmax = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float4 f = *reinterpret_cast<const float4*>(a.v + b * a.vsb + kl * a.vst + dt * 16 + 4 * i);
-            x[4 * i] = f.x; x[4 * i + 1] = f.y; x[4 * i + 2] = f.z; x[4 * i + 3] = f.w;
-            bmax = fmaxf(bmax, fmaxf(fmaxf(fabsf(f.x), fabsf(f.y)), fmaxf(fabsf(f.z), fabsf(f.w))));
-        }
+        const float bmax = append_v_block(a, b, kl, dt, x);
         const long long s = key >> 5;
         const int h = (int)(key >> 4) & 1, g = (int)(key & 15) >> 2, j = 4 * h + (int)(key & 3);
         long long ps = b * NPC + s;
@@ -119,7 +110,6 @@ __global__ __launch_bounds__(256) void kv8_append_kernel(const QuantArgs ak, con
     }
 }
 
-// Grids from n alone, as launch_kv_append_ragged's: n keys touch at most (n + 14) / 16 + 1 tiles wherever they start.
 int launch_kv8_append(const Kv8Cache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
                       long long kst, long long vsb, long long vst, const int32_t* lengths, const int32_t* counts, long long n,
                       hipStream_t st, const KvPages* pages) {
@@ -127,11 +117,8 @@ int launch_kv8_append(const Kv8Cache& c, const QuantArgs& ak, const QuantArgs& a
     a.c = c; a.k = k; a.v = v;
     a.ksb = ksb; a.kst = kst; a.vsb = vsb; a.vst = vst;
     a.n = n; a.lengths = lengths; a.counts = counts;
-    const int per = 256 / c.D;
-    const long long kblocks = ((n + 14) / 16 + 1 + per - 1) / per, vblocks = (n * (c.D / 16) + 255) / 256;
-    if (kblocks + vblocks > 0x7FFFFFFFLL) return MI355Q_E_UNSUPPORTED;
-    a.kblocks = (int)kblocks;
-    const dim3 grid((unsigned)(kblocks + vblocks), (unsigned)c.B);
+    dim3 grid;
+    if (const int rc = append_ragged_grid(c.B, c.D, n, a.kblocks, grid)) return rc;
     if (pages) {
         a.pg = *pages;
         hipLaunchKernelGGL(kv8_append_kernel<true>, grid, dim3(256), 0, st, ak, av, a);
@@ -233,11 +220,7 @@ __global__ __launch_bounds__(256) void decode8_scores_kernel(const QuantArgs aq,
     const long long b = blockIdx.y, s = blockIdx.x, cb = dec_cache_row<GQ>(g, b);   // b: launch row (workspace), cb: cache row
     const long long L = dec_length<true>(g, cb), NT = (L + 15) >> 4;
     if (2 * g.pps * s >= NT) {          // a split wholly behind the row's last tile: the empty statistics, no k8 read
-        if (tid < 16) {
-            float* st = g.stats + ((b * g.S + s) * 16 + tid) * 2;
-            st[0] = -INFINITY;
-            st[1] = 0.f;
-        }
+        dec_stats_empty(g, b, s, tid);
         return;
     }
     long long row, qrow;
@@ -406,7 +389,7 @@ __global__ __launch_bounds__(256) void decode8_pv_kernel(const QuantArgs ap, con
     }
 }
 
-// launch_bfp_attention_decode's arithmetic for its ragged, unwindowed forms: the same launch rows, splits and workspace
+// launch_bfp_attention_decode's ragged, unwindowed forms: decode_args_fill with span = L
 int launch_bfp_attention_decode_kv8(const QuantArgs& aq, const QuantArgs& ap, const QuantArgs& ak, const QuantArgs& av, const Kv8Cache& c,
                                     const float* q, float* out, void* workspace, long long M, long long L, int causal, float q_scale,
                                     float scale_div, const long long* strides, int splits, hipStream_t st, const int32_t* lengths, int G,
@@ -414,24 +397,12 @@ int launch_bfp_attention_decode_kv8(const QuantArgs& aq, const QuantArgs& ap, co
     if (!lengths) return MI355Q_E_BADARG;                   // (no uniform launch)
     Decode8Args a{};
     DecodeArgs& g = a.g;
+    long long rows;
+    if (const int rc = decode_args_fill(g, c.B, c.C, c.D, M, L, L, G, splits, strides, workspace, pages, rows)) return rc;
     a.k8 = c.k8; a.v8 = c.v8;
-    if (pages) g.pg = *pages;
     a.k_down = kv8_down(ak); a.v_down = kv8_down(av);
     g.q = q; g.out = out; g.lengths = lengths;
-    g.M = M; g.L = L; g.D = c.D;
-    g.NT = (L + 15) / 16; g.NP = (L + 31) / 32; g.NTC = c.C / 16; g.NPC = (c.C + 31) / 32;
-    g.gw = G ? decode_group_width(G, M) : 1;
-    if (g.gw < 1) return MI355Q_E_BADARG;
-    g.rpc = G ? G / g.gw : 1;
-    const long long rows = c.B * g.rpc;                     // launch rows: the workspace's and the grid's
-    if (rows > 65535) return MI355Q_E_UNSUPPORTED;
-    g.S = decode_splits(rows, L, c.D, splits);
-    g.pps = (int)((g.NP + g.S - 1) / g.S);
-    fill_qo_strides(g, strides, M, c.D);
     g.causal = causal; g.q_scale = q_scale; g.scale_div = scale_div;
-    g.scores = static_cast<float*>(workspace);
-    g.stats = g.scores + rows * g.NT * 256;
-    g.part = g.stats + rows * g.S * 32;
     const dim3 grid((unsigned)g.S, (unsigned)rows);
 #define MI355Q_DECODE8_GO2(DC_, GQ_, PG_)                                                                            \
     hipLaunchKernelGGL((decode8_scores_kernel<DC_, GQ_, PG_>), grid, dim3(256), 0, st, aq, a);                       \

@@ -10,27 +10,17 @@ plus the SGPR count and whether the instruction streams are the same text.  Exit
 SGPRs, spills, scratch, LDS, MFMA or LDS-DMA counts."""
 from __future__ import annotations
 
-import re
 import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
-from kernel_table import demangle, parse, waves  # noqa: E402
+from kernel_table import body, demangle, parse, waves  # noqa: E402
 
 COLS = ("vgpr_count", "sgpr_count", "waves", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
         "group_segment_fixed_size", "instructions", "v_mfma", "global_load_lds")
 SHORT = ("vgpr", "sgpr", "waves", "vspill", "sspill", "scratch", "lds", "insts", "mfma", "ldsdma")
 MUST = ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size",
         "v_mfma", "global_load_lds")
-
-
-def body(path: Path, name: str) -> list[str]:
-    """the kernel's instructions without labels, comments and the symbol names that differ between twins"""
-    text = path.read_text()
-    start = text.index(f"\n{name}:")
-    lines = text[start:text.index(".Lfunc_end", start)].split("\n")
-    ins = [ln.split(";")[0].strip() for ln in lines if ln.startswith("\t") and ln.strip()[:1] not in (".", ";")]
-    return [re.sub(r"\.LBB\d+_", ".LBB_", i) for i in ins]
 
 
 def twin_of(old_name: str, suffix: str) -> str:
