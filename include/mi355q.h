@@ -788,6 +788,28 @@ int mi355q_bfp_attention_decode_kv8_paged(const float* q, const void* k8_pool, c
 int mi355q_bfp_kv8_paged_copy(void* k8_pool, void* v8_pool, const float* stage_src, float* stage_dst, const int32_t* jobs, int64_t n_jobs,
                               int64_t B, int64_t num_pages, int64_t P, int64_t D, void* stream);
 
+/* Block_minifloat cache: the contiguous cache of mi355q_bfp_kv_cache_bytes -- the same kq / vq / stage, sizes, layout and open-tile
+ * rule -- holding what the reference's block_minifloat [1,16] quantisers (block_minifloat.py:44-65, minifloat.py:158-194) make of k^T
+ * and v.  Replaces, for a layer whose matmul_0 / matmul_1 (bmm_0 / bmm_1) are block_minifloat, torch.cat of fp32 K / V
+ * (modeling_llama.py:301-306) and matmul_block_minifloat over all L keys on every step (matmul.py:199-249) -- the second of them with
+ * the softmax in front (modeling_llama.py:318-344).
+ *   qk_params / pv_params: int32[6] each, (width, exponent_width, exponent_bias_width) of data_in, then of weight.  Accepted:
+ *     exponent_width 1 .. 8, mantissa bits width - exponent_width - 1 in 1 .. 7 (a quantised value is then exact in bf16),
+ *     exponent_bias_width 1 .. 8 -- anything else MI355Q_E_UNSUPPORTED.  The append reads the weight sides, the decode all four.
+ * Always the ragged form (`lengths` mandatory, `counts` / max_length as in the *_ragged calls); G = 0 or 1 is the ungrouped form, G > 1
+ * as in mi355q_bfp_attention_decode_grouped.  Every other argument, code and rule is that of mi355q_bfp_kv_append_ragged /
+ * mi355q_bfp_attention_decode_grouped; sizes, workspace bytes, splits and the fp32 read-back are mi355q_bfp_kv_cache_bytes,
+ * mi355q_bfp_attention_decode_workspace_bytes, mi355q_bfp_attention_decode_splits and mi355q_bfp_kv_decode_fp32_ragged themselves.
+ * An all-zero block takes bias 0 (the reference: the smallest non-zero block maximum of the whole tensor -- not observable, a zero is
+ * a zero under any bias).  No paged, windowed or extend form reads this cache. */
+int mi355q_bm_kv_append(void* kq, void* vq, float* stage, const float* k, const float* v, const int32_t* lengths, const int32_t* counts,
+                        int64_t B, int64_t C, int64_t D, int64_t n, int64_t max_length, const int32_t* qk_params, const int32_t* pv_params,
+                        const int64_t* strides, void* stream);
+int mi355q_bm_attention_decode(const float* q, const void* kq, const void* vq, int32_t G, const int32_t* lengths, int32_t causal,
+                               float q_scale, float scale_div, float* out, void* workspace, int64_t B, int64_t M, int64_t max_length,
+                               int64_t C, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
+                               int32_t splits, void* stream);
+
 /* Sliding window: decode and extend with every query bound to its last `window` = W >= 1 keys, its own included -- a query at absolute
  * position p (decode: L_b - M + i; extend: L_b - m_b + i) sees keys max(0, p - W + 1) .. p.  That is the `past_key_value` call with an
  * additive mask that is finfo.min below the window as well as above the horizon: the cache is unchanged, K^T's and P's 16-key blocks

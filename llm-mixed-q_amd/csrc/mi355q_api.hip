@@ -1025,6 +1025,8 @@ int append(const KvCall& d, const float* k, const float* v, void* stream) {
     if (!kv_call_check(d, c, rc)) return rc;
     if (kv_int8(d.storage))
         return launch_kv8_append(c.c8, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.lengths, d.counts, d.n, hs(stream), c.pages);
+    if (d.form & KV_MINIFLOAT)
+        return launch_kvbm_append(c.c, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.lengths, d.counts, d.n, hs(stream));
     if (!(d.form & KV_LENGTHS)) return launch_kv_append(c.c, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.L, d.n, hs(stream));
     return launch_kv_append_ragged(c.c, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.lengths, d.counts, d.n, hs(stream), c.pages);
 }
@@ -1042,6 +1044,9 @@ int decode(const KvCall& d, const float* q, float* out, void* workspace, float q
     if (kv_int8(d.storage))
         return launch_bfp_attention_decode_kv8(c.aq, c.ap, c.ak, c.av, c.c8, q, out, workspace, d.M, d.L, c.causal, q_scale, scale_div, c.strides,
                                                d.splits, hs(stream), d.lengths, c.G, c.pages);
+    if (d.form & KV_MINIFLOAT)
+        return launch_bm_attention_decode(c.aq, c.ap, c.c, q, out, workspace, d.M, d.L, c.causal, q_scale, scale_div, c.strides, d.splits, hs(stream),
+                                          d.lengths, c.G);
     return launch_bfp_attention_decode(c.aq, c.ap, c.c, q, out, workspace, d.M, d.L, c.causal, q_scale, scale_div, c.strides, d.splits, hs(stream),
                                        d.lengths, c.G, c.pages, c.window);
 }
@@ -1254,6 +1259,22 @@ int mi355q_bfp_kv8_paged_copy(void* k8_pool, void* v8_pool, const float* stage_s
     return launch_kv_paged_copy(g, stream);
 }
 
+// block_minifloat cache: KVCache's storage and layout, the block_minifloat quantisers (mi355q_kvbm.h); always the ragged form, contiguous
+int mi355q_bm_kv_append(void* kq, void* vq, float* stage, const float* k, const float* v, const int32_t* lengths, const int32_t* counts,
+                        int64_t B, int64_t C, int64_t D, int64_t n, int64_t max_length, const int32_t* qk_params, const int32_t* pv_params,
+                        const int64_t* strides, void* stream) {
+    return append(KvCall(KV_EXPORTS[KVX_BM_APPEND]).cache(kq, vq, stage, B, C, D).rows(k, v, n).lens(lengths, counts, max_length)
+                      .quant(qk_params, pv_params, strides), k, v, stream);
+}
+
+int mi355q_bm_attention_decode(const float* q, const void* kq, const void* vq, int32_t G, const int32_t* lengths, int32_t causal,
+                               float q_scale, float scale_div, float* out, void* workspace, int64_t B, int64_t M, int64_t max_length,
+                               int64_t C, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
+                               int32_t splits, void* stream) {
+    return decode(KvCall(KV_EXPORTS[KVX_BM_DECODE]).cache(kq, vq, nullptr, B, C, D).lens(lengths, nullptr, max_length)
+                      .query(q, out, workspace, M, G, causal, 0, splits).quant(qk_params, pv_params, strides), q, out, workspace, q_scale, scale_div, stream);
+}
+
 // sliding window: a query sees its last `window` keys; always the ragged form, paged or (block_table == NULL) contiguous
 int64_t mi355q_bfp_attention_decode_window_span(int64_t M, int64_t max_length, int64_t window) {
     if (M < 1 || max_length < 1 || window < 1) return 0;
@@ -1291,9 +1312,11 @@ int mi355q_bfp_attention_extend_window(const float* q, const void* kq, const voi
 // causal, window, splits; qk_params / pv_params / strides as the exports take them.  out: the code, 1 where the export would go on
 // to launch (or to write its sizes), then the normalised call: B, capacity, D, M, L, n, G, window, lg_p, pages set, causal, strides set,
 // the four strides.
-__attribute__((visibility("default"))) int mi355q_debug_kv_call(int32_t id, const int64_t a[27], const int32_t* qk_params, const int32_t* pv_params,
-                                                                 const int64_t* strides, int64_t out[18]) {
-    if (id < 0 || id >= KVX_COUNT || !a || !out) return MI355Q_E_BADARG;
+// mi355q_debug_kv_call knows the 25 ids recorded in tests/golden/kv_api_codes.json, 0 .. KVX_KV8P_DECODE, and refuses every other as it
+// always has; mi355q_debug_kv_call_all is the same function over every id of KvExport (the block_minifloat exports behind them).
+static int debug_kv_call(int32_t id, int32_t ids, const int64_t a[27], const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
+                         int64_t out[18]) {
+    if (id < 0 || id >= ids || !a || !out) return MI355Q_E_BADARG;
     const auto p = [a](int i) { return reinterpret_cast<const void*>(static_cast<uintptr_t>(a[i])); };
     const auto p32 = [a](int i) { return reinterpret_cast<const int32_t*>(static_cast<uintptr_t>(a[i])); };
     const auto p64 = [a](int i) { return reinterpret_cast<const int64_t*>(static_cast<uintptr_t>(a[i])); };
@@ -1309,6 +1332,14 @@ __attribute__((visibility("default"))) int mi355q_debug_kv_call(int32_t id, cons
                                c.st[0], c.st[1], c.st[2], c.st[3]};
     for (int i = 0; i < 18; ++i) out[i] = words[i];
     return 0;
+}
+__attribute__((visibility("default"))) int mi355q_debug_kv_call(int32_t id, const int64_t a[27], const int32_t* qk_params, const int32_t* pv_params,
+                                                                 const int64_t* strides, int64_t out[18]) {
+    return debug_kv_call(id, KVX_KV8P_DECODE + 1, a, qk_params, pv_params, strides, out);
+}
+__attribute__((visibility("default"))) int mi355q_debug_kv_call_all(int32_t id, const int64_t a[27], const int32_t* qk_params,
+                                                                     const int32_t* pv_params, const int64_t* strides, int64_t out[18]) {
+    return debug_kv_call(id, KVX_COUNT, a, qk_params, pv_params, strides, out);
 }
 
 // block_minifloat (fmt 1) / block_log (fmt 2) products: the same two kernels with the other quantisers' block parameters

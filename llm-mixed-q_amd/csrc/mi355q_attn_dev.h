@@ -149,6 +149,91 @@ __device__ __forceinline__ bf16x8 at_pack_p(const float (&pq)[8]) {
     return __builtin_bit_cast(bf16x8, pk);
 }
 
+// ---- block_minifloat (the KV cache of mi355q_kvbm.hip) --------------------------------------------------------------------------
+// shared bias of a block whose largest magnitude is bmax >= 0 (block_minifloat.py:57-59): clamp(floor(log2(bmax)), 0, bias_max).
+// floor(log2(bmax)) is the fp32 exponent field -- except within a few ulps BELOW a power of two, where torch's fp32 log2 rounds up onto
+// the integer (the floor table's band, fraction >= FLOOR_THR_MIN); there, and for subnormals (normalised first; the clamp takes them
+// to 0 either way), some lane of the wave sends everybody to the walk, whose threshold comes from MEMORY as in at_block_exponent_mem.
+// bmax == 0 gives 0: an all-zero block holds exact zeros under any bias.
+__device__ __forceinline__ int at_bm_bias_mem(float bmax, const QuantArgs& a) {
+    const unsigned bits = __float_as_uint(bmax), E = bits >> 23, f = bits & 0x7FFFFFu;
+    if (__any((E == 0u && bits != 0u) || f >= MI355Q_LOG2_FLOOR_THR_MIN)) {
+        int k; unsigned m;
+        split_pos(bmax != 0.f ? bmax : 1.0f, k, m);
+        return clampi(k + ((k < 128 && m >= mi355q_log2_floor_thr[lut_index(k)]) ? 1 : 0), 0, a.bias_max);
+    }
+    return clampi((int)E - 127, 0, a.bias_max);
+}
+// element of a block with shared bias `bias` (minifloat.py:165-194): bm_elem_fused, and -- when ANY lane of the wave holds a value
+// whose |x| + 1e-9 lies in the band below a power of two -- the step again as quant_elem<FMT_BM> does it, floor(log2) from the table in
+// memory.  Both give the same value outside the band, so the lanes that were not near keep theirs.
+__device__ __forceinline__ float at_bm_quant(float x, int bias, int mbits, const QuantArgs& a) {
+    bool near = false;
+    float q = bm_elem_fused(x, 127 - bias, 127 + a.span - bias, mbits, a.shift, a.mant_max, near);
+    if (__any(near)) {
+        const float ax = fabsf(x);
+        int k; unsigned m;
+        split_pos(ax + EPS9, k, m);                                   // (>= 1e-9: normal)
+        const int e_min = -bias;
+        const int e = clampi(k + ((k < 128 && m >= mi355q_log2_floor_thr[lut_index(k)]) ? 1 : 0), e_min, a.span - bias);
+        const float mn = __builtin_ldexpf(ax, -e);
+        const bool normal = e != e_min;
+        const float sm = normal ? clampf(__builtin_rintf(mn * a.shift - a.shift), 0.f, a.mant_max)
+                                : clampf(__builtin_rintf(mn * a.shift * 0.5f), 0.f, a.mant_max);
+        const float frac = normal ? (1.0f + sm * a.inv_shift) : (sm * a.inv_shift * 2.0f);
+        const float qe = __builtin_copysignf(__builtin_ldexpf(1.0f, e) * frac, x);
+        q = ax <= ATOL ? x : qe;
+    }
+    return q;
+}
+// at_quant_q_frag under block_minifloat: the same lanes, loads and block maximum (lanes l, l ^ 16 of a chunk), the block's bias from
+// at_bm_bias_mem, the elements through at_bm_quant
+template <int DC>
+__device__ __forceinline__ void at_bm_quant_q_frag(bf16x8 (&qf)[DC], const float* __restrict__ qp, float q_scale, int lg, const QuantArgs& aq) {
+    const int mb = (int)__builtin_log2f(aq.shift);
+#pragma unroll
+    for (int c = 0; c < DC; ++c) {
+        float4 lo = *reinterpret_cast<const float4*>(qp + 32 * c + 8 * lg);
+        float4 hi = *reinterpret_cast<const float4*>(qp + 32 * c + 8 * lg + 4);
+        if (q_scale != 0.f) {
+            lo.x *= q_scale; lo.y *= q_scale; lo.z *= q_scale; lo.w *= q_scale;
+            hi.x *= q_scale; hi.y *= q_scale; hi.z *= q_scale; hi.w *= q_scale;
+        }
+        float bmax = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fmaxf(fabsf(lo.z), fabsf(lo.w))),
+                           fmaxf(fmaxf(fabsf(hi.x), fabsf(hi.y)), fmaxf(fabsf(hi.z), fabsf(hi.w))));
+        bmax = at_max2_16(bmax);
+        const int bias = at_bm_bias_mem(bmax, aq);
+        uint4 pk;
+        pk.x = pack_bf16(at_bm_quant(lo.x, bias, mb, aq), at_bm_quant(lo.y, bias, mb, aq));
+        pk.y = pack_bf16(at_bm_quant(lo.z, bias, mb, aq), at_bm_quant(lo.w, bias, mb, aq));
+        pk.z = pack_bf16(at_bm_quant(hi.x, bias, mb, aq), at_bm_quant(hi.y, bias, mb, aq));
+        pk.w = pack_bf16(at_bm_quant(hi.z, bias, mb, aq), at_bm_quant(hi.w, bias, mb, aq));
+        qf[c] = __builtin_bit_cast(bf16x8, pk);
+    }
+}
+// at_quant_p_block under block_minifloat.  A block of probabilities has a maximum <= 1, so its bias is 0 whatever the block holds --
+// no maximum, no reduction over the query's four lanes, no table -- and with bias 0 the element exponent clamp(floor(log2(p + 1e-9)),
+// 0, span) is 0 = e_min for every 0 <= p < 2: the subnormal branch alone, q = 2 min(rint(p 2^mbits / 2), 2^mbits - 1) / 2^mbits
+// (p = 1 stays 1; the band below 1 rounds to exponent 0 as well).  half_up = 2^(mbits - 1), two_dn = 2^(1 - mbits).
+// The values come out in TWO parts: pq the quantised probabilities (0 where p passes through), pt the probabilities p <= 1e-8 the
+// reference passes through unquantised (0 elsewhere).  pq times a quantised V is a sum of exactly representable terms; the pass-through
+// terms lie far below its last bit, and the matrix unit's accumulator does not round such an addend to nearest as the reference's fp32
+// product does -- one ulp of the output, which a coarse quantiser behind the attention (the out-projection's) turns into a whole step
+// wherever the exact sum sits on one of its ties, as sums of a few 4-bit values often do.  The caller accumulates the two parts apart
+// and adds them once, on the VALU.  Returns whether this lane holds a non-zero pass-through value.
+__device__ __forceinline__ bool at_bm_quant_p_block(const float (&pr)[4], float* pq, float* pt, float half_up, float two_dn, const QuantArgs& ap) {
+    bool tiny = false;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float m = fminf(__builtin_rintf(pr[e] * half_up), ap.mant_max);
+        const bool pass = pr[e] <= ATOL;
+        pq[e] = pass ? 0.f : m * two_dn;
+        pt[e] = pass ? pr[e] : 0.f;
+        tiny |= pass && pr[e] != 0.f;
+    }
+    return tiny;
+}
+
 // ---- softmax statistics of a lane that walks its query's keys 32 a step -------------------------------------------------------
 // (m_run, l_run) = (maximum, sum of exp(x - maximum)) over the scores seen so far, from (-inf, 0); a score of -inf is not a key.
 // Re-based when the maximum of ANY lane of the wave moves (rare after the first tiles; exp(-inf) = 0 takes care of the first one).

@@ -14,6 +14,7 @@
 #include "mi355q_internal.h"
 #include "mi355q_decode.h"
 #include "mi355q_kv8.h"
+#include "mi355q_kvbm.h"
 
 namespace mi355q {
 
@@ -40,6 +41,23 @@ inline int kv8_quant_args(const int32_t* qk_params, const int32_t* pv_params, Qu
     int rc;
     if ((rc = decode_quant_args(qk_params + 3, ak)) != 0 || (rc = decode_quant_args(pv_params + 3, av)) != 0) return rc;
     return int8 && (qk_params[3] > 8 || pv_params[3] > 8) ? MI355Q_E_UNSUPPORTED : 0;
+}
+// the block_minifloat quantiser of one operand: {width, exponent width, exponent bias width} at pr.  Exponent width 1 .. 8, mantissa
+// bits width - exponent width - 1 in 1 .. 7 (a quantised value must be exact in bf16), bias width 1 .. 8; anything else is unsupported
+inline int bm_quant_args(const int32_t* pr, QuantArgs& a) {
+    const int mbits = pr[0] - pr[1] - 1;
+    if (pr[1] < 1 || pr[1] > 8 || mbits < 1 || mbits > 7 || pr[2] < 1 || pr[2] > 8) return MI355Q_E_UNSUPPORTED;
+    a.b0 = 1; a.b1 = 16;
+    a.span = (1 << pr[1]) - 1;
+    a.bias_max = (1 << pr[2]) - 1;
+    set_mantissa(a, mbits);
+    return 0;
+}
+// the quantisers of a block_minifloat call: the cached operands' (y sides: append) or Q's and P's (x sides: decode)
+inline int bm_quant_pair(const int32_t* qk_params, const int32_t* pv_params, int side, QuantArgs& a, QuantArgs& b) {
+    int rc;
+    if ((rc = bm_quant_args(qk_params + side, a)) != 0 || (rc = bm_quant_args(pv_params + side, b)) != 0) return rc;
+    return 0;
 }
 inline int decode_cache_shape(int64_t B, int64_t C, int64_t D) {
     if (B < 1 || C < 1 || D < 1 || B > 65535) return MI355Q_E_BADARG;
@@ -76,13 +94,15 @@ enum : unsigned {
                         // (else G < 0 is refused and G <= 1 becomes 0, the ungrouped kernels)
     KV_WINDOW = 4,      // the *_window exports: causal and window >= 1 or BADARG, window clamped to L, causal passed as 1;
                         // block_table == NULL is the contiguous cache of max_pages * P keys
+    KV_MINIFLOAT = 8,   // the mi355q_bm_* exports: qk_params / pv_params are block_minifloat's {width, exponent width, exponent bias
+                        // width} (bm_quant_args) and the launchers are those of mi355q_kvbm.h; storage and layout stay KV_BF16's
 };
 // the exports in the order of include/mi355q.h (mi355q_debug_kv_call's export id)
 enum KvExport {
     KVX_CACHE_BYTES, KVX_APPEND, KVX_DECODE_FP32, KVX_DECODE, KVX_APPEND_RAGGED, KVX_DECODE_FP32_RAGGED, KVX_DECODE_RAGGED, KVX_EXTEND,
     KVX_DECODE_GROUPED, KVX_EXTEND_GROUPED, KVX_PAGED_BYTES, KVX_APPEND_PAGED, KVX_DECODE_FP32_PAGED, KVX_DECODE_PAGED, KVX_EXTEND_PAGED,
     KVX_KV8_CACHE_BYTES, KVX_KV8_APPEND, KVX_KV8_DECODE_FP32, KVX_DECODE_KV8, KVX_DECODE_WINDOW, KVX_EXTEND_WINDOW,
-    KVX_KV8P_BYTES, KVX_KV8P_APPEND, KVX_KV8P_DECODE_FP32, KVX_KV8P_DECODE, KVX_COUNT
+    KVX_KV8P_BYTES, KVX_KV8P_APPEND, KVX_KV8P_DECODE_FP32, KVX_KV8P_DECODE, KVX_BM_APPEND, KVX_BM_DECODE, KVX_COUNT
 };
 
 // one call of a KV-cache export: the form (what KV_EXPORTS says of the export), then the raw arguments; what an export does not
@@ -143,6 +163,7 @@ constexpr KvCall KV_EXPORTS[KVX_COUNT] = {
     {KV_PAGED, KV_DECODE, KV_LENGTHS | KV_WINDOW}, {KV_PAGED, KV_EXTEND, KV_LENGTHS | KV_WINDOW},
     {KV_INT8_PAGED, KV_BYTES, 0},     {KV_INT8_PAGED, KV_APPEND, KV_LENGTHS}, {KV_INT8_PAGED, KV_DEQUANT, KV_LENGTHS},
     {KV_INT8_PAGED, KV_DECODE, KV_LENGTHS},
+    {KV_BF16, KV_APPEND, KV_LENGTHS | KV_MINIFLOAT}, {KV_BF16, KV_DECODE, KV_LENGTHS | KV_MINIFLOAT},
 };
 
 // what the launchers take of a call that passed
@@ -161,7 +182,7 @@ struct KvChecked {
 // true: launch with `k`.  false: return rc (an MI355Q_E_* code, or 0 where there is nothing to do)
 inline bool kv_call_check(const KvCall& d, KvChecked& k, int& rc) {
     const bool attn = d.op == KV_DECODE || d.op == KV_EXTEND, int8 = kv_int8(d.storage), paged_form = kv_paged(d.storage);
-    const bool windowed = (d.form & KV_WINDOW) != 0;
+    const bool windowed = (d.form & KV_WINDOW) != 0, minifloat = (d.form & KV_MINIFLOAT) != 0;
     const auto stop = [&rc](int code) { rc = code; return false; };
     const auto misaligned = [](std::initializer_list<const void*> ptrs, uintptr_t to) {      // (an optional NULL passes)
         uintptr_t bits = 0;
@@ -189,7 +210,8 @@ inline bool kv_call_check(const KvCall& d, KvChecked& k, int& rc) {
         if (int8 && (rc = kv8_quant_args(d.qk_params, d.pv_params, k.ak, k.av)) != 0) return false;    // (int8: before the early 0)
         if (d.n == 0) return stop(0);
         if (no_cache || !d.stage || !d.k || !d.v) return stop(MI355Q_E_BADARG);
-        if (!int8 && (rc = kv8_quant_args(d.qk_params, d.pv_params, k.ak, k.av, false)) != 0) return false;
+        if (!int8 && (rc = minifloat ? bm_quant_pair(d.qk_params, d.pv_params, 3, k.ak, k.av) : kv8_quant_args(d.qk_params, d.pv_params, k.ak, k.av, false)) != 0)
+            return false;
         if (misaligned({d.kq, d.vq, d.stage, d.k, d.v}, 16) || misaligned({d.lengths, d.counts, d.block_table}, 4)) return stop(MI355Q_E_ALIGN);
         const long long dflt[4] = {d.n * d.D, d.D, d.n * d.D, d.D};
         for (int i = 0; i < 4; ++i) {
@@ -211,8 +233,12 @@ inline bool kv_call_check(const KvCall& d, KvChecked& k, int& rc) {
         if (decode && k.G && d.B * (k.G / decode_group_width(k.G, d.M)) > 65535) return stop(MI355Q_E_UNSUPPORTED);   // (the grid's second dimension)
         if (d.L > cap || no_cache || !d.q || !d.out || (decode && !d.workspace) || !d.qk_params || !d.pv_params || (d.counts && !d.lengths))
             return stop(MI355Q_E_BADARG);
-        if ((rc = decode_quant_args(d.qk_params, k.aq)) != 0 || (rc = decode_quant_args(d.pv_params, k.ap)) != 0 ||
-            (int8 && (rc = kv8_quant_args(d.qk_params, d.pv_params, k.ak, k.av)) != 0))
+        if (minifloat) {
+            // (the cached operands' parameters are checked too: a cache the append would refuse is refused here)
+            if ((rc = bm_quant_pair(d.qk_params, d.pv_params, 0, k.aq, k.ap)) != 0 || (rc = bm_quant_pair(d.qk_params, d.pv_params, 3, k.ak, k.av)) != 0)
+                return false;
+        } else if ((rc = decode_quant_args(d.qk_params, k.aq)) != 0 || (rc = decode_quant_args(d.pv_params, k.ap)) != 0 ||
+                   (int8 && (rc = kv8_quant_args(d.qk_params, d.pv_params, k.ak, k.av)) != 0))
             return false;
         if (misaligned({d.q, d.kq, d.vq, d.out, d.workspace}, 16) || misaligned({d.lengths, d.counts, d.block_table}, 4)) return stop(MI355Q_E_ALIGN);
         if (d.strides) {

@@ -481,6 +481,12 @@ class DecodeState:
     """One cache per layer and the current length, for `model(new_ids, cache=state)`.
     mode "block_fp": ops.KVCache + the split-key decode kernel -- both attention products block_fp [1,16] with widths <= 9 and a
         head_dim the kernel takes, else ValueError here, naming the reason.
+    mode "block": EACH layer gets the cache of its own format -- ops.KVCache where both products are block_fp (the calls of mode
+        "block_fp", unchanged), ops.MinifloatKVCache where both are block_minifloat; any other format, a bypassed product or two
+        formats in one layer: ValueError here, naming the layer.  A block_minifloat layer's prompt runs, behind its append, the
+        registry steps of the layer's full forward (the products, the mask, the softmax).  What the block_minifloat cache has no kernel
+        for is refused by name: extend=True, a sliding-window model, pages; a mixed call and more than 16 new tokens behind a non-empty
+        cache keep raising NotImplementedError.
     mode "fp32": the reference's literal route for ANY arithmetic (modeling_llama.py:301-344): torch.cat of fp32 K / V per layer, the
         products through the registry's functions, the causal mask [n, L] with the offset of modeling_llama.py:53-79.
     Ragged batches (`model(ids, cache=state, counts=[...])`, mode "block_fp" only): `lengths` holds every sequence's own length on the
@@ -503,10 +509,22 @@ class DecodeState:
     Paged caches: PagedDecodeState below (this constructor's parameters stay as they are)."""
     paged = False
 
+    @property
+    def cached(self) -> bool:
+        """the layers hold quantised caches (modes "block_fp" and "block"; "fp32" keeps fp32 K / V tensors)"""
+        return self.mode != "fp32"
+
     def __init__(self, model, batch: int, capacity: int, mode: str = "block_fp", extend: bool = False):
-        from .quantize.quantized_functions import decode_cache_params
-        if mode not in ("block_fp", "fp32"):
-            raise ValueError(f"DecodeState: mode {mode!r} is neither 'block_fp' nor 'fp32'")
+        from .quantize.quantized_functions import decode_cache_kind, decode_cache_params
+        if mode not in ("block_fp", "block", "fp32"):
+            raise ValueError(f"DecodeState: mode {mode!r} is neither 'block_fp' nor 'block' nor 'fp32'")
+        if mode == "block":
+            if extend:
+                raise NotImplementedError("DecodeState(mode='block'): extend=True: no extend (chunked prefill) kernel reads the block_minifloat cache")
+            if getattr(model.cfg, "sliding_window", None) is not None:
+                raise NotImplementedError("DecodeState(mode='block'): a sliding-window model: no windowed kernel reads the block_minifloat cache")
+            if self.paged:
+                raise NotImplementedError("DecodeState(mode='block'): page_size: the block_minifloat cache is not paged")
         attns = [layer.self_attn for layer in model.layers]
         if any(getattr(a, "mi355q_head_shard", None) is not None for a in attns):
             raise NotImplementedError("incremental decoding of head-sharded models")
@@ -518,15 +536,17 @@ class DecodeState:
         if self.capacity > model.cfg.max_positions + 15:
             raise ValueError(f"DecodeState: capacity {capacity} exceeds the model's {model.cfg.max_positions} positions")
         self.kv = [None] * len(attns)
-        if mode == "block_fp":
+        if self.cached:
             dev = next(model.parameters()).device
             for i, a in enumerate(attns):
                 c0, c1 = (a.qc["bmm_0"], a.qc["bmm_1"]) if "bmm_0" in a.qc else (a.qc["matmul_0"], a.qc["matmul_1"])
                 try:
-                    qk, pv = decode_cache_params(c0, c1, a.hd)
+                    kind, qk, pv = ("block_fp",) + decode_cache_params(c0, c1, a.hd) if mode == "block_fp" else decode_cache_kind(c0, c1, a.hd)
                 except ValueError as e:
-                    raise ValueError(f"DecodeState(mode='block_fp'), layer {i}: {e}") from None
-                self.kv[i] = self._new_cache(self.batch * getattr(a, "nkv", a.nh), a.hd, qk, pv, dev)
+                    raise ValueError(f"DecodeState(mode={mode!r}), layer {i}: {e}") from None
+                rows = self.batch * getattr(a, "nkv", a.nh)
+                self.kv[i] = self._new_cache(rows, a.hd, qk, pv, dev) if kind == "block_fp" else \
+                    ops.MinifloatKVCache(rows, self.capacity, a.hd, qk, pv, dev)
             if len({getattr(a, "nkv", a.nh) for a in attns}) == 1:    # (else: no ragged use; the per-row tensors are one set for all layers)
                 self.heads = getattr(attns[0], "nkv", attns[0].nh)    # cache rows a sequence: the KV heads
                 self.rows_before, self.rows_after, self._rows_counts = (torch.zeros(self.batch * self.heads, dtype=torch.int32, device=dev)
@@ -539,7 +559,7 @@ class DecodeState:
         self.length = 0
         self.lengths, self.ragged, self._call = [0] * self.batch, self.paged, None
         for i, c in enumerate(self.kv):
-            if self.mode == "block_fp":
+            if self.cached:
                 c.reset()
             else:
                 self.kv[i] = None
@@ -547,7 +567,7 @@ class DecodeState:
     def release(self, b: int) -> None:
         """sequence b is finished: its length becomes 0, so that a new sequence can start in slot b while the others continue (with
         extend=True: the mixed route); paged caches give its pages back to every layer's pool.  Nothing is cleared."""
-        if self.mode != "block_fp":
+        if not self.cached:
             raise NotImplementedError("DecodeState.release with mode='fp32': its rows have one common length")
         if not 0 <= int(b) < self.batch:
             raise ValueError(f"DecodeState.release: sequence {b} outside 0 .. {self.batch - 1}")
@@ -609,7 +629,7 @@ class DecodeState:
     def begin_ragged(self, counts, n: int, max_positions: int):
         """One ragged call: checks, the route, and the per-row tensors -- before any layer's cache is written.  -> positions [B, n]
         (host list of lists; padded positions repeat the row's last one)"""
-        if self.mode != "block_fp":
+        if not self.cached:
             raise NotImplementedError("counts= with mode='fp32': the reference serves unequal prompts by left padding + attention_mask, "
                                       "which under block quantisation gives different numbers (a pad key shares a 16-key block of K^T "
                                       "with real keys and moves their exponent); ragged batches run on the block_fp cache only")
@@ -661,7 +681,26 @@ class DecodeState:
                 heads = c.B // self.batch
                 c.trim([l for l in self.lengths for _ in range(heads)], self.window)
 
-    def _attend_ragged(self, idx, q, k, v, c0, c1, scale_div):
+    def _reference_steps(self, q, k, v, c0, c1, scale_div, style):
+        """the reference's steps (modeling_llama.py:309-344) for n queries at the last n of k's L positions: the two products through
+        the registry's functions, the causal mask [n, L] with the offset of modeling_llama.py:53-79 -- what mode "fp32" runs on its
+        concatenated K / V and what a block_minifloat layer's prompt runs in mode "block"""
+        B, nh, n, hd = q.shape
+        if k.shape[1] != nh:                                    # (grouped queries: the un-repeated K / V are kept, repeated at use)
+            k, v = _repeat_kv(k, nh // k.shape[1]), _repeat_kv(v, nh // k.shape[1])
+        L = k.shape[2]
+        if style == "bmm":
+            fold = lambda t: t.reshape(B * nh, t.shape[2], hd)
+            q, k, v = fold(q), fold(k), fold(v)
+        w = get_quantized_func(style, c0)(q, k.transpose(-1, -2), config=c0)
+        if scale_div:
+            w = w / scale_div
+        mask = _causal_mask(n, L, self.window, w.dtype, w.device)
+        w = torch.max(w + mask, w.new_full((), torch.finfo(w.dtype).min))
+        p = F.softmax(w, dim=-1, dtype=torch.float32).to(q.dtype)
+        return get_quantized_func(style, c1)(p, v, config=c1).view(B, nh, n, hd)
+
+    def _attend_ragged(self, idx, q, k, v, c0, c1, scale_div, style="matmul"):
         B, nh, n, hd = q.shape
         call, cache = self._call, self.kv[idx]
         gq = {} if k.shape[1] == nh else dict(group=nh // k.shape[1])      # (grouped queries: k, v have the KV heads only)
@@ -684,7 +723,9 @@ class DecodeState:
         # the sequence alone runs); prefill is not the hot path here
         o = q.new_zeros(B, nh, n, hd)
         for b, c in enumerate(call["counts"]):
-            if c:
+            if c and isinstance(cache, ops.MinifloatKVCache):   # (no one-pass attention function: the layer's full-forward steps)
+                o[b, :, :c] = self._reference_steps(q[b:b + 1, :, :c], k[b:b + 1, :, :c], v[b:b + 1, :, :c], c0, c1, scale_div, style)[0]
+            elif c:
                 o[b, :, :c] = get_quantized_func("attention", c1)(q[b:b + 1, :, :c], k[b:b + 1, :, :c], v[b:b + 1, :, :c], c0, c1, causal=True,
                                                                   scale_div=scale_div).reshape(nh, c, hd)
         return o
@@ -693,10 +734,10 @@ class DecodeState:
         """q, k, v [B, heads, n, hd] of the new tokens (q scaled / turned already) -> attention output [B, heads, n, hd]"""
         B, nh, n, hd = q.shape
         if self._call is not None:
-            return self._attend_ragged(idx, q, k, v, c0, c1, scale_div)
+            return self._attend_ragged(idx, q, k, v, c0, c1, scale_div, style)
         if self.length + n > self.capacity:
             raise ValueError(f"DecodeState: {self.length} + {n} tokens exceed the capacity {self.capacity}")
-        if self.mode == "block_fp":
+        if self.cached:
             cache = self.kv[idx]
             assert cache.length == self.length
             wide = self.length and n > ops.DECODE_MAX_QUERIES
@@ -707,6 +748,9 @@ class DecodeState:
             if self.window is not None:
                 gq["window"] = self.window
                 wide = wide or (self.length == 0 and n > self.window)      # (a prompt longer than the window: the windowed extend kernel)
+            if self.length == 0 and isinstance(cache, ops.MinifloatKVCache):
+                # the prompt of a block_minifloat layer: no one-pass attention function, the steps of the layer's full forward
+                return self._reference_steps(q, k, v, c0, c1, scale_div, style)
             if self.length == 0 and not wide:
                 # the prompt's own queries against the prompt: the existing attention function (M = n)
                 if "group" in gq:
@@ -717,19 +761,7 @@ class DecodeState:
         if self.kv[idx] is not None:
             k, v = torch.cat([self.kv[idx][0], k], dim=2), torch.cat([self.kv[idx][1], v], dim=2)
         self.kv[idx] = (k, v)
-        if k.shape[1] != nh:                                    # (grouped queries: the un-repeated K / V are kept, repeated at use)
-            k, v = _repeat_kv(k, nh // k.shape[1]), _repeat_kv(v, nh // k.shape[1])
-        L = k.shape[2]
-        if style == "bmm":
-            fold = lambda t: t.reshape(B * nh, t.shape[2], hd)
-            q, k, v = fold(q), fold(k), fold(v)
-        w = get_quantized_func(style, c0)(q, k.transpose(-1, -2), config=c0)
-        if scale_div:
-            w = w / scale_div
-        mask = _causal_mask(n, L, self.window, w.dtype, w.device)
-        w = torch.max(w + mask, w.new_full((), torch.finfo(w.dtype).min))
-        p = F.softmax(w, dim=-1, dtype=torch.float32).to(q.dtype)
-        return get_quantized_func(style, c1)(p, v, config=c1).view(B, nh, n, hd)
+        return self._reference_steps(q, k, v, c0, c1, scale_div, style)
 
 
 class PagedDecodeState(DecodeState):
@@ -744,6 +776,8 @@ class PagedDecodeState(DecodeState):
     def __init__(self, model, batch: int, capacity: int, mode: str = "block_fp", extend: bool = False, page_size: int = None,
                  num_pages: int = None):
         self.paged = page_size is not None
+        if self.paged and mode == "block":
+            raise NotImplementedError("PagedDecodeState(mode='block'): page_size: the block_minifloat cache is not paged")
         if self.paged and mode != "block_fp":
             raise ValueError("PagedDecodeState: page_size belongs to mode 'block_fp' (the fp32 route is not paged)")
         if num_pages is not None and not self.paged:

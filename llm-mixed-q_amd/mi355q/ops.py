@@ -1990,6 +1990,90 @@ class PackedKVCache(_KVCacheBase):
 
 
 
+def _minifloat_params(params, what):
+    """(width, exponent width, exponent bias width) of data_in, then of weight, as the block_minifloat cache takes them"""
+    p = tuple(int(x) for x in params)
+    if len(p) != 6:
+        raise ValueError(f"{what}: (x width, x exponent width, x exponent bias width, y width, y exponent width, y exponent bias width) expected")
+    for i in (0, 3):
+        if not 1 <= p[i + 1] <= 8:
+            raise ValueError(f"{what}: exponent width {p[i + 1]} outside 1 .. 8")
+        if not 1 <= p[i] - p[i + 1] - 1 <= 7:
+            raise ValueError(f"{what}: width {p[i]} with exponent width {p[i + 1]} leaves {p[i] - p[i + 1] - 1} mantissa bits, outside 1 .. 7 "
+                             "(a quantised value must be exact in bf16)")
+        if not 1 <= p[i + 2] <= 8:
+            raise ValueError(f"{what}: exponent bias width {p[i + 2]} outside 1 .. 8")
+    return p
+
+
+class MinifloatKVCache(_KVCacheBase):
+    """`KVCache` for a layer whose two attention products are block_minifloat [1,16]: the same storage (kq, vq, stage), sizes, layout and
+    open-tile rule, holding what the reference's block_minifloat quantisers make of K^T (blocks of 16 keys at one d) and V (blocks of
+    16 d of one key) -- values of at most 7 mantissa bits, exact in bf16 (csrc/mi355q_kvbm.h).  qk_params / pv_params: (width,
+    exponent_width, exponent_bias_width) of data_in, then of weight.  Same append / reset / dequantised / length / lengths= / counts= /
+    max_length= contract; a class of its own, NOT a KVCache: only bfp_attention_decode's route for it (form `bm`) reads it, with the
+    block_minifloat Q and P quantisers (no window, no pages, no fork / reorder, no bfp_attention_extend).  dequantised() gives the
+    reference quantiser's values rounded to bf16, bit for bit; an all-zero block stores zeros (the reference's fill from the tensor's
+    other blocks cannot show in a zero).  The kernels exist in the ragged form only: a call without `lengths` brings every row's
+    `length` as a device tensor."""
+
+    def __init__(self, B: int, capacity: int, D: int, qk_params, pv_params, device):
+        import ctypes
+        qk, pv = _minifloat_params(qk_params, "MinifloatKVCache qk_params"), _minifloat_params(pv_params, "MinifloatKVCache pv_params")
+        # (the shape checks of every cache; the parameter words it makes are block_fp's and are replaced by this cache's own)
+        self._init_rows(int(B), int(D), (2, 1, 0, 2, 1, 0), (2, 1, 0, 2, 1, 0), device, int(capacity))
+        self.qk_params, self.pv_params = qk, pv
+        self._pa, self._pb = (ctypes.c_int32 * 6)(*self.qk_params), (ctypes.c_int32 * 6)(*self.pv_params)
+        self.capacity, self.length = int(capacity), 0
+        # (zeroed: a V slot no key has reached meets a probability of exactly 0 and must be finite)
+        self.kq, self.vq, self.stage = self._zeroed("mi355q_bfp_kv_cache_bytes", self.B, self.capacity, self.D)
+
+    def reset(self) -> None:
+        # nothing to clear, as in KVCache.reset
+        self.length = 0
+
+    def append(self, k: torch.Tensor, v: torch.Tensor, *, lengths: torch.Tensor = None, counts: torch.Tensor = None,
+               max_length: int = None) -> None:
+        """KVCache.append under the block_minifloat quantisers: n >= 1 new fp32 rows k, v [B, n, D] (or [1, H, n, D] head views) become
+        keys length .. length + n - 1, or -- ragged -- row b's first counts[b] rows become its keys lengths[b] .. (lengths BEFORE the call)."""
+        import ctypes
+        k3, v3, n, strides = self._append_args(k, v, lengths, counts, max_length)
+        ragged = lengths is not None
+        if not ragged:      # (the kernels read lengths from the device: every row at `length`)
+            lengths, max_length = _window_lengths(self, None, None)
+        _kv_call(self.device, "mi355q_bm_kv_append", (
+            _ptr(self.kq), _ptr(self.vq), _ptr(self.stage), _ptr(k3), _ptr(v3), _ptr(lengths), _ptr(counts), self.B, self.capacity, self.D, n,
+            int(max_length), ctypes.addressof(self._pa), ctypes.addressof(self._pb), ctypes.addressof(strides), _stream_ptr(self.device)))
+        if not ragged:
+            self.length += n
+
+    def dequantised(self, lengths: torch.Tensor = None, max_length: int = None):
+        """the cache's quantised K and V as fp32 [B, length, D] (tests, debugging); ragged: [B, max_length, D], zeros behind each
+        row's lengths[b].  The read-back of KVCache: the layout is its own."""
+        k, v = self._dequantised_out(lengths, max_length)
+        if lengths is None:
+            lengths, max_length = _window_lengths(self, None, None)
+        _kv_call(self.device, "mi355q_bfp_kv_decode_fp32_ragged", (_ptr(self.kq), _ptr(self.vq), _ptr(lengths), _ptr(k), _ptr(v), self.B,
+                                                                     self.capacity, self.D, int(max_length), _stream_ptr(self.device)))
+        return k, v
+
+    def _refuse(self, what):
+        raise NotImplementedError(f"MinifloatKVCache.{what}: the block_minifloat cache is contiguous and has no {what} (pages, fork and reorder "
+                                  "belong to PagedKVCache, a block_fp cache)")
+
+    def fork(self, *a, **kw):
+        self._refuse("fork")
+
+    def reorder(self, *a, **kw):
+        self._refuse("reorder")
+
+    def ensure(self, *a, **kw):
+        self._refuse("ensure")
+
+    def trim(self, *a, **kw):
+        self._refuse("trim")
+
+
 class PagedPackedKVCache(_PagedHost):
     """`PagedKVCache` with the int8-mantissa storage of `PackedKVCache`: pools of pages whose pieces are 512 mantissa bytes and 32
     shared-exponent bytes (csrc/mi355q_kv8.h, paged pools) -- 17/32 of PagedKVCache's K and V bytes and of a decode step's K / V traffic,
@@ -2140,6 +2224,7 @@ def _cached_attention(op, q, cache, causal, scale_div, q_scale, token_major, spl
       _paged     a PagedKVCache                                   G, lengths, the block table, the paged dimensions
       _kv8       a PackedKVCache (decode only)                    G, lengths (as _window), k8 / v8 for kq / vq
       _kv8_paged a PagedPackedKVCache (decode only)               as _paged, k8 / v8 for kq / vq
+      bm         a MinifloatKVCache (decode only)                 as _kv8 on kq / vq: the export is mi355q_bm_attention_decode
       _grouped   group != 1                                       G, lengths or NULL
       _ragged    lengths are given (decode only)                  lengths
       (none)     else                                             decode: L = cache.length; extend: lengths or NULL
@@ -2152,9 +2237,10 @@ def _cached_attention(op, q, cache, causal, scale_div, q_scale, token_major, spl
     sp = _stream_ptr(q.device)
     strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
     paged, packed, windowed = isinstance(cache, _PagedHost), isinstance(cache, (PackedKVCache, PagedPackedKVCache)), window is not None
-    form = "_window" if windowed else "_kv8_paged" if paged and packed else "_paged" if paged else "_kv8" if packed else "_grouped" if group != 1 else \
+    minifloat = isinstance(cache, MinifloatKVCache)
+    form = "bm" if minifloat else "_window" if windowed else "_kv8_paged" if paged and packed else "_paged" if paged else "_kv8" if packed else "_grouped" if group != 1 else \
         "_ragged" if decode and lengths is not None else ""
-    if windowed or packed:
+    if windowed or packed or minifloat:
         lengths, L = _window_lengths(cache, lengths, max_length)
     else:
         L = int(max_length) if lengths is not None else cache.length
@@ -2168,7 +2254,7 @@ def _cached_attention(op, q, cache, causal, scale_div, q_scale, token_major, spl
         capacity = (cache.max_pages, cache.num_pages, cache.page_size) if paged else (1, 1, cache.capacity)
     else:
         capacity = (cache.capacity,)
-    _kv_call(q.device, f"mi355q_bfp_attention_{op}{form}", (
+    _kv_call(q.device, "mi355q_bm_attention_decode" if minifloat else f"mi355q_bfp_attention_{op}{form}", (
         _ptr(q3), *((_ptr(cache.k8), _ptr(cache.v8)) if packed else (_ptr(cache.kq), _ptr(cache.vq))), *which,
         *((1, int(window)) if windowed else (int(bool(causal)),)), float(q_scale) if q_scale else 0.0, float(scale_div) if scale_div else 0.0,
         _ptr(out), *((_ptr(_decode_workspace(q, cache, M, D, group, sp)),) if decode else ()), cache.B, M, L, *capacity, D,
@@ -2201,8 +2287,15 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     (PagedKVCache.trim).
     `cache` may be a PackedKVCache (int8 mantissas, 17/32 of the K / V bytes): the same keywords with the same meaning and the bits
     of the same call on a KVCache holding the same keys; `window` is refused (NotImplementedError).  Its paged form is a
-    PagedPackedKVCache (always with `lengths`), with the same bits and the same refusal."""
-    if isinstance(cache, (PackedKVCache, PagedPackedKVCache)):
+    PagedPackedKVCache (always with `lengths`), with the same bits and the same refusal.
+    `cache` may be a MinifloatKVCache (both products block_minifloat): the same keywords with the same meaning, Q and P through the
+    block_minifloat quantisers of the cache's parameters; `window` is refused (NotImplementedError)."""
+    if isinstance(cache, MinifloatKVCache):
+        if window is not None:
+            raise NotImplementedError("mi355q.bfp_attention_decode: no sliding-window kernel reads a MinifloatKVCache (block_minifloat); "
+                                      "window= needs a KVCache or a PagedKVCache")
+        why = _decode_call_check(q, cache, splits, lengths, max_length, group)
+    elif isinstance(cache, (PackedKVCache, PagedPackedKVCache)):
         if window is not None:
             raise NotImplementedError(f"mi355q.bfp_attention_decode: no sliding-window kernel reads a {type(cache).__name__} (int8 mantissas); "
                                       "window= needs a KVCache or a PagedKVCache")
@@ -2267,6 +2360,9 @@ def bfp_attention_extend(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     `cache` may be a PagedKVCache (always with `lengths`): the bits of the same call on a KVCache holding the same keys.
     Sliding window (`window` = W >= 1, causal only) as bfp_attention_decode: row b's query i, at p = lengths[b] - counts[b] + i, sees
     keys max(0, p - W + 1) .. p; a block of 64 queries walks the keys from the 32-key step of its first query's lower bound on."""
+    if isinstance(cache, MinifloatKVCache):
+        raise NotImplementedError("mi355q.bfp_attention_extend: no extend kernel reads a MinifloatKVCache (block_minifloat); chunked prefill "
+                                  "needs a KVCache or a PagedKVCache")
     if isinstance(cache, (PackedKVCache, PagedPackedKVCache)):
         raise NotImplementedError(f"mi355q.bfp_attention_extend: no extend kernel reads a {type(cache).__name__} (int8 mantissas); chunked prefill "
                                   "needs a KVCache or a PagedKVCache")

@@ -286,6 +286,46 @@ def attention_decode_block_fp(q, cache, config_qk, config_pv, causal=True, scale
                                     max_length=max_length, group=group, window=window)
 
 
+def decode_cache_kind(config_qk, config_pv, head_dim):
+    """(name, qk_params, pv_params) of the KV cache that serves the two products' configs: "block_fp" -> ops.KVCache with
+    decode_cache_params' words, "block_minifloat" -> ops.MinifloatKVCache with (width, exponent_width, exponent_bias_width) of data_in,
+    then of weight -- or ValueError naming why no cache serves them (bypassed, two formats, block_log and the unblocked formats, a
+    block size or width a cache does not take): such a layer decodes on the reference's route, torch.cat of fp32 K / V."""
+    from ... import ops
+    names = [("bypassed" if c.get("bypass", False) else c.get("name")) for c in (config_qk, config_pv)]
+    if names == ["block_fp", "block_fp"]:
+        return ("block_fp",) + decode_cache_params(config_qk, config_pv, head_dim)
+    if names != ["block_minifloat", "block_minifloat"]:
+        raise ValueError(f"KV cache: the attention products are {names[0]} and {names[1]}; a cache serves two block_fp or two block_minifloat products")
+    for which, c in (("first", config_qk), ("second", config_pv)):
+        for side in ("data_in", "weight"):
+            bs = list(c[f"{side}_block_size"])
+            if ops.resolve_blocking([2, 32, 32], bs, True)[3:] != (1, 16):
+                raise ValueError(f"block_minifloat KV cache: {side}_block_size {bs} of the {which} product is not [1, 16]")
+            w, ew, bw = (int(c[f"{side}_{key}"]) for key in ("width", "exponent_width", "exponent_bias_width"))
+            if not (1 <= ew <= 8 and 1 <= w - ew - 1 <= 7 and 1 <= bw <= 8):
+                raise ValueError(f"block_minifloat KV cache: {side} (width, exponent_width, exponent_bias_width) = ({w}, {ew}, {bw}) of the {which} "
+                                 "product: exponent width and bias width 1 .. 8, mantissa bits 1 .. 7 (exact in bf16)")
+    if head_dim % 32 != 0 or head_dim > ops.ATTENTION_MAX_HEAD_DIM:
+        raise ValueError(f"block_minifloat KV cache: head_dim {head_dim} is not a multiple of 32 up to {ops.ATTENTION_MAX_HEAD_DIM}")
+    par = lambda c: (c["data_in_width"], c["data_in_exponent_width"], c["data_in_exponent_bias_width"], c["weight_width"],
+                     c["weight_exponent_width"], c["weight_exponent_bias_width"])
+    return "block_minifloat", par(config_qk), par(config_pv)
+
+
+def attention_decode_block_minifloat(q, cache, config_qk, config_pv, causal=True, scale_div=None, q_scale=None, lengths=None, max_length=None,
+                                     group=1, window=None):
+    """attention_decode_block_fp for two block_minifloat products: the last M <= 16 positions against an `ops.MinifloatKVCache` that
+    already holds their keys (ops.bfp_attention_decode's route for it).  Registry key "attention_decode", name "block_minifloat"; no
+    additive mask, no other route, and `window` is refused there by name."""
+    from ... import ops
+    if decode_cache_kind(config_qk, config_pv, q.shape[-1])[0] != "block_minifloat":
+        raise ValueError("attention_decode_block_minifloat: the two products are block_fp (attention_decode_block_fp serves them)")
+    return ops.bfp_attention_decode(q, cache, causal=causal, scale_div=scale_div, q_scale=q_scale,
+                                    token_major=bool(config_pv.get("mi355q_token_major_output", False)), lengths=lengths,
+                                    max_length=max_length, group=group, window=window)
+
+
 def attention_extend_block_fp(q, cache, config_qk, config_pv, causal=True, scale_div=None, q_scale=None, lengths=None, counts=None,
                               max_length=None, group=1, window=None):
     """The attention core for the last M positions -- any M -- against an `ops.KVCache` that already holds their keys (chunked
@@ -427,6 +467,6 @@ QUANTIZED_FUNC_MAP = {
 # Additions that take something other than tensors (a KV cache): looked up by get_quantized_func like the map above, kept apart
 # from it because QUANTIZED_FUNC_MAP's keys are pinned to the reference's ops plus the softmax / attention folds.
 EXTRA_FUNC_MAP = {
-    "attention_decode": {"block_fp": attention_decode_block_fp},
+    "attention_decode": {"block_fp": attention_decode_block_fp, "block_minifloat": attention_decode_block_minifloat},
     "attention_extend": {"block_fp": attention_extend_block_fp},
 }

@@ -4,7 +4,8 @@
 //   and their 6, 6 and 4 values
 // and exits 1 at the first row whose code differs or that would launch.  Behind them: the rows below for the four ids of the paged
 // int8-mantissa cache (KVX_KV8P_*), which the recorded table does not hold -- a valid call of each, which must pass with the paged view
-// and the int8 cache filled, and its refusals with the code written next to them.  Build and run: see the Makefile next to this file.
+// and the int8 cache filled, and its refusals with the code written next to them -- and, the same way, rows for the two ids of the
+// block_minifloat cache (KVX_BM_APPEND, KVX_BM_DECODE), whose quantiser words are (width, exponent width, exponent bias width).  Build and run: see the Makefile next to this file.
 #include <cstdio>
 #include <string>
 
@@ -67,6 +68,57 @@ static int new_rows() {
     return n;
 }
 
+// the block_minifloat ids: contiguous, always ragged; the append reads the weight sides of the words, the decode all four
+static int bm_rows() {
+    const int32_t good[6] = {8, 4, 8, 8, 4, 8}, bfp[6] = {6, 8, 127, 6, 8, 127}, x_bad[6] = {12, 9, 0, 8, 4, 8}, m0[6] = {8, 4, 8, 5, 4, 8},
+                  m8[6] = {8, 4, 8, 12, 3, 8}, bw9[6] = {8, 4, 8, 8, 4, 9};
+    const void* a = reinterpret_cast<const void*>(static_cast<uintptr_t>(0x10000));
+    const int32_t* a32 = static_cast<const int32_t*>(a);
+    const int64_t odd_st[4] = {32, 32, 34, 32};
+    const NewRow rows[] = {
+        {KVX_BM_APPEND, "", 0, true},                                {KVX_BM_APPEND, "nolengths", MI355Q_E_BADARG, false},
+        {KVX_BM_APPEND, "over", MI355Q_E_UNSUPPORTED, false},        {KVX_BM_APPEND, "n0", 0, false},
+        {KVX_BM_APPEND, "n0 m0", 0, false},                          // (as for the bf16 cache: the early 0 comes before the quantiser words)
+        {KVX_BM_APPEND, "bfp", MI355Q_E_UNSUPPORTED, false},         {KVX_BM_APPEND, "m0", MI355Q_E_UNSUPPORTED, false},
+        {KVX_BM_APPEND, "m8", MI355Q_E_UNSUPPORTED, false},          {KVX_BM_APPEND, "bw9", MI355Q_E_UNSUPPORTED, false},
+        {KVX_BM_APPEND, "xbad", 0, true},                            // the x sides are not the append's
+        {KVX_BM_APPEND, "odd", MI355Q_E_ALIGN, false},               {KVX_BM_APPEND, "stride", MI355Q_E_ALIGN, false},
+        {KVX_BM_APPEND, "D48", MI355Q_E_UNSUPPORTED, false},
+        {KVX_BM_DECODE, "", 0, true},                                {KVX_BM_DECODE, "nolengths", MI355Q_E_BADARG, false},
+        {KVX_BM_DECODE, "over", MI355Q_E_BADARG, false},             {KVX_BM_DECODE, "M17", MI355Q_E_UNSUPPORTED, false},
+        {KVX_BM_DECODE, "bfp", MI355Q_E_UNSUPPORTED, false},         {KVX_BM_DECODE, "xbad", MI355Q_E_UNSUPPORTED, false},
+        {KVX_BM_DECODE, "m0", MI355Q_E_UNSUPPORTED, false},          {KVX_BM_DECODE, "m8", MI355Q_E_UNSUPPORTED, false},
+        {KVX_BM_DECODE, "bw9", MI355Q_E_UNSUPPORTED, false},         {KVX_BM_DECODE, "odd", MI355Q_E_ALIGN, false},
+        {KVX_BM_DECODE, "stride", MI355Q_E_ALIGN, false},            {KVX_BM_DECODE, "Gneg", MI355Q_E_BADARG, false},
+    };
+    int n = 0;
+    for (const NewRow& r : rows) {
+        const std::string w = r.what;
+        const auto has = [&w](const char* s) { return w.find(s) != std::string::npos; };
+        const bool append = r.id == KVX_BM_APPEND, n0 = has("n0");
+        const int32_t* words = has("bfp") ? bfp : has("xbad") ? x_bad : has("m0") ? m0 : has("m8") ? m8 : has("bw9") ? bw9 : good;
+        const void* kq = has("odd") ? reinterpret_cast<const void*>(static_cast<uintptr_t>(0x10008)) : a;
+        KvCall d = KV_EXPORTS[r.id];
+        d.cache(kq, a, a, 4, 64, has("D48") ? 48 : 32).rows(a, a, n0 ? 0 : 5)
+            .lens(has("nolengths") ? nullptr : a32, append ? a32 : nullptr, has("over") ? (append ? 60 : 65) : 40)
+            .query(a, a, a, has("M17") ? 17 : 4, has("Gneg") ? -1 : 2, 1, 0, 0).quant(words, words, has("stride") ? odd_st : nullptr);
+        KvChecked c;
+        int rc = 99;
+        const bool go = kv_call_check(d, c, rc);
+        bool ok = go == r.go && rc == r.code;
+        if (go)       // what the launchers get: the bf16 cache, no pages, and the block_minifloat quantisers' words
+            ok = ok && c.c.C == 64 && c.c.D == 32 && c.c.B == 4 && c.pages == nullptr && c.c8.k8 == nullptr && c.ak.span == 15 && c.ak.bias_max == 255 &&
+                 c.av.shift == 8.0f && c.av.mant_max == 7.0f && (append || (c.G == 2 && c.aq.span == 15 && c.ap.shift == 8.0f && c.causal == 1));
+        if (!ok) {
+            std::printf("block_minifloat row %d (export %d, '%s'): code %d (launch %d), expected %d (launch %d)\n", n, (int)r.id, r.what, rc, (int)go,
+                        r.code, (int)r.go);
+            return -1;
+        }
+        ++n;
+    }
+    return n;
+}
+
 int main() {
     long long id, code, a[27], given[3], vals[3][6];
     const int len[3] = {6, 6, 4};
@@ -100,7 +152,9 @@ int main() {
         ++rows;
     }
     const int added = new_rows();
-    if (added < 0) return 1;
-    std::printf("kv_call_rows: %d rows, every code as recorded; %d rows of the paged int8-mantissa ids, every code as written\n", rows, added);
+    const int added_bm = bm_rows();
+    if (added < 0 || added_bm < 0) return 1;
+    std::printf("kv_call_rows: %d rows, every code as recorded; %d rows of the paged int8-mantissa ids and %d of the block_minifloat ids, every code as written\n",
+                rows, added, added_bm);
     return rows ? 0 : 2;
 }
