@@ -110,6 +110,17 @@ __device__ __forceinline__ f32x4 v9_mma(const i32x4& fw, const i32x4& fx, const 
 #define V9_GLDS4(gp, lds) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" ::"v"(gp), "s"(lds) : "memory")
 #define V9_BLDS16(vo, rs, so, lds) asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(vo), "s"(rs), "s"(so), "s"(lds) : "memory")
 #define V9_BLDS4(vo, rs, so, lds) asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dword %0, %1, %2 offen lds" ::"v"(vo), "s"(rs), "s"(so), "s"(lds) : "memory")
+// The 16-byte stores of y in the one-pass epilogue.  The tile kernel that ships (this unit) stores WRITE-THROUGH (sc1): a plain
+// store leaves its line dirty in the XCD's L2 and the launch cannot end before every compute unit's 256 KiB have been written
+// back; written through, the lines leave while the epilogue still runs -- 0.9-1.4 us of the 4096^3 step.
+// The line is dropped from L2, which costs the reader nothing here: y (64 MiB) does not fit the L2s anyway.  (s_nop 1 inside
+// the string: the compiler does not pad behind inline assembly, and its next instruction may write the data registers.)
+// The mixed, gated and residual units keep the plain store they were measured with.
+#if defined(V9_MIXED_TU) || defined(V9_GATED_TU) || defined(V9_RESID_TU)
+#define V9_STORE16(p, v) (*reinterpret_cast<f32x4*>(p) = (v))
+#else
+#define V9_STORE16(p, v) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory")
+#endif
 __device__ __forceinline__ i32x4 v9_desc(const void* base, int bytes) {       // raw buffer descriptor of `bytes` bytes at `base`
     const unsigned long long b = reinterpret_cast<unsigned long long>(base);
     return i32x4{(int)(unsigned)b, (int)(unsigned)(b >> 32), bytes, 0x00020000};
@@ -881,11 +892,7 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
                             if (col + r < Ni) val[r] += rr[r];
                 }
                 if (vec_ok && col + 3 < Ni) {
-                    // (experiment, MI355Q_V9_DBG bits 8 / 16 / 32: write-through / system-scope / non-temporal stores)
-                    if (a.dbg & 8) asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(yrow + j * 16), "v"(val) : "memory");
-                    else if (a.dbg & 16) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(yrow + j * 16), "v"(val) : "memory");
-                    else if (a.dbg & 32) asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(yrow + j * 16), "v"(val) : "memory");
-                    else *reinterpret_cast<f32x4*>(yrow + j * 16) = val;
+                    *reinterpret_cast<f32x4*>(yrow + j * 16) = val;
                 } else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
@@ -1225,8 +1232,7 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
                 for (int j = 0; j < 4; ++j) {
                     const int col = n0 + wn * 64 + j * 16 + lq * 4;
                     if (vec_ok && col + 3 < Ni) {
-                        if (a.dbg & 8) asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(yrow + j * 16), "v"(val[j]) : "memory");
-                        else *reinterpret_cast<f32x4*>(yrow + j * 16) = val[j];
+                        V9_STORE16(yrow + j * 16, val[j]);
                     } else {
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
