@@ -15,6 +15,7 @@
 #include "mi355q_decode.h"
 #include "mi355q_kv8.h"
 #include "mi355q_extend.h"
+#include "mi355q_linear_call.h"
 #include "mi355q_kv_call.h"
 #include "mi355q_kv_copy.h"
 #include "mi355q_align_row.h"
@@ -56,33 +57,43 @@ struct GemmTiming {
     }
 } g_timing;
 
-}  // namespace
-namespace mi355q { KernelEvents g_kernel_events = {nullptr, nullptr}; }
-namespace {
-bool bad_shape(int64_t lead, int64_t rows, int64_t cols, int32_t b0, int32_t b1) {
-    return lead < 0 || rows < 0 || cols < 0 || b0 < 1 || b1 < 1;
+// the bracket around one launch
+template <class Launch>
+int timed(hipStream_t st, Launch launch) {
+    hipEvent_t te = g_timing.begin(st);
+    const int rc = launch();
+    g_timing.end(te, st);
+    return rc;
 }
 
-int fill_common(QuantArgs& a, const float* x, float* y, void* workspace, int64_t lead, int64_t rows,
-                int64_t cols, int32_t b0, int32_t b1, uint32_t flags) {
-    if (bad_shape(lead, rows, cols, b0, b1)) return MI355Q_E_BADARG;
-    a = QuantArgs{};
-    a.x = x;
-    a.y = y;
-    a.ws = static_cast<unsigned*>(workspace);
-    a.lead = lead; a.rows = rows; a.cols = cols;
-    a.b0 = b0; a.b1 = b1;
-    a.n_elems = lead * rows * cols;
-    a.nbr = (rows + b0 - 1) / b0;
-    a.nbc = (cols + b1 - 1) / b1;
-    a.n_blocks = lead * a.nbr * a.nbc;
-    a.flags = flags;
-    if (a.n_elems == 0) return 1 << 30;   // nothing to do (caller returns 0)
-    if (x == nullptr) return MI355Q_E_BADARG;
-    if ((flags & MI355Q_ZERO_BLOCK_FAST) == 0u && workspace == nullptr) return MI355Q_E_BADARG;
-    return 0;
+int bucket_cap_of(int32_t cap) { return cap == 0 ? ROW_BCAP : cap; }
+bool bucket_cap_bad(int32_t cap, int32_t least = 0) { return cap < least || cap > ROW_BCAP_MAX; }
+
+// a mi355q_bfp_operand: what a product requires of it -- the fields that must be there, row_aligned (-1: any), list_cap resolving to
+// ROW_BCAP -- and what is wrong with it: BADARG, BADARG, UNSUPPORTED, ALIGN.  Each product looks at the faults of its two operands in
+// its own recorded order (plain: both operands' pointers, K, both widths, ..., alignment; _multi: each weight whole, then x with its
+// width BEHIND the unsupported forms), so the faults are named here and the order stays with the product
+enum : unsigned { OP_MANT = 1, OP_EXP = 2, OP_ROWFLAG = 4, OP_GSCALE = 8, OP_LIST = 16, OP_TILED = 7, OP_ALL = 31 };
+struct OperandNeeds { unsigned fields; int row_aligned; bool lds_buckets; };
+struct OperandFaults { bool missing, mbits, form, misaligned; };
+OperandFaults operand_faults(const mi355q_bfp_operand& o, OperandNeeds n) {
+    const unsigned has = (o.mant ? OP_MANT : 0u) | (o.exp ? OP_EXP : 0u) | (o.rowflag ? OP_ROWFLAG : 0u) | (o.gscale ? OP_GSCALE : 0u) |
+                         (o.list ? OP_LIST : 0u);
+    return {(n.fields & ~has) != 0u, o.mbits < 1 || o.mbits > 7,
+            (n.row_aligned >= 0 && o.row_aligned != n.row_aligned) || (n.lds_buckets && bucket_cap_of(o.list_cap) != ROW_BCAP),
+            misaligned16({o.mant})};
+}
+constexpr OperandNeeds ANY_ROWS = {OP_TILED, -1, false};    // mi355q_bfp_gemm_aligned: the rest depends on the route
+constexpr OperandNeeds ONE_LAUNCH = {OP_ALL, 1, true};      // the tile kernel's own operand: whole rows, lists, 120-entry buckets
+// the launch arguments every product of two checked operands starts from
+GemmArgs gemm_args(const mi355q_bfp_operand& x, const mi355q_bfp_operand& w, const float* bias, float* y, int64_t M, int64_t N, int64_t K,
+                   int64_t ldy) {
+    return GemmArgs{x.mant, x.exp, w.mant, w.exp, bias, y, M, N, K, ldy,
+                    x.exp_bias + x.mbits + w.exp_bias + w.mbits, x.row_aligned ? 1 : 0,
+                    x.exp_bias + x.mbits, w.exp_bias + w.mbits, ROW_BCAP, ROW_BCAP, 0};
 }
 }  // namespace
+namespace mi355q { KernelEvents g_kernel_events = {nullptr, nullptr}; }
 
 extern "C" {
 
@@ -102,20 +113,13 @@ int mi355q_block_fp_quantize(const float* x, float* y, int8_t* mant, uint8_t* ex
                              int64_t cols, int32_t b0, int32_t b1, int32_t width, int32_t exponent_width,
                              int32_t exponent_bias, uint32_t flags, void* workspace, void* stream) {
     QuantArgs a;
-    const int rc = fill_common(a, x, y, workspace, lead, rows, cols, b0, b1, flags);
-    if (rc == (1 << 30)) return 0;
-    if (rc) return rc;
+    int rc;
+    if (!fill_common(a, x, y, workspace, lead, rows, cols, b0, b1, flags, rc)) return rc;
     if ((mant == nullptr) != (exp == nullptr)) return MI355Q_E_BADARG;
     if (y == nullptr && mant == nullptr) return MI355Q_E_BADARG;
-    if (exponent_width < 1 || exponent_width > 8) return MI355Q_E_BADARG;
-    if (width < 2 || width > (mant ? 8 : 25)) return MI355Q_E_BADARG;
-    if (exponent_bias == MI355Q_BIAS_DEFAULT) exponent_bias = (1 << (exponent_width - 1)) - 1;
+    if (block_fp_args(a, width, exponent_width, exponent_bias, {mant ? 8 : 25, MI355Q_E_BADARG, MI355Q_E_BADARG})) return MI355Q_E_BADARG;
     a.mant = mant;
     a.code = exp;
-    a.code_bias = exponent_bias;
-    a.e_min = -exponent_bias;
-    a.e_max = (1 << exponent_width) - 1 - exponent_bias;
-    set_mantissa(a, width - 1);
     return launch_quant(a, 0, /*needs_fixup=*/mant != nullptr, static_cast<hipStream_t>(stream));
 }
 
@@ -123,26 +127,13 @@ int mi355q_block_fp_quantize_bf16(const float* x, uint16_t* y, int64_t lead, int
                                   int32_t b1, int32_t width, int32_t exponent_width, int32_t exponent_bias,
                                   void* workspace, void* stream) {
     QuantArgs a;
-    const int rc = fill_common(a, x, nullptr, workspace, lead, rows, cols, b0, b1, MI355Q_ZERO_BLOCK_FAST);
-    if (rc == (1 << 30)) return 0;
-    if (rc) return rc;
+    int rc;
+    if (!fill_common(a, x, nullptr, workspace, lead, rows, cols, b0, b1, MI355Q_ZERO_BLOCK_FAST, rc)) return rc;
     if (y == nullptr) return MI355Q_E_BADARG;
-    if (exponent_width < 1 || exponent_width > 8 || width < 2) return MI355Q_E_BADARG;
-    if (width > 9) return MI355Q_E_UNSUPPORTED;            // a quantised value must fit bf16's 8 significant bits
-    if (exponent_bias == MI355Q_BIAS_DEFAULT) exponent_bias = (1 << (exponent_width - 1)) - 1;
+    // (a quantised value must fit bf16's 8 significant bits)
+    if ((rc = block_fp_args(a, width, exponent_width, exponent_bias, {9, MI355Q_E_BADARG, MI355Q_E_UNSUPPORTED})) != 0) return rc;
     a.ybf = y;
-    a.code_bias = exponent_bias;
-    a.e_min = -exponent_bias;
-    a.e_max = (1 << exponent_width) - 1 - exponent_bias;
-    set_mantissa(a, width - 1);
     return launch_quant(a, 0, /*needs_fixup=*/false, static_cast<hipStream_t>(stream));
-}
-
-static bool pre_op_ok(int32_t pre_op, const float* x2, bool rows_kernel = false) {
-    const bool norm = pre_op == MI355Q_PRE_RMSNORM || pre_op == MI355Q_PRE_LAYERNORM;
-    if (norm && !rows_kernel) return false;                              // (needs the whole row in one workgroup)
-    if (pre_op != MI355Q_PRE_NONE && pre_op != MI355Q_PRE_RELU && pre_op != MI355Q_PRE_SILU_MUL && !norm) return false;
-    return (pre_op != MI355Q_PRE_SILU_MUL && !norm) || (x2 != nullptr && reinterpret_cast<uintptr_t>(x2) % 16 == 0);
 }
 
 int mi355q_block_fp_quantize_bf16_tiled(const float* x, float* y, uint16_t* y_tiled, int64_t rows, int64_t K, int32_t width,
@@ -164,21 +155,15 @@ int mi355q_block_fp_quantize_bf16_tiled_norm(const float* x, const float* x2, in
                                              int32_t exponent_bias, void* workspace, void* stream) {
     if (pre_op == MI355Q_PRE_LAYERNORM || !pre_op_ok(pre_op, x2, pre_op == MI355Q_PRE_RMSNORM) || !(eps >= 0.f)) return MI355Q_E_BADARG;
     QuantArgs a;
-    const int rc = fill_common(a, x, y, workspace, 1, rows, K, 1, 16, MI355Q_ZERO_BLOCK_FAST);
-    if (rc == (1 << 30)) return 0;
-    if (rc) return rc;
+    int rc;
+    if (!fill_common(a, x, y, workspace, 1, rows, K, 1, 16, MI355Q_ZERO_BLOCK_FAST, rc)) return rc;
     a.x2 = x2;
     a.pre_op = pre_op;
     a.pre_eps = eps;
     if (y_tiled == nullptr) return MI355Q_E_BADARG;
-    if (exponent_width < 1 || exponent_width > 8 || width < 2) return MI355Q_E_BADARG;
-    if (width > 9 || K % 32 != 0) return MI355Q_E_UNSUPPORTED;   // bf16's 8 significant bits; whole 64-byte K-steps
+    if ((rc = block_fp_args(a, width, exponent_width, exponent_bias, {9, MI355Q_E_BADARG, MI355Q_E_UNSUPPORTED})) != 0) return rc;
+    if (K % 32 != 0) return MI355Q_E_UNSUPPORTED;               // (bf16's 8 significant bits: above;) whole 64-byte K-steps
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(y_tiled)) % 16) return MI355Q_E_ALIGN;
-    if (exponent_bias == MI355Q_BIAS_DEFAULT) exponent_bias = (1 << (exponent_width - 1)) - 1;
-    a.code_bias = exponent_bias;
-    a.e_min = -exponent_bias;
-    a.e_max = (1 << exponent_width) - 1 - exponent_bias;
-    set_mantissa(a, width - 1);
     return launch_quant_bf16_tiled(a, y_tiled, static_cast<hipStream_t>(stream));
 }
 
@@ -186,18 +171,15 @@ int mi355q_block_minifloat_quantize_bf16_tiled(const float* x, uint16_t* y_tiled
                                                int32_t exponent_width, int32_t exponent_bias_width, void* workspace,
                                                void* stream) {
     QuantArgs a;
-    const int rc = fill_common(a, x, nullptr, workspace, 1, rows, K, 1, 16, MI355Q_ZERO_BLOCK_FAST);
-    if (rc == (1 << 30)) return 0;
-    if (rc) return rc;
+    int rc;
+    if (!fill_common(a, x, nullptr, workspace, 1, rows, K, 1, 16, MI355Q_ZERO_BLOCK_FAST, rc)) return rc;
     if (y_tiled == nullptr) return MI355Q_E_BADARG;
     const int mbits = width - exponent_width - 1;
     if (exponent_width < 1 || exponent_width > 8 || mbits < 0 || mbits > 23) return MI355Q_E_BADARG;
     if (exponent_bias_width < 1 || exponent_bias_width > 8) return MI355Q_E_BADARG;
     if (mbits > 7 || K % 32 != 0) return MI355Q_E_UNSUPPORTED;      // bf16's 8 significant bits; whole 64-byte K-steps
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y_tiled)) % 16) return MI355Q_E_ALIGN;
-    a.span = (1 << exponent_width) - 1;
-    a.bias_max = (1 << exponent_bias_width) - 1;
-    set_mantissa(a, mbits);
+    block_minifloat_fill(a, mbits, exponent_width, exponent_bias_width);
     return launch_quant_bf16_tiled(a, y_tiled, static_cast<hipStream_t>(stream), false, 1);
 }
 
@@ -249,14 +231,12 @@ int mi355q_bfp_gemm_packed_small(const uint16_t* x_tiled, const uint8_t* packed,
 
 int mi355q_bf16_tile(const float* x, uint16_t* y_tiled, int64_t rows, int64_t K, void* stream) {
     QuantArgs a;
-    const int rc = fill_common(a, x, nullptr, nullptr, 1, rows, K, 1, 16, MI355Q_ZERO_BLOCK_FAST);
-    if (rc == (1 << 30)) return 0;
-    if (rc) return rc;
+    int rc;
+    if (!fill_common(a, x, nullptr, nullptr, 1, rows, K, 1, 16, MI355Q_ZERO_BLOCK_FAST, rc)) return rc;
     if (y_tiled == nullptr) return MI355Q_E_BADARG;
     if (K % 32 != 0) return MI355Q_E_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y_tiled)) % 16) return MI355Q_E_ALIGN;
-    a.code_bias = 127; a.e_min = -127; a.e_max = 128;
-    set_mantissa(a, 7);
+    block_fp_fill(a, 8, 8, 127);                                 // bf16 itself
     return launch_quant_bf16_tiled(a, y_tiled, static_cast<hipStream_t>(stream), /*cast_only=*/true);
 }
 
@@ -271,7 +251,25 @@ int mi355q_fp32_split_tile(const float* x, uint16_t* y_tiled, int64_t rows, int6
 
 static int bf16_gemm_tiled_impl(const uint16_t* x_tiled, const uint16_t* w_tiled, const float* bias, float* y, int64_t M, int64_t N,
                                 int64_t K, int64_t ldy, int32_t x_segments, int64_t x_segment_stride_bytes, void* stream,
-                                const float* residual = nullptr, int64_t ldr = 0);
+                                const float* residual = nullptr, int64_t ldr = 0) {
+    if (M < 0 || N < 0 || K < 0 || ldy < N) return MI355Q_E_BADARG;
+    if (M == 0 || N == 0) return 0;
+    if (!y || (K > 0 && (!x_tiled || !w_tiled))) return MI355Q_E_BADARG;
+    if (K % 32 != 0 || K == 0) return MI355Q_E_UNSUPPORTED;
+    if ((reinterpret_cast<uintptr_t>(x_tiled) | reinterpret_cast<uintptr_t>(w_tiled)) % 16) return MI355Q_E_ALIGN;
+    GemmArgs a{};
+    a.xm = reinterpret_cast<const int8_t*>(x_tiled);
+    a.wm = reinterpret_cast<const int8_t*>(w_tiled);
+    a.bias = bias;
+    a.y = y;
+    a.M = M; a.N = N; a.K = 2 * K; a.ldy = ldy;      // (the tile kernel counts the contraction in bytes)
+    a.x_segs = x_segments;
+    a.x_seg_stride = x_segment_stride_bytes;
+    a.resid = residual;
+    a.ldr = ldr;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return timed(st, [&] { return launch_bf16_gemm_tiled(a, st); });
+}
 
 int mi355q_bf16_gemm_tiled(const uint16_t* x_tiled, const uint16_t* w_tiled, const float* bias, float* y, int64_t M, int64_t N,
                            int64_t K, int64_t ldy, void* stream) {
@@ -294,46 +292,18 @@ int mi355q_bf16_gemm_tiled_seg(const uint16_t* x_tiled, const uint16_t* w_tiled,
     return bf16_gemm_tiled_impl(x_tiled, w_tiled, bias, y, M, N, K, ldy, x_segments, x_segment_stride_bytes, stream);
 }
 
-static int bf16_gemm_tiled_impl(const uint16_t* x_tiled, const uint16_t* w_tiled, const float* bias, float* y, int64_t M, int64_t N,
-                                int64_t K, int64_t ldy, int32_t x_segments, int64_t x_segment_stride_bytes, void* stream,
-                                const float* residual, int64_t ldr) {
-    if (M < 0 || N < 0 || K < 0 || ldy < N) return MI355Q_E_BADARG;
-    if (M == 0 || N == 0) return 0;
-    if (!y || (K > 0 && (!x_tiled || !w_tiled))) return MI355Q_E_BADARG;
-    if (K % 32 != 0 || K == 0) return MI355Q_E_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(x_tiled) | reinterpret_cast<uintptr_t>(w_tiled)) % 16) return MI355Q_E_ALIGN;
-    GemmArgs a{};
-    a.xm = reinterpret_cast<const int8_t*>(x_tiled);
-    a.wm = reinterpret_cast<const int8_t*>(w_tiled);
-    a.bias = bias;
-    a.y = y;
-    a.M = M; a.N = N; a.K = 2 * K; a.ldy = ldy;      // (the tile kernel counts the contraction in bytes)
-    a.x_segs = x_segments;
-    a.x_seg_stride = x_segment_stride_bytes;
-    a.resid = residual;
-    a.ldr = ldr;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipEvent_t te = g_timing.begin(st);
-    const int rc = launch_bf16_gemm_tiled(a, st);
-    g_timing.end(te, st);
-    return rc;
-}
-
 int mi355q_block_minifloat_quantize(const float* x, float* y, uint8_t* bias, int64_t lead, int64_t rows, int64_t cols,
                                     int32_t b0, int32_t b1, int32_t width, int32_t exponent_width,
                                     int32_t exponent_bias_width, uint32_t flags, void* workspace, void* stream) {
     QuantArgs a;
-    const int rc = fill_common(a, x, y, workspace, lead, rows, cols, b0, b1, flags);
-    if (rc == (1 << 30)) return 0;
-    if (rc) return rc;
+    int rc;
+    if (!fill_common(a, x, y, workspace, lead, rows, cols, b0, b1, flags, rc)) return rc;
     if (y == nullptr) return MI355Q_E_BADARG;
     const int mbits = width - exponent_width - 1;
     if (exponent_width < 1 || exponent_width > 8 || mbits < 0 || mbits > 23) return MI355Q_E_BADARG;
     if (exponent_bias_width < 1 || exponent_bias_width > 8) return MI355Q_E_BADARG;
     a.code = bias;
-    a.span = (1 << exponent_width) - 1;
-    a.bias_max = (1 << exponent_bias_width) - 1;
-    set_mantissa(a, mbits);
+    block_minifloat_fill(a, mbits, exponent_width, exponent_bias_width);
     return launch_quant(a, 1, /*needs_fixup=*/bias != nullptr, static_cast<hipStream_t>(stream));
 }
 
@@ -341,16 +311,13 @@ int mi355q_block_log_quantize(const float* x, float* y, uint8_t* bias, int64_t l
                               int32_t b0, int32_t b1, int32_t width, int32_t exponent_bias_width, uint32_t flags,
                               void* workspace, void* stream) {
     QuantArgs a;
-    const int rc = fill_common(a, x, y, workspace, lead, rows, cols, b0, b1, flags);
-    if (rc == (1 << 30)) return 0;
-    if (rc) return rc;
+    int rc;
+    if (!fill_common(a, x, y, workspace, lead, rows, cols, b0, b1, flags, rc)) return rc;
     if (y == nullptr) return MI355Q_E_BADARG;
     if (width < 2 || width > 9) return MI355Q_E_BADARG;       // exponent code of width-1 <= 8 bits
     if (exponent_bias_width < 1 || exponent_bias_width > 8) return MI355Q_E_BADARG;
     a.code = bias;
-    a.span = (1 << (width - 1)) - 1;
-    a.bias_max = (1 << exponent_bias_width) - 1;
-    set_mantissa(a, 0);
+    block_minifloat_fill(a, 0, width - 1, exponent_bias_width);
     return launch_quant(a, 2, /*needs_fixup=*/true, static_cast<hipStream_t>(stream));
 }
 
@@ -360,36 +327,30 @@ int mi355q_block_minifloat_quantize_bf16(const float* x, uint16_t* y, int64_t le
                                          int32_t b1, int32_t width, int32_t exponent_width, int32_t exponent_bias_width,
                                          void* workspace, void* stream) {
     QuantArgs a;
-    const int rc = fill_common(a, x, nullptr, workspace, lead, rows, cols, b0, b1, MI355Q_ZERO_BLOCK_FAST);
-    if (rc == (1 << 30)) return 0;
-    if (rc) return rc;
+    int rc;
+    if (!fill_common(a, x, nullptr, workspace, lead, rows, cols, b0, b1, MI355Q_ZERO_BLOCK_FAST, rc)) return rc;
     if (y == nullptr) return MI355Q_E_BADARG;
     const int mbits = width - exponent_width - 1;
     if (exponent_width < 1 || exponent_width > 8 || mbits < 0) return MI355Q_E_BADARG;
     if (mbits > 7) return MI355Q_E_UNSUPPORTED;              // a quantised value must fit bf16's 8 significant bits
     if (exponent_bias_width < 1 || exponent_bias_width > 8) return MI355Q_E_BADARG;
     a.ybf = y;
-    a.span = (1 << exponent_width) - 1;
-    a.bias_max = (1 << exponent_bias_width) - 1;
-    set_mantissa(a, mbits);
+    block_minifloat_fill(a, mbits, exponent_width, exponent_bias_width);
     return launch_quant(a, 1, /*needs_fixup=*/false, static_cast<hipStream_t>(stream));     // (an all-zero block stays zero)
 }
 
 int mi355q_block_log_quantize_bf16(const float* x, uint16_t* y, int64_t lead, int64_t rows, int64_t cols, int32_t b0,
                                    int32_t b1, int32_t width, int32_t exponent_bias_width, void* workspace, void* stream) {
     QuantArgs a;
-    const int rc = fill_common(a, x, nullptr, workspace, lead, rows, cols, b0, b1, 0u);
-    if (rc == (1 << 30)) return 0;
-    if (rc) return rc;
+    int rc;
+    if (!fill_common(a, x, nullptr, workspace, lead, rows, cols, b0, b1, 0u, rc)) return rc;
     if (y == nullptr) return MI355Q_E_BADARG;
     if (width < 2 || width > 9) return MI355Q_E_BADARG;
     if (exponent_bias_width < 1 || exponent_bias_width > 8) return MI355Q_E_BADARG;
     // (all-zero blocks take the tensor-global fill -- a non-zero value here: the fix-up pass writes bf16 in its row-block form only)
     if (b0 != 1 || b1 != 16 || cols % 16 || reinterpret_cast<uintptr_t>(y) % 16) return MI355Q_E_UNSUPPORTED;
     a.ybf = y;
-    a.span = (1 << (width - 1)) - 1;
-    a.bias_max = (1 << exponent_bias_width) - 1;
-    set_mantissa(a, 0);
+    block_minifloat_fill(a, 0, width - 1, exponent_bias_width);
     return launch_quant(a, 2, /*needs_fixup=*/true, static_cast<hipStream_t>(stream));
 }
 
@@ -400,7 +361,7 @@ int mi355q_minifloat_quantize(const float* x, float* y, int64_t n, int32_t width
     if (!x || !y) return MI355Q_E_BADARG;
     const int mbits = width - exponent_width - 1;
     if (exponent_width < 1 || exponent_width > 8 || mbits < 0 || mbits > 23) return MI355Q_E_BADARG;
-    if (exponent_bias == MI355Q_BIAS_DEFAULT) exponent_bias = (1 << (exponent_width - 1)) - 1;
+    exponent_bias = default_bias(exponent_bias, exponent_width);
     if (exponent_bias < -100 || exponent_bias > 140) return MI355Q_E_UNSUPPORTED;      // (exponents must stay inside fp32's)
     QuantArgs a{};
     a.x = x; a.y = y; a.n_elems = n;
@@ -415,7 +376,7 @@ int mi355q_log_quantize(const float* x, float* y, int64_t n, int32_t width, int3
     if (n < 0 || width < 2 || width > 9) return MI355Q_E_BADARG;      // exponent code of width - 1 <= 8 bits
     if (n == 0) return 0;
     if (!x || !y) return MI355Q_E_BADARG;
-    if (exponent_bias == MI355Q_BIAS_DEFAULT) exponent_bias = (1 << (width - 2)) - 1;
+    exponent_bias = default_bias(exponent_bias, width - 1);
     if (exponent_bias < -100 || exponent_bias > 140) return MI355Q_E_UNSUPPORTED;
     QuantArgs a{};
     a.x = x; a.y = y; a.n_elems = n;
@@ -454,26 +415,20 @@ size_t mi355q_bfp_rowflag_bytes(int64_t rows, int64_t K) {
 
 int64_t mi355q_bfp_rows_pad(int64_t rows) { return rows <= 0 ? 0 : (rows + 255) / 256 * 256 + 256; }
 
-
 size_t mi355q_bfp_tiled_bytes(int64_t rows, int64_t K) {
     if (rows <= 0 || K <= 0) return 0;
     return static_cast<size_t>((rows + 127) / 128 * 128) * static_cast<size_t>((K + 63) / 64 * 64);
 }
 
-
-
-
-static int bucket_cap_of(int32_t cap) { return cap == 0 ? ROW_BCAP : cap; }
-
 size_t mi355q_bfp_row_list_bytes(int64_t rows, int32_t bucket_cap) {
-    if (rows < 0 || bucket_cap < 0 || bucket_cap > ROW_BCAP_MAX) return 0;
+    if (rows < 0 || bucket_cap_bad(bucket_cap)) return 0;
     return (size_t)row_list_words(rows, bucket_cap_of(bucket_cap)) * 4;
 }
 
 int mi355q_bfp_align_rows(const int8_t* mant_in, const uint8_t* exp_in, int8_t* mant_tiled, uint8_t* exp_out,
                           uint8_t* rowflag, float* rowscale, int32_t* list, int32_t exp_offset, int64_t rows, int64_t K,
                           int32_t bucket_cap, void* stream) {
-    if (rows < 0 || K < 0 || bucket_cap < 0 || bucket_cap > ROW_BCAP_MAX) return MI355Q_E_BADARG;
+    if (rows < 0 || K < 0 || bucket_cap_bad(bucket_cap)) return MI355Q_E_BADARG;
     if (rows == 0 || K == 0) return 0;
     if (!mant_in || !exp_in || !mant_tiled || !exp_out || !rowflag || !rowscale) return MI355Q_E_BADARG;
     if (K % 64 != 0 || K > MI355Q_ROW_ALIGN_MAX_K) return MI355Q_E_UNSUPPORTED;
@@ -513,53 +468,33 @@ int mi355q_block_fp_quantize_aligned_rows_norm(const float* x, const float* x2, 
                                                      bucket_cap, stream);
 }
 
-static int quantize_aligned_rows_impl(const float* x, const float* x2, const float* x3, int32_t pre_op, float eps,
-                                      int8_t* mant_tiled, uint8_t* exp_out, uint8_t* rowflag, float* rowscale,
-                                      int32_t* list, int32_t* list_to_clear, int64_t rows, int64_t K, int64_t seg_len,
-                                      int64_t seg_stride, int32_t width, int32_t exponent_width, int32_t exponent_bias,
-                                      int32_t bucket_cap, void* stream) {
-    if (seg_len < 0 || seg_stride < 0) return MI355Q_E_BADARG;
-    if (seg_len > 0 && (seg_len % 4 || seg_stride % 4 || K % seg_len || seg_stride < rows * seg_len)) return MI355Q_E_BADARG;
-    if (!pre_op_ok(pre_op, x2, true) || !(eps >= 0.f) || reinterpret_cast<uintptr_t>(x3) % 16) return MI355Q_E_BADARG;
-    if (rows < 0 || K < 0 || bucket_cap < MI355Q_ROW_NO_ALIGN || bucket_cap > ROW_BCAP_MAX) return MI355Q_E_BADARG;
-    if (rows == 0 || K == 0) return 0;
-    if (!x || !mant_tiled || !exp_out || !rowflag || !rowscale || (!list && bucket_cap >= 0) || (list && list_to_clear == list))
-        return MI355Q_E_BADARG;
-    if (K % 64 != 0 || K > MI355Q_ROW_ALIGN_MAX_K) return MI355Q_E_UNSUPPORTED;
-    if (exponent_width < 1 || exponent_width > 8 || width < 2 || width > 8) return MI355Q_E_BADARG;
-    if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(mant_tiled) % 16) return MI355Q_E_ALIGN;
-    if (exponent_bias == MI355Q_BIAS_DEFAULT) exponent_bias = (1 << (exponent_width - 1)) - 1;
-    if (exponent_bias < 0) return MI355Q_E_UNSUPPORTED;          // biased uint8 exponent codes: non-negative biases only
-    QuantArgs a{};
-    a.x = x;
-    a.x2 = x2;
-    a.pre_op = pre_op;
-    a.pre_eps = eps;
-    a.x3 = pre_op == MI355Q_PRE_LAYERNORM ? x3 : nullptr;
-    a.code = exp_out;
-    a.lead = 1; a.rows = rows; a.cols = K;
-    a.b0 = 1; a.b1 = 16;
-    a.n_elems = rows * K;
-    a.nbr = rows; a.nbc = K / 16;
-    a.n_blocks = rows * (K / 16);
-    a.flags = MI355Q_ZERO_BLOCK_FAST;
-    a.code_bias = exponent_bias;
-    a.e_min = -exponent_bias;
-    a.e_max = (1 << exponent_width) - 1 - exponent_bias;
-    a.seg_len = seg_len == K ? 0 : seg_len;                 // (one segment: plain rows)
-    a.seg_stride = seg_stride;
-    set_mantissa(a, width - 1);
-    return launch_quant_align_rows(a, mant_tiled, rowflag, rowscale, exponent_bias + width - 1, list, list_to_clear,
-                                   static_cast<hipStream_t>(stream), bucket_cap < 0 ? -1 : bucket_cap_of(bucket_cap));
-}
-
 int mi355q_block_fp_quantize_aligned_rows_seg(const float* x, const float* x2, const float* x3, int32_t pre_op, float eps,
                                               int8_t* mant_tiled, uint8_t* exp_out, uint8_t* rowflag, float* rowscale,
                                               int32_t* list, int32_t* list_to_clear, int64_t rows, int64_t K, int64_t seg_len,
                                               int64_t seg_stride, int32_t width, int32_t exponent_width, int32_t exponent_bias,
                                               int32_t bucket_cap, void* stream) {
-    return quantize_aligned_rows_impl(x, x2, x3, pre_op, eps, mant_tiled, exp_out, rowflag, rowscale, list, list_to_clear, rows, K,
-                                      seg_len, seg_stride, width, exponent_width, exponent_bias, bucket_cap, stream);
+    if (seg_len < 0 || seg_stride < 0) return MI355Q_E_BADARG;
+    if (seg_len > 0 && (seg_len % 4 || seg_stride % 4 || K % seg_len || seg_stride < rows * seg_len)) return MI355Q_E_BADARG;
+    if (!pre_op_ok(pre_op, x2, true) || !(eps >= 0.f) || reinterpret_cast<uintptr_t>(x3) % 16) return MI355Q_E_BADARG;
+    if (rows < 0 || K < 0 || bucket_cap_bad(bucket_cap, MI355Q_ROW_NO_ALIGN)) return MI355Q_E_BADARG;
+    if (rows == 0 || K == 0) return 0;
+    if (!x || !mant_tiled || !exp_out || !rowflag || !rowscale || (!list && bucket_cap >= 0) || (list && list_to_clear == list))
+        return MI355Q_E_BADARG;
+    if (K % 64 != 0 || K > MI355Q_ROW_ALIGN_MAX_K) return MI355Q_E_UNSUPPORTED;
+    QuantArgs a{};
+    if (block_fp_args(a, width, exponent_width, exponent_bias, {8, MI355Q_E_BADARG, MI355Q_E_BADARG})) return MI355Q_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(mant_tiled) % 16) return MI355Q_E_ALIGN;
+    if (a.code_bias < 0) return MI355Q_E_UNSUPPORTED;            // biased uint8 exponent codes: non-negative biases only
+    fill_rows(a, x, rows, K);
+    a.x2 = x2;
+    a.pre_op = pre_op;
+    a.pre_eps = eps;
+    a.x3 = pre_op == MI355Q_PRE_LAYERNORM ? x3 : nullptr;
+    a.code = exp_out;
+    a.seg_len = seg_len == K ? 0 : seg_len;                 // (one segment: plain rows)
+    a.seg_stride = seg_stride;
+    return launch_quant_align_rows(a, mant_tiled, rowflag, rowscale, a.code_bias + width - 1, list, list_to_clear,
+                                   static_cast<hipStream_t>(stream), bucket_cap < 0 ? -1 : bucket_cap_of(bucket_cap));
 }
 
 // the class-aware activation quantiser of the mixed contraction (mi355q.h; mi355q_quant_cls.hip)
@@ -567,7 +502,7 @@ int mi355q_block_fp_quantize_classes(const float* x, const uint16_t* colmap, int
                                      uint8_t* exp_out, uint8_t* rowflag, float* rowscale, int32_t* list, int32_t* list_to_clear,
                                      void* x1_bf16_tiled, int64_t rows, int64_t K, int32_t width, int32_t exponent_width,
                                      int32_t exponent_bias, int32_t bucket_cap, void* stream) {
-    if (rows < 0 || K < 0 || n0_blocks < 0 || n1_blocks < 0 || bucket_cap < 0 || bucket_cap > ROW_BCAP_MAX) return MI355Q_E_BADARG;
+    if (rows < 0 || K < 0 || n0_blocks < 0 || n1_blocks < 0 || bucket_cap_bad(bucket_cap)) return MI355Q_E_BADARG;
     if (rows == 0 || K == 0) return 0;
     if (!x || !colmap || !mant_tiled || !exp_out || !rowflag || !rowscale || !list || !x1_bf16_tiled || list_to_clear == list)
         return MI355Q_E_BADARG;
@@ -575,197 +510,149 @@ int mi355q_block_fp_quantize_classes(const float* x, const uint16_t* colmap, int
     if (K % 64 != 0 || K > MI355Q_ROW_ALIGN_MAX_K || (n0_blocks + n1_blocks) * 16 != K || n0_blocks % 4 || n1_blocks % 2 || n0_blocks >= 32768 ||
         n1_blocks >= 32768)
         return MI355Q_E_UNSUPPORTED;
-    if (exponent_width < 1 || exponent_width > 8 || width < 2 || width > 8) return MI355Q_E_BADARG;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(mant_tiled) | reinterpret_cast<uintptr_t>(x1_bf16_tiled)) % 16) return MI355Q_E_ALIGN;
-    if (exponent_bias == MI355Q_BIAS_DEFAULT) exponent_bias = (1 << (exponent_width - 1)) - 1;
-    if (exponent_bias < 0) return MI355Q_E_UNSUPPORTED;
     QuantArgs a{};
-    a.x = x;
+    if (block_fp_args(a, width, exponent_width, exponent_bias, {8, MI355Q_E_BADARG, MI355Q_E_BADARG})) return MI355Q_E_BADARG;
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(mant_tiled) | reinterpret_cast<uintptr_t>(x1_bf16_tiled)) % 16) return MI355Q_E_ALIGN;
+    if (a.code_bias < 0) return MI355Q_E_UNSUPPORTED;
+    fill_rows(a, x, rows, K);
     a.code = exp_out;
-    a.lead = 1; a.rows = rows; a.cols = K;
-    a.b0 = 1; a.b1 = 16;
-    a.n_elems = rows * K;
-    a.nbr = rows; a.nbc = K / 16;
-    a.n_blocks = rows * (K / 16);
-    a.flags = MI355Q_ZERO_BLOCK_FAST;
-    a.code_bias = exponent_bias;
-    a.e_min = -exponent_bias;
-    a.e_max = (1 << exponent_width) - 1 - exponent_bias;
-    set_mantissa(a, width - 1);
-    return launch_quant_classes(a, colmap, (int)n0_blocks, (int)n1_blocks, mant_tiled, rowflag, rowscale, exponent_bias + width - 1, list,
+    return launch_quant_classes(a, colmap, (int)n0_blocks, (int)n1_blocks, mant_tiled, rowflag, rowscale, a.code_bias + width - 1, list,
                                 list_to_clear, static_cast<uint16_t*>(x1_bf16_tiled), static_cast<hipStream_t>(stream),
                                 bucket_cap_of(bucket_cap));
 }
 
-static int gemm_aligned_impl(const mi355q_bfp_operand* x, const mi355q_bfp_operand* w, const float* bias, float* y,
-                            int64_t M, int64_t N, int64_t K, int64_t ldy, void* stream, const float* residual = nullptr, int64_t ldr = 0) {
+// y = x . w^T + bias on ROW-aligned tiled operands; with `residual` the add rides the store (the one-launch route only).  variant: what
+// mi355q_bfp_gemm_set_variant set (0 the planned tile launch, 2 the blockwise kernel, 8 the tile kernel without lists)
+static int gemm_aligned_impl(const mi355q_bfp_operand* x, const mi355q_bfp_operand* w, const float* bias, float* y, int64_t M, int64_t N,
+                             int64_t K, int64_t ldy, void* stream, int variant, const float* residual = nullptr, int64_t ldr = 0) {
     if (!x || !w || M < 0 || N < 0 || K < 0 || ldy < N) return MI355Q_E_BADARG;
     if (M == 0 || N == 0) return 0;
-    if (!y || (K > 0 && (!x->mant || !x->exp || !w->mant || !w->exp || !x->rowflag || !w->rowflag)))
-        return MI355Q_E_BADARG;
+    const OperandFaults fx = operand_faults(*x, ANY_ROWS), fw = operand_faults(*w, ANY_ROWS);
+    if (!y || (K > 0 && (fx.missing || fw.missing))) return MI355Q_E_BADARG;
     if (K % 64 != 0) return MI355Q_E_UNSUPPORTED;   // tiled operands; use mi355q_bfp_gemm otherwise
-    if (x->mbits < 1 || x->mbits > 7 || w->mbits < 1 || w->mbits > 7) return MI355Q_E_BADARG;
+    if (fx.mbits || fw.mbits) return MI355Q_E_BADARG;
     // both operands in the same alignment flavour; x may also be in row format with NOTHING aligned (row_aligned = 2)
     if (x->row_aligned != w->row_aligned && !(x->row_aligned == 2 && w->row_aligned == 1)) return MI355Q_E_BADARG;
     if (!x->row_aligned && x->list && w->list && x->list_cap != w->list_cap) return MI355Q_E_BADARG;
-    if ((reinterpret_cast<uintptr_t>(x->mant) | reinterpret_cast<uintptr_t>(w->mant)) % 16) return MI355Q_E_ALIGN;
-    GemmArgs a{x->mant, x->exp, w->mant, w->exp, bias, y, M, N, K, ldy,
-               x->exp_bias + x->mbits + w->exp_bias + w->mbits, x->row_aligned ? 1 : 0,
-               x->exp_bias + x->mbits, w->exp_bias + w->mbits,
-               ROW_BCAP, ROW_BCAP, 0};
-    const int variant = g_gemm_variant.load();
+    if (fx.misaligned || fw.misaligned) return MI355Q_E_ALIGN;
+    if (!x->row_aligned) return MI355Q_E_UNSUPPORTED;      // (operands aligned per 256-value group: the format went with its kernel)
+    GemmArgs a = gemm_args(*x, *w, bias, y, M, N, K, ldy);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (x->row_aligned) {
-        // ROW-aligned operands: plain int8 GEMM with one scale per row + exception add-back in its epilogue; the
-        // second launch only acts when an exception bucket overflowed (then it forms the whole product blockwise)
-        if (!x->gscale || !w->gscale) return MI355Q_E_BADARG;
-        if (w->list_cap < 0 || w->list_cap > ROW_BCAP_MAX) return MI355Q_E_BADARG;
-        a.w_bcap = bucket_cap_of(w->list_cap);          // (before the early return: the kernel below indexes w's buckets)
-        if (residual && x->row_aligned == 2) return MI355Q_E_UNSUPPORTED;      // (the residual add rides the one-launch route's stores only)
-        if (x->row_aligned == 2)            // unaligned activations: the blockwise-exact kernel, w's exception blocks per tile
-            return launch_bfp_gemm_aligned(a, x->rowflag, w->rowflag, nullptr, w->list, st);
-        if (x->list_cap < 0 || x->list_cap > ROW_BCAP_MAX) return MI355Q_E_BADARG;
-        a.x_bcap = bucket_cap_of(x->list_cap);
-        // x's exception blocks: in-LDS vectors of the GEMM (120-entry buckets) or the row post-pass (larger buckets)
-        a.x_post = a.x_bcap != ROW_BCAP ? 1 : 0;
-        const bool fast_ok = x->list && w->list && K % 128 == 0 && K <= MI355Q_ROW_ALIGN_MAX_K && a.w_bcap == ROW_BCAP;
-        if (residual && (variant == 2 || variant == 8 || !fast_ok || a.x_post)) return MI355Q_E_UNSUPPORTED;
-        a.resid = residual;
-        a.ldr = ldr;
-        if (variant == 2 || !fast_ok)
-            return launch_bfp_gemm_aligned(a, x->rowflag, w->rowflag, x->list, w->list, st);
-        if (variant == 8) return launch_bfp_gemm_v8(a, x->gscale, w->gscale, nullptr, nullptr, st);
-        // ONE launch: the row-scale GEMM forms the correction vectors of its tile's exception blocks itself and adds them
-        // in its epilogue; if an exception bucket overflowed anywhere its workgroups form the whole product
-        // blockwise-exact between them instead (decided on the device)
-        a.x_mbits = x->mbits;
-        a.w_mbits = w->mbits;
-        hipEvent_t te = g_timing.begin(st);
-        int rc = launch_bfp_gemm_v8(a, x->gscale, w->gscale, x->list, w->list, st, x->rowflag, w->rowflag);
-        g_timing.end(te, st);
-        if (rc == 0 && a.x_post) rc = launch_bfp_gemm_rowpost(a, x->list, w->list, x->gscale, w->gscale, st);
-        return rc;
-    }
-    return MI355Q_E_UNSUPPORTED;      // (operands aligned per 256-value group: the format went with its kernel in round 5)
+    if (!x->gscale || !w->gscale || bucket_cap_bad(w->list_cap)) return MI355Q_E_BADARG;
+    a.w_bcap = bucket_cap_of(w->list_cap);          // (before the early return: the kernel below indexes w's buckets)
+    if (residual && x->row_aligned == 2) return MI355Q_E_UNSUPPORTED;
+    if (x->row_aligned == 2)            // unaligned activations: the blockwise-exact kernel, w's exception blocks per tile
+        return launch_bfp_gemm_aligned(a, x->rowflag, w->rowflag, nullptr, w->list, st);
+    if (bucket_cap_bad(x->list_cap)) return MI355Q_E_BADARG;
+    a.x_bcap = bucket_cap_of(x->list_cap);
+    // x's exception blocks: in-LDS vectors of the GEMM (120-entry buckets) or the row post-pass (larger buckets)
+    a.x_post = a.x_bcap != ROW_BCAP ? 1 : 0;
+    const bool fast_ok = x->list && w->list && K % 128 == 0 && K <= MI355Q_ROW_ALIGN_MAX_K && a.w_bcap == ROW_BCAP;
+    if (residual && (variant == 2 || variant == 8 || !fast_ok || a.x_post)) return MI355Q_E_UNSUPPORTED;
+    a.resid = residual;
+    a.ldr = ldr;
+    if (variant == 2 || !fast_ok) return launch_bfp_gemm_aligned(a, x->rowflag, w->rowflag, x->list, w->list, st);
+    if (variant == 8) return launch_bfp_gemm_v8(a, x->gscale, w->gscale, nullptr, nullptr, st);
+    // ONE launch: the row-scale GEMM forms the correction vectors of its tile's exception blocks itself and adds them in its epilogue;
+    // if an exception bucket overflowed anywhere its workgroups form the whole product blockwise-exact between them instead (decided on
+    // the device)
+    a.x_mbits = x->mbits;
+    a.w_mbits = w->mbits;
+    int rc = timed(st, [&] { return launch_bfp_gemm_v8(a, x->gscale, w->gscale, x->list, w->list, st, x->rowflag, w->rowflag); });
+    if (rc == 0 && a.x_post) rc = launch_bfp_gemm_rowpost(a, x->list, w->list, x->gscale, w->gscale, st);
+    return rc;
 }
 
 int mi355q_bfp_gemm_aligned(const mi355q_bfp_operand* x, const mi355q_bfp_operand* w, const float* bias, float* y,
                             int64_t M, int64_t N, int64_t K, int64_t ldy, void* stream) {
-    return gemm_aligned_impl(x, w, bias, y, M, N, K, ldy, stream);
+    return gemm_aligned_impl(x, w, bias, y, M, N, K, ldy, stream, g_gemm_variant.load());
 }
 
 int mi355q_bfp_gemm_aligned_res(const mi355q_bfp_operand* x, const mi355q_bfp_operand* w, const float* bias, const float* residual,
                                 int64_t ldr, float* y, int64_t M, int64_t N, int64_t K, int64_t ldy, void* stream) {
     if (!residual || ldr < N || ldr % 4 != 0) return MI355Q_E_BADARG;
-    if (reinterpret_cast<uintptr_t>(residual) % 16) return MI355Q_E_ALIGN;
-    return gemm_aligned_impl(x, w, bias, y, M, N, K, ldy, stream, residual, ldr);
+    if (misaligned16({residual})) return MI355Q_E_ALIGN;
+    return gemm_aligned_impl(x, w, bias, y, M, N, K, ldy, stream, g_gemm_variant.load(), residual, ldr);
 }
 
-// y = x . w^T + bias with the contraction in two column classes (mi355q.h): class 0 = K0 values as row-aligned int8 operands with
-// their exception lists (what mi355q_bfp_gemm_aligned multiplies), class 1 = K1 values as tiled bf16 operands (what
-// mi355q_bf16_gemm_tiled multiplies) -- one launch of the 256 x 256 tile kernel
-int mi355q_bfp_gemm_mixed(const mi355q_bfp_operand* x0, const mi355q_bfp_operand* w0, const void* x1, const void* w1, const float* bias,
-                          float* y, int64_t M, int64_t N, int64_t K0, int64_t K1, int64_t ldy, void* stream) {
-    if (!x0 || !w0 || M < 0 || N < 0 || K0 < 0 || K1 < 0 || ldy < N) return MI355Q_E_BADARG;
+// ONE launch of the 256 x 256 tile kernel on its own operands (mi355q.h).  epi_op 0, mi355q_bfp_gemm_mixed: the contraction in two
+// column classes, class 0 = K values as row-aligned int8 operands with their exception lists, class 1 = K1 values as tiled bf16
+// operands x1 / w1, y with ldy.  epi_op 1 / 2, mi355q_bfp_gemm_aligned_gated / _relu: x . [gate; up]^T with the gated MLP's elementwise
+// step, or x . w^T with relu, and the consumer's quantiser q_* in the store epilogue: y = scratch, yb = out_bf16_tiled, N = the layer's width
+static int gemm_one_launch(int epi_op, const mi355q_bfp_operand* x, const mi355q_bfp_operand* w, const void* x1, const void* w1,
+                           const float* bias, float* y, void* yb, int64_t M, int64_t N, int64_t K, int64_t K1, int64_t ldy, int32_t q_width,
+                           int32_t q_exponent_width, int32_t q_exponent_bias, void* stream) {
+    QuantArgs q{};
+    if (!x || !w || M < 0 || N < 0 || K < 0 || (!epi_op && (K1 < 0 || ldy < N))) return MI355Q_E_BADARG;
     if (M == 0 || N == 0) return 0;
-    if (!y || !x1 || !w1 || !x0->mant || !x0->exp || !w0->mant || !w0->exp || !x0->rowflag || !w0->rowflag || !x0->gscale || !w0->gscale ||
-        !x0->list || !w0->list)
-        return MI355Q_E_BADARG;
-    if (x0->mbits < 1 || x0->mbits > 7 || w0->mbits < 1 || w0->mbits > 7) return MI355Q_E_BADARG;
-    if (x0->row_aligned != 1 || w0->row_aligned != 1 || bucket_cap_of(x0->list_cap) != ROW_BCAP || bucket_cap_of(w0->list_cap) != ROW_BCAP ||
-        K0 % 128 != 0 || K0 < 256 || K0 > MI355Q_ROW_ALIGN_MAX_K || K1 % 64 != 0 || K1 < 128 || K1 > MI355Q_ROW_ALIGN_MAX_K)
+    const OperandFaults fx = operand_faults(*x, ONE_LAUNCH), fw = operand_faults(*w, ONE_LAUNCH);
+    if (!y || (epi_op ? !yb : (!x1 || !w1)) || fx.missing || fw.missing) return MI355Q_E_BADARG;
+    if (fx.mbits || fw.mbits) return MI355Q_E_BADARG;
+    // (the consumer's values exact in bf16: <= 8 mantissa bits)
+    if (epi_op && block_fp_args(q, q_width, q_exponent_width, q_exponent_bias, {9, MI355Q_E_UNSUPPORTED, MI355Q_E_UNSUPPORTED}))
         return MI355Q_E_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(x0->mant) | reinterpret_cast<uintptr_t>(w0->mant) | reinterpret_cast<uintptr_t>(x1) | reinterpret_cast<uintptr_t>(w1)) % 16)
-        return MI355Q_E_ALIGN;
-    GemmArgs a{x0->mant, x0->exp, w0->mant, w0->exp, bias, y, M, N, K0, ldy,
-               x0->exp_bias + x0->mbits + w0->exp_bias + w0->mbits, 1,
-               x0->exp_bias + x0->mbits, w0->exp_bias + w0->mbits,
-               ROW_BCAP, ROW_BCAP, 0};
-    a.x_mbits = x0->mbits;
-    a.w_mbits = w0->mbits;
+    if (fx.form || fw.form || K % 128 != 0 || K < 256 || K > MI355Q_ROW_ALIGN_MAX_K ||
+        (epi_op ? N % 32 != 0 : (K1 % 64 != 0 || K1 < 128 || K1 > MI355Q_ROW_ALIGN_MAX_K)))
+        return MI355Q_E_UNSUPPORTED;
+    if (fx.misaligned || fw.misaligned || (epi_op ? misaligned16({yb, y}) : misaligned16({x1, w1}))) return MI355Q_E_ALIGN;
+    if (epi_op == 1) N *= 2;
+    GemmArgs a = gemm_args(*x, *w, bias, y, M, N, K, epi_op ? N : ldy);
+    a.x_mbits = x->mbits;
+    a.w_mbits = w->mbits;
     a.xm1 = static_cast<const int8_t*>(x1);
     a.wm1 = static_cast<const int8_t*>(w1);
     a.K1 = K1;
+    a.yb = yb;
+    a.epi_op = epi_op;
+    if (epi_op) {
+        a.q_mbits = q_width - 1;
+        a.q_emin = q.e_min;
+        a.q_emax = q.e_max;
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipEvent_t te = g_timing.begin(st);
-    const int rc = launch_bfp_gemm_v9_mixed(a, x0->gscale, w0->gscale, x0->list, w0->list, st, x0->rowflag, w0->rowflag);
-    g_timing.end(te, st);
-    return rc;
+    const auto launch = epi_op ? launch_bfp_gemm_v9_gated : launch_bfp_gemm_v9_mixed;
+    return timed(st, [&] { return launch(a, x->gscale, w->gscale, x->list, w->list, st, x->rowflag, w->rowflag); });
 }
 
-// x . [gate; up]^T with the gated MLP's elementwise step and the consumer's quantiser in the store epilogue (mi355q.h); epi_op 2:
-// x . w^T with relu and the consumer's quantiser there (I = the layer's out_features)
-static int gemm_aligned_epilogue_impl(const mi355q_bfp_operand* x, const mi355q_bfp_operand* w, const float* bias, float* scratch,
-                                      void* out_bf16_tiled, int64_t M, int64_t I, int64_t K, int32_t q_width, int32_t q_exponent_width,
-                                      int32_t q_exponent_bias, void* stream, int epi_op) {
-    if (!x || !w || M < 0 || I < 0 || K < 0) return MI355Q_E_BADARG;
-    if (M == 0 || I == 0) return 0;
-    if (!scratch || !out_bf16_tiled || !x->mant || !x->exp || !w->mant || !w->exp || !x->rowflag || !w->rowflag || !x->gscale || !w->gscale ||
-        !x->list || !w->list)
-        return MI355Q_E_BADARG;
-    if (x->mbits < 1 || x->mbits > 7 || w->mbits < 1 || w->mbits > 7) return MI355Q_E_BADARG;
-    if (q_exponent_width < 1 || q_exponent_width > 8 || q_width < 2 || q_width > 9) return MI355Q_E_UNSUPPORTED;     // (exact in bf16: <= 8 mantissa bits)
-    if (q_exponent_bias == MI355Q_BIAS_DEFAULT) q_exponent_bias = (1 << (q_exponent_width - 1)) - 1;
-    if (x->row_aligned != 1 || w->row_aligned != 1 || bucket_cap_of(x->list_cap) != ROW_BCAP || bucket_cap_of(w->list_cap) != ROW_BCAP ||
-        K % 128 != 0 || K < 256 || K > MI355Q_ROW_ALIGN_MAX_K || I % 32 != 0)
-        return MI355Q_E_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(x->mant) | reinterpret_cast<uintptr_t>(w->mant) | reinterpret_cast<uintptr_t>(out_bf16_tiled) |
-         reinterpret_cast<uintptr_t>(scratch)) % 16)
-        return MI355Q_E_ALIGN;
-    const int64_t N = epi_op == 2 ? I : 2 * I;
-    GemmArgs a{x->mant, x->exp, w->mant, w->exp, bias, scratch, M, N, K, N,
-               x->exp_bias + x->mbits + w->exp_bias + w->mbits, 1,
-               x->exp_bias + x->mbits, w->exp_bias + w->mbits,
-               ROW_BCAP, ROW_BCAP, 0};
-    a.x_mbits = x->mbits;
-    a.w_mbits = w->mbits;
-    a.yb = out_bf16_tiled;
-    a.q_mbits = q_width - 1;
-    a.q_emin = -q_exponent_bias;
-    a.q_emax = (1 << q_exponent_width) - 1 - q_exponent_bias;
-    a.epi_op = epi_op;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipEvent_t te = g_timing.begin(st);
-    const int rc = launch_bfp_gemm_v9_gated(a, x->gscale, w->gscale, x->list, w->list, st, x->rowflag, w->rowflag);
-    g_timing.end(te, st);
-    return rc;
+int mi355q_bfp_gemm_mixed(const mi355q_bfp_operand* x0, const mi355q_bfp_operand* w0, const void* x1, const void* w1, const float* bias,
+                          float* y, int64_t M, int64_t N, int64_t K0, int64_t K1, int64_t ldy, void* stream) {
+    return gemm_one_launch(0, x0, w0, x1, w1, bias, y, nullptr, M, N, K0, K1, ldy, 0, 0, 0, stream);
 }
 
 int mi355q_bfp_gemm_aligned_gated(const mi355q_bfp_operand* x, const mi355q_bfp_operand* w, const float* bias, float* scratch,
                                   void* out_bf16_tiled, int64_t M, int64_t I, int64_t K, int32_t q_width, int32_t q_exponent_width,
                                   int32_t q_exponent_bias, void* stream) {
-    return gemm_aligned_epilogue_impl(x, w, bias, scratch, out_bf16_tiled, M, I, K, q_width, q_exponent_width, q_exponent_bias, stream, 1);
+    return gemm_one_launch(1, x, w, nullptr, nullptr, bias, scratch, out_bf16_tiled, M, I, K, 0, 0, q_width, q_exponent_width,
+                           q_exponent_bias, stream);
 }
 
 int mi355q_bfp_gemm_aligned_relu(const mi355q_bfp_operand* x, const mi355q_bfp_operand* w, const float* bias, float* scratch,
                                  void* out_bf16_tiled, int64_t M, int64_t N, int64_t K, int32_t q_width, int32_t q_exponent_width,
                                  int32_t q_exponent_bias, void* stream) {
-    return gemm_aligned_epilogue_impl(x, w, bias, scratch, out_bf16_tiled, M, N, K, q_width, q_exponent_width, q_exponent_bias, stream, 2);
+    return gemm_one_launch(2, x, w, nullptr, nullptr, bias, scratch, out_bf16_tiled, M, N, K, 0, 0, q_width, q_exponent_width,
+                           q_exponent_bias, stream);
 }
 
-static int gemm_aligned_multi_impl(const mi355q_bfp_operand* x, const mi355q_bfp_operand* const* w, const float* const* bias,
+// `count` weights of one shape against ONE x in one grid: the same flavour, scales and bucket size everywhere
+int mi355q_bfp_gemm_aligned_multi(const mi355q_bfp_operand* x, const mi355q_bfp_operand* const* w, const float* const* bias,
                                   float* const* y, int32_t count, int64_t M, int64_t N, int64_t K, int64_t ldy, void* stream) {
     if (!x || !w || !y || count < 1 || count > 3 || M < 0 || N < 0 || K < 0 || ldy < N) return MI355Q_E_BADARG;
     if (M == 0 || N == 0) return 0;
     for (int i = 0; i < count; ++i) {
-        if (!w[i] || !y[i] || !w[i]->mant || !w[i]->exp || !w[i]->rowflag || !w[i]->gscale || !w[i]->list) return MI355Q_E_BADARG;
-        // one grid over all of them: the same flavour, scales and bucket size everywhere
-        if (w[i]->row_aligned != 1 || w[i]->mbits != w[0]->mbits || w[i]->exp_bias != w[0]->exp_bias ||
-            bucket_cap_of(w[i]->list_cap) != ROW_BCAP)
-            return MI355Q_E_UNSUPPORTED;
-        if (reinterpret_cast<uintptr_t>(w[i]->mant) % 16) return MI355Q_E_ALIGN;
+        if (!w[i] || !y[i]) return MI355Q_E_BADARG;
+        const OperandFaults fw = operand_faults(*w[i], ONE_LAUNCH);
+        if (fw.missing) return MI355Q_E_BADARG;
+        if (fw.form || w[i]->mbits != w[0]->mbits || w[i]->exp_bias != w[0]->exp_bias) return MI355Q_E_UNSUPPORTED;
+        if (fw.misaligned) return MI355Q_E_ALIGN;
     }
-    if (!x->mant || !x->exp || !x->rowflag || !x->gscale || !x->list) return MI355Q_E_BADARG;
-    if (x->row_aligned != 1 || bucket_cap_of(x->list_cap) != ROW_BCAP || K % 128 != 0 || K > MI355Q_ROW_ALIGN_MAX_K ||
-        g_gemm_variant.load() != 0)
-        return MI355Q_E_UNSUPPORTED;                  // (callers then launch mi355q_bfp_gemm_aligned per weight)
-    if (x->mbits < 1 || x->mbits > 7 || w[0]->mbits < 1 || w[0]->mbits > 7) return MI355Q_E_BADARG;
-    if (reinterpret_cast<uintptr_t>(x->mant) % 16) return MI355Q_E_ALIGN;
-    if (count == 1) return gemm_aligned_impl(x, w[0], bias ? bias[0] : nullptr, y[0], M, N, K, ldy, stream);
-    GemmArgs a{x->mant, x->exp, w[0]->mant, w[0]->exp, bias ? bias[0] : nullptr, y[0], M, N, K, ldy,
-               x->exp_bias + x->mbits + w[0]->exp_bias + w[0]->mbits, 1,
-               x->exp_bias + x->mbits, w[0]->exp_bias + w[0]->mbits,
-               ROW_BCAP, ROW_BCAP, 0};
+    const OperandFaults fx = operand_faults(*x, ONE_LAUNCH);
+    const int variant = g_gemm_variant.load();
+    if (fx.missing) return MI355Q_E_BADARG;
+    if (fx.form || K % 128 != 0 || K > MI355Q_ROW_ALIGN_MAX_K || variant != 0) return MI355Q_E_UNSUPPORTED;     // (callers then launch per weight)
+    if (fx.mbits || w[0]->mbits < 1 || w[0]->mbits > 7) return MI355Q_E_BADARG;
+    if (fx.misaligned) return MI355Q_E_ALIGN;
+    if (count == 1) return gemm_aligned_impl(x, w[0], bias ? bias[0] : nullptr, y[0], M, N, K, ldy, stream, variant);
+    GemmArgs a = gemm_args(*x, *w[0], bias ? bias[0] : nullptr, y[0], M, N, K, ldy);
     a.ngroup = count;
     for (int i = 0; i < count; ++i) {
         a.g_wm[i] = w[i]->mant; a.g_we[i] = w[i]->exp; a.g_sw[i] = w[i]->gscale; a.g_wlist[i] = w[i]->list;
@@ -776,10 +663,6 @@ static int gemm_aligned_multi_impl(const mi355q_bfp_operand* x, const mi355q_bfp
     return launch_bfp_gemm_v8(a, x->gscale, w[0]->gscale, x->list, w[0]->list, static_cast<hipStream_t>(stream), x->rowflag, w[0]->rowflag);
 }
 
-int mi355q_bfp_gemm_aligned_multi(const mi355q_bfp_operand* x, const mi355q_bfp_operand* const* w, const float* const* bias,
-                                  float* const* y, int32_t count, int64_t M, int64_t N, int64_t K, int64_t ldy, void* stream) {
-    return gemm_aligned_multi_impl(x, w, bias, y, count, M, N, K, ldy, stream);
-}
 
 // ---- W4A4 / W5A5 on the MX scaled matrix instruction (mi355q_mx.hip)
 size_t mi355q_mx_plane_bytes(int64_t rows, int64_t K, int32_t plane) {
@@ -791,21 +674,11 @@ size_t mi355q_mx_plane_bytes(int64_t rows, int64_t K, int32_t plane) {
 static int mx_quant_args(QuantArgs& a, const float* x, int64_t rows, int64_t K, int32_t width, int32_t exponent_width, int32_t exponent_bias) {
     if (rows < 0 || K < 0) return MI355Q_E_BADARG;
     if (K % 128 != 0 || K > MI355Q_ROW_ALIGN_MAX_K) return MI355Q_E_UNSUPPORTED;
-    if (exponent_width < 1 || exponent_width > 8 || width < 2 || width > 5) return MI355Q_E_UNSUPPORTED;   // <= 4 mantissa bits: exact in e2m3
-    if (exponent_bias == MI355Q_BIAS_DEFAULT) exponent_bias = (1 << (exponent_width - 1)) - 1;
-    if (exponent_bias < 0) return MI355Q_E_UNSUPPORTED;
-    a = QuantArgs{};
-    a.x = x;
-    a.lead = 1; a.rows = rows; a.cols = K;
-    a.b0 = 1; a.b1 = 16;
-    a.n_elems = rows * K;
-    a.nbr = rows; a.nbc = K / 16;
-    a.n_blocks = rows * (K / 16);
-    a.flags = MI355Q_ZERO_BLOCK_FAST;
-    a.code_bias = exponent_bias;
-    a.e_min = -exponent_bias;
-    a.e_max = (1 << exponent_width) - 1 - exponent_bias;
-    set_mantissa(a, width - 1);
+    QuantArgs q{};
+    // (<= 4 mantissa bits: exact in e2m3)
+    if (block_fp_args(q, width, exponent_width, exponent_bias, {5, MI355Q_E_UNSUPPORTED, MI355Q_E_UNSUPPORTED}) || q.code_bias < 0) return MI355Q_E_UNSUPPORTED;
+    a = q;
+    fill_rows(a, x, rows, K);
     return 0;
 }
 
@@ -844,10 +717,7 @@ int mi355q_mx_gemm(const uint8_t* x16, const uint8_t* x8, const uint8_t* xs, con
     a.bias = bias; a.y = y;
     a.M = M; a.N = N; a.K = K; a.ldy = ldy;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipEvent_t te = g_timing.begin(st);
-    const int rc = launch_mx_gemm(a, st);
-    g_timing.end(te, st);
-    return rc;
+    return timed(st, [&] { return launch_mx_gemm(a, st); });
 }
 
 size_t mi355q_bfp_matmul_workspace_bytes(int64_t B, int64_t K, int64_t N) {
@@ -870,16 +740,9 @@ static int bfp_matmul_impl(bool softmax, const float* mask, long long causal_off
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(workspace)) % 16)
         return MI355Q_E_ALIGN;
     QuantArgs ax{}, ay{};
-    auto fill = [](QuantArgs& a, int width, int ew, int bias) {
-        if (bias == MI355Q_BIAS_DEFAULT) bias = (1 << (ew - 1)) - 1;
-        a.b0 = 1; a.b1 = 16;
-        a.code_bias = bias;
-        a.e_min = -bias;
-        a.e_max = (1 << ew) - 1 - bias;
-        set_mantissa(a, width - 1);
-    };
-    fill(ax, x_width, x_exponent_width, x_exponent_bias);
-    fill(ay, y_width, y_exponent_width, y_exponent_bias);
+    ax.b0 = ay.b0 = 1; ax.b1 = ay.b1 = 16;
+    block_fp_fill(ax, x_width, x_exponent_width, x_exponent_bias);
+    block_fp_fill(ay, y_width, y_exponent_width, y_exponent_bias);
     return launch_bfp_qmatmul(ax, ay, x, y, out, workspace, B, M, K, N, static_cast<hipStream_t>(stream), softmax, mask, causal_off);
 }
 
@@ -955,13 +818,8 @@ int mi355q_bfp_attention_fused(const float* q, const float* k, const float* v, c
         if (!consumer_params || consumer_params[0] < 2 || consumer_params[1] < 1 || consumer_params[1] > 8 || (cos && heads != B)) return MI355Q_E_BADARG;
         if (consumer_params[0] > 9) return MI355Q_E_UNSUPPORTED;
         if (reinterpret_cast<uintptr_t>(out_bf16_tiled) % 16) return MI355Q_E_ALIGN;
-        int bias = consumer_params[2];
-        if (bias == MI355Q_BIAS_DEFAULT) bias = (1 << (consumer_params[1] - 1)) - 1;
         ao.b0 = 1; ao.b1 = 16;
-        ao.code_bias = bias;
-        ao.e_min = -bias;
-        ao.e_max = (1 << consumer_params[1]) - 1 - bias;
-        set_mantissa(ao, consumer_params[0] - 1);
+        block_fp_fill(ao, consumer_params[0], consumer_params[1], consumer_params[2]);
         if (!out) out = reinterpret_cast<float*>(out_bf16_tiled);       // (never written; keeps the argument checks below uniform)
     }
     if (cos || sin || position_ids) {
@@ -983,13 +841,8 @@ int mi355q_bfp_attention_fused(const float* q, const float* k, const float* v, c
     QuantArgs a[4] = {};
     for (int i = 0; i < 4; ++i) {
         const int32_t* pr = (i < 2 ? qk_params : pv_params) + 3 * (i & 1);
-        int bias = pr[2];
-        if (bias == MI355Q_BIAS_DEFAULT) bias = (1 << (pr[1] - 1)) - 1;
         a[i].b0 = 1; a[i].b1 = 16;
-        a[i].code_bias = bias;
-        a[i].e_min = -bias;
-        a[i].e_max = (1 << pr[1]) - 1 - bias;
-        set_mantissa(a[i], pr[0] - 1);
+        block_fp_fill(a[i], pr[0], pr[1], pr[2]);
     }
     long long st6[8];
     if (strides)
@@ -1359,9 +1212,7 @@ static int values_matmul_impl(int fmt, bool softmax, const float* mask, long lon
             const int mbits = width - ew - 1;
             if (ew < 1 || ew > 8 || mbits < 0 || mbits > 23 || ebw < 1 || ebw > 8) return MI355Q_E_BADARG;
             if (mbits > 7) return MI355Q_E_UNSUPPORTED;          // a quantised value must fit bf16's 8 significant bits
-            a.span = (1 << ew) - 1;
-            a.bias_max = (1 << ebw) - 1;
-            set_mantissa(a, mbits);
+            block_minifloat_fill(a, mbits, ew, ebw);
             return 0;
         };
         int rc = fill(ax, x_width, x_exponent_width, x_exponent_bias_width);
@@ -1369,9 +1220,7 @@ static int values_matmul_impl(int fmt, bool softmax, const float* mask, long lon
         if (rc) return rc;
     } else {
         if (x_width < 2 || x_width > 9 || x_exponent_bias_width < 1 || x_exponent_bias_width > 8) return MI355Q_E_BADARG;
-        ax.span = (1 << (x_width - 1)) - 1;
-        ax.bias_max = (1 << x_exponent_bias_width) - 1;
-        set_mantissa(ax, 0);
+        block_minifloat_fill(ax, 0, x_width - 1, x_exponent_bias_width);
         set_mantissa(ay, 0);
     }
     if (K % 16 != 0 || N % 16 != 0) return MI355Q_E_UNSUPPORTED;      // blocks of 16 along K (x) and N (y) tile the operands

@@ -15,25 +15,14 @@
 #include "mi355q_decode.h"
 #include "mi355q_kv8.h"
 #include "mi355q_kvbm.h"
+#include "mi355q_linear_call.h"
 
 namespace mi355q {
 
-inline void set_mantissa(QuantArgs& a, int mbits) {
-    a.shift = std::ldexp(1.0f, mbits);
-    a.inv_shift = std::ldexp(1.0f, -mbits);
-    a.mant_max = a.shift - 1.0f;
-}
-// the block_fp quantiser of one operand: {width, exponent width, exponent bias} at pr
+// the block_fp quantiser of one operand: {width, exponent width, exponent bias} at pr; a quantised value must fit bf16's 8 significant bits
 inline int decode_quant_args(const int32_t* pr, QuantArgs& a) {
-    if (pr[0] < 2 || pr[1] < 1 || pr[1] > 8) return MI355Q_E_BADARG;
-    if (pr[0] > 9) return MI355Q_E_UNSUPPORTED;               // a quantised value must fit bf16's 8 significant bits
-    int bias = pr[2];
-    if (bias == MI355Q_BIAS_DEFAULT) bias = (1 << (pr[1] - 1)) - 1;
+    if (const int rc = block_fp_args(a, pr[0], pr[1], pr[2], {9, MI355Q_E_BADARG, MI355Q_E_UNSUPPORTED})) return rc;
     a.b0 = 1; a.b1 = 16;
-    a.code_bias = bias;
-    a.e_min = -bias;
-    a.e_max = (1 << pr[1]) - 1 - bias;
-    set_mantissa(a, pr[0] - 1);
     return 0;
 }
 // the quantisers of the CACHED operands (the y side of qk_params and pv_params); int8: a mantissa must fit a byte
@@ -48,9 +37,7 @@ inline int bm_quant_args(const int32_t* pr, QuantArgs& a) {
     const int mbits = pr[0] - pr[1] - 1;
     if (pr[1] < 1 || pr[1] > 8 || mbits < 1 || mbits > 7 || pr[2] < 1 || pr[2] > 8) return MI355Q_E_UNSUPPORTED;
     a.b0 = 1; a.b1 = 16;
-    a.span = (1 << pr[1]) - 1;
-    a.bias_max = (1 << pr[2]) - 1;
-    set_mantissa(a, mbits);
+    block_minifloat_fill(a, mbits, pr[1], pr[2]);
     return 0;
 }
 // the quantisers of a block_minifloat call: the cached operands' (y sides: append) or Q's and P's (x sides: decode)
