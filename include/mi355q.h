@@ -788,6 +788,36 @@ int mi355q_bfp_attention_decode_kv8_paged(const float* q, const void* k8_pool, c
 int mi355q_bfp_kv8_paged_copy(void* k8_pool, void* v8_pool, const float* stage_src, float* stage_dst, const int32_t* jobs, int64_t n_jobs,
                               int64_t B, int64_t num_pages, int64_t P, int64_t D, void* stream);
 
+/* 4-bit-mantissa cache: the contiguous int8-mantissa cache above for CACHED operands of width <= 4, whose mantissa |m| <= 7 is a signed
+ * NIBBLE, two to a byte, plus one shared-exponent byte per 16-value block -- 4 + 1/2 bits a value, exactly 9/32 of
+ * mi355q_bfp_kv_cache_bytes' K and V bytes and 9/17 of mi355q_bfp_kv8_cache_bytes' (the stage is the same).  Layout: csrc/mi355q_kv4.h
+ * -- pieces of 288 bytes, k4 [B][C / 16][D / 32][288], v4 [B][ceil(C / 32)][D / 16][288]; the two nibbles of a byte are two values of ONE
+ * block, so the append stores whole bytes and never reads the cache.  The kernels rebuild the bf16 MFMA fragments in registers from the
+ * same integer and the same exponent through the same conversion: append, decode_fp32 and decode give the bits of the kv8 calls, and so
+ * of the *_ragged / *_grouped calls on a bf16 cache, holding the same keys (decode: with the same number of splits), with the kv8
+ * cache's ONE exception: an input 0 < |x| <= 1e-8 is stored as 0. */
+/* mi355q_bfp_kv4_cache_bytes: the sizes of k4, v4 and stage for B rows of capacity C (C % 16 == 0) and head_dim D (D % 32 == 0,
+ * D <= 128); arguments and codes of mi355q_bfp_kv8_cache_bytes. */
+int mi355q_bfp_kv4_cache_bytes(int64_t B, int64_t C, int64_t D, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_bytes);
+/* mi355q_bfp_kv4_append: row b's first counts[b] (NULL: n) rows of k, v become its keys lengths[b] .. ; arguments, check order and codes
+ * of mi355q_bfp_kv8_append, but a cached operand (the y side of qk_params or of pv_params) of width above 4 is MI355Q_E_UNSUPPORTED,
+ * where kv8 refuses above 8, before the "nothing to do" return of 0.  v4 must be zeroed once before the first append. */
+int mi355q_bfp_kv4_append(void* k4, void* v4, float* stage, const float* k, const float* v, const int32_t* lengths,
+                          const int32_t* counts, int64_t B, int64_t C, int64_t D, int64_t n, int64_t max_length,
+                          const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides, void* stream);
+/* mi355q_bfp_kv4_decode_fp32: the cache's values as the decode kernels rebuild them, fp32 [B, max_length, D], zeros behind lengths[b];
+ * arguments and codes of mi355q_bfp_kv8_decode_fp32 with the width rule above. */
+int mi355q_bfp_kv4_decode_fp32(const void* k4, const void* v4, const int32_t* lengths, float* k_out, float* v_out, int64_t B, int64_t C,
+                               int64_t D, int64_t max_length, const int32_t* qk_params, const int32_t* pv_params, void* stream);
+/* mi355q_bfp_attention_decode_kv4: mi355q_bfp_attention_decode_kv8 on this cache -- always the ragged form (`lengths` mandatory), G = 0
+ * or 1 the ungrouped form, G > 1 as in mi355q_bfp_attention_decode_grouped; workspace and splits are
+ * mi355q_bfp_attention_decode_workspace_bytes' / _splits'.  Same check order and codes with the width rule above (the x sides, Q and P,
+ * stay 2 .. 9).  No paged, windowed or extend form reads this cache. */
+int mi355q_bfp_attention_decode_kv4(const float* q, const void* k4, const void* v4, int32_t G, const int32_t* lengths, int32_t causal,
+                                    float q_scale, float scale_div, float* out, void* workspace, int64_t B, int64_t M,
+                                    int64_t max_length, int64_t C, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
+                                    const int64_t* strides, int32_t splits, void* stream);
+
 /* Block_minifloat cache: the contiguous cache of mi355q_bfp_kv_cache_bytes -- the same kq / vq / stage, sizes, layout and open-tile
  * rule -- holding what the reference's block_minifloat [1,16] quantisers (block_minifloat.py:44-65, minifloat.py:158-194) make of k^T
  * and v.  Replaces, for a layer whose matmul_0 / matmul_1 (bmm_0 / bmm_1) are block_minifloat, torch.cat of fp32 K / V

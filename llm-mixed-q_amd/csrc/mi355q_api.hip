@@ -14,6 +14,7 @@
 #include "mi355q_gemv.h"
 #include "mi355q_decode.h"
 #include "mi355q_kv8.h"
+#include "mi355q_kv4.h"
 #include "mi355q_extend.h"
 #include "mi355q_linear_call.h"
 #include "mi355q_kv_call.h"
@@ -856,7 +857,7 @@ int mi355q_bfp_attention_fused(const float* q, const float* k, const float* v, c
                                 out_bf16_tiled ? &ao : nullptr, q_scale);
 }
 
-// ---- the KV cache and the attention that reads it (mi355q_decode.h, mi355q_extend.h, mi355q_kv8.h) ------------------------------
+// ---- the KV cache and the attention that reads it (mi355q_decode.h, mi355q_extend.h, mi355q_kv8.h, mi355q_kv4.h) ---------------
 // Every export below fills a KvCall, has kv_call_check (mi355q_kv_call.h) refuse it or fill what the launchers take, and launches.
 // Uniform, ragged (per-row lengths on the device), grouped (G query rows a cache row), paged (pools of pages and a page table per row),
 // int8 mantissas (kv8) and the sliding window differ in the KV_EXPORTS entry they start from and in the arguments they have.
@@ -867,8 +868,8 @@ int sizes(const KvCall& d, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_by
     int rc;
     if (!kv_call_check(d, c, rc)) return rc;
     const int64_t rows = kv_paged(d.storage) ? d.num_pages : d.B, keys = kv_paged(d.storage) ? d.P : d.C;      // (a page is a cache row of P keys)
-    *k_bytes = kv_int8(d.storage) ? kv8_k_bytes(rows, keys, d.D) : kv_k_bytes(rows, keys, d.D);
-    *v_bytes = kv_int8(d.storage) ? kv8_v_bytes(rows, keys, d.D) : kv_v_bytes(rows, keys, d.D);
+    *k_bytes = kv_int4(d.storage) ? kv4_k_bytes(rows, keys, d.D) : kv_int8(d.storage) ? kv8_k_bytes(rows, keys, d.D) : kv_k_bytes(rows, keys, d.D);
+    *v_bytes = kv_int4(d.storage) ? kv4_v_bytes(rows, keys, d.D) : kv_int8(d.storage) ? kv8_v_bytes(rows, keys, d.D) : kv_v_bytes(rows, keys, d.D);
     *stage_bytes = kv_stage_bytes(d.B, d.D);
     return 0;
 }
@@ -876,6 +877,8 @@ int append(const KvCall& d, const float* k, const float* v, void* stream) {
     KvChecked c;
     int rc;
     if (!kv_call_check(d, c, rc)) return rc;
+    if (kv_int4(d.storage))
+        return launch_kv4_append(c.c4, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.lengths, d.counts, d.n, hs(stream));
     if (kv_int8(d.storage))
         return launch_kv8_append(c.c8, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.lengths, d.counts, d.n, hs(stream), c.pages);
     if (d.form & KV_MINIFLOAT)
@@ -887,6 +890,7 @@ int dequantise(const KvCall& d, float* k_out, float* v_out, void* stream) {
     KvChecked c;
     int rc;
     if (!kv_call_check(d, c, rc)) return rc;
+    if (kv_int4(d.storage)) return launch_kv4_decode_fp32(c.c4, c.ak, c.av, k_out, v_out, d.L, d.lengths, hs(stream));
     if (kv_int8(d.storage)) return launch_kv8_decode_fp32(c.c8, c.ak, c.av, k_out, v_out, d.L, d.lengths, hs(stream), c.pages);
     return launch_kv_decode_fp32(c.c, k_out, v_out, d.L, hs(stream), d.lengths, c.pages);
 }
@@ -894,6 +898,9 @@ int decode(const KvCall& d, const float* q, float* out, void* workspace, float q
     KvChecked c;
     int rc;
     if (!kv_call_check(d, c, rc)) return rc;
+    if (kv_int4(d.storage))
+        return launch_bfp_attention_decode_kv4(c.aq, c.ap, c.ak, c.av, c.c4, q, out, workspace, d.M, d.L, c.causal, q_scale, scale_div, c.strides,
+                                               d.splits, hs(stream), d.lengths, c.G);
     if (kv_int8(d.storage))
         return launch_bfp_attention_decode_kv8(c.aq, c.ap, c.ak, c.av, c.c8, q, out, workspace, d.M, d.L, c.causal, q_scale, scale_div, c.strides,
                                                d.splits, hs(stream), d.lengths, c.G, c.pages);
@@ -1112,6 +1119,33 @@ int mi355q_bfp_kv8_paged_copy(void* k8_pool, void* v8_pool, const float* stage_s
     return launch_kv_paged_copy(g, stream);
 }
 
+// 4-bit-mantissa cache: two mantissa nibbles a byte and one exponent byte a block (mi355q_kv4.h); always the ragged form, contiguous
+int mi355q_bfp_kv4_cache_bytes(int64_t B, int64_t C, int64_t D, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_bytes) {
+    return sizes(KvCall(KV_EXPORTS[KVX_KV4_CACHE_BYTES]).cache(nullptr, nullptr, nullptr, B, C, D).sizes(k_bytes, v_bytes, stage_bytes), k_bytes, v_bytes,
+                 stage_bytes);
+}
+
+int mi355q_bfp_kv4_append(void* k4, void* v4, float* stage, const float* k, const float* v, const int32_t* lengths,
+                          const int32_t* counts, int64_t B, int64_t C, int64_t D, int64_t n, int64_t max_length,
+                          const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides, void* stream) {
+    return append(KvCall(KV_EXPORTS[KVX_KV4_APPEND]).cache(k4, v4, stage, B, C, D).rows(k, v, n).lens(lengths, counts, max_length)
+                      .quant(qk_params, pv_params, strides), k, v, stream);
+}
+
+int mi355q_bfp_kv4_decode_fp32(const void* k4, const void* v4, const int32_t* lengths, float* k_out, float* v_out, int64_t B, int64_t C,
+                               int64_t D, int64_t max_length, const int32_t* qk_params, const int32_t* pv_params, void* stream) {
+    return dequantise(KvCall(KV_EXPORTS[KVX_KV4_DECODE_FP32]).cache(k4, v4, nullptr, B, C, D).rows(k_out, v_out, 0).lens(lengths, nullptr, max_length)
+                          .quant(qk_params, pv_params, nullptr), k_out, v_out, stream);
+}
+
+int mi355q_bfp_attention_decode_kv4(const float* q, const void* k4, const void* v4, int32_t G, const int32_t* lengths, int32_t causal,
+                                    float q_scale, float scale_div, float* out, void* workspace, int64_t B, int64_t M,
+                                    int64_t max_length, int64_t C, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
+                                    const int64_t* strides, int32_t splits, void* stream) {
+    return decode(KvCall(KV_EXPORTS[KVX_DECODE_KV4]).cache(k4, v4, nullptr, B, C, D).lens(lengths, nullptr, max_length)
+                      .query(q, out, workspace, M, G, causal, 0, splits).quant(qk_params, pv_params, strides), q, out, workspace, q_scale, scale_div, stream);
+}
+
 // block_minifloat cache: KVCache's storage and layout, the block_minifloat quantisers (mi355q_kvbm.h); always the ragged form, contiguous
 int mi355q_bm_kv_append(void* kq, void* vq, float* stage, const float* k, const float* v, const int32_t* lengths, const int32_t* counts,
                         int64_t B, int64_t C, int64_t D, int64_t n, int64_t max_length, const int32_t* qk_params, const int32_t* pv_params,
@@ -1166,10 +1200,11 @@ int mi355q_bfp_attention_extend_window(const float* q, const void* kq, const voi
 // to launch (or to write its sizes), then the normalised call: B, capacity, D, M, L, n, G, window, lg_p, pages set, causal, strides set,
 // the four strides.
 // mi355q_debug_kv_call knows the 25 ids recorded in tests/golden/kv_api_codes.json, 0 .. KVX_KV8P_DECODE, and refuses every other as it
-// always has; mi355q_debug_kv_call_all is the same function over every id of KvExport (the block_minifloat exports behind them).
+// always has; mi355q_debug_kv_call_all is the same function over every id of KvExport (the block_minifloat exports behind them, then
+// -- behind KVX_NONE_27, an id it has always refused and still does -- the 4-bit-mantissa exports, 28 .. 31).
 static int debug_kv_call(int32_t id, int32_t ids, const int64_t a[27], const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
                          int64_t out[18]) {
-    if (id < 0 || id >= ids || !a || !out) return MI355Q_E_BADARG;
+    if (id < 0 || id >= ids || id == KVX_NONE_27 || !a || !out) return MI355Q_E_BADARG;
     const auto p = [a](int i) { return reinterpret_cast<const void*>(static_cast<uintptr_t>(a[i])); };
     const auto p32 = [a](int i) { return reinterpret_cast<const int32_t*>(static_cast<uintptr_t>(a[i])); };
     const auto p64 = [a](int i) { return reinterpret_cast<const int64_t*>(static_cast<uintptr_t>(a[i])); };
@@ -1180,7 +1215,7 @@ static int debug_kv_call(int32_t id, int32_t ids, const int64_t a[27], const int
     KvChecked c;
     int rc;
     const bool go = kv_call_check(d, c, rc);
-    const int64_t cap = kv_int8(d.storage) ? c.c8.C : c.c.C;
+    const int64_t cap = kv_int4(d.storage) ? c.c4.C : kv_int8(d.storage) ? c.c8.C : c.c.C;
     const int64_t words[18] = {rc, go, d.B, cap, d.D, d.M, d.L, d.n, c.G, c.window, c.pg.lg_p, c.pages != nullptr, c.causal, c.strides != nullptr,
                                c.st[0], c.st[1], c.st[2], c.st[3]};
     for (int i = 0; i < 18; ++i) out[i] = words[i];

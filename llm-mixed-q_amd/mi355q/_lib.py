@@ -116,6 +116,11 @@ SIGNATURES = {
     "mi355q_bfp_attention_decode_kv8_paged": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, C.c_float, C.c_float, _vp, _vp, _i64, _i64, _i64,
                                                         _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp]),
     "mi355q_bfp_kv8_paged_copy": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
+    "mi355q_bfp_kv4_cache_bytes": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp]),
+    "mi355q_bfp_kv4_append": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "mi355q_bfp_kv4_decode_fp32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "mi355q_bfp_attention_decode_kv4": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, C.c_float, C.c_float, _vp, _vp, _i64, _i64, _i64,
+                                                  _i64, _i64, _vp, _vp, _vp, _i32, _vp]),
     "mi355q_bm_kv_append": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "mi355q_bm_attention_decode": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, C.c_float, C.c_float, _vp, _vp, _i64, _i64, _i64,
                                              _i64, _i64, _vp, _vp, _vp, _i32, _vp]),

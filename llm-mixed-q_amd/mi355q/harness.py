@@ -819,6 +819,53 @@ class PackedDecodeState(DecodeState):
             raise ValueError(f"PackedDecodeState: {e}") from None
 
 
+class NibbleDecodeState(DecodeState):
+    """DecodeState(model, batch, capacity, mode) on ops.NibbleKVCache: every layer's K and V as 4-bit mantissas, two to a byte, with one
+    exponent byte per block of 16 -- 9/32 of the cache bytes and of a decode step's K / V traffic, for models whose cached attention
+    operands all have width <= 4 (else ValueError here, naming the width).  The numbers are DecodeState's and PackedDecodeState's, bit
+    for bit (ops.PackedKVCache names the one exception, inputs of magnitude <= 1e-8).  What the nibble cache has no kernel for is
+    refused here, by name: extend=True (chunked prefill), a sliding-window model, and mode "fp32", which has no quantised cache at all."""
+
+    def __init__(self, model, batch: int, capacity: int, mode: str = "block_fp", extend: bool = False):
+        if mode != "block_fp":
+            raise ValueError(f"NibbleDecodeState: mode {mode!r}: the 4-bit-mantissa cache is a block_fp cache (mode 'fp32' keeps fp32 K / V)")
+        if extend:
+            raise NotImplementedError("NibbleDecodeState: extend=True: no extend (chunked prefill) kernel reads the 4-bit-mantissa cache")
+        if getattr(model.cfg, "sliding_window", None) is not None:
+            raise NotImplementedError("NibbleDecodeState: a sliding-window model: no windowed kernel reads the 4-bit-mantissa cache")
+        super().__init__(model, batch, capacity, mode, extend)
+
+    def _new_cache(self, rows, hd, qk, pv, dev):
+        try:
+            return ops.NibbleKVCache(rows, self.capacity, hd, qk, pv, dev)
+        except ValueError as e:
+            raise ValueError(f"NibbleDecodeState: {e}") from None
+
+
+class NarrowestDecodeState(DecodeState):
+    """DecodeState(model, batch, capacity, mode) with the narrowest storage EACH layer allows, for a model whose layers differ in their
+    attention widths: ops.NibbleKVCache where both cached operands (the y sides of the layer's two products) have width <= 4, else
+    ops.PackedKVCache where both have width <= 8, else ops.KVCache.  `kinds` says which layer got what: a list of "nibble" / "int8" /
+    "bf16", one entry per layer.  The three storages give the same bits for the same keys, so the numbers are DecodeState's.
+    Contiguous only, and the refusals of the packed states, by name: extend=True, a sliding-window model, mode "fp32"."""
+
+    def __init__(self, model, batch: int, capacity: int, mode: str = "block_fp", extend: bool = False):
+        if mode != "block_fp":
+            raise ValueError(f"NarrowestDecodeState: mode {mode!r}: the mantissa caches are block_fp caches (mode 'fp32' keeps fp32 K / V)")
+        if extend:
+            raise NotImplementedError("NarrowestDecodeState: extend=True: no extend (chunked prefill) kernel reads the mantissa caches")
+        if getattr(model.cfg, "sliding_window", None) is not None:
+            raise NotImplementedError("NarrowestDecodeState: a sliding-window model: no windowed kernel reads the mantissa caches")
+        self.kinds = []
+        super().__init__(model, batch, capacity, mode, extend)
+
+    def _new_cache(self, rows, hd, qk, pv, dev):
+        widest = max(int(qk[3]), int(pv[3]))
+        kind, cls = ("nibble", ops.NibbleKVCache) if widest <= 4 else ("int8", ops.PackedKVCache) if widest <= 8 else ("bf16", ops.KVCache)
+        self.kinds.append(kind)
+        return cls(rows, self.capacity, hd, qk, pv, dev)
+
+
 class PagedPackedDecodeState(PagedDecodeState):
     """PagedDecodeState(model, batch, capacity, mode, extend, page_size, num_pages) on ops.PagedPackedKVCache: paged caches of int8
     mantissas, 17/32 of the paged state's K and V bytes and of a decode step's K / V traffic, with its release / fork / reorder and its
@@ -894,13 +941,19 @@ def _forward_cached(model, input_ids, labels, state: DecodeState, counts=None):
     return fp32_linear(x, model.lm_head, model.mi355q_lm_head), None
 
 
+# generate's kv_storage: the state class and what its refusals call the storage
+_KV_STORAGES = {"int8": (PackedDecodeState, "int8-mantissa cache"), "nibble": (NibbleDecodeState, "4-bit-mantissa cache"),
+                "narrowest": (NarrowestDecodeState, "per-layer choice of mantissa caches")}
+
+
 def _new_state(model, batch, capacity, mode, extend, page_size, num_pages, kv_storage=None):
     if kv_storage is not None:
-        if kv_storage != "int8":
-            raise ValueError(f"generate: kv_storage = {kv_storage!r} is neither None (bf16 values) nor 'int8' (mantissa bytes)")
+        if kv_storage not in _KV_STORAGES:
+            raise ValueError(f"generate: kv_storage = {kv_storage!r} is neither None (bf16 values) nor 'int8' (mantissa bytes) nor 'nibble' "
+                             "(4-bit mantissas) nor 'narrowest' (per layer, the narrowest of the three its widths allow)")
         if page_size is not None or num_pages is not None:
-            raise NotImplementedError("generate: kv_storage='int8' with page_size / num_pages: the int8-mantissa cache is not paged")
-        return PackedDecodeState(model, batch, capacity, mode, extend=extend)
+            raise NotImplementedError(f"generate: kv_storage={kv_storage!r} with page_size / num_pages: the {_KV_STORAGES[kv_storage][1]} is not paged")
+        return _KV_STORAGES[kv_storage][0](model, batch, capacity, mode, extend=extend)
     if page_size is None and num_pages is None:
         return DecodeState(model, batch, capacity, mode, extend=extend)
     return PagedDecodeState(model, batch, capacity, mode, extend=extend, page_size=page_size, num_pages=num_pages)
@@ -917,7 +970,9 @@ def generate(model, prompt_ids, new_tokens: int, mode: str = "block_fp", chunk: 
     prompts every call gives each row whatever it has left, up to `chunk`.
     `page_size` / `num_pages`: paged caches (PagedDecodeState); the tokens and logits are those of the contiguous caches.
     `kv_storage`: None keeps the caches' values as bf16; "int8" stores mantissa bytes (PackedDecodeState: 17/32 of the cache bytes, the
-    same tokens and logits; not with `chunk`, pages or a sliding-window model)."""
+    same tokens and logits; not with `chunk`, pages or a sliding-window model); "nibble" stores 4-bit mantissas (NibbleDecodeState: 9/32
+    of the cache bytes, for models whose cached attention operands have width <= 4; the same tokens and logits, the same refusals);
+    "narrowest" gives each layer the narrowest of the three storages its widths allow (NarrowestDecodeState)."""
     if chunk is not None and int(chunk) < 1:
         raise ValueError(f"generate: chunk = {chunk} < 1")
     if isinstance(prompt_ids, (list, tuple)):

@@ -1500,7 +1500,7 @@ def _kv_call(device, export, args):
 
 
 class _KVCacheBase:
-    """What KVCache, PagedKVCache, PackedKVCache and PagedPackedKVCache share: the constructor's checks, the quantiser parameter words (`_pa`, `_pb`), the
+    """What KVCache, PagedKVCache, PackedKVCache, NibbleKVCache and PagedPackedKVCache share: the constructor's checks, the quantiser parameter words (`_pa`, `_pb`), the
     zeroed storage, and the checks of append / dequantised.  A subclass adds its storage's names, its exports' arguments and -- the paged
     one -- its allocator.  Messages carry the subclass's name."""
     RAGGED_ONLY = False         # PagedKVCache: lengths= is mandatory
@@ -1989,6 +1989,59 @@ class PackedKVCache(_KVCacheBase):
         return k, v
 
 
+class NibbleKVCache(_KVCacheBase):
+    """`PackedKVCache` for layers whose CACHED operands -- the y side of qk_params and of pv_params -- have width <= 4: the mantissa,
+    |m| <= 7, is a signed nibble, two to a byte, with one shared-exponent byte per block of 16 -- 4 + 1/2 bits a value, 9/32 of KVCache's
+    K and V bytes and of a decode step's K / V traffic, 9/17 of PackedKVCache's (layout: csrc/mi355q_kv4.h; the two nibbles of a byte
+    are two values of one block, so an append stores whole bytes and never reads the cache).  Same constructor arguments and the same
+    append / reset / dequantised / length / lengths= / counts= / max_length= contract; a class of its own, NOT a PackedKVCache or a
+    KVCache: only bfp_attention_decode's route for it (form `_kv4`) reads its bytes (no window, no pages, no bfp_attention_extend).  The
+    decode kernels rebuild the bf16 fragments in registers, so dequantised() and bfp_attention_decode give PackedKVCache's and KVCache's
+    bits for the same keys (decode: with the same `splits`), with PackedKVCache's one exception: an input 0 < |x| <= 1e-8 is stored
+    as 0.  Q and P (the x sides), which are not stored, keep 2 .. 9.  The kernels exist in the ragged form only: a call without
+    `lengths` brings every row's `length` as a device tensor."""
+
+    def __init__(self, B: int, capacity: int, D: int, qk_params, pv_params, device):
+        self._init_rows(int(B), int(D), qk_params, pv_params, device, int(capacity))
+        for name, p in (("qk_params (K)", self.qk_params), ("pv_params (V)", self.pv_params)):
+            if int(p[3]) > 4:
+                raise ValueError(f"NibbleKVCache {name}: cached operand of width {p[3]} > 4: its mantissa, up to 2^{int(p[3]) - 1} - 1 in "
+                                 "magnitude, does not fit the 4 bits the cache stores (PackedKVCache takes width 8, KVCache width 9)")
+        self.capacity, self.length = int(capacity), 0
+        # (zeroed: a V slot no key has reached is mantissa 0, a finite 0 under any exponent byte, for the probability of exactly 0 it meets)
+        self.k4, self.v4, self.stage = self._zeroed("mi355q_bfp_kv4_cache_bytes", self.B, self.capacity, self.D)
+
+    def reset(self) -> None:
+        # nothing to clear, as in KVCache.reset: stale mantissa nibbles and exponent bytes rebuild to finite values
+        self.length = 0
+
+    def append(self, k: torch.Tensor, v: torch.Tensor, *, lengths: torch.Tensor = None, counts: torch.Tensor = None,
+               max_length: int = None) -> None:
+        """KVCache.append on the nibble storage: n >= 1 new fp32 rows k, v [B, n, D] (or [1, H, n, D] head views) become keys
+        length .. length + n - 1, or -- ragged -- row b's first counts[b] rows become its keys lengths[b] .. (lengths BEFORE the call)."""
+        import ctypes
+        k3, v3, n, strides = self._append_args(k, v, lengths, counts, max_length)
+        ragged = lengths is not None
+        if not ragged:      # (the kernels read lengths from the device: every row at `length`)
+            lengths, max_length = _window_lengths(self, None, None)
+        _kv_call(self.device, "mi355q_bfp_kv4_append", (
+            _ptr(self.k4), _ptr(self.v4), _ptr(self.stage), _ptr(k3), _ptr(v3), _ptr(lengths), _ptr(counts), self.B, self.capacity, self.D, n,
+            int(max_length), ctypes.addressof(self._pa), ctypes.addressof(self._pb), ctypes.addressof(strides), _stream_ptr(self.device)))
+        if not ragged:
+            self.length += n
+
+    def dequantised(self, lengths: torch.Tensor = None, max_length: int = None):
+        """the cache's K and V as the decode kernels rebuild them, fp32 [B, length, D] (tests, debugging); ragged: [B, max_length, D],
+        zeros behind each row's lengths[b]"""
+        import ctypes
+        k, v = self._dequantised_out(lengths, max_length)
+        if lengths is None:
+            lengths, max_length = _window_lengths(self, None, None)
+        _kv_call(self.device, "mi355q_bfp_kv4_decode_fp32", (
+            _ptr(self.k4), _ptr(self.v4), _ptr(lengths), _ptr(k), _ptr(v), self.B, self.capacity, self.D, int(max_length),
+            ctypes.addressof(self._pa), ctypes.addressof(self._pb), _stream_ptr(self.device)))
+        return k, v
+
 
 def _minifloat_params(params, what):
     """(width, exponent width, exponent bias width) of data_in, then of weight, as the block_minifloat cache takes them"""
@@ -2224,6 +2277,7 @@ def _cached_attention(op, q, cache, causal, scale_div, q_scale, token_major, spl
       _paged     a PagedKVCache                                   G, lengths, the block table, the paged dimensions
       _kv8       a PackedKVCache (decode only)                    G, lengths (as _window), k8 / v8 for kq / vq
       _kv8_paged a PagedPackedKVCache (decode only)               as _paged, k8 / v8 for kq / vq
+      _kv4       a NibbleKVCache (decode only)                    as _kv8, k4 / v4 for kq / vq
       bm         a MinifloatKVCache (decode only)                 as _kv8 on kq / vq: the export is mi355q_bm_attention_decode
       _grouped   group != 1                                       G, lengths or NULL
       _ragged    lengths are given (decode only)                  lengths
@@ -2237,10 +2291,10 @@ def _cached_attention(op, q, cache, causal, scale_div, q_scale, token_major, spl
     sp = _stream_ptr(q.device)
     strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
     paged, packed, windowed = isinstance(cache, _PagedHost), isinstance(cache, (PackedKVCache, PagedPackedKVCache)), window is not None
-    minifloat = isinstance(cache, MinifloatKVCache)
-    form = "bm" if minifloat else "_window" if windowed else "_kv8_paged" if paged and packed else "_paged" if paged else "_kv8" if packed else "_grouped" if group != 1 else \
+    minifloat, nibble = isinstance(cache, MinifloatKVCache), isinstance(cache, NibbleKVCache)
+    form = "bm" if minifloat else "_kv4" if nibble else "_window" if windowed else "_kv8_paged" if paged and packed else "_paged" if paged else "_kv8" if packed else "_grouped" if group != 1 else \
         "_ragged" if decode and lengths is not None else ""
-    if windowed or packed or minifloat:
+    if windowed or packed or minifloat or nibble:
         lengths, L = _window_lengths(cache, lengths, max_length)
     else:
         L = int(max_length) if lengths is not None else cache.length
@@ -2255,7 +2309,7 @@ def _cached_attention(op, q, cache, causal, scale_div, q_scale, token_major, spl
     else:
         capacity = (cache.capacity,)
     _kv_call(q.device, "mi355q_bm_attention_decode" if minifloat else f"mi355q_bfp_attention_{op}{form}", (
-        _ptr(q3), *((_ptr(cache.k8), _ptr(cache.v8)) if packed else (_ptr(cache.kq), _ptr(cache.vq))), *which,
+        _ptr(q3), *((_ptr(cache.k8), _ptr(cache.v8)) if packed else (_ptr(cache.k4), _ptr(cache.v4)) if nibble else (_ptr(cache.kq), _ptr(cache.vq))), *which,
         *((1, int(window)) if windowed else (int(bool(causal)),)), float(q_scale) if q_scale else 0.0, float(scale_div) if scale_div else 0.0,
         _ptr(out), *((_ptr(_decode_workspace(q, cache, M, D, group, sp)),) if decode else ()), cache.B, M, L, *capacity, D,
         ctypes.addressof(cache._pa), ctypes.addressof(cache._pb), ctypes.addressof(strides), *((int(splits or 0),) if decode else ()), sp))
@@ -2288,11 +2342,19 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     `cache` may be a PackedKVCache (int8 mantissas, 17/32 of the K / V bytes): the same keywords with the same meaning and the bits
     of the same call on a KVCache holding the same keys; `window` is refused (NotImplementedError).  Its paged form is a
     PagedPackedKVCache (always with `lengths`), with the same bits and the same refusal.
+    `cache` may be a NibbleKVCache (4-bit mantissas, 9/32 of the K / V bytes; cached operands of width <= 4): the same keywords with the
+    same meaning and the bits of the same call on a PackedKVCache or a KVCache holding the same keys; `window` is refused
+    (NotImplementedError).
     `cache` may be a MinifloatKVCache (both products block_minifloat): the same keywords with the same meaning, Q and P through the
     block_minifloat quantisers of the cache's parameters; `window` is refused (NotImplementedError)."""
     if isinstance(cache, MinifloatKVCache):
         if window is not None:
             raise NotImplementedError("mi355q.bfp_attention_decode: no sliding-window kernel reads a MinifloatKVCache (block_minifloat); "
+                                      "window= needs a KVCache or a PagedKVCache")
+        why = _decode_call_check(q, cache, splits, lengths, max_length, group)
+    elif isinstance(cache, NibbleKVCache):
+        if window is not None:
+            raise NotImplementedError("mi355q.bfp_attention_decode: no sliding-window kernel reads a NibbleKVCache (4-bit mantissas); "
                                       "window= needs a KVCache or a PagedKVCache")
         why = _decode_call_check(q, cache, splits, lengths, max_length, group)
     elif isinstance(cache, (PackedKVCache, PagedPackedKVCache)):
@@ -2362,6 +2424,9 @@ def bfp_attention_extend(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     keys max(0, p - W + 1) .. p; a block of 64 queries walks the keys from the 32-key step of its first query's lower bound on."""
     if isinstance(cache, MinifloatKVCache):
         raise NotImplementedError("mi355q.bfp_attention_extend: no extend kernel reads a MinifloatKVCache (block_minifloat); chunked prefill "
+                                  "needs a KVCache or a PagedKVCache")
+    if isinstance(cache, NibbleKVCache):
+        raise NotImplementedError("mi355q.bfp_attention_extend: no extend kernel reads a NibbleKVCache (4-bit mantissas); chunked prefill "
                                   "needs a KVCache or a PagedKVCache")
     if isinstance(cache, (PackedKVCache, PagedPackedKVCache)):
         raise NotImplementedError(f"mi355q.bfp_attention_extend: no extend kernel reads a {type(cache).__name__} (int8 mantissas); chunked prefill "
