@@ -112,28 +112,7 @@ def test_gemm_matches_reference_semantics_fp32_linear():
 # ---------------------------------------------------------------------------------------------------
 # ROW-aligned operands (one exponent per row; int8 GEMM with row / column scales; bucketed exception lists)
 # ---------------------------------------------------------------------------------------------------
-def _row_exceptions(al, rows, nkb):
-    from mi355q import ops
-    over, ent = ops.row_list_entries(al.sparse, rows, al.list_cap)
-    mant = np.zeros((rows, nkb, 16), np.int64)
-    exp = np.zeros((rows, nkb), np.int64)
-    mask = np.zeros((rows, nkb), bool)
-    for e in ent:
-        assert not mask[e[0], e[1]], "a block is listed once"
-        assert e[0] // 256 == e[0] // 256
-        mask[e[0], e[1]] = True
-        exp[e[0], e[1]] = e[2]
-        mant[e[0], e[1]] = e[4:8].astype(np.int32).view(np.int8)
-    return over, mant, exp, mask
-
-
-def _untile(tiled, rows, K):
-    """tiled aligned mantissas (1-KiB pieces of 16 rows x 64 B laid out [block 0..3][row 0..15][16 B]) -> [rows, K] int8"""
-    t = tiled.cpu().numpy().view(np.int8)
-    kp = K // 64
-    rp = (t.size // (kp * 1024)) * 16
-    return np.ascontiguousarray(t[: (rp // 16) * kp * 1024].reshape(rp // 16, kp, 4, 16, 16).transpose(0, 3, 1, 2, 4)
-                                ).reshape(rp, K)[:rows]
+from tests.row_edges_util import _row_exceptions, _untile      # (shared with tests/test_gpu_row_quantiser_edges.py)  # noqa: E402
 
 
 @pytest.mark.parametrize("width", [6, 4, 8])
