@@ -878,7 +878,7 @@ int append(const KvCall& d, const float* k, const float* v, void* stream) {
     int rc;
     if (!kv_call_check(d, c, rc)) return rc;
     if (kv_int4(d.storage))
-        return launch_kv4_append(c.c4, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.lengths, d.counts, d.n, hs(stream));
+        return launch_kv4_append(c.c4, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.lengths, d.counts, d.n, hs(stream), c.pages);
     if (kv_int8(d.storage))
         return launch_kv8_append(c.c8, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.lengths, d.counts, d.n, hs(stream), c.pages);
     if (d.form & KV_MINIFLOAT)
@@ -890,7 +890,7 @@ int dequantise(const KvCall& d, float* k_out, float* v_out, void* stream) {
     KvChecked c;
     int rc;
     if (!kv_call_check(d, c, rc)) return rc;
-    if (kv_int4(d.storage)) return launch_kv4_decode_fp32(c.c4, c.ak, c.av, k_out, v_out, d.L, d.lengths, hs(stream));
+    if (kv_int4(d.storage)) return launch_kv4_decode_fp32(c.c4, c.ak, c.av, k_out, v_out, d.L, d.lengths, hs(stream), c.pages);
     if (kv_int8(d.storage)) return launch_kv8_decode_fp32(c.c8, c.ak, c.av, k_out, v_out, d.L, d.lengths, hs(stream), c.pages);
     return launch_kv_decode_fp32(c.c, k_out, v_out, d.L, hs(stream), d.lengths, c.pages);
 }
@@ -900,7 +900,7 @@ int decode(const KvCall& d, const float* q, float* out, void* workspace, float q
     if (!kv_call_check(d, c, rc)) return rc;
     if (kv_int4(d.storage))
         return launch_bfp_attention_decode_kv4(c.aq, c.ap, c.ak, c.av, c.c4, q, out, workspace, d.M, d.L, c.causal, q_scale, scale_div, c.strides,
-                                               d.splits, hs(stream), d.lengths, c.G);
+                                               d.splits, hs(stream), d.lengths, c.G, c.pages);
     if (kv_int8(d.storage))
         return launch_bfp_attention_decode_kv8(c.aq, c.ap, c.ak, c.av, c.c8, q, out, workspace, d.M, d.L, c.causal, q_scale, scale_div, c.strides,
                                                d.splits, hs(stream), d.lengths, c.G, c.pages);

@@ -107,7 +107,7 @@ int launch_kv_append_ragged(const KvCache& c, const QuantArgs& ak, const QuantAr
                             long long kst, long long vsb, long long vst, const int32_t* lengths, const int32_t* counts, long long n,
                             hipStream_t st, const KvPages* pages = nullptr);
 // the grid of a ragged append of up to n keys a row, from n alone: K blocks (-> kblocks) in front of V blocks, by B rows; more than 2^31
-// - 1 blocks: MI355Q_E_UNSUPPORTED.  launch_kv_append_ragged's and, in mi355q_kv8.hip, launch_kv8_append's
+// - 1 blocks: MI355Q_E_UNSUPPORTED.  launch_kv_append_ragged's and, in mi355q_kvp.hip, the mantissa caches' append's
 int append_ragged_grid(long long B, int D, long long n, int& kblocks, dim3& grid);
 // the staging pass of launch_kv_append_ragged alone (n > 1: the new open tile's fp32 rows, behind the append kernel that read the old
 // ones): for the int8-mantissa cache of mi355q_kv8.h, whose stage is this one.  Reads c.stage, c.B, c.C and c.D only
@@ -155,7 +155,7 @@ int decode_group_width(long long G, long long M);
 // What a decode launch derives from its shapes, for a cache of B rows, capacity C, head_dim D: tile and pair counts of `span` keys (L,
 // or decode_window_span), group width and launch rows (-> rows), splits, pps, q / out strides, the workspace carve-up, the page table.
 // The grid is (g.S, rows).  Pointers to q, out, lengths and K / V, the window and the softmax's scalars stay with the caller.  Returns an
-// error code (group width, more than 65535 rows).  launch_bfp_attention_decode's and, in mi355q_kv8.hip, launch_bfp_attention_decode_kv8's
+// error code (group width, more than 65535 rows).  launch_bfp_attention_decode's and, in mi355q_kvp.hip, the mantissa caches' decode's
 int decode_args_fill(DecodeArgs& g, long long B, long long C, int D, long long M, long long L, long long span, int G, int splits,
                      const long long* strides, void* workspace, const KvPages* pages, long long& rows);
 // lengths != NULL: the ragged form, L = max_length.  G >= 1: the grouped form (q / out hold c.B * G rows, the workspace is that of
@@ -167,7 +167,7 @@ int launch_bfp_attention_decode(const QuantArgs& aq, const QuantArgs& ap, const 
                                 const KvPages* pages = nullptr, long long window = 0);
 
 // phase C alone (nothing to do with one split): the partial outputs of `rows` launch rows summed in split order.  It reads no K / V,
-// so the int8-mantissa decode of mi355q_kv8.hip ends in it too
+// so the mantissa caches' decode of mi355q_kvp.hip ends in it too
 void launch_decode_sum(const DecodeArgs& g, bool grouped, long long rows, hipStream_t st);
 
 }  // namespace mi355q

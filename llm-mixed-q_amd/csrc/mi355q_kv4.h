@@ -1,4 +1,5 @@
-// The 4-bit-mantissa block_fp KV cache (mi355q_kv4.hip): the cache of mi355q_kv8.h for CACHED operands of width <= 4, whose mantissa
+// The 4-bit-mantissa block_fp KV cache (mi355q_kvp.hip, storage NibblePieces): the cache of mi355q_kv8.h for CACHED operands of width <= 4,
+// whose mantissa
 // |m| <= 2^(width - 1) - 1 <= 7 fits a signed nibble: 4 + 1/2 bits a value, 9/32 of the bf16 cache's K and V bytes and decode traffic,
 // 9/17 of the int8-mantissa cache's.  No arithmetic changes: the kernels rebuild the bf16 fragment the MFMA consumes in registers, and
 // every fragment halfword is the int8-mantissa cache's and the bf16 cache's, bit for bit (the one deviation of mi355q_kv8.h carries over).
@@ -25,17 +26,18 @@
 // launch.  THE RULE of mi355q_kv8.h therefore stays: plain byte stores, and NO STORE EVER READS THE CACHE.  Do not widen them into
 // read-modify-write words, and do not re-pair the nibbles.
 //
-// The rebuild: m = the sign-extended 4-bit field at bit 8 (j & 3) + 4 (l & 1) of the lane's word (v_bfe_i32), then kv8_rebuild's
+// The rebuild: m = the sign-extended 4-bit field at bit 8 (j & 3) + 4 (l & 1) of the lane's word (v_bfe_i32), then the int8 rebuild's
 // pack_bf16(ldexpf((float)m, code - exponent_bias - mbits)): the same fp32 value through the same conversion, hence the int8-mantissa
 // cache's halfword.  Widths: |m| <= 7 needs width <= 4 of the CACHED operands (the y side of qk_params and of pv_params); Q and P keep
 // 2 .. 9.  THE ONE DEVIATION of mi355q_kv8.h: 0 < |x| <= 1e-8 is stored as 0.  A stale piece (after reset(), or storage that was not
 // zeroed) pairs stale nibbles with stale or new exponent bytes: any pair of bytes an append wrote rebuilds to a finite value, which is
 // all a slot behind a row's length needs.
 //
-// Kernels: ragged forms only (a device lengths array), contiguous only: no pages, no window, no extend.  The decode kernels are
-// decode8_scores_kernel / decode8_pv_kernel<DC, GQ, false> of mi355q_kv8.hip with another way of getting a fragment into registers; split
-// partition, workspace, Q / P quantisers, softmax, (-inf, 0) paths and the grouped column map are those of mi355q_decode.hip, phase C
-// is its launch_decode_sum unchanged.
+// Kernels: ragged forms only (a device lengths array), contiguous only: no pages, no window, no extend.  They are the kernels of
+// mi355q_kvp.hip -- one body for this storage and the int8 one -- instantiated with NibblePieces and PG = false: only the piece
+// constants, the place of a lane's bytes and nibble, the store and the rebuild are this storage's own; split partition, workspace, Q / P
+// quantisers, softmax, (-inf, 0) paths and the grouped column map are those of mi355q_decode.hip, phase C is its launch_decode_sum
+// unchanged.
 #ifndef MI355Q_KV4_H
 #define MI355Q_KV4_H
 #include <hip/hip_runtime.h>
@@ -59,18 +61,21 @@ struct Kv4Cache {
 inline long long kv4_k_bytes(long long B, long long C, long long D) { return B * (C / 16) * (D / 32) * KV4_PIECE; }
 inline long long kv4_v_bytes(long long B, long long C, long long D) { return B * ((C + 31) / 32) * (D / 16) * KV4_PIECE; }
 
+// The three launchers are mi355q_kvp.hip's templates on the nibble storage, which has no paged kernels: pages != NULL is
+// MI355Q_E_UNSUPPORTED.
 // launch_kv8_append on the nibble storage (ak / av: the quantisers of the cached operands, width <= 4)
 int launch_kv4_append(const Kv4Cache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
                       long long kst, long long vsb, long long vst, const int32_t* lengths, const int32_t* counts, long long n,
-                      hipStream_t st);
+                      hipStream_t st, const KvPages* pages = nullptr);
 // the cache's values, as the decode kernels rebuild them, back as fp32 [B, L, D]; zeros behind row b's lengths[b]
 int launch_kv4_decode_fp32(const Kv4Cache& c, const QuantArgs& ak, const QuantArgs& av, float* k_out, float* v_out, long long L,
-                           const int32_t* lengths, hipStream_t st);
+                           const int32_t* lengths, hipStream_t st, const KvPages* pages = nullptr);
 // launch_bfp_attention_decode_kv8's contiguous forms on the nibble cache: L = max_length, G >= 1 the grouped form, G == 0 one query
 // row a cache row; workspace and splits as there
 int launch_bfp_attention_decode_kv4(const QuantArgs& aq, const QuantArgs& ap, const QuantArgs& ak, const QuantArgs& av, const Kv4Cache& c,
                                     const float* q, float* out, void* workspace, long long M, long long L, int causal, float q_scale,
-                                    float scale_div, const long long* strides, int splits, hipStream_t st, const int32_t* lengths, int G);
+                                    float scale_div, const long long* strides, int splits, hipStream_t st, const int32_t* lengths, int G,
+                                    const KvPages* pages = nullptr);
 
 }  // namespace mi355q
 #endif

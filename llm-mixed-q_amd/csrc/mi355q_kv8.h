@@ -1,4 +1,4 @@
-// The int8-mantissa block_fp KV cache (mi355q_kv8.hip): the cache of mi355q_decode.h with every quantised value stored as what it is
+// The int8-mantissa block_fp KV cache (mi355q_kvp.hip, storage Int8Pieces): the cache of mi355q_decode.h with every quantised value stored as what it is
 // -- a signed mantissa of at most 8 bits and a power of two that the 16 values of its block share -- instead of as bf16: 1 + 1/16
 // bytes a value, 17/32 of the bf16 cache's K and V bytes and decode traffic.  No arithmetic changes: the kernels rebuild the bf16
 // fragment the MFMA consumes in registers, and every fragment halfword is the bf16 cache's, bit for bit (one stated deviation below).
@@ -44,8 +44,8 @@
 // neighbouring threads of the same launch write too (16 keys of a tile share a piece with the other d): byte stores never read, so no
 // thread's store can undo another's -- do not widen them into read-modify-write words.
 //
-// Kernels: ragged forms only (a device lengths array; the Python layer supplies one for the uniform call), no window, no
-// extend.  The decode kernels are the
+// Kernels (mi355q_kvp.hip, instantiated with Int8Pieces; the same bodies serve the nibble storage of mi355q_kv4.h): ragged forms only (a
+// device lengths array; the Python layer supplies one for the uniform call), no window, no extend.  The decode kernels are the
 // RG = true, WN = false kernels of mi355q_decode.hip with another way of getting a K or V fragment into registers; split
 // partition, workspace, Q / P quantisers, softmax, (-inf, 0) paths and the grouped column map are theirs, phase C is theirs unchanged.
 #ifndef MI355Q_KV8_H

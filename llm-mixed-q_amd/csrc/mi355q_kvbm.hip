@@ -5,11 +5,12 @@
 // make of k^T and v, in the block_fp cache's layout (mi355q_decode.h: bf16 halfwords in MFMA fragment order -- the layout does not care
 // which quantiser made them), and a step quantises the new key, the open 16-key tile, Q and P only.
 // What this file owns, in the ragged form only (RG = true; not paged, no window), typed like kv_append_kernel<true, false> and
-// decode_scores_kernel / decode_pv_kernel<DC, true, GQ, false> of mi355q_decode.hip as mi355q_kv8.hip's kernels are: the append with the
+// decode_scores_kernel / decode_pv_kernel<DC, true, GQ, false> of mi355q_decode.hip as mi355q_kvp.hip's kernels are: the append with the
 // block_minifloat store (kvbm_store_block) and phases A and B with the block_minifloat Q and P quantisers (mi355q_attn_dev.h:
-// at_bm_quant_q_frag, at_bm_quant_p_block).  A change to the K walk, the per-tile statistics and their reduction, the zero partial
-// output, the row statistics or the wave reduction is made in all three files: workspace, split partition and the order of every sum
-// are those of mi355q_decode.hip.  What it takes from elsewhere: append_row, append_v_block, the column helpers and dec_stats_empty
+// at_bm_quant_q_frag, at_bm_quant_p_block).  These bodies are twins of mi355q_decode.hip's ragged kernels: a change there to the K
+// walk, the per-tile statistics and their reduction, the zero partial output, the row statistics or the wave reduction is mirrored
+// here once (and once in mi355q_kvp.hip, for both mantissa storages): workspace, split partition and the order of every sum are those
+// of mi355q_decode.hip.  What it takes from elsewhere: append_row, append_v_block, the column helpers and dec_stats_empty
 // (mi355q_decode_dev.h); from mi355q_decode.hip the staging pass (launch_kv_stage_ragged), phase C (launch_decode_sum) and the host
 // arithmetic of both launches (append_ragged_grid, decode_args_fill).
 // Hazards: the two quantisers call __any (the rare table walks), so every lane that reaches them must do so with its wave's other

@@ -796,6 +796,19 @@ class PagedDecodeState(DecodeState):
                                 num_pages=rows * max_pages if self.num_pages is None else self.num_pages)
 
 
+def _refuse_beyond_mantissa_cache(cls, model, mode, extend):
+    """the three refusals every state on a mantissa cache opens with: what no kernel of the storage serves, by the state's name and by
+    what the class calls its storage (STORAGE; a plural where the state chooses among several)"""
+    name, noun = cls.__name__, cls.STORAGE
+    if mode != "block_fp":
+        is_a = "are block_fp caches" if noun.endswith("s") else "is a block_fp cache"
+        raise ValueError(f"{name}: mode {mode!r}: the {noun} {is_a} (mode 'fp32' keeps fp32 K / V)")
+    if extend:
+        raise NotImplementedError(f"{name}: extend=True: no extend (chunked prefill) kernel reads the {noun}")
+    if getattr(model.cfg, "sliding_window", None) is not None:
+        raise NotImplementedError(f"{name}: a sliding-window model: no windowed kernel reads the {noun}")
+
+
 class PackedDecodeState(DecodeState):
     """DecodeState(model, batch, capacity, mode) on ops.PackedKVCache: every layer's K and V as int8 mantissas with one exponent byte
     per block of 16, 17/32 of the cache bytes and of a decode step's K / V traffic.  The numbers are DecodeState's, bit for bit
@@ -803,13 +816,10 @@ class PackedDecodeState(DecodeState):
     here, by name: extend=True (chunked prefill), a sliding-window model, and mode "fp32", which has no quantised cache at all.  A
     prompt runs the prefill attention function on its fp32 K / V, as in DecodeState: it reads no cache."""
 
+    STORAGE = "int8-mantissa cache"
+
     def __init__(self, model, batch: int, capacity: int, mode: str = "block_fp", extend: bool = False):
-        if mode != "block_fp":
-            raise ValueError(f"PackedDecodeState: mode {mode!r}: the int8-mantissa cache is a block_fp cache (mode 'fp32' keeps fp32 K / V)")
-        if extend:
-            raise NotImplementedError("PackedDecodeState: extend=True: no extend (chunked prefill) kernel reads the int8-mantissa cache")
-        if getattr(model.cfg, "sliding_window", None) is not None:
-            raise NotImplementedError("PackedDecodeState: a sliding-window model: no windowed kernel reads the int8-mantissa cache")
+        _refuse_beyond_mantissa_cache(type(self), model, mode, extend)
         super().__init__(model, batch, capacity, mode, extend)
 
     def _new_cache(self, rows, hd, qk, pv, dev):
@@ -826,13 +836,10 @@ class NibbleDecodeState(DecodeState):
     for bit (ops.PackedKVCache names the one exception, inputs of magnitude <= 1e-8).  What the nibble cache has no kernel for is
     refused here, by name: extend=True (chunked prefill), a sliding-window model, and mode "fp32", which has no quantised cache at all."""
 
+    STORAGE = "4-bit-mantissa cache"
+
     def __init__(self, model, batch: int, capacity: int, mode: str = "block_fp", extend: bool = False):
-        if mode != "block_fp":
-            raise ValueError(f"NibbleDecodeState: mode {mode!r}: the 4-bit-mantissa cache is a block_fp cache (mode 'fp32' keeps fp32 K / V)")
-        if extend:
-            raise NotImplementedError("NibbleDecodeState: extend=True: no extend (chunked prefill) kernel reads the 4-bit-mantissa cache")
-        if getattr(model.cfg, "sliding_window", None) is not None:
-            raise NotImplementedError("NibbleDecodeState: a sliding-window model: no windowed kernel reads the 4-bit-mantissa cache")
+        _refuse_beyond_mantissa_cache(type(self), model, mode, extend)
         super().__init__(model, batch, capacity, mode, extend)
 
     def _new_cache(self, rows, hd, qk, pv, dev):
@@ -849,13 +856,10 @@ class NarrowestDecodeState(DecodeState):
     "bf16", one entry per layer.  The three storages give the same bits for the same keys, so the numbers are DecodeState's.
     Contiguous only, and the refusals of the packed states, by name: extend=True, a sliding-window model, mode "fp32"."""
 
+    STORAGE = "mantissa caches"
+
     def __init__(self, model, batch: int, capacity: int, mode: str = "block_fp", extend: bool = False):
-        if mode != "block_fp":
-            raise ValueError(f"NarrowestDecodeState: mode {mode!r}: the mantissa caches are block_fp caches (mode 'fp32' keeps fp32 K / V)")
-        if extend:
-            raise NotImplementedError("NarrowestDecodeState: extend=True: no extend (chunked prefill) kernel reads the mantissa caches")
-        if getattr(model.cfg, "sliding_window", None) is not None:
-            raise NotImplementedError("NarrowestDecodeState: a sliding-window model: no windowed kernel reads the mantissa caches")
+        _refuse_beyond_mantissa_cache(type(self), model, mode, extend)
         self.kinds = []
         super().__init__(model, batch, capacity, mode, extend)
 
@@ -874,16 +878,13 @@ class PagedPackedDecodeState(PagedDecodeState):
     extend=True (chunked prefill), a sliding-window model, and mode "fp32"; a mixed call and a call with more than 16 new tokens behind
     a non-empty row therefore keep raising DecodeState's NotImplementedError."""
 
+    STORAGE = PackedDecodeState.STORAGE
+
     def __init__(self, model, batch: int, capacity: int, mode: str = "block_fp", extend: bool = False, page_size: int = None,
                  num_pages: int = None):
-        if mode != "block_fp":
-            raise ValueError(f"PagedPackedDecodeState: mode {mode!r}: the int8-mantissa cache is a block_fp cache (mode 'fp32' keeps fp32 K / V)")
-        if page_size is None:
+        if mode == "block_fp" and page_size is None:        # (behind the refusal of another mode, in front of the other two)
             raise ValueError("PagedPackedDecodeState: page_size is mandatory (the contiguous int8-mantissa state is PackedDecodeState)")
-        if extend:
-            raise NotImplementedError("PagedPackedDecodeState: extend=True: no extend (chunked prefill) kernel reads the int8-mantissa cache")
-        if getattr(model.cfg, "sliding_window", None) is not None:
-            raise NotImplementedError("PagedPackedDecodeState: a sliding-window model: no windowed kernel reads the int8-mantissa cache")
+        _refuse_beyond_mantissa_cache(type(self), model, mode, extend)
         super().__init__(model, batch, capacity, mode, extend, page_size, num_pages)
 
     def _new_cache(self, rows, hd, qk, pv, dev):
@@ -942,8 +943,8 @@ def _forward_cached(model, input_ids, labels, state: DecodeState, counts=None):
 
 
 # generate's kv_storage: the state class and what its refusals call the storage
-_KV_STORAGES = {"int8": (PackedDecodeState, "int8-mantissa cache"), "nibble": (NibbleDecodeState, "4-bit-mantissa cache"),
-                "narrowest": (NarrowestDecodeState, "per-layer choice of mantissa caches")}
+_KV_STORAGES = {"int8": (PackedDecodeState, PackedDecodeState.STORAGE), "nibble": (NibbleDecodeState, NibbleDecodeState.STORAGE),
+                "narrowest": (NarrowestDecodeState, "per-layer choice of " + NarrowestDecodeState.STORAGE)}
 
 
 def _new_state(model, batch, capacity, mode, extend, page_size, num_pages, kv_storage=None):

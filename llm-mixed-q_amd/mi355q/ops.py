@@ -1500,10 +1500,12 @@ def _kv_call(device, export, args):
 
 
 class _KVCacheBase:
-    """What KVCache, PagedKVCache, PackedKVCache, NibbleKVCache and PagedPackedKVCache share: the constructor's checks, the quantiser parameter words (`_pa`, `_pb`), the
-    zeroed storage, and the checks of append / dequantised.  A subclass adds its storage's names, its exports' arguments and -- the paged
-    one -- its allocator.  Messages carry the subclass's name."""
+    """What KVCache, PagedKVCache, PackedKVCache, NibbleKVCache, MinifloatKVCache and PagedPackedKVCache share: the constructor's checks,
+    the quantiser parameter words (`_pa`, `_pb`), the zeroed storage, the checks of append / dequantised, the width check of a mantissa
+    storage and the append of the caches whose kernels are ragged only.  A subclass adds its storage's names (STORAGE), its exports'
+    arguments and -- the paged one -- its allocator.  Messages carry the subclass's name."""
     RAGGED_ONLY = False         # PagedKVCache: lengths= is mandatory
+    STORAGE = ("kq", "vq")      # the attributes that hold K and V, as the exports take them
 
     def _init_rows(self, B, D, qk_params, pv_params, device, capacity=None):
         import ctypes
@@ -1558,6 +1560,27 @@ class _KVCacheBase:
         k3, ksb, kst = _as_heads_view(k)
         v3, vsb, vst = _as_heads_view(v)
         return k3, v3, n, (ctypes.c_int64 * 4)(ksb, kst, vsb, vst)
+
+    def _check_cached_width(self):
+        """a mantissa storage (WIDTH: the widest cached operand it holds, FITS: what the message calls its field and who takes more)"""
+        for name, p in (("qk_params (K)", self.qk_params), ("pv_params (V)", self.pv_params)):
+            if int(p[3]) > self.WIDTH:
+                raise ValueError(f"{type(self).__name__} {name}: cached operand of width {p[3]} > {self.WIDTH}: its mantissa, up to "
+                                 f"2^{int(p[3]) - 1} - 1 in magnitude, does not fit {self.FITS}")
+
+    def _append_by_lengths(self, export, k, v, lengths, counts, max_length):
+        """append through an export that exists in the ragged form only: the uniform call brings every row's `length` as a device tensor"""
+        import ctypes
+        k3, v3, n, strides = self._append_args(k, v, lengths, counts, max_length)
+        ragged = lengths is not None
+        if not ragged:      # (the kernels read lengths from the device: every row at `length`)
+            lengths, max_length = _window_lengths(self, None, None)
+        _kv_call(self.device, export, (
+            *(_ptr(getattr(self, name)) for name in self.STORAGE), _ptr(self.stage), _ptr(k3), _ptr(v3), _ptr(lengths), _ptr(counts), self.B,
+            self.capacity, self.D, n, int(max_length), ctypes.addressof(self._pa), ctypes.addressof(self._pb), ctypes.addressof(strides),
+            _stream_ptr(self.device)))
+        if not ragged:
+            self.length += n
 
     def _dequantised_out(self, lengths, max_length):
         """dequantised's checks -> the empty fp32 outputs k, v [B, max_length (uniform: length), D]"""
@@ -1633,7 +1656,7 @@ class _PagedHost(_KVCacheBase):
     constructor between `_init_pages` and `_init_table`, and adds append / dequantised.  Messages carry the subclass's name."""
 
     RAGGED_ONLY = True
-    POOLS = ("kq", "vq")
+    POOLS = _KVCacheBase.STORAGE
     COPY_EXPORT = "mi355q_bfp_kv_paged_copy"
 
     def _init_pages(self, B, D, qk_params, pv_params, device, page_size, num_pages, max_pages, pad_page):
@@ -1935,7 +1958,45 @@ class PagedKVCache(_PagedHost):
         return k, v
 
 
-class PackedKVCache(_KVCacheBase):
+class _MantissaKVCache(_KVCacheBase):
+    """PackedKVCache and NibbleKVCache, all but their names: a contiguous cache of mantissas and shared-exponent bytes.  A subclass says
+    how wide a cached operand may be (WIDTH) and what the refusal calls the field it must fit (FITS), names its storage attributes
+    (STORAGE) and its exports (EXPORT: the prefix of _cache_bytes / _append / _decode_fp32)."""
+    WIDTH = FITS = EXPORT = None
+
+    def __init__(self, B: int, capacity: int, D: int, qk_params, pv_params, device):
+        self._init_rows(int(B), int(D), qk_params, pv_params, device, int(capacity))
+        self._check_cached_width()
+        self.capacity, self.length = int(capacity), 0
+        # (zeroed: a V slot no key has reached is mantissa 0, a finite 0 under any exponent byte, for the probability of exactly 0 it meets)
+        k, v, self.stage = self._zeroed(self.EXPORT + "_cache_bytes", self.B, self.capacity, self.D)
+        setattr(self, self.STORAGE[0], k)
+        setattr(self, self.STORAGE[1], v)
+
+    def reset(self) -> None:
+        # nothing to clear, as in KVCache.reset: stale mantissas and exponent bytes rebuild to finite values
+        self.length = 0
+
+    def append(self, k: torch.Tensor, v: torch.Tensor, *, lengths: torch.Tensor = None, counts: torch.Tensor = None,
+               max_length: int = None) -> None:
+        """KVCache.append on the mantissa storage: n >= 1 new fp32 rows k, v [B, n, D] (or [1, H, n, D] head views) become keys
+        length .. length + n - 1, or -- ragged -- row b's first counts[b] rows become its keys lengths[b] .. (lengths BEFORE the call)."""
+        self._append_by_lengths(self.EXPORT + "_append", k, v, lengths, counts, max_length)
+
+    def dequantised(self, lengths: torch.Tensor = None, max_length: int = None):
+        """the cache's K and V as the decode kernels rebuild them, fp32 [B, length, D] (tests, debugging); ragged: [B, max_length, D],
+        zeros behind each row's lengths[b]"""
+        import ctypes
+        k, v = self._dequantised_out(lengths, max_length)
+        if lengths is None:
+            lengths, max_length = _window_lengths(self, None, None)
+        _kv_call(self.device, self.EXPORT + "_decode_fp32", (
+            *(_ptr(getattr(self, name)) for name in self.STORAGE), _ptr(lengths), _ptr(k), _ptr(v), self.B, self.capacity, self.D,
+            int(max_length), ctypes.addressof(self._pa), ctypes.addressof(self._pb), _stream_ptr(self.device)))
+        return k, v
+
+
+class PackedKVCache(_MantissaKVCache):
     """`KVCache` with every quantised value stored as what it is -- a signed mantissa byte, and one shared-exponent byte per block of
     16 -- instead of as bf16: 1 + 1/16 bytes a value, 17/32 of KVCache's K and V bytes and of a decode step's K / V traffic (layout:
     csrc/mi355q_kv8.h).  Same constructor arguments and the same append / reset / dequantised / length / lengths= / counts= /
@@ -1947,49 +2008,11 @@ class PackedKVCache(_KVCacheBase):
     Q and P (the x sides), which are not stored, keep 2 .. 9.  The kernels exist in the ragged form only: a call without `lengths`
     brings every row's `length` as a device tensor."""
 
-    def __init__(self, B: int, capacity: int, D: int, qk_params, pv_params, device):
-        self._init_rows(int(B), int(D), qk_params, pv_params, device, int(capacity))
-        for name, p in (("qk_params (K)", self.qk_params), ("pv_params (V)", self.pv_params)):
-            if int(p[3]) > 8:
-                raise ValueError(f"PackedKVCache {name}: cached operand of width {p[3]} > 8: its mantissa, up to 2^{int(p[3]) - 1} - 1 in "
-                                 "magnitude, does not fit the int8 the cache stores (KVCache takes width 9)")
-        self.capacity, self.length = int(capacity), 0
-        # (zeroed: a V slot no key has reached is mantissa 0, a finite 0 under any exponent byte, for the probability of exactly 0 it meets)
-        self.k8, self.v8, self.stage = self._zeroed("mi355q_bfp_kv8_cache_bytes", self.B, self.capacity, self.D)
-
-    def reset(self) -> None:
-        # nothing to clear, as in KVCache.reset: stale mantissa and exponent bytes rebuild to finite values
-        self.length = 0
-
-    def append(self, k: torch.Tensor, v: torch.Tensor, *, lengths: torch.Tensor = None, counts: torch.Tensor = None,
-               max_length: int = None) -> None:
-        """KVCache.append on the packed storage: n >= 1 new fp32 rows k, v [B, n, D] (or [1, H, n, D] head views) become keys
-        length .. length + n - 1, or -- ragged -- row b's first counts[b] rows become its keys lengths[b] .. (lengths BEFORE the call)."""
-        import ctypes
-        k3, v3, n, strides = self._append_args(k, v, lengths, counts, max_length)
-        ragged = lengths is not None
-        if not ragged:      # (the kernels read lengths from the device: every row at `length`)
-            lengths, max_length = _window_lengths(self, None, None)
-        _kv_call(self.device, "mi355q_bfp_kv8_append", (
-            _ptr(self.k8), _ptr(self.v8), _ptr(self.stage), _ptr(k3), _ptr(v3), _ptr(lengths), _ptr(counts), self.B, self.capacity, self.D, n,
-            int(max_length), ctypes.addressof(self._pa), ctypes.addressof(self._pb), ctypes.addressof(strides), _stream_ptr(self.device)))
-        if not ragged:
-            self.length += n
-
-    def dequantised(self, lengths: torch.Tensor = None, max_length: int = None):
-        """the cache's K and V as the decode kernels rebuild them, fp32 [B, length, D] (tests, debugging); ragged: [B, max_length, D],
-        zeros behind each row's lengths[b]"""
-        import ctypes
-        k, v = self._dequantised_out(lengths, max_length)
-        if lengths is None:
-            lengths, max_length = _window_lengths(self, None, None)
-        _kv_call(self.device, "mi355q_bfp_kv8_decode_fp32", (
-            _ptr(self.k8), _ptr(self.v8), _ptr(lengths), _ptr(k), _ptr(v), self.B, self.capacity, self.D, int(max_length),
-            ctypes.addressof(self._pa), ctypes.addressof(self._pb), _stream_ptr(self.device)))
-        return k, v
+    WIDTH, FITS = 8, "the int8 the cache stores (KVCache takes width 9)"
+    STORAGE, EXPORT = ("k8", "v8"), "mi355q_bfp_kv8"
 
 
-class NibbleKVCache(_KVCacheBase):
+class NibbleKVCache(_MantissaKVCache):
     """`PackedKVCache` for layers whose CACHED operands -- the y side of qk_params and of pv_params -- have width <= 4: the mantissa,
     |m| <= 7, is a signed nibble, two to a byte, with one shared-exponent byte per block of 16 -- 4 + 1/2 bits a value, 9/32 of KVCache's
     K and V bytes and of a decode step's K / V traffic, 9/17 of PackedKVCache's (layout: csrc/mi355q_kv4.h; the two nibbles of a byte
@@ -2001,46 +2024,8 @@ class NibbleKVCache(_KVCacheBase):
     as 0.  Q and P (the x sides), which are not stored, keep 2 .. 9.  The kernels exist in the ragged form only: a call without
     `lengths` brings every row's `length` as a device tensor."""
 
-    def __init__(self, B: int, capacity: int, D: int, qk_params, pv_params, device):
-        self._init_rows(int(B), int(D), qk_params, pv_params, device, int(capacity))
-        for name, p in (("qk_params (K)", self.qk_params), ("pv_params (V)", self.pv_params)):
-            if int(p[3]) > 4:
-                raise ValueError(f"NibbleKVCache {name}: cached operand of width {p[3]} > 4: its mantissa, up to 2^{int(p[3]) - 1} - 1 in "
-                                 "magnitude, does not fit the 4 bits the cache stores (PackedKVCache takes width 8, KVCache width 9)")
-        self.capacity, self.length = int(capacity), 0
-        # (zeroed: a V slot no key has reached is mantissa 0, a finite 0 under any exponent byte, for the probability of exactly 0 it meets)
-        self.k4, self.v4, self.stage = self._zeroed("mi355q_bfp_kv4_cache_bytes", self.B, self.capacity, self.D)
-
-    def reset(self) -> None:
-        # nothing to clear, as in KVCache.reset: stale mantissa nibbles and exponent bytes rebuild to finite values
-        self.length = 0
-
-    def append(self, k: torch.Tensor, v: torch.Tensor, *, lengths: torch.Tensor = None, counts: torch.Tensor = None,
-               max_length: int = None) -> None:
-        """KVCache.append on the nibble storage: n >= 1 new fp32 rows k, v [B, n, D] (or [1, H, n, D] head views) become keys
-        length .. length + n - 1, or -- ragged -- row b's first counts[b] rows become its keys lengths[b] .. (lengths BEFORE the call)."""
-        import ctypes
-        k3, v3, n, strides = self._append_args(k, v, lengths, counts, max_length)
-        ragged = lengths is not None
-        if not ragged:      # (the kernels read lengths from the device: every row at `length`)
-            lengths, max_length = _window_lengths(self, None, None)
-        _kv_call(self.device, "mi355q_bfp_kv4_append", (
-            _ptr(self.k4), _ptr(self.v4), _ptr(self.stage), _ptr(k3), _ptr(v3), _ptr(lengths), _ptr(counts), self.B, self.capacity, self.D, n,
-            int(max_length), ctypes.addressof(self._pa), ctypes.addressof(self._pb), ctypes.addressof(strides), _stream_ptr(self.device)))
-        if not ragged:
-            self.length += n
-
-    def dequantised(self, lengths: torch.Tensor = None, max_length: int = None):
-        """the cache's K and V as the decode kernels rebuild them, fp32 [B, length, D] (tests, debugging); ragged: [B, max_length, D],
-        zeros behind each row's lengths[b]"""
-        import ctypes
-        k, v = self._dequantised_out(lengths, max_length)
-        if lengths is None:
-            lengths, max_length = _window_lengths(self, None, None)
-        _kv_call(self.device, "mi355q_bfp_kv4_decode_fp32", (
-            _ptr(self.k4), _ptr(self.v4), _ptr(lengths), _ptr(k), _ptr(v), self.B, self.capacity, self.D, int(max_length),
-            ctypes.addressof(self._pa), ctypes.addressof(self._pb), _stream_ptr(self.device)))
-        return k, v
+    WIDTH, FITS = 4, "the 4 bits the cache stores (PackedKVCache takes width 8, KVCache width 9)"
+    STORAGE, EXPORT = ("k4", "v4"), "mi355q_bfp_kv4"
 
 
 def _minifloat_params(params, what):
@@ -2089,16 +2074,7 @@ class MinifloatKVCache(_KVCacheBase):
                max_length: int = None) -> None:
         """KVCache.append under the block_minifloat quantisers: n >= 1 new fp32 rows k, v [B, n, D] (or [1, H, n, D] head views) become
         keys length .. length + n - 1, or -- ragged -- row b's first counts[b] rows become its keys lengths[b] .. (lengths BEFORE the call)."""
-        import ctypes
-        k3, v3, n, strides = self._append_args(k, v, lengths, counts, max_length)
-        ragged = lengths is not None
-        if not ragged:      # (the kernels read lengths from the device: every row at `length`)
-            lengths, max_length = _window_lengths(self, None, None)
-        _kv_call(self.device, "mi355q_bm_kv_append", (
-            _ptr(self.kq), _ptr(self.vq), _ptr(self.stage), _ptr(k3), _ptr(v3), _ptr(lengths), _ptr(counts), self.B, self.capacity, self.D, n,
-            int(max_length), ctypes.addressof(self._pa), ctypes.addressof(self._pb), ctypes.addressof(strides), _stream_ptr(self.device)))
-        if not ragged:
-            self.length += n
+        self._append_by_lengths("mi355q_bm_kv_append", k, v, lengths, counts, max_length)
 
     def dequantised(self, lengths: torch.Tensor = None, max_length: int = None):
         """the cache's quantised K and V as fp32 [B, length, D] (tests, debugging); ragged: [B, max_length, D], zeros behind each
@@ -2140,15 +2116,13 @@ class PagedPackedKVCache(_PagedHost):
     There is no extend kernel and no sliding window on this storage: `trim`, `window=` and bfp_attention_extend raise
     NotImplementedError."""
 
-    POOLS = ("k8", "v8")
+    STORAGE = POOLS = PackedKVCache.STORAGE
     COPY_EXPORT = "mi355q_bfp_kv8_paged_copy"
+    WIDTH, FITS = 8, "the int8 the cache stores (PagedKVCache takes width 9)"
 
     def __init__(self, B: int, D: int, qk_params, pv_params, device, *, page_size: int, num_pages: int, max_pages: int, pad_page: int = None):
         self._init_pages(B, D, qk_params, pv_params, device, page_size, num_pages, max_pages, pad_page)
-        for name, p in (("qk_params (K)", self.qk_params), ("pv_params (V)", self.pv_params)):
-            if int(p[3]) > 8:
-                raise ValueError(f"PagedPackedKVCache {name}: cached operand of width {p[3]} > 8: its mantissa, up to 2^{int(p[3]) - 1} - 1 in "
-                                 "magnitude, does not fit the int8 the cache stores (PagedKVCache takes width 9)")
+        self._check_cached_width()
         self.k8, self.v8, self.stage = self._zeroed("mi355q_bfp_kv8_paged_bytes", self.num_pages, self.page_size, self.B, self.D)
         self._init_table(pad_page)
 
@@ -2309,7 +2283,7 @@ def _cached_attention(op, q, cache, causal, scale_div, q_scale, token_major, spl
     else:
         capacity = (cache.capacity,)
     _kv_call(q.device, "mi355q_bm_attention_decode" if minifloat else f"mi355q_bfp_attention_{op}{form}", (
-        _ptr(q3), *((_ptr(cache.k8), _ptr(cache.v8)) if packed else (_ptr(cache.k4), _ptr(cache.v4)) if nibble else (_ptr(cache.kq), _ptr(cache.vq))), *which,
+        _ptr(q3), *(_ptr(getattr(cache, name)) for name in cache.STORAGE), *which,
         *((1, int(window)) if windowed else (int(bool(causal)),)), float(q_scale) if q_scale else 0.0, float(scale_div) if scale_div else 0.0,
         _ptr(out), *((_ptr(_decode_workspace(q, cache, M, D, group, sp)),) if decode else ()), cache.B, M, L, *capacity, D,
         ctypes.addressof(cache._pa), ctypes.addressof(cache._pb), ctypes.addressof(strides), *((int(splits or 0),) if decode else ()), sp))

@@ -2,14 +2,17 @@
 instantiations whose new parameter has the value that must leave the device code alone -- and the new build's other instantiations
 against those twins.
 
-    python tools/isa/kernel_twins.py <old dir> <new dir> <suffix> [> profiles/....txt]
+    python tools/isa/kernel_twins.py <old dir> <new dir> <suffix> [--rename <regex> <replacement>]... [> profiles/....txt]
 
 <suffix> is what the twin's demangled template argument list ends with behind the old one's, e.g. ", false" (decode_scores_kernel<1,
-true> -> decode_scores_kernel<1, true, false>; a kernel that was no template, f -> f<false>).  Per pair: the figures of kernel_table.py
+true> -> decode_scores_kernel<1, true, false>; a kernel that was no template, f -> f<false>).  --rename pairs an old kernel with a
+RENAMED one: every pair is applied (re.sub) to the old kernel's demangled name in front of the suffix rule ("" for none), and an old
+file that has no file of its name in the new build is held against the kernels of all the new build's files.  Per pair: the figures of kernel_table.py
 plus the SGPR count and whether the instruction streams are the same text.  Exit status 1 if a twin is missing or differs in VGPRs,
 SGPRs, spills, scratch, LDS, MFMA or LDS-DMA counts."""
 from __future__ import annotations
 
+import re
 import sys
 from pathlib import Path
 
@@ -29,10 +32,15 @@ def twin_of(old_name: str, suffix: str) -> str:
 
 def main() -> int:
     old_dir, new_dir, suffix = Path(sys.argv[1]), Path(sys.argv[2]), sys.argv[3]
+    renames = [(sys.argv[i + 1], sys.argv[i + 2]) for i, a in enumerate(sys.argv) if a == "--rename"]
     bad = 0
     for old_s in sorted(old_dir.glob("*.s")):
-        new_s = new_dir / old_s.name
-        old, new = parse(old_s), parse(new_s)
+        new_files = [new_dir / old_s.name] if (new_dir / old_s.name).exists() else sorted(new_dir.glob("*.s"))
+        old, new, where = parse(old_s), {}, {}
+        for f in new_files:
+            rows = parse(f)
+            new.update(rows)
+            where.update(dict.fromkeys(rows, f))
         on, nn = demangle(sorted(old)), demangle(sorted(new))
         by_name = {d: m for m, d in nn.items()}
         for rows in (old, new):
@@ -42,7 +50,10 @@ def main() -> int:
         print("  ".join(f"{s:>9}" for s in SHORT) + "  same text  kernel")
         twins = set()
         for m in sorted(old, key=on.get):
-            t = by_name.get(twin_of(on[m], suffix)) or by_name.get(on[m])          # (a kernel the change did not touch keeps its name)
+            name = on[m]
+            for pattern, repl in renames:
+                name = re.sub(pattern, repl, name)
+            t = (by_name.get(twin_of(name, suffix)) if suffix else None) or by_name.get(name)      # (a kernel the change did not touch keeps its name)
             if t is None:
                 print(f"NO TWIN  {on[m]}")
                 bad += 1
@@ -51,7 +62,7 @@ def main() -> int:
             o, w = old[m], new[t]
             fail = any(o[k] != w[k] for k in MUST)
             bad += fail
-            same = body(old_s, m) == body(new_s, t)
+            same = body(old_s, m) == body(where[t], t)
             print("  ".join(f"{str(o[c]) + '/' + str(w[c]):>9}" for c in COLS) + f"  {'yes' if same else 'no':>9}  {nn[t]}" + ("   <-- FAIL" if fail else ""))
         print("-- new instantiations")
         print("  ".join(f"{s:>9}" for s in SHORT) + "  kernel")

@@ -3,8 +3,8 @@
 block_fp KV cache, in the method of tools/time_decode_minifloat.py: D = 128, 8 KV heads, width 4, batch 1 / 8 / 32 (rows = batch x 8),
 L = 512 / 2048 / 8192 keys.
 
-    nibble      ops.NibbleKVCache (csrc/mi355q_kv4.hip): 9/32 of the bf16 cache's K / V bytes
-    int8        ops.PackedKVCache (csrc/mi355q_kv8.hip): 17/32
+    nibble      ops.NibbleKVCache (csrc/mi355q_kvp.hip, NibblePieces): 9/32 of the bf16 cache's K / V bytes
+    int8        ops.PackedKVCache (csrc/mi355q_kvp.hip, Int8Pieces): 17/32
     bf16        ops.KVCache (csrc/mi355q_decode.hip)
 
 The three outputs of the first step are compared as bits first.  Per case the step runs over distinct caches -- as many as make one
