@@ -741,7 +741,7 @@ int mi355q_bfp_kv_paged_copy(void* kq_pool, void* vq_pool, const float* stage_sr
 
 /* Int8-mantissa cache: the contiguous cache above with every quantised value stored as a signed mantissa BYTE plus one shared-exponent
  * byte per 16-value block -- 1 + 1/16 bytes a value, exactly 17/32 of mi355q_bfp_kv_cache_bytes' K and V bytes (the stage is the
- * same) and of a decode step's K / V traffic.  Layout: csrc/mi355q_kv8.h.  The kernels rebuild the bf16 MFMA fragments in registers,
+ * same) and of a decode step's K / V traffic.  Layout: csrc/mi355q_kvp.h.  The kernels rebuild the bf16 MFMA fragments in registers,
  * pack_bf16(ldexp(mantissa, exponent - mantissa bits)), which is the halfword the bf16 cache stores: append, decode_fp32 and decode
  * give the bits of their *_ragged / *_grouped counterparts on a bf16 cache holding the same keys (decode: with the same number of
  * splits), with ONE exception: an input 0 < |x| <= 1e-8, which the bf16 cache passes through unquantised, is stored as 0.
@@ -762,7 +762,7 @@ int mi355q_bfp_attention_decode_kv8(const float* q, const void* k8, const void* 
                                     const int64_t* strides, int32_t splits, void* stream);
 
 /* Int8-mantissa cache in PAGES: the pools of the paged cache above, in the same page order, holding the 544-byte pieces of the int8-mantissa
- * cache (csrc/mi355q_kv8.h):  k8_pool [num_pages][P / 16][D / 32][544],  v8_pool [num_pages][P / 32][D / 16][544]  -- a page of either pool
+ * cache (csrc/mi355q_kvp.h):  k8_pool [num_pages][P / 16][D / 32][544],  v8_pool [num_pages][P / 32][D / 16][544]  -- a page of either pool
  * is P * D * 17 / 16 bytes (mi355q_bfp_kv8_paged_bytes; exactly 17/32 of mi355q_bfp_kv_paged_bytes' K and V bytes), stage stays
  * [B][16][D] fp32 per row, block_table is the paged cache's int32 [B][max_pages].  Only a piece's place goes through the table, page ids
  * are clamped into 0 .. num_pages - 1 (a wrong table gives wrong numbers, never an address outside the pools), and only logical pages
@@ -790,7 +790,7 @@ int mi355q_bfp_kv8_paged_copy(void* k8_pool, void* v8_pool, const float* stage_s
 
 /* 4-bit-mantissa cache: the contiguous int8-mantissa cache above for CACHED operands of width <= 4, whose mantissa |m| <= 7 is a signed
  * NIBBLE, two to a byte, plus one shared-exponent byte per 16-value block -- 4 + 1/2 bits a value, exactly 9/32 of
- * mi355q_bfp_kv_cache_bytes' K and V bytes and 9/17 of mi355q_bfp_kv8_cache_bytes' (the stage is the same).  Layout: csrc/mi355q_kv4.h
+ * mi355q_bfp_kv_cache_bytes' K and V bytes and 9/17 of mi355q_bfp_kv8_cache_bytes' (the stage is the same).  Layout: csrc/mi355q_kvp.h
  * -- pieces of 288 bytes, k4 [B][C / 16][D / 32][288], v4 [B][ceil(C / 32)][D / 16][288]; the two nibbles of a byte are two values of ONE
  * block, so the append stores whole bytes and never reads the cache.  The kernels rebuild the bf16 MFMA fragments in registers from the
  * same integer and the same exponent through the same conversion: append, decode_fp32 and decode give the bits of the kv8 calls, and so

@@ -13,8 +13,7 @@
 #include "mi355q_internal.h"
 #include "mi355q_gemv.h"
 #include "mi355q_decode.h"
-#include "mi355q_kv8.h"
-#include "mi355q_kv4.h"
+#include "mi355q_kvp.h"
 #include "mi355q_extend.h"
 #include "mi355q_linear_call.h"
 #include "mi355q_kv_call.h"
@@ -857,7 +856,7 @@ int mi355q_bfp_attention_fused(const float* q, const float* k, const float* v, c
                                 out_bf16_tiled ? &ao : nullptr, q_scale);
 }
 
-// ---- the KV cache and the attention that reads it (mi355q_decode.h, mi355q_extend.h, mi355q_kv8.h, mi355q_kv4.h) ---------------
+// ---- the KV cache and the attention that reads it (mi355q_decode.h, mi355q_extend.h, mi355q_kvp.h, mi355q_kvbm.h) --------------
 // Every export below fills a KvCall, has kv_call_check (mi355q_kv_call.h) refuse it or fill what the launchers take, and launches.
 // Uniform, ragged (per-row lengths on the device), grouped (G query rows a cache row), paged (pools of pages and a page table per row),
 // int8 mantissas (kv8) and the sliding window differ in the KV_EXPORTS entry they start from and in the arguments they have.
@@ -868,8 +867,9 @@ int sizes(const KvCall& d, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_by
     int rc;
     if (!kv_call_check(d, c, rc)) return rc;
     const int64_t rows = kv_paged(d.storage) ? d.num_pages : d.B, keys = kv_paged(d.storage) ? d.P : d.C;      // (a page is a cache row of P keys)
-    *k_bytes = kv_int4(d.storage) ? kv4_k_bytes(rows, keys, d.D) : kv_int8(d.storage) ? kv8_k_bytes(rows, keys, d.D) : kv_k_bytes(rows, keys, d.D);
-    *v_bytes = kv_int4(d.storage) ? kv4_v_bytes(rows, keys, d.D) : kv_int8(d.storage) ? kv8_v_bytes(rows, keys, d.D) : kv_v_bytes(rows, keys, d.D);
+    const KvMantissa m = kv_mantissa(d.storage);
+    *k_bytes = kv_mantissas(d.storage) ? kvp_k_bytes(m, rows, keys, d.D) : kv_k_bytes(rows, keys, d.D);
+    *v_bytes = kv_mantissas(d.storage) ? kvp_v_bytes(m, rows, keys, d.D) : kv_v_bytes(rows, keys, d.D);
     *stage_bytes = kv_stage_bytes(d.B, d.D);
     return 0;
 }
@@ -877,10 +877,8 @@ int append(const KvCall& d, const float* k, const float* v, void* stream) {
     KvChecked c;
     int rc;
     if (!kv_call_check(d, c, rc)) return rc;
-    if (kv_int4(d.storage))
-        return launch_kv4_append(c.c4, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.lengths, d.counts, d.n, hs(stream), c.pages);
-    if (kv_int8(d.storage))
-        return launch_kv8_append(c.c8, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.lengths, d.counts, d.n, hs(stream), c.pages);
+    if (kv_mantissas(d.storage))
+        return launch_kvp_append(kv_mantissa(d.storage), c.cp, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.lengths, d.counts, d.n, hs(stream), c.pages);
     if (d.form & KV_MINIFLOAT)
         return launch_kvbm_append(c.c, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.lengths, d.counts, d.n, hs(stream));
     if (!(d.form & KV_LENGTHS)) return launch_kv_append(c.c, c.ak, c.av, k, v, c.st[0], c.st[1], c.st[2], c.st[3], d.L, d.n, hs(stream));
@@ -890,20 +888,17 @@ int dequantise(const KvCall& d, float* k_out, float* v_out, void* stream) {
     KvChecked c;
     int rc;
     if (!kv_call_check(d, c, rc)) return rc;
-    if (kv_int4(d.storage)) return launch_kv4_decode_fp32(c.c4, c.ak, c.av, k_out, v_out, d.L, d.lengths, hs(stream), c.pages);
-    if (kv_int8(d.storage)) return launch_kv8_decode_fp32(c.c8, c.ak, c.av, k_out, v_out, d.L, d.lengths, hs(stream), c.pages);
+    if (kv_mantissas(d.storage))
+        return launch_kvp_decode_fp32(kv_mantissa(d.storage), c.cp, c.ak, c.av, k_out, v_out, d.L, d.lengths, hs(stream), c.pages);
     return launch_kv_decode_fp32(c.c, k_out, v_out, d.L, hs(stream), d.lengths, c.pages);
 }
 int decode(const KvCall& d, const float* q, float* out, void* workspace, float q_scale, float scale_div, void* stream) {
     KvChecked c;
     int rc;
     if (!kv_call_check(d, c, rc)) return rc;
-    if (kv_int4(d.storage))
-        return launch_bfp_attention_decode_kv4(c.aq, c.ap, c.ak, c.av, c.c4, q, out, workspace, d.M, d.L, c.causal, q_scale, scale_div, c.strides,
-                                               d.splits, hs(stream), d.lengths, c.G, c.pages);
-    if (kv_int8(d.storage))
-        return launch_bfp_attention_decode_kv8(c.aq, c.ap, c.ak, c.av, c.c8, q, out, workspace, d.M, d.L, c.causal, q_scale, scale_div, c.strides,
-                                               d.splits, hs(stream), d.lengths, c.G, c.pages);
+    if (kv_mantissas(d.storage))
+        return launch_bfp_attention_decode_kvp(kv_mantissa(d.storage), c.aq, c.ap, c.ak, c.av, c.cp, q, out, workspace, d.M, d.L, c.causal, q_scale,
+                                               scale_div, c.strides, d.splits, hs(stream), d.lengths, c.G, c.pages);
     if (d.form & KV_MINIFLOAT)
         return launch_bm_attention_decode(c.aq, c.ap, c.c, q, out, workspace, d.M, d.L, c.causal, q_scale, scale_div, c.strides, d.splits, hs(stream),
                                           d.lengths, c.G);
@@ -1119,7 +1114,7 @@ int mi355q_bfp_kv8_paged_copy(void* k8_pool, void* v8_pool, const float* stage_s
     return launch_kv_paged_copy(g, stream);
 }
 
-// 4-bit-mantissa cache: two mantissa nibbles a byte and one exponent byte a block (mi355q_kv4.h); always the ragged form, contiguous
+// 4-bit-mantissa cache: two mantissa nibbles a byte and one exponent byte a block (mi355q_kvp.h); always the ragged form, contiguous
 int mi355q_bfp_kv4_cache_bytes(int64_t B, int64_t C, int64_t D, int64_t* k_bytes, int64_t* v_bytes, int64_t* stage_bytes) {
     return sizes(KvCall(KV_EXPORTS[KVX_KV4_CACHE_BYTES]).cache(nullptr, nullptr, nullptr, B, C, D).sizes(k_bytes, v_bytes, stage_bytes), k_bytes, v_bytes,
                  stage_bytes);
@@ -1215,7 +1210,7 @@ static int debug_kv_call(int32_t id, int32_t ids, const int64_t a[27], const int
     KvChecked c;
     int rc;
     const bool go = kv_call_check(d, c, rc);
-    const int64_t cap = kv_int4(d.storage) ? c.c4.C : kv_int8(d.storage) ? c.c8.C : c.c.C;
+    const int64_t cap = kv_mantissas(d.storage) ? c.cp.C : c.c.C;
     const int64_t words[18] = {rc, go, d.B, cap, d.D, d.M, d.L, d.n, c.G, c.window, c.pg.lg_p, c.pages != nullptr, c.causal, c.strides != nullptr,
                                c.st[0], c.st[1], c.st[2], c.st[3]};
     for (int i = 0; i < 18; ++i) out[i] = words[i];

@@ -27,7 +27,7 @@ __device__ __forceinline__ float at_quant(float x, int up, int down, float mant_
     return fabsf(x) <= ATOL ? x : q;
 }
 // the signed integer mantissa at_quant scales back down -- at_quant(x) = ldexp(at_quant_mant(x), down) for |x| > 1e-8 -- and 0 where
-// at_quant passes x through (|x| <= 1e-8): what a cache of mantissas and block exponents stores (mi355q_kv8.h)
+// at_quant passes x through (|x| <= 1e-8): what a cache of mantissas and block exponents stores (mi355q_kvp.h)
 __device__ __forceinline__ float at_quant_mant(float x, int up, float mant_max) {
     const float m = fminf(__builtin_rintf(__builtin_ldexpf(fabsf(x) + EPS9, up)), mant_max);
     return fabsf(x) <= ATOL ? 0.f : __builtin_copysignf(m, x);

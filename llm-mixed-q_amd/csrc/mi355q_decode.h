@@ -16,7 +16,7 @@
 // Values are those of attn_pack_k / attn_pack_v (|x| <= 1e-8 passes through, rounded to bf16) with ONE difference: a zero is
 // always stored as +0.  A negative value whose mantissa rounds to 0 is -0 in the prefill fragments (copysign) and +0 in the
 // oracle's block_fp_quantize (its mantissas are integers); the products cannot tell, the bit-for-bit cache tests can.
-// (mi355q_kv8.h: the same cache with each value as a mantissa byte plus one exponent byte a block, 17/32 of these bytes; its one
+// (mi355q_kvp.h: the same cache with each value as a mantissa byte plus one exponent byte a block, 17/32 of these bytes; its one
 // further difference -- 0 < |x| <= 1e-8, stored here rounded to bf16, is stored there as 0 -- is noted next to its layout.)
 // The length L lives on the host: an append at L writes keys L .. L + n - 1, a decode at L reads keys 0 .. L - 1.
 //
@@ -110,7 +110,7 @@ int launch_kv_append_ragged(const KvCache& c, const QuantArgs& ak, const QuantAr
 // - 1 blocks: MI355Q_E_UNSUPPORTED.  launch_kv_append_ragged's and, in mi355q_kvp.hip, the mantissa caches' append's
 int append_ragged_grid(long long B, int D, long long n, int& kblocks, dim3& grid);
 // the staging pass of launch_kv_append_ragged alone (n > 1: the new open tile's fp32 rows, behind the append kernel that read the old
-// ones): for the int8-mantissa cache of mi355q_kv8.h, whose stage is this one.  Reads c.stage, c.B, c.C and c.D only
+// ones): for the mantissa caches of mi355q_kvp.h, whose stage is this one.  Reads c.stage, c.B, c.C and c.D only
 void launch_kv_stage_ragged(const KvCache& c, const float* k, long long ksb, long long kst, const int32_t* lengths, const int32_t* counts,
                             long long n, hipStream_t st);
 // the cache's quantised values back as fp32 [B, L, D] (tests, debugging); lengths != NULL: zeros behind row b's lengths[b]

@@ -193,7 +193,7 @@ int launch_kv_append_ragged(const KvCache& c, const QuantArgs& ak, const QuantAr
     return (int)hipGetLastError();
 }
 
-// the staging pass alone, for a cache that keeps its quantised values elsewhere (mi355q_kv8.hip): stage, B, C and D are all it reads of c
+// the staging pass alone, for a cache that keeps its quantised values elsewhere (mi355q_kvp.hip): stage, B, C and D are all it reads of c
 void launch_kv_stage_ragged(const KvCache& c, const float* k, long long ksb, long long kst, const int32_t* lengths, const int32_t* counts,
                             long long n, hipStream_t st) {
     AppendArgs a{};

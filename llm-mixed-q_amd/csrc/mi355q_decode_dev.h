@@ -1,4 +1,4 @@
-// Device code the kernels of mi355q_decode.hip (bf16 cache) and mi355q_kv8.hip (int8-mantissa cache) share, one copy of each: a ragged
+// Device code the kernels of mi355q_decode.hip (bf16 cache) and mi355q_kvp.hip (mantissa caches) share, one copy of each: a ragged
 // row's (length, count) of an append and the V walk that gathers a block, a paged cache's table lookup, what a lane of the split-key
 // decode kernels knows of its column -- horizon, length, the grouped column map -- and the empty split's statistics.  All force-inlined,
 // and only what leaves every kernel's instruction text as it was with the code in place (profiles/decode_shared_isa.txt, which also

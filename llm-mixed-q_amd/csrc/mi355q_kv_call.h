@@ -1,7 +1,7 @@
 // The argument check of the KV-cache exports (mi355q_api.hip, from mi355q_bfp_kv_cache_bytes to mi355q_bfp_attention_extend_window):
 // ONE checked descriptor for what used to be 21 copies of shape check, NULL check, quantiser decoding, alignment check and stride loop.
 // Host code only -- no kernel, no launch, no HIP call: an export fills a KvCall, kv_call_check() refuses it with the export's return
-// code or fills a KvChecked with what the launchers of mi355q_decode.h / mi355q_extend.h / mi355q_kv8.h / mi355q_kv4.h take, and the export launches.
+// code or fills a KvChecked with what the launchers of mi355q_decode.h / mi355q_extend.h / mi355q_kvp.h / mi355q_kvbm.h take, and the export launches.
 // What differs between two exports of one (storage, operation) is data: KV_EXPORTS below.  A returned code is ABI: the ORDER of the
 // checks is recorded in tests/golden/kv_api_codes.json, and mi355q_debug_kv_call (mi355q_api.hip) shows this function to the tests.
 #ifndef MI355Q_KV_CALL_H
@@ -13,8 +13,7 @@
 #include "mi355q.h"
 #include "mi355q_internal.h"
 #include "mi355q_decode.h"
-#include "mi355q_kv8.h"
-#include "mi355q_kv4.h"
+#include "mi355q_kvp.h"
 #include "mi355q_kvbm.h"
 #include "mi355q_linear_call.h"
 
@@ -26,9 +25,9 @@ inline int decode_quant_args(const int32_t* pr, QuantArgs& a) {
     a.b0 = 1; a.b1 = 16;
     return 0;
 }
-// the quantisers of the CACHED operands (the y side of qk_params and pv_params); `widest`: 8 where a mantissa must fit a byte, 4 a
-// nibble, 9 where the cache stores bf16
-inline int kv8_quant_args(const int32_t* qk_params, const int32_t* pv_params, QuantArgs& ak, QuantArgs& av, int widest = 8) {
+// the quantisers of the CACHED operands (the y side of qk_params and pv_params); `widest`: kvp_widest() of a mantissa storage (8 where
+// a mantissa must fit a byte, 4 a nibble), 9 where the cache stores bf16
+inline int cached_quant_args(const int32_t* qk_params, const int32_t* pv_params, QuantArgs& ak, QuantArgs& av, int widest) {
     int rc;
     if ((rc = decode_quant_args(qk_params + 3, ak)) != 0 || (rc = decode_quant_args(pv_params + 3, av)) != 0) return rc;
     return qk_params[3] > widest || pv_params[3] > widest ? MI355Q_E_UNSUPPORTED : 0;
@@ -74,10 +73,9 @@ inline int window_cache_shape(int64_t B, int64_t max_pages, int64_t num_pages, i
 
 enum KvStorage { KV_BF16, KV_INT8, KV_PAGED, KV_INT8_PAGED, KV_INT4 };   // KV_PAGED: the cache comes as (max_pages, num_pages, P) and a block
                                                                 // table; KV_INT8_PAGED: both -- int8-mantissa pieces in paged pools;
-                                                                // KV_INT4: two 4-bit mantissas a byte (mi355q_kv4.h), contiguous only
-constexpr bool kv_int8(KvStorage s) { return s == KV_INT8 || s == KV_INT8_PAGED; }
-constexpr bool kv_int4(KvStorage s) { return s == KV_INT4; }
-constexpr bool kv_mantissas(KvStorage s) { return kv_int8(s) || kv_int4(s); }      // mantissa and exponent bytes, rebuilt by the kernels
+                                                                // KV_INT4: two 4-bit mantissas a byte (mi355q_kvp.h), contiguous only
+constexpr bool kv_mantissas(KvStorage s) { return s == KV_INT8 || s == KV_INT8_PAGED || s == KV_INT4; }   // mantissa and exponent bytes, rebuilt by the kernels
+constexpr KvMantissa kv_mantissa(KvStorage s) { return s == KV_INT4 ? KV_M4 : KV_M8; }                    // which, where kv_mantissas(s)
 constexpr bool kv_paged(KvStorage s) { return s == KV_PAGED || s == KV_INT8_PAGED; }
 enum KvOp { KV_BYTES, KV_APPEND, KV_DEQUANT, KV_DECODE, KV_EXTEND };
 enum : unsigned {
@@ -166,11 +164,10 @@ constexpr KvCall KV_EXPORTS[KVX_COUNT] = {
 // what the launchers take of a call that passed
 struct KvChecked {
     KvCache c;                  // storage KV_BF16 / KV_PAGED (C: the row's logical capacity)
-    Kv8Cache c8;                // storage KV_INT8 / KV_INT8_PAGED (C: the row's logical capacity)
-    Kv4Cache c4;                // storage KV_INT4
+    KvpCache cp;                // storage KV_INT8 / KV_INT8_PAGED / KV_INT4: kv_mantissa(storage)'s pieces (C: the row's logical capacity)
     KvPages pg;
     const KvPages* pages;       // &pg with a block table, else NULL
-    QuantArgs aq, ap, ak, av;   // Q and P (decode, extend); the cached K and V (append; int8 / int4: every operation)
+    QuantArgs aq, ap, ak, av;   // Q and P (decode, extend); the cached K and V (append; mantissa storage: every operation)
     int G, causal;              // normalised: 0 the ungrouped kernels; causal 0 / 1
     long long window;           // clamped to L; 0: none
     long long st[4];
@@ -179,8 +176,8 @@ struct KvChecked {
 
 // true: launch with `k`.  false: return rc (an MI355Q_E_* code, or 0 where there is nothing to do)
 inline bool kv_call_check(const KvCall& d, KvChecked& k, int& rc) {
-    const bool attn = d.op == KV_DECODE || d.op == KV_EXTEND, int8 = kv_mantissas(d.storage), paged_form = kv_paged(d.storage);
-    const int widest = kv_int4(d.storage) ? 4 : 8;           // (`int8` below: mantissa storage of either width, refused above `widest`)
+    const bool attn = d.op == KV_DECODE || d.op == KV_EXTEND, mant = kv_mantissas(d.storage), paged_form = kv_paged(d.storage);
+    const int widest = mant ? kvp_widest(kv_mantissa(d.storage)) : 9;     // (the widest cached operand the storage holds)
     const bool windowed = (d.form & KV_WINDOW) != 0, minifloat = (d.form & KV_MINIFLOAT) != 0;
     const auto stop = [&rc](int code) { rc = code; return false; };
     const auto misaligned = [](std::initializer_list<const void*> ptrs, uintptr_t to) {      // (an optional NULL passes)
@@ -206,10 +203,10 @@ inline bool kv_call_check(const KvCall& d, KvChecked& k, int& rc) {
     if (d.op == KV_APPEND) {
         if (d.L < 0 || d.n < 0 || !d.qk_params || !d.pv_params) return stop(MI355Q_E_BADARG);
         if (d.L + d.n > cap) return stop(paged_form ? MI355Q_E_BADARG : MI355Q_E_UNSUPPORTED);        // (nothing is written)
-        if (int8 && (rc = kv8_quant_args(d.qk_params, d.pv_params, k.ak, k.av, widest)) != 0) return false;    // (int8: before the early 0)
+        if (mant && (rc = cached_quant_args(d.qk_params, d.pv_params, k.ak, k.av, widest)) != 0) return false;    // (mantissas: before the early 0)
         if (d.n == 0) return stop(0);
         if (no_cache || !d.stage || !d.k || !d.v) return stop(MI355Q_E_BADARG);
-        if (!int8 && (rc = minifloat ? bm_quant_pair(d.qk_params, d.pv_params, 3, k.ak, k.av) : kv8_quant_args(d.qk_params, d.pv_params, k.ak, k.av, 9)) != 0)
+        if (!mant && (rc = minifloat ? bm_quant_pair(d.qk_params, d.pv_params, 3, k.ak, k.av) : cached_quant_args(d.qk_params, d.pv_params, k.ak, k.av, widest)) != 0)
             return false;
         if (misaligned({d.kq, d.vq, d.stage, d.k, d.v}, 16) || misaligned({d.lengths, d.counts, d.block_table}, 4)) return stop(MI355Q_E_ALIGN);
         const long long dflt[4] = {d.n * d.D, d.D, d.n * d.D, d.D};
@@ -219,8 +216,8 @@ inline bool kv_call_check(const KvCall& d, KvChecked& k, int& rc) {
         }
         k.strides = k.st;
     } else if (d.op == KV_DEQUANT) {
-        if (d.L < 0 || d.L > cap || (int8 && (!d.qk_params || !d.pv_params))) return stop(MI355Q_E_BADARG);
-        if (int8 && (rc = kv8_quant_args(d.qk_params, d.pv_params, k.ak, k.av, widest)) != 0) return false;
+        if (d.L < 0 || d.L > cap || (mant && (!d.qk_params || !d.pv_params))) return stop(MI355Q_E_BADARG);
+        if (mant && (rc = cached_quant_args(d.qk_params, d.pv_params, k.ak, k.av, widest)) != 0) return false;
         if (d.L == 0) return stop(0);
         if (no_cache || !d.k || !d.v) return stop(MI355Q_E_BADARG);
     } else {
@@ -237,7 +234,7 @@ inline bool kv_call_check(const KvCall& d, KvChecked& k, int& rc) {
             if ((rc = bm_quant_pair(d.qk_params, d.pv_params, 0, k.aq, k.ap)) != 0 || (rc = bm_quant_pair(d.qk_params, d.pv_params, 3, k.ak, k.av)) != 0)
                 return false;
         } else if ((rc = decode_quant_args(d.qk_params, k.aq)) != 0 || (rc = decode_quant_args(d.pv_params, k.ap)) != 0 ||
-                   (int8 && (rc = kv8_quant_args(d.qk_params, d.pv_params, k.ak, k.av, widest)) != 0))
+                   (mant && (rc = cached_quant_args(d.qk_params, d.pv_params, k.ak, k.av, widest)) != 0))
             return false;
         if (misaligned({d.q, d.kq, d.vq, d.out, d.workspace}, 16) || misaligned({d.lengths, d.counts, d.block_table}, 4)) return stop(MI355Q_E_ALIGN);
         if (d.strides) {
@@ -250,12 +247,10 @@ inline bool kv_call_check(const KvCall& d, KvChecked& k, int& rc) {
         k.causal = windowed || d.causal != 0;
         k.window = !windowed ? 0 : d.window > d.L ? d.L : d.window;      // (a window over every key the call can hold: the same mask)
     }
-    if (kv_int4(d.storage)) k.c4 = Kv4Cache{static_cast<uint8_t*>(const_cast<void*>(d.kq)), static_cast<uint8_t*>(const_cast<void*>(d.vq)),
-                                            static_cast<float*>(const_cast<void*>(d.stage)), d.B, cap, (int)d.D};
-    else if (int8) k.c8 = Kv8Cache{static_cast<uint8_t*>(const_cast<void*>(d.kq)), static_cast<uint8_t*>(const_cast<void*>(d.vq)),
-                              static_cast<float*>(const_cast<void*>(d.stage)), d.B, cap, (int)d.D};
-    else k.c = KvCache{static_cast<uint16_t*>(const_cast<void*>(d.kq)), static_cast<uint16_t*>(const_cast<void*>(d.vq)),
-                       static_cast<float*>(const_cast<void*>(d.stage)), d.B, cap, (int)d.D};
+    void *const kq = const_cast<void*>(d.kq), *const vq = const_cast<void*>(d.vq);         // (the one cast; the element type is the storage's)
+    float* const stage = static_cast<float*>(const_cast<void*>(d.stage));
+    if (mant) k.cp = KvpCache{static_cast<uint8_t*>(kq), static_cast<uint8_t*>(vq), stage, d.B, cap, (int)d.D};
+    else k.c = KvCache{static_cast<uint16_t*>(kq), static_cast<uint16_t*>(vq), stage, d.B, cap, (int)d.D};
     k.pages = paged_form && d.block_table ? &k.pg : nullptr;
     rc = 0;
     return true;

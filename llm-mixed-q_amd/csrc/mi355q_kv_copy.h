@@ -5,7 +5,7 @@
 // A JOB is int32 x 4 on the device, 16 bytes: (src_page, dst_page, src_row, dst_row).
 //   pages   src_page, dst_page >= 0: the WHOLE page src_page of both pools becomes page dst_page -- P / 16 tiles x D / 32 KiB of K^T and
 //           P / 32 pairs x D / 16 KiB of V (mi355q_decode.h: paged cache), P * D * 2 bytes each; of the int8-mantissa pools
-//           (mi355q_kv8.h, mi355q_bfp_kv8_paged_copy) the same pieces at 544 bytes, P * D * 17 / 16 bytes each.  Whole pages: a recycled page may hold
+//           (mi355q_kvp.h, mi355q_bfp_kv8_paged_copy) the same pieces at 544 bytes, P * D * 17 / 16 bytes each.  Whole pages: a recycled page may hold
 //           anything behind the row's keys, and copying all of it keeps the kernel free of per-row lengths.  Either id negative: no page
 //           copy.  Ids are clamped into 0 .. num_pages - 1 like every paged kernel's: a wrong job gives wrong numbers, never an address
 //           outside the pools.
@@ -40,7 +40,7 @@ struct KvCopyArgs {
 };
 
 // true: launch with `g`.  false: return rc (an MI355Q_E_* code, or 0 where there is nothing to do).  The order of the checks is ABI.
-// int8: the pools hold the 544-byte pieces of mi355q_kv8.h -- only the size of a page differs (P * D is a multiple of 1024: whole units)
+// int8: the pools hold the 544-byte pieces of mi355q_kvp.h -- only the size of a page differs (P * D is a multiple of 1024: whole units)
 inline bool kv_copy_check(const void* kq, const void* vq, const void* stage_src, const void* stage_dst, const void* jobs, int64_t n_jobs,
                           int64_t B, int64_t num_pages, int64_t P, int64_t D, bool int8, KvCopyArgs& g, int& rc) {
     const auto stop = [&rc](int code) { rc = code; return false; };

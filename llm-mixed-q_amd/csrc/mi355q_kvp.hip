@@ -1,7 +1,7 @@
 // mi355q_kvp.hip -- the block_fp KV caches that store a mantissa and a shared exponent instead of bf16, and the split-key decode
 // attention on them.  Two storages, one set of kernels:
-//   Int8Pieces    int8 mantissas, 544-byte pieces, contiguous or paged pools (PG)       layout and the one deviation: mi355q_kv8.h
-//   NibblePieces  4-bit mantissas, two to a byte, 288-byte pieces, contiguous only      layout and the pairing of nibbles: mi355q_kv4.h
+//   Int8Pieces    int8 mantissas, 544-byte pieces, contiguous or paged pools (PG)       KV_M8 } layout, the one deviation and the pairing
+//   NibblePieces  4-bit mantissas, two to a byte, 288-byte pieces, contiguous only      KV_M4 } of nibbles: mi355q_kvp.h
 //
 // A storage is a trait struct and a template parameter ST of every kernel.  It owns its piece constants (PIECE, CODES), the place of a
 // lane's 8 mantissa bytes and of its nibble in them (PAIR, NIB), the append's store of one block (store_block), one value of the
@@ -27,14 +27,13 @@
 #include "mi355q_attn_dev.h"
 #include "mi355q_decode.h"
 #include "mi355q_decode_dev.h"
-#include "mi355q_kv8.h"
-#include "mi355q_kv4.h"
+#include "mi355q_kvp.h"
 
 namespace mi355q {
 
 // ---- the two storages -------------------------------------------------------------------------------------------------------
 struct Int8Pieces {
-    static constexpr int PIECE = KV8_PIECE, CODES = 512;        // a piece's bytes; where its exponent bytes start
+    static constexpr int PIECE = KVP_M8_PIECE, CODES = KVP_M8_CODES;       // a piece's bytes; where its exponent bytes start
     static constexpr bool PAGED = true;                         // PG = true kernels exist
     // lane l's 8 mantissa bytes start at 8 (l >> PAIR), its mantissa at bit NIB (l & 1) of each: the whole byte.  (Constants and no
     // functions: a helper is optimised on its own before it is inlined, and that moved the nibble kernels' text.)
@@ -75,7 +74,7 @@ struct Int8Pieces {
 };
 
 struct NibblePieces {
-    static constexpr int PIECE = KV4_PIECE, CODES = KV4_CODES;
+    static constexpr int PIECE = KVP_M4_PIECE, CODES = KVP_M4_CODES;
     static constexpr bool PAGED = false;                        // contiguous only: the launchers refuse `pages`
     // the two lanes of a pair share 8 mantissa bytes at 8 (l >> 1); lane l's mantissa is the nibble at bit 4 (l & 1) of each
     static constexpr int PAIR = 1;
@@ -84,7 +83,7 @@ struct NibblePieces {
 
     // one block of 16 values x with maximum bmax: the mantissas of lanes 2 e and 2 e + 1 of a lane group, at one slot, are the two
     // nibbles of ONE byte, 8 bytes apart in k4 (the 16 keys of a tile at one d) and in v4 (the 16 d of one key) alike; the block's
-    // exponent code goes to *code.  Plain byte stores of whole bytes: nothing is read (mi355q_kv4.h).
+    // exponent code goes to *code.  Plain byte stores of whole bytes: nothing is read (mi355q_kvp.h).
     __device__ static __forceinline__ void store_block(uint8_t* __restrict__ dst, uint8_t* __restrict__ code, const float (&x)[16],
                                                        float bmax, const QuantArgs& a) {
         const int mbits = (int)__builtin_log2f(a.shift);
@@ -116,17 +115,6 @@ struct NibblePieces {
         return __builtin_bit_cast(bf16x8, pk);
     }
 };
-
-// either storage's cache as the kernels take it (Kv8Cache / Kv4Cache under one set of names)
-struct KvpCache {
-    uint8_t* k;
-    uint8_t* v;
-    float* stage;
-    long long B, C;
-    int D;
-};
-static KvpCache kvp_cache(const Kv8Cache& c) { return KvpCache{c.k8, c.v8, c.stage, c.B, c.C, c.D}; }
-static KvpCache kvp_cache(const Kv4Cache& c) { return KvpCache{c.k4, c.v4, c.stage, c.B, c.C, c.D}; }
 
 // exponent code -> the ldexp argument of a mantissa: p - mbits = code - exponent_bias - mbits
 static int down(const QuantArgs& a) { return -(a.code_bias + (int)__builtin_log2f(a.shift)); }
@@ -519,38 +507,35 @@ static int kvp_decode(const QuantArgs& aq, const QuantArgs& ap, const QuantArgs&
     return (int)hipGetLastError();
 }
 
-// ---- the launchers mi355q_kv8.h and mi355q_kv4.h declare: the instantiations ---------------------------------------------------
-int launch_kv8_append(const Kv8Cache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
+// ---- the launchers mi355q_kvp.h declares: one switch on the storage an operation (a new storage: its trait struct above, a case here) ----
+int launch_kvp_append(KvMantissa m, const KvpCache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
                       long long kst, long long vsb, long long vst, const int32_t* lengths, const int32_t* counts, long long n,
                       hipStream_t st, const KvPages* pages) {
-    return kvp_append<Int8Pieces>(kvp_cache(c), ak, av, k, v, ksb, kst, vsb, vst, lengths, counts, n, st, pages);
+    switch (m) {
+        case KV_M8: return kvp_append<Int8Pieces>(c, ak, av, k, v, ksb, kst, vsb, vst, lengths, counts, n, st, pages);
+        case KV_M4: return kvp_append<NibblePieces>(c, ak, av, k, v, ksb, kst, vsb, vst, lengths, counts, n, st, pages);
+    }
+    return MI355Q_E_BADARG;
 }
-int launch_kv4_append(const Kv4Cache& c, const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, long long ksb,
-                      long long kst, long long vsb, long long vst, const int32_t* lengths, const int32_t* counts, long long n,
-                      hipStream_t st, const KvPages* pages) {
-    return kvp_append<NibblePieces>(kvp_cache(c), ak, av, k, v, ksb, kst, vsb, vst, lengths, counts, n, st, pages);
-}
-int launch_kv8_decode_fp32(const Kv8Cache& c, const QuantArgs& ak, const QuantArgs& av, float* k_out, float* v_out, long long L,
+int launch_kvp_decode_fp32(KvMantissa m, const KvpCache& c, const QuantArgs& ak, const QuantArgs& av, float* k_out, float* v_out, long long L,
                            const int32_t* lengths, hipStream_t st, const KvPages* pages) {
-    return kvp_decode_fp32<Int8Pieces>(kvp_cache(c), ak, av, k_out, v_out, L, lengths, st, pages);
+    switch (m) {
+        case KV_M8: return kvp_decode_fp32<Int8Pieces>(c, ak, av, k_out, v_out, L, lengths, st, pages);
+        case KV_M4: return kvp_decode_fp32<NibblePieces>(c, ak, av, k_out, v_out, L, lengths, st, pages);
+    }
+    return MI355Q_E_BADARG;
 }
-int launch_kv4_decode_fp32(const Kv4Cache& c, const QuantArgs& ak, const QuantArgs& av, float* k_out, float* v_out, long long L,
-                           const int32_t* lengths, hipStream_t st, const KvPages* pages) {
-    return kvp_decode_fp32<NibblePieces>(kvp_cache(c), ak, av, k_out, v_out, L, lengths, st, pages);
-}
-int launch_bfp_attention_decode_kv8(const QuantArgs& aq, const QuantArgs& ap, const QuantArgs& ak, const QuantArgs& av, const Kv8Cache& c,
-                                    const float* q, float* out, void* workspace, long long M, long long L, int causal, float q_scale,
-                                    float scale_div, const long long* strides, int splits, hipStream_t st, const int32_t* lengths, int G,
-                                    const KvPages* pages) {
-    return kvp_decode<Int8Pieces>(aq, ap, ak, av, kvp_cache(c), q, out, workspace, M, L, causal, q_scale, scale_div, strides, splits, st,
-                                  lengths, G, pages);
-}
-int launch_bfp_attention_decode_kv4(const QuantArgs& aq, const QuantArgs& ap, const QuantArgs& ak, const QuantArgs& av, const Kv4Cache& c,
-                                    const float* q, float* out, void* workspace, long long M, long long L, int causal, float q_scale,
-                                    float scale_div, const long long* strides, int splits, hipStream_t st, const int32_t* lengths, int G,
-                                    const KvPages* pages) {
-    return kvp_decode<NibblePieces>(aq, ap, ak, av, kvp_cache(c), q, out, workspace, M, L, causal, q_scale, scale_div, strides, splits, st,
-                                    lengths, G, pages);
+int launch_bfp_attention_decode_kvp(KvMantissa m, const QuantArgs& aq, const QuantArgs& ap, const QuantArgs& ak, const QuantArgs& av,
+                                    const KvpCache& c, const float* q, float* out, void* workspace, long long M, long long L, int causal,
+                                    float q_scale, float scale_div, const long long* strides, int splits, hipStream_t st,
+                                    const int32_t* lengths, int G, const KvPages* pages) {
+    switch (m) {
+        case KV_M8:
+            return kvp_decode<Int8Pieces>(aq, ap, ak, av, c, q, out, workspace, M, L, causal, q_scale, scale_div, strides, splits, st, lengths, G, pages);
+        case KV_M4:
+            return kvp_decode<NibblePieces>(aq, ap, ak, av, c, q, out, workspace, M, L, causal, q_scale, scale_div, strides, splits, st, lengths, G, pages);
+    }
+    return MI355Q_E_BADARG;
 }
 
 }  // namespace mi355q

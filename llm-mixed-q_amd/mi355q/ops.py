@@ -1999,7 +1999,7 @@ class _MantissaKVCache(_KVCacheBase):
 class PackedKVCache(_MantissaKVCache):
     """`KVCache` with every quantised value stored as what it is -- a signed mantissa byte, and one shared-exponent byte per block of
     16 -- instead of as bf16: 1 + 1/16 bytes a value, 17/32 of KVCache's K and V bytes and of a decode step's K / V traffic (layout:
-    csrc/mi355q_kv8.h).  Same constructor arguments and the same append / reset / dequantised / length / lengths= / counts= /
+    csrc/mi355q_kvp.h).  Same constructor arguments and the same append / reset / dequantised / length / lengths= / counts= /
     max_length= contract; a class of its own, NOT a KVCache: only bfp_attention_decode's packed route reads it (no window, no pages,
     no bfp_attention_extend).  The decode kernels rebuild the bf16 fragments in registers, so dequantised() and
     bfp_attention_decode give KVCache's bits for the same keys (decode: with the same `splits`), with one exception: an input
@@ -2015,7 +2015,7 @@ class PackedKVCache(_MantissaKVCache):
 class NibbleKVCache(_MantissaKVCache):
     """`PackedKVCache` for layers whose CACHED operands -- the y side of qk_params and of pv_params -- have width <= 4: the mantissa,
     |m| <= 7, is a signed nibble, two to a byte, with one shared-exponent byte per block of 16 -- 4 + 1/2 bits a value, 9/32 of KVCache's
-    K and V bytes and of a decode step's K / V traffic, 9/17 of PackedKVCache's (layout: csrc/mi355q_kv4.h; the two nibbles of a byte
+    K and V bytes and of a decode step's K / V traffic, 9/17 of PackedKVCache's (layout: csrc/mi355q_kvp.h; the two nibbles of a byte
     are two values of one block, so an append stores whole bytes and never reads the cache).  Same constructor arguments and the same
     append / reset / dequantised / length / lengths= / counts= / max_length= contract; a class of its own, NOT a PackedKVCache or a
     KVCache: only bfp_attention_decode's route for it (form `_kv4`) reads its bytes (no window, no pages, no bfp_attention_extend).  The
@@ -2105,7 +2105,7 @@ class MinifloatKVCache(_KVCacheBase):
 
 class PagedPackedKVCache(_PagedHost):
     """`PagedKVCache` with the int8-mantissa storage of `PackedKVCache`: pools of pages whose pieces are 512 mantissa bytes and 32
-    shared-exponent bytes (csrc/mi355q_kv8.h, paged pools) -- 17/32 of PagedKVCache's K and V bytes and of a decode step's K / V traffic,
+    shared-exponent bytes (csrc/mi355q_kvp.h, paged pools) -- 17/32 of PagedKVCache's K and V bytes and of a decode step's K / V traffic,
     with its pages, prefix sharing, fork and reorder.  PagedKVCache's constructor and interface -- ensure / assign / release /
     share_prefix / fork / reorder / reset / append / dequantised / pages_for, `stage_alt`, `block_table`, `free` / `refs` / `held`, all
     of them the same code (_PagedHost) -- on the storage `k8`, `v8`, `stage`; always addressed in the ragged form.  The cached operands

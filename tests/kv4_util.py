@@ -1,5 +1,5 @@
 """Shared by the 4-bit-mantissa KV cache tests (tests/test_kv4_host.py, tests/test_gpu_kv4_*.py): a numpy restatement of the piece layout
-of csrc/mi355q_kv4.h, written from the header's text and not from the kernels; block_fp configs whose Q / P side (data_in_*) and cached
+of csrc/mi355q_kvp.h, written from the header's text and not from the kernels; block_fp configs whose Q / P side (data_in_*) and cached
 side (weight_*) differ in width; and tiny Llama models whose layers differ in their attention widths."""
 import sys
 from pathlib import Path

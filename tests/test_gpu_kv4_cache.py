@@ -1,4 +1,4 @@
-"""ops.NibbleKVCache (two 4-bit mantissas a byte + one exponent byte a block, csrc/mi355q_kv4.h) holds what ops.PackedKVCache and
+"""ops.NibbleKVCache (two 4-bit mantissas a byte + one exponent byte a block, csrc/mi355q_kvp.h) holds what ops.PackedKVCache and
 ops.KVCache hold: dequantised() of the three compared as bits after every append, and against np_oracle.block_fp_quantize of k^T and of
 v; the raw bytes unpacked by the numpy restatement of the documented layout (tests/kv4_util.py) give the same values.  Bit equality is
 claimed for inputs without 0 < |x| <= 1e-8 (asserted of the seeded inputs); the planted cases show what happens at exactly those values
@@ -69,7 +69,7 @@ def test_contents_equal_the_other_caches(D, width):
         kq, vq = _quantised_kv(k[:, :at], v[:, :at], width)
         assert np.array_equal(_u32(k4), kq.view(np.uint32)), f"K differs from block_fp_quantize at length {at}"
         assert np.array_equal(_u32(v4), vq.view(np.uint32)), f"V differs from block_fp_quantize at length {at}"
-        # the raw bytes, read as csrc/mi355q_kv4.h words them: the same values (keys the cache does not hold yet: mantissa 0)
+        # the raw bytes, read as csrc/mi355q_kvp.h words them: the same values (keys the cache does not hold yet: mantissa 0)
         K, V = _raw(nibble, width)
         assert np.array_equal(_u32(K[:, :at]), _u32(k4)) and np.array_equal(_u32(V[:, :at]), _u32(v4)), f"the documented layout at length {at}"
         assert not K[:, at:(at + 15) // 16 * 16].any(), "the open tile's keys behind the length are not mantissa 0"
@@ -136,7 +136,7 @@ def test_planted_blocks():
     nibbles of a byte -- and a V block the 16 d of one key -- its neighbouring d are.  Planted in both: +7 next to -7 (a sign extension
     leaking into the partner nibble would show), an all-negative block, a block whose even lanes are 0 and whose odd lanes are mantissa -1
     and the reverse (ONE lane of each holds -7: a block needs a maximum to put the others at mantissa 1), an all-zero block, and THE ONE
-    DEVIATION of csrc/mi355q_kv8.h, carried over: |x| = 1e-8 and 1e-9 among ordinary values, which KVCache passes through unquantised,
+    DEVIATION of csrc/mi355q_kvp.h's int8 storage, carried over: |x| = 1e-8 and 1e-9 among ordinary values, which KVCache passes through unquantised,
     are stored as exactly 0."""
     import torch
     B, L, D, width = 1, 16, 32, 4
@@ -163,7 +163,7 @@ def test_planted_blocks():
         assert np.array_equal(a4.view(np.uint32)[~dev], a16.view(np.uint32)[~dev]), f"{name}: a value outside the deviation differs from KVCache"
         assert (np.abs(x[dev]) <= 1e-8).all() and (x[dev] != 0).all()
         assert (a4.view(np.uint32)[dev] == 0).all(), \
-            f"{name}: the one deviation (csrc/mi355q_kv8.h, carried over by mi355q_kv4.h): 0 < |x| <= 1e-8 is stored as +0, got {a4[dev]}"
+            f"{name}: the one deviation (csrc/mi355q_kvp.h: the int8 storage's, carried over by the nibble storage): 0 < |x| <= 1e-8 is stored as +0, got {a4[dev]}"
         assert (a16[dev] != 0).all(), f"{name}: the bf16 cache no longer passes such a value through"
     kq, vq = _quantised_kv(k, v, width)
     assert np.array_equal(k4.view(np.uint32)[~dk], kq.view(np.uint32)[~dk]) and np.array_equal(v4.view(np.uint32)[~dv], vq.view(np.uint32)[~dv])

@@ -1,4 +1,4 @@
-"""ops.PackedKVCache (int8 mantissas + one exponent byte a block, csrc/mi355q_kv8.h) holds what ops.KVCache holds: dequantised() of the
+"""ops.PackedKVCache (int8 mantissas + one exponent byte a block, csrc/mi355q_kvp.h) holds what ops.KVCache holds: dequantised() of the
 two compared as bits after every append, and against np_oracle.block_fp_quantize of k^T and of v.  Bit equality is claimed for inputs
 without 0 < |x| <= 1e-8 (asserted of the seeded inputs); the planted cases show what happens at exactly those values."""
 import sys

@@ -1,4 +1,4 @@
-"""ops.bfp_attention_decode on an ops.PackedKVCache (int8 mantissas, csrc/mi355q_kv8.hip).  Every case is held FIRST to the
+"""ops.bfp_attention_decode on an ops.PackedKVCache (int8 mantissas, csrc/mi355q_kvp.hip).  Every case is held FIRST to the
 fp64-softmax oracle of tests/window_util.py on each row's own keys, within its bounds, and only then compared, as bits, with the same
 call on an ops.KVCache filled with the same keys under the same `splits`.  Rows of (117, 41, 0) keys in a capacity of 128: a short row
 -- which splits = 2 leaves an empty split -- and an empty one."""

@@ -1,4 +1,4 @@
-"""ops.PagedPackedKVCache (int8 mantissas in paged pools, csrc/mi355q_kv8.hip with PG = true) on the GPU.  The arithmetic is that of
+"""ops.PagedPackedKVCache (int8 mantissas in paged pools, csrc/mi355q_kvp.hip with PG = true) on the GPU.  The arithmetic is that of
 ops.PackedKVCache -- only a piece's place goes through the page table -- so EVERY comparison with the other caches here is bit equality;
 the decode cases are first held to the fp64-softmax oracle with the helper and the bounds of tests/test_gpu_kv8_decode.py.
 Four cache rows reach (37, 64, 5, 0) keys by appends of 1, 15, 17 and 33 input rows; their pages are placed by hand, interleaved and out

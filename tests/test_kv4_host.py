@@ -1,4 +1,4 @@
-"""The 4-bit-mantissa KV cache (ops.NibbleKVCache, csrc/mi355q_kv4.h), what a machine without a GPU can say about it: the class's place
+"""The 4-bit-mantissa KV cache (ops.NibbleKVCache, csrc/mi355q_kvp.h), what a machine without a GPU can say about it: the class's place
 among the cache classes and its refusals by name, the two decode states and generate's spellings, the byte counts, the new exports'
 call check read next to the kv8 exports' through mi355q_debug_kv_call_all, and the numpy restatement of the piece layout that the GPU
 tests hold the kernels to (tests/kv4_util.py)."""

@@ -1,4 +1,4 @@
-"""The int8-mantissa KV cache (ops.PackedKVCache, csrc/mi355q_kv8.h), what a machine without a GPU can say about it: byte counts,
+"""The int8-mantissa KV cache (ops.PackedKVCache, csrc/mi355q_kvp.h), what a machine without a GPU can say about it: byte counts,
 the constructor's and the entry points' refusals, the decode state's refusals, the ABI version."""
 import ctypes
 import sys

@@ -1,4 +1,4 @@
-"""The paged int8-mantissa KV cache (ops.PagedPackedKVCache, csrc/mi355q_kv8.h: paged pools), what a machine without a GPU can say about
+"""The paged int8-mantissa KV cache (ops.PagedPackedKVCache, csrc/mi355q_kvp.h: paged pools), what a machine without a GPU can say about
 it: the constructor's refusals, the class's place among the cache classes, the host plans (which are PagedKVCache's, from shared code),
 the refusals of the five new exports and of the entry points above them, the argument check as mi355q_debug_kv_call shows it, the byte
 counts, and the ABI version."""

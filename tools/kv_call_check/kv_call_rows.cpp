@@ -56,7 +56,7 @@ static int new_rows() {
         const bool go = kv_call_check(d, c, rc);
         bool ok = go == r.go && rc == r.code;
         if (go && r.id != KVX_KV8P_BYTES)      // what the launchers get: the int8 cache at the rows' logical capacity, and the page table
-            ok = ok && c.c8.C == 192 && c.c8.D == 32 && c.c8.B == 4 && c.pages == &c.pg && c.pg.lg_p == 6 && c.pg.num_pages == 12 && c.pg.max_pages == 3 &&
+            ok = ok && c.cp.C == 192 && c.cp.D == 32 && c.cp.B == 4 && c.pages == &c.pg && c.pg.lg_p == 6 && c.pg.num_pages == 12 && c.pg.max_pages == 3 &&
                  c.c.kq == nullptr && (r.id != KVX_KV8P_DECODE || c.G == 2);
         if (!ok) {
             std::printf("new row %d (export %d, '%s'): code %d (launch %d), expected %d (launch %d)\n", n, (int)r.id, r.what, rc, (int)go, r.code,
@@ -107,7 +107,7 @@ static int bm_rows() {
         const bool go = kv_call_check(d, c, rc);
         bool ok = go == r.go && rc == r.code;
         if (go)       // what the launchers get: the bf16 cache, no pages, and the block_minifloat quantisers' words
-            ok = ok && c.c.C == 64 && c.c.D == 32 && c.c.B == 4 && c.pages == nullptr && c.c8.k8 == nullptr && c.ak.span == 15 && c.ak.bias_max == 255 &&
+            ok = ok && c.c.C == 64 && c.c.D == 32 && c.c.B == 4 && c.pages == nullptr && c.cp.k == nullptr && c.ak.span == 15 && c.ak.bias_max == 255 &&
                  c.av.shift == 8.0f && c.av.mant_max == 7.0f && (append || (c.G == 2 && c.aq.span == 15 && c.ap.shift == 8.0f && c.causal == 1));
         if (!ok) {
             std::printf("block_minifloat row %d (export %d, '%s'): code %d (launch %d), expected %d (launch %d)\n", n, (int)r.id, r.what, rc, (int)go,
