@@ -46,7 +46,10 @@ struct Int8Pieces {
     __device__ static __forceinline__ void store_block(uint8_t* __restrict__ dst, uint8_t* __restrict__ code, const float (&x)[16],
                                                        float bmax, const QuantArgs& a) {
         const int mbits = (int)__builtin_log2f(a.shift);
-        const int p = at_block_exponent_mem(bmax, a);
+        // (an all-zero block: the lowest exponent's code, whatever its wave's other blocks are -- at_block_exponent_mem gives -bias on its
+        //  common path and 0 when ANOTHER lane's maximum sends the wave to the table walk, and the piece's bytes must not depend on that)
+        const int pw = at_block_exponent_mem(bmax, a);
+        const int p = bmax != 0.f ? pw : a.e_min;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const float m = bmax != 0.f ? at_quant_mant(x[e], mbits - p, a.mant_max) : 0.f;      // (|m| <= mant_max <= 127)
@@ -87,7 +90,8 @@ struct NibblePieces {
     __device__ static __forceinline__ void store_block(uint8_t* __restrict__ dst, uint8_t* __restrict__ code, const float (&x)[16],
                                                        float bmax, const QuantArgs& a) {
         const int mbits = (int)__builtin_log2f(a.shift);
-        const int p = at_block_exponent_mem(bmax, a);
+        const int pw = at_block_exponent_mem(bmax, a);
+        const int p = bmax != 0.f ? pw : a.e_min;                                                        // (as in Int8Pieces::store_block)
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float lo = bmax != 0.f ? at_quant_mant(x[2 * e], mbits - p, a.mant_max) : 0.f;        // (|m| <= mant_max <= 7)
