@@ -6,10 +6,15 @@
 // on constants: cdna guide, "DVFS give-back" item 1), no LDS, no global traffic.  SURVEY 8d asks for the achievable figure next to
 // the nominal 5 POPS; round 3 measured 4.28 POPS with near-constant operands (tools/ubench/mx_rate.hip, profiles/r03_mx_rate.txt).
 // Also returns the clock the loop ran at: delta s_memtime (shader cycles) / delta s_memrealtime (100 MHz), median over workgroups.
+//
+// mi355q_debug_quant_rows_plan / _builds: what the row quantiser's launchers would do, without launching (mi355q_quant_plan.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
 #include <vector>
+
+#include "mi355q.h"
+#include "mi355q_internal.h"
 
 namespace {
 using i32x4 = __attribute__((ext_vector_type(4))) int;
@@ -91,4 +96,32 @@ extern "C" __attribute__((visibility("default"))) int mi355q_debug_mfma_i8_peak(
     (void)hipFree(sink);
     (void)hipFree(clk);
     return (int)hipGetLastError();
+}
+
+// The plan of a row quantiser launch, without launching (no HIP call: works without a GPU).  shape = kind (0 int8 rows, 1 MX rows,
+// 2 class-aware rows), rows, cols, pre_op, segmented; env = the 3 words of RowsEnv in declaration order, or NULL for the process
+// environment; out = the 9 words of RowsPlan in declaration order, then three zeros.
+extern "C" __attribute__((visibility("default"))) int mi355q_debug_quant_rows_plan(const int64_t shape[5], const int32_t* e, int32_t out[12]) {
+    using namespace mi355q;
+    if (!shape || !out) return MI355Q_E_BADARG;
+    const RowsEnv env = e ? RowsEnv{e[0], e[1] != 0, e[2]} : read_rows_env();
+    const RowsPlan p = plan_quant_rows(RowsShape{(int)shape[0], shape[1], shape[2], (int)shape[3], shape[4] != 0}, env);
+    const int32_t words[12] = {p.maxit, p.full, p.seg, p.mx, p.pre, p.st16, p.wps, (int32_t)p.grid, p.rc};
+    for (int i = 0; i < 12; ++i) out[i] = words[i];
+    return 0;
+}
+// ... and the builds the three launchers can look up: returns how many, and writes the first `cap` of them as 8 words each -- kind, then
+// the first 7 words of RowsPlan
+extern "C" __attribute__((visibility("default"))) int mi355q_debug_quant_rows_builds(int32_t* out, int32_t cap) {
+    using namespace mi355q;
+    std::vector<RowsPlan> all;
+    quant_rows_builds(all);
+    const size_t classes_from = all.size();
+    quant_class_builds(all);
+    for (size_t i = 0; out && i < (size_t)cap && i < all.size(); ++i) {
+        const RowsPlan& b = all[i];
+        const int32_t words[8] = {i >= classes_from ? ROWS_CLASSES : b.mx ? ROWS_MX : ROWS_INT8, b.maxit, b.full, b.seg, b.mx, b.pre, b.st16, b.wps};
+        for (int j = 0; j < 8; ++j) out[8 * i + j] = words[j];
+    }
+    return (int)all.size();
 }

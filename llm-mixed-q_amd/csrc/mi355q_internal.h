@@ -4,6 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
+#include "mi355q_quant_plan.h"
+
 namespace mi355q {
 
 // One quantiser launch: `lead` planes of rows x cols fp32 tiled by b0 x b1 blocks.
@@ -48,6 +52,11 @@ int launch_fp32_split_tile(const float* x, uint16_t* yt, long long rows, long lo
 // the class-aware activation quantiser of the mixed contraction (mi355q_quant_cls.hip): cmap[kb] = position | class << 15
 int launch_quant_classes(const QuantArgs& a, const uint16_t* cmap, int n0, int n1, int8_t* mt, uint8_t* flag, float* rscale,
                          int exp_offset, int* list, int* list_to_clear, uint16_t* bt, hipStream_t st, int bcap);
+// for the row quantiser's diagnostic hooks (mi355q_diag.hip): the MI355Q_QROWS_* switches as a launch finds them (mi355q_quant.hip), and
+// the builds the launchers look up, appended -- template arguments; grid and rc 0
+RowsEnv read_rows_env();
+void quant_rows_builds(std::vector<RowsPlan>& out);
+void quant_class_builds(std::vector<RowsPlan>& out);
 int launch_bfp_qmatmul(const QuantArgs& ax, const QuantArgs& ay, const float* x, const float* y, float* out, void* yt,
                        long long B, long long M, long long K, long long N, hipStream_t st, bool softmax = false,
                        const float* mask = nullptr, long long causal_off = -1, int fmt = 0);

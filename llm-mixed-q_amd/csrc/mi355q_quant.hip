@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <stdlib.h>
+
 #include <map>
 #include <mutex>
 #include <utility>
@@ -933,78 +935,68 @@ __global__ __launch_bounds__(256, WPS) void bfp_quant_align_rows_kernel(const Qu
     }
 }
 
+// The environment switches of the row quantiser: A/B runs only (tools/dbg/qrows_ab.py, tools/timing/time_qrows_pre.py,
+// tools/prof/ab_step.py) -- none of them changes a result, the default route needs none.  Read here and nowhere else.
+//   MI355Q_QROWS_GRID=n      workgroups of an int8 launch whose rows are not segmented (several rows a workgroup, the next row's
+//                            loads in flight), rows behind a pre-op included; <= 0: as unset.  Read on every launch.
+//   MI355Q_QROWS_VARIANT=0   round 5's build (every pre-op compiled in, dword stores) on 1024 workgroups, no short-row builds.  Read
+//                            on every launch.
+//   MI355Q_QROWS_SHORT=0     rows of <= 2048 values on the four-slab build, of <= 12288 on the sixteen-slab one.  Latched at the first read.
+RowsEnv read_rows_env() {
+    static const int short_rows = getenv("MI355Q_QROWS_SHORT") ? atoi(getenv("MI355Q_QROWS_SHORT")) : 1;
+    const char *grid = getenv("MI355Q_QROWS_GRID"), *variant = getenv("MI355Q_QROWS_VARIANT");
+    return RowsEnv{grid && atoi(grid) > 0 ? atoi(grid) : 0, variant && atoi(variant) == 0, short_rows};
+}
+
+// every build of bfp_quant_align_rows_kernel that plan_quant_rows (mi355q_quant_plan.h) can ask for, once; the benchmark's comes first
+struct RowsBuild {
+    RowsPlan args;              // the template arguments; grid and rc 0
+    void (*kernel)(QuantArgs, int8_t*, uint8_t*, float*, int, int*, int*, int, MxOut);
+};
+template <int MAXIT, bool FULL, bool SEG, bool MX, int PRE, bool ST16>
+constexpr RowsBuild build() { return {{MAXIT, FULL, SEG, MX, PRE, ST16, 1, 0, 0}, bfp_quant_align_rows_kernel<MAXIT, FULL, SEG, MX, PRE, ST16, 1>}; }
+// plain rows (PRE 0) and rows behind a pre-op: only that pre-op's code compiled in, 16-byte stores where no lane needs a guard
+template <int MAXIT, bool FULL, int PRE> constexpr RowsBuild lean() { return build<MAXIT, FULL, false, false, PRE, FULL>(); }
+template <int MAXIT, int PRE> constexpr RowsBuild segmented() { return build<MAXIT, false, true, false, PRE, false>(); }
+template <int MAXIT, bool FULL> constexpr RowsBuild round5() { return build<MAXIT, FULL, false, false, 1, false>(); }      // MI355Q_QROWS_VARIANT=0
+template <int MAXIT, bool FULL> constexpr RowsBuild mx_operand() { return build<MAXIT, FULL, false, true, 0, false>(); }   // mi355q_mx.hip
+static const RowsBuild rows_builds[] = {
+    lean<4, true, 0>(), lean<4, true, 2>(), lean<4, true, 3>(), lean<4, true, 4>(), lean<1, false, 0>(), lean<1, false, 2>(), lean<1, false, 3>(), lean<1, false, 4>(),
+    lean<2, false, 0>(), lean<2, false, 2>(), lean<2, false, 3>(), lean<2, false, 4>(), lean<4, false, 0>(), lean<4, false, 2>(), lean<4, false, 3>(), lean<4, false, 4>(),
+    lean<8, true, 0>(), lean<8, true, 2>(), lean<8, true, 3>(), lean<8, true, 4>(), lean<8, false, 0>(), lean<8, false, 2>(), lean<8, false, 3>(), lean<8, false, 4>(),
+    lean<12, false, 0>(), lean<12, false, 2>(), lean<12, false, 3>(), lean<12, false, 4>(), lean<16, true, 0>(), lean<16, true, 2>(), lean<16, true, 3>(), lean<16, true, 4>(),
+    lean<16, false, 0>(), lean<16, false, 2>(), lean<16, false, 3>(), lean<16, false, 4>(),
+    segmented<4, 0>(), segmented<4, 2>(), segmented<4, 3>(), segmented<4, 4>(), segmented<8, 0>(), segmented<8, 2>(), segmented<8, 3>(), segmented<8, 4>(),
+    segmented<16, 0>(), segmented<16, 2>(), segmented<16, 3>(), segmented<16, 4>(),
+    round5<4, true>(), round5<4, false>(), round5<8, true>(), round5<8, false>(), round5<16, true>(), round5<16, false>(),
+    mx_operand<4, true>(), mx_operand<1, false>(), mx_operand<2, false>(), mx_operand<4, false>(), mx_operand<8, true>(), mx_operand<8, false>(),
+    mx_operand<16, true>(), mx_operand<16, false>(),
+};
+void quant_rows_builds(std::vector<RowsPlan>& out) {
+    for (const RowsBuild& b : rows_builds) out.push_back(b.args);
+}
+
+static int launch_rows_plan(const RowsPlan& p, hipStream_t st, const QuantArgs& a, int8_t* mt, uint8_t* flag, float* rscale, int exp_offset,
+                            int* list, int* list_to_clear, int bcap, const MxOut& mx) {
+    if (p.rc) return p.rc;
+    for (const RowsBuild& b : rows_builds) {
+        if (!same_build(b.args, p)) continue;
+        hipLaunchKernelGGL(b.kernel, p.grid, 256, 0, st, a, mt, flag, rscale, exp_offset, list, list_to_clear, bcap, mx);
+        return (int)hipGetLastError();
+    }
+    return MI355Q_E_UNSUPPORTED;        // (a plan outside the table: tests/test_quant_rows_plan.py holds the two to each other)
+}
+
 int launch_quant_align_rows(const QuantArgs& a, int8_t* mt, uint8_t* flag, float* rscale, int exp_offset, int* list,
                             int* list_to_clear, hipStream_t st, int bcap) {
-    long long grid = a.rows;
-    if (grid > 65536) grid = 65536;
-    // plain rows: a fixed grid of SIX workgroups per compute unit (what the build without the pre-op code admits: 77 registers),
-    // several rows each with the next row's loads in flight.  Round 6, tools/dbg/qrows_ab.py -> profiles/r06_qrows_variants.txt, at
-    // 4096 x 4096: 20.6 us (round 5: 121 registers, 4 workgroups a compute unit, dword stores) -> 19.2 (no pre-op code, 16-byte
-    // stores) -> 18.0 (six workgroups a compute unit).  MI355Q_QROWS_GRID / MI355Q_QROWS_VARIANT = 0 (round 5's kernel): A/B runs.
-    const int qgrid_env = getenv("MI355Q_QROWS_GRID") ? atoi(getenv("MI355Q_QROWS_GRID")) : 0;
-    const bool old = getenv("MI355Q_QROWS_VARIANT") && atoi(getenv("MI355Q_QROWS_VARIANT")) == 0;
-    const int qgrid = qgrid_env > 0 ? qgrid_env : (old ? 1024 : 1536);
-    if (qgrid > 0 && a.pre_op == 0 && !a.seg_len && grid > qgrid) grid = qgrid;
-    if (qgrid_env > 0 && a.pre_op != 0 && !a.seg_len && grid > qgrid_env) grid = qgrid_env;       // (A/B: rows behind a pre-op take one workgroup each)
-    if (grid < 1) grid = 1;
-    // segmented rows: the round-5 build; rows with a pre-op in front: its code compiled in; plain rows: the lean build.  16-byte
-    // stores where every lane holds a block in every slab (the guarded flavour of that transpose put its scalars in scratch memory)
-#define MI355Q_LAUNCH_ROWS_T(...)                                                                                     \
-    hipLaunchKernelGGL((bfp_quant_align_rows_kernel<__VA_ARGS__>), (unsigned)grid, 256, 0, st, a, mt, flag, rscale, exp_offset, list, \
-                       list_to_clear, bcap)
-#define MI355Q_LAUNCH_ROWS(MAXIT_, FULL_)                                                                             \
-    if (a.seg_len && a.pre_op == MI355Q_PRE_RMSNORM) MI355Q_LAUNCH_ROWS_T(MAXIT_, false, true, false, 2);             \
-    else if (a.seg_len && a.pre_op == MI355Q_PRE_LAYERNORM) MI355Q_LAUNCH_ROWS_T(MAXIT_, false, true, false, 3);      \
-    else if (a.seg_len && a.pre_op) MI355Q_LAUNCH_ROWS_T(MAXIT_, false, true, false, 4);                              \
-    else if (a.seg_len) MI355Q_LAUNCH_ROWS_T(MAXIT_, false, true, false, 0);                                          \
-    else if (old) MI355Q_LAUNCH_ROWS_T(MAXIT_, FULL_, false);                                                         \
-    else if (a.pre_op == MI355Q_PRE_RMSNORM) MI355Q_LAUNCH_ROWS_T(MAXIT_, FULL_, false, false, 2, FULL_);             \
-    else if (a.pre_op == MI355Q_PRE_LAYERNORM) MI355Q_LAUNCH_ROWS_T(MAXIT_, FULL_, false, false, 3, FULL_);           \
-    else if (a.pre_op) MI355Q_LAUNCH_ROWS_T(MAXIT_, FULL_, false, false, 4, FULL_);                                   \
-    else MI355Q_LAUNCH_ROWS_T(MAXIT_, FULL_, false, false, 0, FULL_)
-    // (round 6: rows of <= 1024 / <= 2048 values -- OPT-125m / 350m / 1.3B widths -- hold one / two slabs a lane instead of four guarded
-    //  ones: fewer registers, more rows resident on a compute unit.  MI355Q_QROWS_SHORT=0: the four-slab build for them too, A/B runs)
-    static const int short_rows = getenv("MI355Q_QROWS_SHORT") ? atoi(getenv("MI355Q_QROWS_SHORT")) : 1;
-    if (a.cols == 4096) MI355Q_LAUNCH_ROWS(4, true);            // every lane holds a block in every slab: no guards
-    else if (short_rows && !a.seg_len && !old && a.cols <= 1024) MI355Q_LAUNCH_ROWS(1, false);
-    else if (short_rows && !a.seg_len && !old && a.cols <= 2048) MI355Q_LAUNCH_ROWS(2, false);
-    else if (a.cols <= 4096) MI355Q_LAUNCH_ROWS(4, false);
-    else if (a.cols == 8192) MI355Q_LAUNCH_ROWS(8, true);
-    else if (a.cols <= 8192) MI355Q_LAUNCH_ROWS(8, false);
-    else if (short_rows && !a.seg_len && !old && a.cols <= 12288) MI355Q_LAUNCH_ROWS(12, false);      // (Llama-7B's 11008: 11 slabs of 16)
-    else if (a.cols == 16384) MI355Q_LAUNCH_ROWS(16, true);
-    else if (a.cols <= 16384) MI355Q_LAUNCH_ROWS(16, false);
-    else
-        return MI355Q_E_UNSUPPORTED;
-#undef MI355Q_LAUNCH_ROWS
-#undef MI355Q_LAUNCH_ROWS_T
-    return (int)hipGetLastError();
+    const RowsPlan p = plan_quant_rows(RowsShape{ROWS_INT8, a.rows, a.cols, a.pre_op, a.seg_len != 0}, read_rows_env());
+    return launch_rows_plan(p, st, a, mt, flag, rscale, exp_offset, list, list_to_clear, bcap, MxOut{});
 }
 
 // block_fp -> MX operand (mi355q_mx.hip): rows x K fp32, K % 128 == 0, width <= 5; `bad` is RAISED, never cleared here
 int launch_quant_mx_rows(const QuantArgs& a, uint8_t* c16, uint8_t* c8, uint8_t* sc, int* bad, int* bad_clear, hipStream_t st) {
-    long long grid = a.rows;
-    constexpr int qgrid = 1536;                             // (six resident workgroups a compute unit at 77 registers, like the int8 flavour)
-    if (qgrid > 0 && a.pre_op == 0 && grid > qgrid) grid = qgrid;
-    if (grid > 65536) grid = 65536;
-    if (grid < 1) grid = 1;
-    const MxOut mx{c16, c8, sc, bad, bad_clear};
-#define MI355Q_LAUNCH_MX(MAXIT_, FULL_)                                                                               \
-    hipLaunchKernelGGL((bfp_quant_align_rows_kernel<MAXIT_, FULL_, false, true, 0>), (unsigned)grid, 256, 0, st, a, nullptr, nullptr, nullptr, \
-                       0, nullptr, nullptr, -1, mx)
-    // (round 6: the build without the pre-op code -- this entry never has one -- and the short-row builds, as the int8 flavour)
-    if (a.cols == 4096) MI355Q_LAUNCH_MX(4, true);
-    else if (a.cols <= 1024) MI355Q_LAUNCH_MX(1, false);
-    else if (a.cols <= 2048) MI355Q_LAUNCH_MX(2, false);
-    else if (a.cols <= 4096) MI355Q_LAUNCH_MX(4, false);
-    else if (a.cols == 8192) MI355Q_LAUNCH_MX(8, true);
-    else if (a.cols <= 8192) MI355Q_LAUNCH_MX(8, false);
-    else if (a.cols == 16384) MI355Q_LAUNCH_MX(16, true);
-    else if (a.cols <= 16384) MI355Q_LAUNCH_MX(16, false);
-    else
-        return MI355Q_E_UNSUPPORTED;
-#undef MI355Q_LAUNCH_MX
-    return (int)hipGetLastError();
+    const RowsPlan p = plan_quant_rows(RowsShape{ROWS_MX, a.rows, a.cols, a.pre_op, false}, RowsEnv{});
+    return launch_rows_plan(p, st, a, nullptr, nullptr, nullptr, 0, nullptr, nullptr, -1, MxOut{c16, c8, sc, bad, bad_clear});
 }
 
 // ---------------------------------------------------------------------------------------

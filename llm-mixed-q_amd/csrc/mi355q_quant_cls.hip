@@ -206,25 +206,30 @@ __global__ __launch_bounds__(256, WPS) void bfp_quant_classes_kernel(const Quant
     }
 }
 
+#undef CLS_C1
+
+// every build plan_quant_rows (mi355q_quant_plan.h) can ask for, once
+struct ClassBuild {
+    RowsPlan args;              // MAXIT, FULL and WPS; everything else 0
+    void (*kernel)(QuantArgs, const uint16_t*, int, int, int8_t*, uint8_t*, float*, int, int*, int*, int, uint16_t*);
+};
+template <int MAXIT, bool FULL>
+constexpr ClassBuild build() { return {{MAXIT, FULL, false, false, 0, false, 1, 0, 0}, bfp_quant_classes_kernel<MAXIT, FULL, 1>}; }
+static const ClassBuild class_builds[] = {build<4, true>(), build<4, false>(), build<8, false>(), build<16, false>()};
+void quant_class_builds(std::vector<RowsPlan>& out) {
+    for (const ClassBuild& b : class_builds) out.push_back(b.args);
+}
+
 int launch_quant_classes(const QuantArgs& a, const uint16_t* cmap, int n0, int n1, int8_t* mt, uint8_t* flag, float* rscale,
                          int exp_offset, int* list, int* list_to_clear, uint16_t* bt, hipStream_t st, int bcap) {
-    if (a.rows * a.cols >= (1ll << 30)) return MI355Q_E_UNSUPPORTED;       // (32-bit byte offsets inside the kernel)
-    long long grid = a.rows;
-    const long long cap = a.cols == 4096 ? 1536 : 1024;          // (K = 4096: 75 registers, six workgroups a compute unit)
-    if (grid > cap) grid = cap;
-    if (grid < 1) grid = 1;
-#define MI355Q_LAUNCH_CLS(MAXIT_, FULL_, WPS_)                                                                        \
-    hipLaunchKernelGGL((bfp_quant_classes_kernel<MAXIT_, FULL_, WPS_>), (unsigned)grid, 256, 0, st, a, cmap, n0, n1, mt, flag, rscale, \
-                       exp_offset, list, list_to_clear, bcap, bt)
-    if (a.cols == 4096) MI355Q_LAUNCH_CLS(4, true, 1);
-    else if (a.cols <= 4096) MI355Q_LAUNCH_CLS(4, false, 1);
-    else if (a.cols <= 8192) MI355Q_LAUNCH_CLS(8, false, 1);
-    else if (a.cols <= 16384) MI355Q_LAUNCH_CLS(16, false, 1);
-    else
-        return MI355Q_E_UNSUPPORTED;
-#undef MI355Q_LAUNCH_CLS
-    return (int)hipGetLastError();
+    const RowsPlan p = plan_quant_rows(RowsShape{ROWS_CLASSES, a.rows, a.cols, a.pre_op, false}, RowsEnv{});
+    if (p.rc) return p.rc;
+    for (const ClassBuild& b : class_builds) {
+        if (!same_build(b.args, p)) continue;
+        hipLaunchKernelGGL(b.kernel, p.grid, 256, 0, st, a, cmap, n0, n1, mt, flag, rscale, exp_offset, list, list_to_clear, bcap, bt);
+        return (int)hipGetLastError();
+    }
+    return MI355Q_E_UNSUPPORTED;
 }
-#undef CLS_C1
 
 }  // namespace mi355q

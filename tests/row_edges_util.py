@@ -229,8 +229,8 @@ def edge_counts(x, width, ew=8, bias=127):
 # the layouts the GPU tests run (tests/test_gpu_row_quantiser_edges.py), checked on the CPU by tests/test_row_edges_host.py
 # ---------------------------------------------------------------------------------------------------
 ELEMENT_WIDTHS = (2, 4, 5, 6, 8)
-ELEMENT_SHORT_K = (64, 320, 1024)                          # MAXIT 1
-ELEMENT_LONG_K = (1088, 2048, 2112, 4096, 5120, 8192, 11008, 12352, 16384)   # MAXIT 2, 2, 4, 4 FULL, 8, 8 FULL, 12, 16, 16 FULL
+ELEMENT_SHORT_K = (64, 320, 1024)
+ELEMENT_LONG_K = (1088, 2048, 2112, 4096, 5120, 8192, 11008, 12352, 16384)   # one K per build: planned_build(), tests/test_quant_rows_plan.py
 ELEMENT_LONG_ROWS = 19
 GRID_WALK_ROWS = 429                                       # rows of short(64) the grid-walk case takes (not a multiple of 128)
 
@@ -242,6 +242,40 @@ OVERFLOW_K, OVERFLOW_WIDTH = 1024, 8                       # short(1024) at W8: 
 
 MX_WIDTHS = (4, 5)
 MX_ROWS = {256: 456, 4096: 38}                             # no exception blocks: every 32-group's two blocks share an exponent
+
+
+def rows_env_words(env):
+    """the 3 words of RowsEnv (csrc/mi355q_quant_plan.h) for a set of environment strings: what read_rows_env() makes of them"""
+    return [max(int(env.get("MI355Q_QROWS_GRID", 0)), 0), int("MI355Q_QROWS_VARIANT" in env and int(env["MI355Q_QROWS_VARIANT"]) == 0),
+            int(env.get("MI355Q_QROWS_SHORT", 1))]
+
+
+@functools.lru_cache(maxsize=None)
+def _rows_plan_hook():
+    import ctypes as C
+    from mi355q import _lib
+    fn = C.CDLL(str(_lib.library_path())).mi355q_debug_quant_rows_plan
+    fn.restype = C.c_int
+    fn.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    return fn
+
+
+def rows_plan(kind, rows, cols, pre_op=0, segmented=0, env=None):
+    """[maxit, full, seg, mx, pre, st16, wps, grid, rc] of a row quantiser launch, from mi355q_debug_quant_rows_plan (no GPU, no launch).
+    kind: 0 int8 rows, 1 MX rows, 2 class-aware rows; env: environment strings, None: the process environment"""
+    import ctypes as C
+    out = (C.c_int32 * 12)(*([-99] * 12))
+    words = None if env is None else (C.c_int32 * 3)(*rows_env_words(env))
+    assert _rows_plan_hook()((C.c_int64 * 5)(kind, rows, cols, pre_op, segmented), words, out) == 0
+    assert list(out[9:]) == [0, 0, 0]
+    return [out[i] & 0xFFFFFFFF if i == 7 else out[i] for i in range(9)]
+
+
+def planned_build(K, pre_op=0, segmented=0, kind=0, env=None):
+    """(kind, MAXIT, FULL, SEG, MX, PRE, ST16, WPS): the compiled build a call of the GPU edge tests runs"""
+    plan = rows_plan(kind, ELEMENT_LONG_ROWS, K, pre_op, segmented, env or {})
+    assert plan[8] == 0
+    return (kind, *plan[:7])
 
 
 def _frozen(x):
