@@ -865,6 +865,25 @@ int mi355q_bfp_attention_extend_window(const float* q, const void* kq, const voi
                                        int64_t num_pages, int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
                                        const int64_t* strides, void* stream);
 
+/* Attention sinks (StreamingLLM; csrc/mi355q_sink.h): the *_window calls with the first `sinks` = S keys, 0 <= S <= 16, visible to every query
+ * beside its window -- a query at absolute position p sees keys {0 .. min(S, p + 1) - 1} and {max(0, p - W + 1) .. p}, the `past_key_value`
+ * call with an additive mask that is finfo.min between the sinks and the window too.  Positions are the absolute ones baked into the keys;
+ * the cache is unchanged and the 16-key blocks stay aligned to absolute key index.  Arguments and refusals are those of the *_window calls,
+ * with `sinks` last (outside 0 .. 16: MI355Q_E_BADARG, before any launch); sinks == 0 launches the *_window kernels, the same bits.
+ * A row whose window has left key pair 0 costs one more key pair: the decode partition, the default number of splits and the workspace
+ * are those of min(max_length, span + 32) keys, span = mi355q_bfp_attention_decode_window_span -- mi355q_bfp_attention_decode_workspace_bytes
+ * of that many keys.  A paged call looks up logical page 0 beside the pages of visible keys: table entry 0 must name the row's first page. */
+int mi355q_bfp_attention_decode_sink(const float* q, const void* kq, const void* vq, int32_t G, const int32_t* lengths,
+                                     const int32_t* block_table, int32_t causal, int64_t window, float q_scale, float scale_div,
+                                     float* out, void* workspace, int64_t B, int64_t M, int64_t max_length, int64_t max_pages,
+                                     int64_t num_pages, int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
+                                     const int64_t* strides, int32_t splits, void* stream, int64_t sinks);
+int mi355q_bfp_attention_extend_sink(const float* q, const void* kq, const void* vq, int32_t G, const int32_t* lengths,
+                                     const int32_t* counts, const int32_t* block_table, int32_t causal, int64_t window, float q_scale,
+                                     float scale_div, float* out, int64_t B, int64_t M, int64_t max_length, int64_t max_pages,
+                                     int64_t num_pages, int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
+                                     const int64_t* strides, void* stream, int64_t sinks);
+
 /* ---- the un-blocked quantisers -------------------------------------------------------------------------------------
  * replaces: quantizers/minifloat.py:134-196 (minifloat_ieee_quantizer: implicit leading one, subnormals at the lowest
  *           exponent), :21-86 (minifloat_denorm_quantizer: no implicit one, exponent ceil(log2(|x| + 1e-9)) per element)

@@ -17,6 +17,7 @@
 #include "mi355q_extend.h"
 #include "mi355q_linear_call.h"
 #include "mi355q_kv_call.h"
+#include "mi355q_sink.h"
 #include "mi355q_kv_copy.h"
 #include "mi355q_align_row.h"
 
@@ -902,6 +903,9 @@ int decode(const KvCall& d, const float* q, float* out, void* workspace, float q
     if (d.form & KV_MINIFLOAT)
         return launch_bm_attention_decode(c.aq, c.ap, c.c, q, out, workspace, d.M, d.L, c.causal, q_scale, scale_div, c.strides, d.splits, hs(stream),
                                           d.lengths, c.G);
+    if (d.form & KV_SINKS)
+        return launch_bfp_attention_decode_sink(c.aq, c.ap, c.c, q, out, workspace, d.M, d.L, q_scale, scale_div, c.strides, d.splits, hs(stream),
+                                                d.lengths, c.G, c.pages, c.window, c.sinks);
     return launch_bfp_attention_decode(c.aq, c.ap, c.c, q, out, workspace, d.M, d.L, c.causal, q_scale, scale_div, c.strides, d.splits, hs(stream),
                                        d.lengths, c.G, c.pages, c.window);
 }
@@ -909,6 +913,9 @@ int extend(const KvCall& d, const float* q, float* out, float q_scale, float sca
     KvChecked c;
     int rc;
     if (!kv_call_check(d, c, rc)) return rc;
+    if (d.form & KV_SINKS)
+        return launch_bfp_attention_extend_sink(c.aq, c.ap, c.c, q, out, d.M, d.L, q_scale, scale_div, c.strides, d.lengths, d.counts, hs(stream), c.G,
+                                                c.pages, c.window, c.sinks);
     return launch_bfp_attention_extend(c.aq, c.ap, c.c, q, out, d.M, d.L, c.causal, q_scale, scale_div, c.strides, d.lengths, d.counts, hs(stream),
                                        c.G, c.pages, c.window);
 }
@@ -1188,6 +1195,29 @@ int mi355q_bfp_attention_extend_window(const float* q, const void* kq, const voi
                   q, out, q_scale, scale_div, stream);
 }
 
+// attention sinks (mi355q_sink.h): the *_window calls with the first `sinks` keys (0 .. 16) visible to every query beside its window
+int mi355q_bfp_attention_decode_sink(const float* q, const void* kq, const void* vq, int32_t G, const int32_t* lengths,
+                                     const int32_t* block_table, int32_t causal, int64_t window, float q_scale, float scale_div,
+                                     float* out, void* workspace, int64_t B, int64_t M, int64_t max_length, int64_t max_pages,
+                                     int64_t num_pages, int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
+                                     const int64_t* strides, int32_t splits, void* stream, int64_t sinks) {
+    return decode(KvCall(KV_EXPORTS[KVX_DECODE_SINK]).pools(kq, vq, nullptr, block_table, B, max_pages, num_pages, P, D)
+                      .lens(lengths, nullptr, max_length).query(q, out, workspace, M, G, causal, window, splits).sunk(sinks)
+                      .quant(qk_params, pv_params, strides),
+                  q, out, workspace, q_scale, scale_div, stream);
+}
+
+int mi355q_bfp_attention_extend_sink(const float* q, const void* kq, const void* vq, int32_t G, const int32_t* lengths,
+                                     const int32_t* counts, const int32_t* block_table, int32_t causal, int64_t window, float q_scale,
+                                     float scale_div, float* out, int64_t B, int64_t M, int64_t max_length, int64_t max_pages,
+                                     int64_t num_pages, int64_t P, int64_t D, const int32_t* qk_params, const int32_t* pv_params,
+                                     const int64_t* strides, void* stream, int64_t sinks) {
+    return extend(KvCall(KV_EXPORTS[KVX_EXTEND_SINK]).pools(kq, vq, nullptr, block_table, B, max_pages, num_pages, P, D)
+                      .lens(lengths, counts, max_length).query(q, out, nullptr, M, G, causal, window, 0).sunk(sinks)
+                      .quant(qk_params, pv_params, strides),
+                  q, out, q_scale, scale_div, stream);
+}
+
 // diagnostic hook, not part of include/mi355q.h: what kv_call_check -- the function every export above calls -- makes of a call,
 // without launching (no HIP call: works without a GPU).  id: a KvExport; a: 14 addresses, never dereferenced (kq, vq, stage, k, v, q,
 // out, workspace, lengths, counts, block_table, k_bytes, v_bytes, stage_bytes), then B, C, max_pages, num_pages, P, D, M, L, n, G,
@@ -1196,10 +1226,12 @@ int mi355q_bfp_attention_extend_window(const float* q, const void* kq, const voi
 // the four strides.
 // mi355q_debug_kv_call knows the 25 ids recorded in tests/golden/kv_api_codes.json, 0 .. KVX_KV8P_DECODE, and refuses every other as it
 // always has; mi355q_debug_kv_call_all is the same function over every id of KvExport (the block_minifloat exports behind them, then
-// -- behind KVX_NONE_27, an id it has always refused and still does -- the 4-bit-mantissa exports, 28 .. 31).
+// -- behind KVX_NONE_27, an id it has always refused and still does -- the 4-bit-mantissa exports, 28 .. 31, then -- behind KVX_NONE_32,
+// refused likewise -- the attention-sink exports, 33 and 34.  For those two ids, and for no other, `a` holds a 28th word, a[27] = sinks,
+// and out[9] stays the window: the normalised sinks are returned in place of n, out[7], which no attention export has).
 static int debug_kv_call(int32_t id, int32_t ids, const int64_t a[27], const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
                          int64_t out[18]) {
-    if (id < 0 || id >= ids || id == KVX_NONE_27 || !a || !out) return MI355Q_E_BADARG;
+    if (id < 0 || id >= ids || kvx_hole(id) || !a || !out) return MI355Q_E_BADARG;
     const auto p = [a](int i) { return reinterpret_cast<const void*>(static_cast<uintptr_t>(a[i])); };
     const auto p32 = [a](int i) { return reinterpret_cast<const int32_t*>(static_cast<uintptr_t>(a[i])); };
     const auto p64 = [a](int i) { return reinterpret_cast<const int64_t*>(static_cast<uintptr_t>(a[i])); };
@@ -1207,11 +1239,13 @@ static int debug_kv_call(int32_t id, int32_t ids, const int64_t a[27], const int
     d.cache(p(0), p(1), p(2), a[14], a[15], a[19]).pools(p(0), p(1), p(2), p32(10), a[14], a[16], a[17], a[18], a[19]).sizes(p64(11), p64(12), p64(13))
         .rows(p(3), p(4), a[22]).lens(p32(8), p32(9), a[21]).query(p(5), p(6), p(7), a[20], (int32_t)a[23], (int32_t)a[24], a[25], (int32_t)a[26])
         .quant(qk_params, pv_params, strides);
+    const bool sunk = (d.form & KV_SINKS) != 0;
+    if (sunk) d.sunk(a[27]);
     KvChecked c;
     int rc;
     const bool go = kv_call_check(d, c, rc);
     const int64_t cap = kv_mantissas(d.storage) ? c.cp.C : c.c.C;
-    const int64_t words[18] = {rc, go, d.B, cap, d.D, d.M, d.L, d.n, c.G, c.window, c.pg.lg_p, c.pages != nullptr, c.causal, c.strides != nullptr,
+    const int64_t words[18] = {rc, go, d.B, cap, d.D, d.M, d.L, sunk ? c.sinks : d.n, c.G, c.window, c.pg.lg_p, c.pages != nullptr, c.causal, c.strides != nullptr,
                                c.st[0], c.st[1], c.st[2], c.st[3]};
     for (int i = 0; i < 18; ++i) out[i] = words[i];
     return 0;

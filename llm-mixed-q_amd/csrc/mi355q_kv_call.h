@@ -1,4 +1,4 @@
-// The argument check of the KV-cache exports (mi355q_api.hip, from mi355q_bfp_kv_cache_bytes to mi355q_bfp_attention_extend_window):
+// The argument check of the KV-cache exports (mi355q_api.hip, from mi355q_bfp_kv_cache_bytes to mi355q_bfp_attention_extend_sink):
 // ONE checked descriptor for what used to be 21 copies of shape check, NULL check, quantiser decoding, alignment check and stride loop.
 // Host code only -- no kernel, no launch, no HIP call: an export fills a KvCall, kv_call_check() refuses it with the export's return
 // code or fills a KvChecked with what the launchers of mi355q_decode.h / mi355q_extend.h / mi355q_kvp.h / mi355q_kvbm.h take, and the export launches.
@@ -86,6 +86,7 @@ enum : unsigned {
                         // block_table == NULL is the contiguous cache of max_pages * P keys
     KV_MINIFLOAT = 8,   // the mi355q_bm_* exports: qk_params / pv_params are block_minifloat's {width, exponent width, exponent bias
                         // width} (bm_quant_args) and the launchers are those of mi355q_kvbm.h; storage and layout stay KV_BF16's
+    KV_SINKS = 16,      // the *_sink exports (with KV_WINDOW): sinks outside 0 .. 16 is BADARG; the launchers are those of mi355q_sink.h
 };
 // the exports in the order of include/mi355q.h (mi355q_debug_kv_call's export id)
 enum KvExport {
@@ -95,8 +96,11 @@ enum KvExport {
     KVX_KV8P_BYTES, KVX_KV8P_APPEND, KVX_KV8P_DECODE_FP32, KVX_KV8P_DECODE, KVX_BM_APPEND, KVX_BM_DECODE,
     KVX_NONE_27,        // no export: mi355q_debug_kv_call_all has always refused id 27, the first id behind the block_minifloat
                         // exports, and tests/test_kvbm_host.py holds it to that -- the id stays refused and the next exports start at 28
-    KVX_KV4_CACHE_BYTES, KVX_KV4_APPEND, KVX_KV4_DECODE_FP32, KVX_DECODE_KV4, KVX_COUNT
+    KVX_KV4_CACHE_BYTES, KVX_KV4_APPEND, KVX_KV4_DECODE_FP32, KVX_DECODE_KV4,
+    KVX_NONE_32,        // no export either: tests/test_kv4_host.py holds id 32, the first id behind the 4-bit-mantissa exports, refused
+    KVX_DECODE_SINK, KVX_EXTEND_SINK, KVX_COUNT
 };
+constexpr bool kvx_hole(int id) { return id == KVX_NONE_27 || id == KVX_NONE_32; }
 
 // one call of a KV-cache export: the form (what KV_EXPORTS says of the export), then the raw arguments; what an export does not
 // take stays 0 / NULL.  L is the host's length: L of the uniform exports, max_length of the others.  k / v: the append's new rows or
@@ -114,6 +118,7 @@ struct KvCall {
     int32_t splits;
     const int32_t *qk_params, *pv_params;
     const int64_t* strides;
+    int64_t sinks;              // the *_sink exports' (KV_SINKS); behind every field the other exports fill
 
     KvCall& cache(const void* kq_, const void* vq_, const void* stage_, int64_t B_, int64_t C_, int64_t D_) {
         kq = kq_; vq = vq_; stage = stage_; B = B_; C = C_; D = D_;
@@ -141,6 +146,10 @@ struct KvCall {
         q = q_; out = out_; workspace = workspace_; M = M_; G = G_; causal = causal_; window = window_; splits = splits_;
         return *this;
     }
+    KvCall& sunk(int64_t sinks_) {
+        sinks = sinks_;
+        return *this;
+    }
     KvCall& quant(const int32_t* qk, const int32_t* pv, const int64_t* strides_) {
         qk_params = qk; pv_params = pv; strides = strides_;
         return *this;
@@ -159,6 +168,8 @@ constexpr KvCall KV_EXPORTS[KVX_COUNT] = {
     {KV_BF16, KV_APPEND, KV_LENGTHS | KV_MINIFLOAT}, {KV_BF16, KV_DECODE, KV_LENGTHS | KV_MINIFLOAT},
     {KV_BF16, KV_BYTES, 0},           // (KVX_NONE_27: never looked up)
     {KV_INT4, KV_BYTES, 0},           {KV_INT4, KV_APPEND, KV_LENGTHS}, {KV_INT4, KV_DEQUANT, KV_LENGTHS}, {KV_INT4, KV_DECODE, KV_LENGTHS},
+    {KV_BF16, KV_BYTES, 0},           // (KVX_NONE_32: never looked up)
+    {KV_PAGED, KV_DECODE, KV_LENGTHS | KV_WINDOW | KV_SINKS}, {KV_PAGED, KV_EXTEND, KV_LENGTHS | KV_WINDOW | KV_SINKS},
 };
 
 // what the launchers take of a call that passed
@@ -170,6 +181,7 @@ struct KvChecked {
     QuantArgs aq, ap, ak, av;   // Q and P (decode, extend); the cached K and V (append; mantissa storage: every operation)
     int G, causal;              // normalised: 0 the ungrouped kernels; causal 0 / 1
     long long window;           // clamped to L; 0: none
+    long long sinks;            // the *_sink exports': 0 .. 16; else 0
     long long st[4];
     const long long* strides;   // st or NULL (decode / extend: fill_qo_strides' contiguous default); the append's are always st
 };
@@ -190,6 +202,7 @@ inline bool kv_call_check(const KvCall& d, KvChecked& k, int& rc) {
     if (d.op == KV_BYTES && (!d.k_bytes || !d.v_bytes || !d.stage_bytes)) return stop(MI355Q_E_BADARG);
     if (attn && (d.M < 0 || d.L < 0 || d.splits < 0 || d.G < ((d.form & KV_GROUPED) ? 1 : 0) || (windowed && (d.window < 1 || !d.causal))))
         return stop(MI355Q_E_BADARG);
+    if (attn && (d.form & KV_SINKS) && (d.sinks < 0 || d.sinks > 16)) return stop(MI355Q_E_BADARG);
     // the cache's shape; `cap`: the keys a row can hold
     if (!paged_form) rc = decode_cache_shape(d.B, d.C, d.D);
     else if (windowed) rc = window_cache_shape(d.B, d.max_pages, d.num_pages, d.P, d.D, d.block_table, &k.pg);
@@ -246,6 +259,7 @@ inline bool kv_call_check(const KvCall& d, KvChecked& k, int& rc) {
         }
         k.causal = windowed || d.causal != 0;
         k.window = !windowed ? 0 : d.window > d.L ? d.L : d.window;      // (a window over every key the call can hold: the same mask)
+        k.sinks = (d.form & KV_SINKS) ? d.sinks : 0;
     }
     void *const kq = const_cast<void*>(d.kq), *const vq = const_cast<void*>(d.vq);         // (the one cast; the element type is the storage's)
     float* const stage = static_cast<float*>(const_cast<void*>(d.stage));

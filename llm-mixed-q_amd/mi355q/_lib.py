@@ -104,6 +104,10 @@ SIGNATURES = {
                                                      _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp]),
     "mi355q_bfp_attention_extend_window": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i64, C.c_float, C.c_float, _vp, _i64, _i64,
                                                      _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "mi355q_bfp_attention_decode_sink": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i64, C.c_float, C.c_float, _vp, _vp, _i64, _i64,
+                                                   _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _i64]),
+    "mi355q_bfp_attention_extend_sink": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i64, C.c_float, C.c_float, _vp, _i64, _i64,
+                                                   _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64]),
     "mi355q_bfp_kv8_cache_bytes": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp]),
     "mi355q_bfp_kv8_append": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "mi355q_bfp_kv8_decode_fp32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),

@@ -245,6 +245,7 @@ class TinyLlamaConfig:
     max_positions: int = 128
     rms_eps: float = 1e-6
     init_std: float = 0.02
+    attention_sinks: int = None    # attention sinks (StreamingLLM; needs sliding_window): the first `attention_sinks` keys stay visible, 0 .. 16; None: none
     sliding_window: int = None     # sliding-window attention (Mistral): a query sees its last `sliding_window` keys, its own included; None: all
     num_kv_heads: int = None       # grouped-query attention: K / V heads, each shared by num_heads // num_kv_heads query heads; None: num_heads
 
@@ -252,6 +253,11 @@ class TinyLlamaConfig:
         w = self.sliding_window
         if w is not None and (isinstance(w, bool) or not isinstance(w, int) or w < 1):
             raise ValueError(f"TinyLlamaConfig: sliding_window = {w!r} is not an integer >= 1")
+        s = self.attention_sinks
+        if s is not None and (isinstance(s, bool) or not isinstance(s, int) or not 0 <= s <= ops.SINKS_MAX):
+            raise ValueError(f"TinyLlamaConfig: attention_sinks = {s!r} is not an integer in 0 .. {ops.SINKS_MAX}")
+        if s is not None and w is None:
+            raise ValueError(f"TinyLlamaConfig: attention_sinks = {s!r} without sliding_window: sinks are what a windowed query keeps seeing")
         if self.num_kv_heads is not None and (self.num_kv_heads < 1 or self.num_heads % self.num_kv_heads != 0):
             raise ValueError(f"TinyLlamaConfig: num_kv_heads = {self.num_kv_heads} does not divide num_heads = {self.num_heads}")
 
@@ -273,12 +279,16 @@ class _RMSNorm(nn.Module):
         return self.weight * (x * torch.rsqrt(v + self.eps)).to(x.dtype)
 
 
-def _causal_mask(n: int, L: int, window, dtype, device):
+def _causal_mask(n: int, L: int, window, dtype, device, sinks=None):
     """the additive mask [n, L] of n queries at the last n of L positions (the offset of modeling_llama.py:53-79): finfo.min above the
-    horizon and, with a sliding window, below it -- query i at p = L - n + i sees keys max(0, p - window + 1) .. p"""
+    horizon and, with a sliding window, below it -- query i at p = L - n + i sees keys max(0, p - window + 1) .. p -- but for the first
+    `sinks` columns, whose lower mask is lifted (attention sinks: keys 0 .. sinks - 1 stay visible up to the horizon)"""
     mask = torch.full((n, L), torch.finfo(dtype).min, device=device).triu(1 + L - n)
     if window is not None:
-        mask = mask + torch.full((n, L), torch.finfo(dtype).min, device=device).tril(L - n - int(window))
+        below = torch.full((n, L), torch.finfo(dtype).min, device=device).tril(L - n - int(window))
+        if sinks:
+            below[:, :int(sinks)] = 0
+        mask = mask + below
     return mask
 
 
@@ -465,7 +475,7 @@ class TinyLlamaForCausalLM(nn.Module):
         B, T = input_ids.shape
         position_ids = torch.arange(T, device=input_ids.device)[None].expand(B, T)
         x = self.embed_tokens(input_ids)
-        mask = _causal_mask(T, T, self.cfg.sliding_window, x.dtype, x.device)[None, None]
+        mask = _causal_mask(T, T, self.cfg.sliding_window, x.dtype, x.device, self.cfg.attention_sinks)[None, None]
         for layer in self.layers:
             x = layer(x, mask, position_ids)
         # (unquantised, modeling_llama.py:772,866: fp32-equivalent on the bf16 MFMA -- quantized_modules.linear.fp32_linear; "vendor" = F.linear)
@@ -506,6 +516,8 @@ class DecodeState:
     window= to the decode and extend functions; a prompt (or a ragged prefill with a row) longer than W runs on the windowed extend
     kernel behind its own append, whatever `extend` says -- the prefill attention function has no window; mode "fp32" adds the window to
     its additive mask.  A paged state gives back, after every call, the pages no later query can see (PagedKVCache.trim).
+    Attention sinks (model.cfg.attention_sinks = S, with a sliding window): every route above passes sinks= next to window=, mode "fp32"
+    lifts the mask's first S columns, and a paged state's trim keeps logical page 0.
     Paged caches: PagedDecodeState below (this constructor's parameters stay as they are)."""
     paged = False
 
@@ -530,6 +542,7 @@ class DecodeState:
             raise NotImplementedError("incremental decoding of head-sharded models")
         self.mode, self.batch, self.length = mode, int(batch), 0
         self.window = getattr(model.cfg, "sliding_window", None)
+        self.sinks = getattr(model.cfg, "attention_sinks", None) or None       # (0 is the plain window)
         self.extend = bool(extend) and mode == "block_fp"
         self.lengths, self.ragged, self._call = [0] * self.batch, self.paged, None
         self.capacity = (int(capacity) + 15) // 16 * 16
@@ -679,7 +692,7 @@ class DecodeState:
             # sliding window: the pages wholly behind every later query's window go back to the pool, in every layer
             for c in self.kv:
                 heads = c.B // self.batch
-                c.trim([l for l in self.lengths for _ in range(heads)], self.window)
+                c.trim([l for l in self.lengths for _ in range(heads)], self.window, self.sinks or 0)
 
     def _reference_steps(self, q, k, v, c0, c1, scale_div, style):
         """the reference's steps (modeling_llama.py:309-344) for n queries at the last n of k's L positions: the two products through
@@ -695,7 +708,7 @@ class DecodeState:
         w = get_quantized_func(style, c0)(q, k.transpose(-1, -2), config=c0)
         if scale_div:
             w = w / scale_div
-        mask = _causal_mask(n, L, self.window, w.dtype, w.device)
+        mask = _causal_mask(n, L, self.window, w.dtype, w.device, self.sinks)
         w = torch.max(w + mask, w.new_full((), torch.finfo(w.dtype).min))
         p = F.softmax(w, dim=-1, dtype=torch.float32).to(q.dtype)
         return get_quantized_func(style, c1)(p, v, config=c1).view(B, nh, n, hd)
@@ -706,6 +719,8 @@ class DecodeState:
         gq = {} if k.shape[1] == nh else dict(group=nh // k.shape[1])      # (grouped queries: k, v have the KV heads only)
         if self.window is not None:
             gq["window"] = self.window
+            if self.sinks:
+                gq["sinks"] = self.sinks
         full = all(c == n for c in call["counts"])
         cache.append(k, v, lengths=self.rows_before, counts=None if full else self._rows_counts, max_length=call["max_before"])
         if call["route"] == "decode":
@@ -747,6 +762,8 @@ class DecodeState:
             gq = {} if k.shape[1] == nh else dict(group=nh // k.shape[1])  # (grouped queries: k, v have the KV heads only)
             if self.window is not None:
                 gq["window"] = self.window
+                if self.sinks:
+                    gq["sinks"] = self.sinks
                 wide = wide or (self.length == 0 and n > self.window)      # (a prompt longer than the window: the windowed extend kernel)
             if self.length == 0 and isinstance(cache, ops.MinifloatKVCache):
                 # the prompt of a block_minifloat layer: no one-pass attention function, the steps of the layer's full forward

@@ -1911,21 +1911,25 @@ class PagedKVCache(_PagedHost):
         self.kq, self.vq, self.stage = self._zeroed("mi355q_bfp_kv_paged_bytes", self.num_pages, self.page_size, self.B, self.D)
         self._init_table(pad_page)
 
-    def trim(self, lengths, window: int) -> None:
+    def trim(self, lengths, window: int, sinks: int = 0) -> None:
         """sliding-window attention: row b (lengths[b] keys, host ints, one per cache row) gives back every logical page i with
         (i + 1) * page_size <= lengths[b] - window + 1 -- keys no query at a position >= lengths[b] sees, so no later windowed call reads
         them (the windowed kernels look up only pages that hold a visible key).  Their table entries become `pad_page`, `held` keeps
         None in their place; a page another row still holds (share_prefix) stays with that row.  One copy_ of the table when anything
-        changed.  Only for rows that are from here on read with this window (or a smaller one)."""
+        changed.  Only for rows that are from here on read with this window (or a smaller one).
+        sinks > 0 (attention sinks, bfp_attention_decode): logical page 0, which holds the sinks, is never given back -- the sink kernels
+        look it up for every row whose window has left it; the rest follows the rule above."""
         if isinstance(window, bool) or not isinstance(window, int) or window < 1:
             raise ValueError(f"PagedKVCache.trim: window = {window!r} is not an integer >= 1")
+        if isinstance(sinks, bool) or not isinstance(sinks, int) or not 0 <= sinks <= SINKS_MAX:
+            raise ValueError(f"PagedKVCache.trim: sinks = {sinks!r} is not an integer in 0 .. {SINKS_MAX}")
         lengths = [int(n) for n in lengths]
         if len(lengths) != self.B:
             raise ValueError(f"PagedKVCache.trim: {len(lengths)} lengths for {self.B} cache rows")
         changed = False
         for b, n in enumerate(lengths):
             held = self.held[b]
-            for i in range(min(max(n - window + 1, 0) // self.page_size, len(held))):
+            for i in range(1 if sinks else 0, min(max(n - window + 1, 0) // self.page_size, len(held))):
                 p = held[i]
                 if p is None:
                     continue
@@ -2126,7 +2130,7 @@ class PagedPackedKVCache(_PagedHost):
         self.k8, self.v8, self.stage = self._zeroed("mi355q_bfp_kv8_paged_bytes", self.num_pages, self.page_size, self.B, self.D)
         self._init_table(pad_page)
 
-    def trim(self, lengths, window: int) -> None:
+    def trim(self, lengths, window: int, sinks: int = 0) -> None:
         raise NotImplementedError("PagedPackedKVCache.trim: no sliding-window kernel reads a PagedPackedKVCache (int8 mantissas), so there is "
                                   "nothing to trim for; windows need a KVCache or a PagedKVCache")
 
@@ -2152,14 +2156,19 @@ class PagedPackedKVCache(_PagedHost):
 _PAGED_NEEDS_LENGTHS = "a paged cache is always addressed in the ragged form: lengths= and max_length= (there is no uniform paged launch)"
 
 
-def _window_check(window, causal):
-    """the reasons a call declines `window`, None when it takes it (None: no window)"""
+SINKS_MAX = 16      # attention sinks: every sink lies in key tile 0 (csrc/mi355q_sink.h)
+
+
+def _window_check(window, causal, sinks=None):
+    """the reasons a call declines `window` or `sinks`, None when it takes them (None: no window, no sinks)"""
     if window is None:
-        return None
+        return None if sinks is None else f"sinks = {sinks!r} without window: attention sinks are the first keys a WINDOWED query keeps seeing"
     if isinstance(window, bool) or not isinstance(window, int) or window < 1:
         return f"window = {window!r} is not an integer >= 1 (the keys a query sees, its own included)"
     if not causal:
         return "window with causal=False: a sliding window bounds a causal query to its last `window` keys"
+    if sinks is not None and (isinstance(sinks, bool) or not isinstance(sinks, int) or not 0 <= sinks <= SINKS_MAX):
+        return f"sinks = {sinks!r} is not an integer in 0 .. {SINKS_MAX} (the first keys every query sees beside its window)"
     return None
 
 
@@ -2174,11 +2183,11 @@ def _window_lengths(cache, lengths, max_length):
     return kept[1], cache.length
 
 
-def _decode_check(q, cache, splits=None, lengths=None, max_length=None, group=1, *, causal=True, window=None):
+def _decode_check(q, cache, splits=None, lengths=None, max_length=None, group=1, *, causal=True, window=None, sinks=None):
     """the reasons bfp_attention_decode declines (q, cache), None when it takes them; nothing here touches the device"""
     if not isinstance(cache, (KVCache, PagedKVCache)):
         return "cache is not a KVCache"
-    why = _window_check(window, causal)
+    why = _window_check(window, causal, sinks)
     if why is not None:
         return why
     if isinstance(cache, PagedKVCache) and lengths is None:
@@ -2241,10 +2250,11 @@ def _decode_workspace(q, cache, M, D, group, sp):
     return ws
 
 
-def _cached_attention(op, q, cache, causal, scale_div, q_scale, token_major, splits, lengths, counts, max_length, group, window):
+def _cached_attention(op, q, cache, causal, scale_div, q_scale, token_major, splits, lengths, counts, max_length, group, window, sinks=None):
     """bfp_attention_decode (op "decode") and bfp_attention_extend ("extend") behind their checks: the ROUTE -- the export
     mi355q_bfp_attention_<op><form> and its arguments, from the cache's kind, lengths, group and window -- and the call.
       form       chosen when                                      takes, next to what every export takes
+      _sink      window is given and sinks is truthy              as _window, and `sinks` behind the stream (sinks None or 0: _window itself)
       _window    window is given (any bf16 cache)                 G, lengths (the uniform call brings cache.length as a device tensor),
                                                                   the block table or NULL, causal = 1, window, the paged dimensions
                                                                   (a contiguous cache: 1 page of `capacity` keys)
@@ -2266,7 +2276,7 @@ def _cached_attention(op, q, cache, causal, scale_div, q_scale, token_major, spl
     strides = (ctypes.c_int64 * 4)(qsb, qsm, osb, osm)
     paged, packed, windowed = isinstance(cache, _PagedHost), isinstance(cache, (PackedKVCache, PagedPackedKVCache)), window is not None
     minifloat, nibble = isinstance(cache, MinifloatKVCache), isinstance(cache, NibbleKVCache)
-    form = "bm" if minifloat else "_kv4" if nibble else "_window" if windowed else "_kv8_paged" if paged and packed else "_paged" if paged else "_kv8" if packed else "_grouped" if group != 1 else \
+    form = "bm" if minifloat else "_kv4" if nibble else "_sink" if windowed and sinks else "_window" if windowed else "_kv8_paged" if paged and packed else "_paged" if paged else "_kv8" if packed else "_grouped" if group != 1 else \
         "_ragged" if decode and lengths is not None else ""
     if windowed or packed or minifloat or nibble:
         lengths, L = _window_lengths(cache, lengths, max_length)
@@ -2286,13 +2296,14 @@ def _cached_attention(op, q, cache, causal, scale_div, q_scale, token_major, spl
         _ptr(q3), *(_ptr(getattr(cache, name)) for name in cache.STORAGE), *which,
         *((1, int(window)) if windowed else (int(bool(causal)),)), float(q_scale) if q_scale else 0.0, float(scale_div) if scale_div else 0.0,
         _ptr(out), *((_ptr(_decode_workspace(q, cache, M, D, group, sp)),) if decode else ()), cache.B, M, L, *capacity, D,
-        ctypes.addressof(cache._pa), ctypes.addressof(cache._pb), ctypes.addressof(strides), *((int(splits or 0),) if decode else ()), sp))
+        ctypes.addressof(cache._pa), ctypes.addressof(cache._pb), ctypes.addressof(strides), *((int(splits or 0),) if decode else ()), sp,
+        *((int(sinks),) if form == "_sink" else ())))
     return out
 
 
 def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True, scale_div: float = None, q_scale: float = None,
                          token_major: bool = False, splits: int = None, lengths: torch.Tensor = None, max_length: int = None,
-                         group: int = 1, window: int = None):
+                         group: int = 1, sinks: int = None, window: int = None):
     """The attention core (modeling_llama.py:309-344) for the LAST M <= 16 positions of a sequence whose L = cache.length keys are in
     `cache` (their own keys included: append first): q [..., M, D] fp32; causal: query i sees keys 0 .. L - M + i, else all L.
     scale_div / q_scale / token_major as bfp_attention.  Keys are split over `splits` workgroups per head (default: decode_splits);
@@ -2313,6 +2324,12 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     visible key pair on: the default is decode_splits(rows, span, D), and work and workspace follow W, not the length.
     W >= max_length (cache.length) gives the bits of window=None.  A paged cache may have trimmed the pages behind the window
     (PagedKVCache.trim).
+    Attention sinks (`sinks` = S, 0 .. 16, only with `window`; StreamingLLM): the first S keys stay visible beside the window -- the query
+    at p sees keys {0 .. min(S, p + 1) - 1} and {max(0, p - W + 1) .. p}, the reference's call with a mask that is finfo.min BETWEEN the
+    sinks and the window too -- so a model trained with full attention can decode on an O(W) cache.  Positions are the absolute ones
+    baked into the keys; nothing is re-rotated.  A row whose window has left key pair 0 costs one more key pair; the splits cover
+    min(max_length, span + 32) keys.  sinks=None and sinks=0 are the windowed call itself: the same export, the same bits.  A paged
+    cache keeps logical page 0 (PagedKVCache.trim(..., sinks=S)).  The mantissa and minifloat caches refuse `sinks` as they refuse `window`.
     `cache` may be a PackedKVCache (int8 mantissas, 17/32 of the K / V bytes): the same keywords with the same meaning and the bits
     of the same call on a KVCache holding the same keys; `window` is refused (NotImplementedError).  Its paged form is a
     PagedPackedKVCache (always with `lengths`), with the same bits and the same refusal.
@@ -2322,33 +2339,33 @@ def bfp_attention_decode(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     `cache` may be a MinifloatKVCache (both products block_minifloat): the same keywords with the same meaning, Q and P through the
     block_minifloat quantisers of the cache's parameters; `window` is refused (NotImplementedError)."""
     if isinstance(cache, MinifloatKVCache):
-        if window is not None:
+        if window is not None or sinks is not None:             # (sinks come with a window: the same refusal)
             raise NotImplementedError("mi355q.bfp_attention_decode: no sliding-window kernel reads a MinifloatKVCache (block_minifloat); "
                                       "window= needs a KVCache or a PagedKVCache")
         why = _decode_call_check(q, cache, splits, lengths, max_length, group)
     elif isinstance(cache, NibbleKVCache):
-        if window is not None:
+        if window is not None or sinks is not None:             # (sinks come with a window: the same refusal)
             raise NotImplementedError("mi355q.bfp_attention_decode: no sliding-window kernel reads a NibbleKVCache (4-bit mantissas); "
                                       "window= needs a KVCache or a PagedKVCache")
         why = _decode_call_check(q, cache, splits, lengths, max_length, group)
     elif isinstance(cache, (PackedKVCache, PagedPackedKVCache)):
-        if window is not None:
+        if window is not None or sinks is not None:             # (sinks come with a window: the same refusal)
             raise NotImplementedError(f"mi355q.bfp_attention_decode: no sliding-window kernel reads a {type(cache).__name__} (int8 mantissas); "
                                       "window= needs a KVCache or a PagedKVCache")
         why = _PAGED_NEEDS_LENGTHS if cache.RAGGED_ONLY and lengths is None else _decode_call_check(q, cache, splits, lengths, max_length, group)
     else:
-        why = _decode_check(q, cache, splits, lengths, max_length, group, causal=causal, window=window)
+        why = _decode_check(q, cache, splits, lengths, max_length, group, causal=causal, window=window, sinks=sinks)
     if why is not None:
         raise ValueError(f"mi355q.bfp_attention_decode: {why}")
-    return _cached_attention("decode", q, cache, causal, scale_div, q_scale, token_major, splits, lengths, None, max_length, group, window)
+    return _cached_attention("decode", q, cache, causal, scale_div, q_scale, token_major, splits, lengths, None, max_length, group, window, sinks)
 
 
 
-def _extend_check(q, cache, lengths=None, counts=None, max_length=None, group=1, *, causal=True, window=None):
+def _extend_check(q, cache, lengths=None, counts=None, max_length=None, group=1, *, causal=True, window=None, sinks=None):
     """the reasons bfp_attention_extend declines (q, cache), None when it takes them; nothing here touches the device"""
     if not isinstance(cache, (KVCache, PagedKVCache)):
         return "cache is not a KVCache"
-    why = _window_check(window, causal)
+    why = _window_check(window, causal, sinks)
     if why is not None:
         return why
     if isinstance(cache, PagedKVCache) and lengths is None:
@@ -2381,7 +2398,7 @@ def _extend_check(q, cache, lengths=None, counts=None, max_length=None, group=1,
 
 def bfp_attention_extend(q: torch.Tensor, cache: KVCache, *, causal: bool = True, scale_div: float = None, q_scale: float = None,
                          token_major: bool = False, lengths: torch.Tensor = None, counts: torch.Tensor = None, max_length: int = None,
-                         group: int = 1, window: int = None):
+                         group: int = 1, sinks: int = None, window: int = None):
     """Chunked prefill: the attention core (modeling_llama.py:309-344) for the LAST M positions -- any M >= 1 -- of a sequence whose
     L = cache.length keys are in `cache` (their own keys included: append first), the reference's `past_key_value` call with M new
     tokens behind a past of L - M.  q [..., M, D] fp32; causal: query i sees keys 0 .. L - M + i, else all L.  scale_div / q_scale /
@@ -2395,7 +2412,9 @@ def bfp_attention_extend(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     and `counts` one entry per CACHE row; each query row gets the bits group=1 gives it on a cache holding the repeated K / V.
     `cache` may be a PagedKVCache (always with `lengths`): the bits of the same call on a KVCache holding the same keys.
     Sliding window (`window` = W >= 1, causal only) as bfp_attention_decode: row b's query i, at p = lengths[b] - counts[b] + i, sees
-    keys max(0, p - W + 1) .. p; a block of 64 queries walks the keys from the 32-key step of its first query's lower bound on."""
+    keys max(0, p - W + 1) .. p; a block of 64 queries walks the keys from the 32-key step of its first query's lower bound on.
+    Attention sinks (`sinks`, only with `window`) as bfp_attention_decode: a block of queries whose walk begins behind step 0 takes step 0
+    first, for the sinks alone."""
     if isinstance(cache, MinifloatKVCache):
         raise NotImplementedError("mi355q.bfp_attention_extend: no extend kernel reads a MinifloatKVCache (block_minifloat); chunked prefill "
                                   "needs a KVCache or a PagedKVCache")
@@ -2405,10 +2424,10 @@ def bfp_attention_extend(q: torch.Tensor, cache: KVCache, *, causal: bool = True
     if isinstance(cache, (PackedKVCache, PagedPackedKVCache)):
         raise NotImplementedError(f"mi355q.bfp_attention_extend: no extend kernel reads a {type(cache).__name__} (int8 mantissas); chunked prefill "
                                   "needs a KVCache or a PagedKVCache")
-    why = _extend_check(q, cache, lengths, counts, max_length, group, causal=causal, window=window)
+    why = _extend_check(q, cache, lengths, counts, max_length, group, causal=causal, window=window, sinks=sinks)
     if why is not None:
         raise ValueError(f"mi355q.bfp_attention_extend: {why}")
-    return _cached_attention("extend", q, cache, causal, scale_div, q_scale, token_major, None, lengths, counts, max_length, group, window)
+    return _cached_attention("extend", q, cache, causal, scale_div, q_scale, token_major, None, lengths, counts, max_length, group, window, sinks)
 
 
 class TiledBf16:

@@ -272,18 +272,19 @@ def decode_cache_params(config_qk, config_pv, head_dim):
 
 
 def attention_decode_block_fp(q, cache, config_qk, config_pv, causal=True, scale_div=None, q_scale=None, lengths=None, max_length=None,
-                              group=1, window=None):
+                              group=1, sinks=None, window=None):
     """The attention core for the last M <= 16 positions against an `ops.KVCache` that already holds their keys (what the reference
     computes from `past_key_value`, modeling_llama.py:301-344): ops.bfp_attention_decode.  An addition to the registry (key
     "attention_decode"); no additive mask, and no other route -- a cache is block_fp by construction (decode_cache_params).
     `lengths` / `max_length`: a ragged batch, every cache row at its own length (ops.bfp_attention_decode).
     `group`: grouped-query attention, `group` query heads per cache row (query head j on KV head j // group).
-    `window`: sliding-window attention, every query bound to its last `window` keys (ops.bfp_attention_decode)."""
+    `window`: sliding-window attention, every query bound to its last `window` keys (ops.bfp_attention_decode).
+    `sinks`: attention sinks, the first `sinks` keys visible beside the window (ops.bfp_attention_decode)."""
     from ... import ops
     decode_cache_params(config_qk, config_pv, q.shape[-1])
     return ops.bfp_attention_decode(q, cache, causal=causal, scale_div=scale_div, q_scale=q_scale,
                                     token_major=bool(config_pv.get("mi355q_token_major_output", False)), lengths=lengths,
-                                    max_length=max_length, group=group, window=window)
+                                    max_length=max_length, group=group, window=window, sinks=sinks)
 
 
 def decode_cache_kind(config_qk, config_pv, head_dim):
@@ -327,16 +328,16 @@ def attention_decode_block_minifloat(q, cache, config_qk, config_pv, causal=True
 
 
 def attention_extend_block_fp(q, cache, config_qk, config_pv, causal=True, scale_div=None, q_scale=None, lengths=None, counts=None,
-                              max_length=None, group=1, window=None):
+                              max_length=None, group=1, sinks=None, window=None):
     """The attention core for the last M positions -- any M -- against an `ops.KVCache` that already holds their keys (chunked
     prefill; the reference's `past_key_value` call with M new tokens, modeling_llama.py:301-344): ops.bfp_attention_extend.
     Registry key "attention_extend"; no additive mask, no other route.  `lengths` / `counts` / `max_length`: a ragged batch, every
-    cache row at its own length with its own number of queries.  `group`, `window`: as attention_decode_block_fp."""
+    cache row at its own length with its own number of queries.  `group`, `window`, `sinks`: as attention_decode_block_fp."""
     from ... import ops
     decode_cache_params(config_qk, config_pv, q.shape[-1])
     return ops.bfp_attention_extend(q, cache, causal=causal, scale_div=scale_div, q_scale=q_scale,
                                     token_major=bool(config_pv.get("mi355q_token_major_output", False)), lengths=lengths,
-                                    counts=counts, max_length=max_length, group=group, window=window)
+                                    counts=counts, max_length=max_length, group=group, window=window, sinks=sinks)
 
 
 def _make(arith, style):

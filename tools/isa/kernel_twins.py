@@ -8,8 +8,9 @@ against those twins.
 true> -> decode_scores_kernel<1, true, false>; a kernel that was no template, f -> f<false>).  --rename pairs an old kernel with a
 RENAMED one: every pair is applied (re.sub) to the old kernel's demangled name in front of the suffix rule ("" for none), and an old
 file that has no file of its name in the new build is held against the kernels of all the new build's files.  Per pair: the figures of kernel_table.py
-plus the SGPR count and whether the instruction streams are the same text.  Exit status 1 if a twin is missing or differs in VGPRs,
-SGPRs, spills, scratch, LDS, MFMA or LDS-DMA counts."""
+plus the SGPR count and whether the instruction streams are the same text.  A file only the new build has (with every old file paired
+by name) is listed whole, as new instantiations.  Exit status 1 if a twin is missing or differs in VGPRs, SGPRs, spills, scratch, LDS,
+MFMA or LDS-DMA counts, or a kernel of a new file spills or uses scratch."""
 from __future__ import annotations
 
 import re
@@ -68,6 +69,18 @@ def main() -> int:
         print("  ".join(f"{s:>9}" for s in SHORT) + "  kernel")
         for m in sorted(set(new) - twins, key=nn.get):
             print("  ".join(f"{new[m][c]:>9}" for c in COLS) + f"  {nn[m]}")
+    # files the change ADDS (no old file of the name, and no old file left to be held against them): every kernel is a new instantiation
+    if all((new_dir / f.name).exists() for f in old_dir.glob("*.s")):
+        for new_s in sorted(f for f in new_dir.glob("*.s") if not (old_dir / f.name).exists()):
+            rows = parse(new_s)
+            names = demangle(sorted(rows))
+            print(f"\n== {new_s.name}: a new file, {len(rows)} kernels")
+            print("  ".join(f"{s:>9}" for s in SHORT) + "  kernel")
+            for m in sorted(rows, key=names.get):
+                rows[m]["waves"] = waves(rows[m]["vgpr_count"])
+                extra = rows[m]["vgpr_spill_count"] or rows[m]["sgpr_spill_count"] or rows[m]["private_segment_fixed_size"]
+                bad += bool(extra)
+                print("  ".join(f"{rows[m][c]:>9}" for c in COLS) + f"  {names[m]}" + ("   <-- FAIL: spills or scratch" if extra else ""))
     print(f"\n{'FAIL: ' + str(bad) + ' kernels' if bad else 'ok: every twin keeps the old figures'}")
     return 1 if bad else 0
 
