@@ -580,6 +580,22 @@ int mi355q_bfp_attention_fused(const float* q, const float* k, const float* v, c
                                int64_t T, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
                                const float* cos, const float* sin, const int64_t* position_ids, int64_t table_rows, int32_t heads,
                                void* stream);
+/* ... for PADDED batches: a per-sequence key mask instead of the additive one.  Replaces the same lines (modeling_opt.py:246-312,
+ * modeling_llama.py:309-344) when the caller passes `attention_mask` -- HF's expanded [batch, 1, T_q, T_k] mask, which differs per batch
+ * element and so is no [M, T] mask of the exports above:
+ *     w(i, j) = max(s(i, j) + causal(i, j) + (key_mask[b / heads][j] ? 0 : finfo.min), finfo.min)
+ * key_mask int32 [B / heads, T], non-zero = a real key; q, k, v are [B = batch x heads, rows, D], `heads` consecutive rows a sequence.
+ * Pad keys stay in every operand and in every quantiser block (K^T, V and the probabilities are quantised over ALL keys, as the
+ * reference's two products do); only the softmax masks them, T int32 a sequence riding with the K fragments -- no [T, T] tensor is read.
+ * A query whose every visible key is masked (a left-padded sequence's pad queries under the causal rule) has w == finfo.min over its
+ * whole row: p = 1 / T for EVERY key, those above its causal horizon included -- the reference's values, which are the next layer's pad
+ * keys; the kernels walk all keys for such a query (a per-sequence first-real-key index made on the device, no host sync).
+ * q_scale as in mi355q_bfp_attention_fused (applied where the kernels quantise q: any head_dim).  An all-ones mask gives the bits of
+ * mi355q_bfp_attention_strided(mask = NULL).  workspace: mi355q_bfp_attention_workspace_bytes(B, T, D).  The checks are those of
+ * mi355q_bfp_attention_strided; key_mask == NULL, heads < 1 or B % heads != 0: MI355Q_E_BADARG; M > T: MI355Q_E_UNSUPPORTED. */
+int mi355q_bfp_attention_padded(const float* q, const float* k, const float* v, const int32_t* key_mask, int64_t heads, int32_t causal,
+                                float q_scale, float scale_div, float* out, void* workspace, int64_t B, int64_t M, int64_t T, int64_t D,
+                                const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides, void* stream);
 
 /* ---- incremental decoding: block_fp KV cache and split-key decode attention ------------------------------------------
  * The reference decodes with `past_key_value`: torch.cat of fp32 K / V (models/llama_quantized/modeling_llama.py:301-306, the

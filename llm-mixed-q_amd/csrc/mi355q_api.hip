@@ -857,6 +857,39 @@ int mi355q_bfp_attention_fused(const float* q, const float* k, const float* v, c
                                 out_bf16_tiled ? &ao : nullptr, q_scale);
 }
 
+int mi355q_bfp_attention_padded(const float* q, const float* k, const float* v, const int32_t* key_mask, int64_t heads, int32_t causal,
+                                float q_scale, float scale_div, float* out, void* workspace, int64_t B, int64_t M, int64_t T, int64_t D,
+                                const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides, void* stream) {
+    // (the checks of mi355q_bfp_attention_fused without its rotary / consumer arguments, and the mask's own)
+    if (B < 0 || M < 0 || T < 0 || D < 0) return MI355Q_E_BADARG;
+    if (!key_mask || heads < 1 || B % heads != 0) return MI355Q_E_BADARG;
+    if (B == 0 || M == 0 || D == 0) return 0;
+    if (!q || !k || !v || !out || !workspace || !qk_params || !pv_params || T == 0 || B > 65535) return MI355Q_E_BADARG;
+    if (causal && T < M) return MI355Q_E_BADARG;
+    for (int i = 0; i < 2; ++i) {
+        const int32_t* pr = i ? pv_params : qk_params;
+        if (pr[0] < 2 || pr[3] < 2 || pr[1] < 1 || pr[1] > 8 || pr[4] < 1 || pr[4] > 8) return MI355Q_E_BADARG;
+        if (pr[0] > 9 || pr[3] > 9) return MI355Q_E_UNSUPPORTED;
+    }
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
+         reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(key_mask)) % 16)
+        return MI355Q_E_ALIGN;
+    QuantArgs a[4] = {};
+    for (int i = 0; i < 4; ++i) {
+        const int32_t* pr = (i < 2 ? qk_params : pv_params) + 3 * (i & 1);
+        a[i].b0 = 1; a[i].b1 = 16;
+        block_fp_fill(a[i], pr[0], pr[1], pr[2]);
+    }
+    long long st8[8];
+    if (strides)
+        for (int i = 0; i < 8; ++i) {
+            if (strides[i] % 4) return MI355Q_E_ALIGN;
+            st8[i] = strides[i];
+        }
+    return launch_bfp_attention_padded(a[0], a[1], a[2], a[3], q, k, v, key_mask, heads, out, workspace, B, M, T, D, causal ? T - M : -1,
+                                       q_scale, scale_div, static_cast<hipStream_t>(stream), strides ? st8 : nullptr);
+}
+
 // ---- the KV cache and the attention that reads it (mi355q_decode.h, mi355q_extend.h, mi355q_kvp.h, mi355q_kvbm.h) --------------
 // Every export below fills a KvCall, has kv_call_check (mi355q_kv_call.h) refuse it or fill what the launchers take, and launches.
 // Uniform, ragged (per-row lengths on the device), grouped (G query rows a cache row), paged (pools of pages and a page table per row),

@@ -780,6 +780,27 @@ int attention_set_kernel(int which) {
     return prev;
 }
 
+int attention_get_kernel() { return g_attention_kernel; }
+
+// The pack launch alone, K and V only, for the padded form (mi355q_attention_padded.hip) -- the same kernel, the same workspace layout
+// as launch_bfp_attention below; no Q fragments, so their area (f.spare: B x NT x D / 32 KiB) is the caller's.
+int launch_attention_pack_kv(const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, void* workspace, long long B,
+                             long long T, long long D, int kw, long long ksb, long long kst, long long vsb, long long vst, hipStream_t st,
+                             AttnFragments& f) {
+    const int pg = kw == 8 ? 8 : 4, per = 256 / (int)D;
+    f.NT = T / 16;
+    f.NPAIR = ((T + 32 * pg - 1) / (32 * pg)) * pg;
+    f.kf = static_cast<uint16_t*>(workspace);
+    f.vf = f.kf + (size_t)B * f.NT * (D / 32) * 512;
+    f.spare = f.vf + (size_t)B * (D / 16) * f.NPAIR * 512;
+    const int kblocks = (int)((f.NT + per - 1) / per), vblocks = (int)(f.NPAIR / pg);
+    const RopeIn rope{nullptr, nullptr, nullptr, 0, 1};
+    hipLaunchKernelGGL(attn_pack_kv_kernel<false>, dim3((unsigned)(kblocks + vblocks), (unsigned)B), 256, 0, st, ak, av, k, v, f.kf, f.vf, T,
+                       (int)D, f.NT, f.NPAIR, kblocks, ksb, kst, vsb, vst, kw, rope, ak, (const float*)nullptr, (uint16_t*)nullptr, vblocks, 0ll,
+                       0ll, 0ll, 0.f);
+    return (int)hipGetLastError();
+}
+
 size_t attention_workspace_bytes(long long B, long long T, long long D) {
     const long long NT = (T + 15) / 16, NPAIR = ((T + 255) / 256) * 8;            // (the widest pair grouping)
     // (K fragments, V fragments, and -- rotary embedding on load -- the Q fragments of as many queries)

@@ -63,6 +63,22 @@ int launch_bfp_qmatmul(const QuantArgs& ax, const QuantArgs& ay, const float* x,
 size_t attention_workspace_bytes(long long B, long long T, long long D);
 int attention_set_kernel(int which);
 int attention_set_qpack(int on);
+int attention_get_kernel();
+// the K / V fragments of a pack launch in the attention workspace (mi355q_attention.hip: launch_attention_pack_kv)
+struct AttnFragments {
+    uint16_t* kf;
+    uint16_t* vf;
+    void* spare;                // the Q fragments' area, unused by a launch that packs none
+    long long NT, NPAIR;
+};
+int launch_attention_pack_kv(const QuantArgs& ak, const QuantArgs& av, const float* k, const float* v, void* workspace, long long B,
+                             long long T, long long D, int kw, long long ksb, long long kst, long long vsb, long long vst, hipStream_t st,
+                             AttnFragments& f);
+// mi355q_attention_padded.hip: the attention pass with a per-sequence key mask [B / heads, T] (non-zero = a real key) instead of an additive one
+int launch_bfp_attention_padded(const QuantArgs& aq, const QuantArgs& ak, const QuantArgs& ap, const QuantArgs& av, const float* q,
+                                const float* k, const float* v, const int* key_mask, long long heads, float* out, void* workspace,
+                                long long B, long long M, long long T, long long D, long long causal_off, float q_scale, float scale_div,
+                                hipStream_t st, const long long* strides);
 int launch_bfp_attention(const QuantArgs& aq, const QuantArgs& ak, const QuantArgs& ap, const QuantArgs& av, const float* q,
                          const float* k, const float* v, const float* mask, float* out, void* workspace, long long B,
                          long long M, long long T, long long D, long long causal_off, float scale_div, hipStream_t st,

@@ -71,6 +71,7 @@ SIGNATURES = {
                                             _i64, _i32, _vp]),
     "mi355q_bfp_attention_fused": (C.c_int, [_vp, _vp, _vp, _vp, _i32, C.c_float, C.c_float, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
                                              _vp, _i64, _i32, _vp]),
+    "mi355q_bfp_attention_padded": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, C.c_float, C.c_float, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "mi355q_bfp_kv_cache_bytes": (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp]),
     "mi355q_bfp_kv_append": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "mi355q_bfp_kv_decode_fp32": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),

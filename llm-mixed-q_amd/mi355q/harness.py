@@ -68,9 +68,10 @@ class _Attention(nn.Module):
         for name in ("q_proj", "k_proj", "v_proj", "out_proj"):
             setattr(self, name, get_quantized_cls("linear", qc[name])(self.h, self.h, bias=True, config=qc[name]))
 
-    def forward(self, x, mask, norm=None, residual=None):
+    def forward(self, x, mask, norm=None, residual=None, key_mask=None):
         """`residual`: returns residual + attention (config["mi355q_fused_residual"] of out_proj: the add in out_proj's stores where
-        that layer's route has it, Linear.forward_residual)"""
+        that layer's route has it, Linear.forward_residual).
+        `key_mask` [B, T]: a padded batch (the model's attention_mask); `mask` is then the dense [B, 1, T, T] mask it stands for."""
         out_ = lambda o: self.out_proj(o) if residual is None else self.out_proj.forward_residual(o, residual)
         # head-sharded (sharded.shard_model(heads=True)): q / k / v arrive as this rank's heads only, the core runs on those, and
         # ONE all-gather of its output stands in front of out_proj
@@ -93,13 +94,14 @@ class _Attention(nn.Module):
             else:
                 qp, kp, vp = self.q_proj(x), self.k_proj(x), self.v_proj(x)
             # (q * scaling, modeling_opt.py:231: formed where the attention pass packs its Q fragments -- q_scale)
+            pad = {} if key_mask is None else {"key_mask": key_mask}
             o = get_quantized_func("attention", c1)(heads(qp), heads(kp), heads(vp), self.qc["bmm_0"], c1, causal=True,
-                                                    q_scale=self.scaling, consumer=_attention_consumer(c1, self.out_proj, hs, B))
+                                                    q_scale=self.scaling, consumer=_attention_consumer(c1, self.out_proj, hs, B), **pad)
             return _project_attention_output(o, self.out_proj, out, B, T, nh * self.hd, residual)
         q = shape(self.q_proj(x) * self.scaling)
         k, v = shape(self.k_proj(x)), shape(self.v_proj(x))
         w = get_quantized_func("bmm", self.qc["bmm_0"])(q, k.transpose(1, 2), config=self.qc["bmm_0"])
-        if c1["name"] in ("block_fp", "block_minifloat") and c1.get("mi355q_fused_softmax", False):
+        if c1["name"] in ("block_fp", "block_minifloat") and c1.get("mi355q_fused_softmax", False) and key_mask is None:
             # mask add, clamp and softmax folded into the product kernel (the harness' mask is the causal one)
             o = get_quantized_func("softmax_bmm", c1)(w, v, config=c1, causal=True)
         else:
@@ -131,16 +133,17 @@ class _DecoderLayer(nn.Module):
         self.fc1 = get_quantized_cls("linear", qc["fc1"])(cfg.hidden_size, cfg.ffn_dim, bias=True, config=qc["fc1"])
         self.fc2 = get_quantized_cls("linear", qc["fc2"])(cfg.ffn_dim, cfg.hidden_size, bias=True, config=qc["fc2"])
 
-    def forward(self, x, mask):
+    def forward(self, x, mask, key_mask=None):
         c1 = self.self_attn.qc["bmm_1"]
+        pad = {} if key_mask is None else {"key_mask": key_mask}
         fused_norm = (self.fc1.config.get("mi355q_fused_norm", False) and c1.get("mi355q_grouped_linear", False)
                       and c1.get("mi355q_fused_attention", False) and c1["name"] == "block_fp")
         ln = lambda m: (m.weight, m.bias, m.eps)
         fres = self.fc2.config.get("mi355q_fused_residual", False)      # the residual adds in out_proj's / fc2's stores
         if fused_norm:      # the LayerNorms are applied by the quantiser of the projections they feed (grouped_linear(norm=...))
-            x = self.self_attn(x, mask, norm=ln(self.self_attn_layer_norm), residual=x) if fres else x + self.self_attn(x, mask, norm=ln(self.self_attn_layer_norm))
+            x = self.self_attn(x, mask, norm=ln(self.self_attn_layer_norm), residual=x, **pad) if fres else x + self.self_attn(x, mask, norm=ln(self.self_attn_layer_norm), **pad)
         else:
-            x = self.self_attn(self.self_attn_layer_norm(x), mask, residual=x) if fres else x + self.self_attn(self.self_attn_layer_norm(x), mask)
+            x = self.self_attn(self.self_attn_layer_norm(x), mask, residual=x, **pad) if fres else x + self.self_attn(self.self_attn_layer_norm(x), mask, **pad)
         shape = x.shape
         h = x.reshape(-1, shape[-1])                       # the MLP sees a 2-D activation (modeling_opt.py:412)
         if fused_norm and self.fc2.config.get("mi355q_fused_activation", False):
@@ -180,6 +183,7 @@ class TinyOPTForCausalLM(nn.Module):
         self.final_layer_norm = nn.LayerNorm(cfg.hidden_size)
         self.lm_head = nn.Linear(cfg.hidden_size, cfg.vocab_size, bias=False)     # not quantised (modeling_opt.py:942-944)
         self.mi355q_lm_head = "split"
+        self.mi355q_pad_position = None          # row 1 of the reference's position table: a pad position's embedding (forward)
         self.apply(self._init)
 
     def _init(self, m):
@@ -198,6 +202,8 @@ class TinyOPTForCausalLM(nn.Module):
         for k, v in sd.items():
             k = k.removeprefix("model.decoder.")
             v = torch.as_tensor(v)
+            if k == "embed_positions.weight":
+                self.mi355q_pad_position = v[1].detach().clone().float()
             own[k] = v[2:2 + self.cfg.max_positions] if k == "embed_positions.weight" else v
         self.load_state_dict(own, strict=True)
         return self
@@ -208,25 +214,48 @@ class TinyOPTForCausalLM(nn.Module):
         for k, v in self.state_dict().items():
             v = v.detach()
             if k == "embed_positions.weight":
-                v = torch.cat([torch.zeros(2, v.shape[1], dtype=v.dtype, device=v.device), v])
+                head = torch.zeros(2, v.shape[1], dtype=v.dtype, device=v.device)
+                if self.mi355q_pad_position is not None:
+                    head[1] = self.mi355q_pad_position.to(device=v.device, dtype=v.dtype)
+                v = torch.cat([head, v])
             out[k if k.startswith("lm_head") else "model.decoder." + k] = v
         return out
 
-    def forward(self, input_ids, labels=None, cache=None, counts=None):
+    def forward(self, input_ids, labels=None, cache=None, counts=None, attention_mask=None):
         """`cache` (a DecodeState): input_ids holds only the NEW tokens, whose positions start at the cache's length; returns their
         logits (the prompt goes through the same call).  None: the whole sequence, as ever.
         `counts` (with a cache): a ragged batch -- input_ids [B, n] is right-padded and row b holds counts[b] real tokens, at
-        positions lengths[b] .. lengths[b] + counts[b] - 1 of ITS sequence; logits at padded positions are unspecified."""
+        positions lengths[b] .. lengths[b] + counts[b] - 1 of ITS sequence; logits at padded positions are unspecified.
+        `attention_mask` [B, T], non-zero = a real token (full forward only): a padded batch as the reference runs it -- pad positions
+        stay in every operand and quantiser block, every layer's softmax masks them as keys (the registry's attention(key_mask=...)),
+        and the learned positions count real tokens only.  None: today's call."""
         if cache is not None:
+            _refuse_mask_with_cache(attention_mask)
             return _forward_cached(self, input_ids, labels, cache, counts)
         if counts is not None:
             raise ValueError("forward(counts=...) belongs to a cached call (cache=DecodeState)")
         B, T = input_ids.shape
-        pos = torch.arange(T, device=input_ids.device)
-        x = self.embed_tokens(input_ids) + self.embed_positions(pos)[None]
-        mask = torch.full((T, T), torch.finfo(x.dtype).min, device=x.device).triu(1)[None, None]
+        if attention_mask is None:
+            pos = torch.arange(T, device=input_ids.device)
+            x = self.embed_tokens(input_ids) + self.embed_positions(pos)[None]
+            mask = torch.full((T, T), torch.finfo(x.dtype).min, device=x.device).triu(1)[None, None]
+            pad = {}
+        else:
+            key_mask = _check_attention_mask(attention_mask, input_ids)
+            # the reference's learned positions (modeling_opt.py:115-140): cumsum(mask) * mask - 1, plus an offset of 2 into its table.  A
+            # pad position gets -1, i.e. row 1 of that table, which lies in the two offset rows this model's table drops: kept by
+            # load_reference_state_dict as mi355q_pad_position, zeros (what reference_state_dict writes there) for a model made here
+            live = key_mask != 0
+            pos = (torch.cumsum(live.long(), dim=1) * live.long() - 1).clamp_(min=0)
+            pad_row = self.mi355q_pad_position
+            pad_row = torch.zeros(self.cfg.hidden_size, device=input_ids.device) if pad_row is None else pad_row.to(input_ids.device)
+            x = self.embed_tokens(input_ids) + torch.where(live[..., None], self.embed_positions(pos), pad_row)
+            neg = torch.finfo(x.dtype).min
+            mask = (torch.full((T, T), neg, device=x.device).triu(1)[None, None]
+                    + torch.where(key_mask != 0, 0.0, neg).to(x.dtype)[:, None, None, :]).clamp_(min=neg)      # (HF's expanded [B, 1, T, T] mask)
+            pad = {"key_mask": key_mask}
         for layer in self.layers:
-            x = layer(x, mask)
+            x = layer(x, mask, **pad)
         # (unquantised, modeling_opt.py:942-944: fp32-equivalent on the bf16 MFMA -- quantized_modules.linear.fp32_linear; "vendor" = F.linear)
         logits = fp32_linear(self.final_layer_norm(x), self.lm_head, self.mi355q_lm_head)
         loss = None
@@ -279,6 +308,20 @@ class _RMSNorm(nn.Module):
         return self.weight * (x * torch.rsqrt(v + self.eps)).to(x.dtype)
 
 
+def _check_attention_mask(attention_mask, input_ids):
+    """attention_mask [B, T] of the models' full forward -> the key mask the layers take (on input_ids' device)"""
+    if not isinstance(attention_mask, torch.Tensor) or tuple(attention_mask.shape) != tuple(input_ids.shape):
+        raise ValueError(f"forward(attention_mask=...): [B, T] = {tuple(input_ids.shape)} expected, got "
+                         f"{tuple(attention_mask.shape) if isinstance(attention_mask, torch.Tensor) else type(attention_mask).__name__}")
+    return (attention_mask != 0).to(device=input_ids.device, dtype=torch.int32).contiguous()
+
+
+def _refuse_mask_with_cache(attention_mask):
+    if attention_mask is not None:
+        raise NotImplementedError("forward(cache=..., attention_mask=...): a cached call serves unequal sequences by DecodeState's ragged route "
+                                  "(counts=), which keeps no pad key in the cache; attention_mask belongs to the full forward")
+
+
 def _causal_mask(n: int, L: int, window, dtype, device, sinks=None):
     """the additive mask [n, L] of n queries at the last n of L positions (the offset of modeling_llama.py:53-79): finfo.min above the
     horizon and, with a sliding window, below it -- query i at p = L - n + i sees keys max(0, p - window + 1) .. p -- but for the first
@@ -321,8 +364,10 @@ class _LlamaAttention(nn.Module):
         self.register_buffer("cos", emb.cos()[None, None], persistent=False)       # [1, 1, pos, hd]
         self.register_buffer("sin", emb.sin()[None, None], persistent=False)
 
-    def forward(self, x, mask, position_ids, norm=None, residual=None):
+    def forward(self, x, mask, position_ids, norm=None, residual=None, key_mask=None):
+        """`key_mask` [B, T]: a padded batch (the model's attention_mask); `mask` is then the dense [B, 1, T, T] mask it stands for"""
         out_ = lambda o: self.o_proj(o) if residual is None else self.o_proj.forward_residual(o, residual)
+        pad = {} if key_mask is None else {"key_mask": key_mask}
         hs = getattr(self, "mi355q_head_shard", None)         # (head-sharded: see _Attention.forward)
         if hs is None:
             out = out_
@@ -353,16 +398,16 @@ class _LlamaAttention(nn.Module):
             # (the rotary embedding applied where the attention pass loads q and k: attention_block_fp(rope=...))
             o = get_quantized_func("attention", c1)(q, k, v, self.qc["matmul_0"], c1, causal=True, scale_div=math.sqrt(self.hd),
                                                     rope=(self.cos[:, :, :T], self.sin[:, :, :T], position_ids, rc),
-                                                    consumer=_attention_consumer(c1, self.o_proj, hs, B))
+                                                    consumer=_attention_consumer(c1, self.o_proj, hs, B), **pad)
             return _project_attention_output(o, self.o_proj, out, B, T, nh * self.hd, residual)
         q, k = get_quantized_func("rotary_positional_encoding", rc)(q, k, self.cos[:, :, :T], self.sin[:, :, :T],
                                                                    position_ids, config=rc)
         if fused:
             o = get_quantized_func("attention", c1)(q, k, v, self.qc["matmul_0"], c1, causal=True, scale_div=math.sqrt(self.hd),
-                                                    consumer=_attention_consumer(c1, self.o_proj, hs, B))
+                                                    consumer=_attention_consumer(c1, self.o_proj, hs, B), **pad)
             return _project_attention_output(o, self.o_proj, out, B, T, nh * self.hd, residual)
         w = get_quantized_func("matmul", self.qc["matmul_0"])(q, k.transpose(2, 3), config=self.qc["matmul_0"])
-        if c1["name"] in ("block_fp", "block_minifloat") and c1.get("mi355q_fused_softmax", False) and not windowed:
+        if c1["name"] in ("block_fp", "block_minifloat") and c1.get("mi355q_fused_softmax", False) and not windowed and key_mask is None:
             o = get_quantized_func("softmax_matmul", c1)(w / math.sqrt(self.hd), v, config=c1, causal=True)
         else:
             w = w / math.sqrt(self.hd) + mask
@@ -398,14 +443,15 @@ class _LlamaLayer(nn.Module):
         self.up_proj = lin("up_proj", cfg.hidden_size, cfg.intermediate_size)
         self.down_proj = lin("down_proj", cfg.intermediate_size, cfg.hidden_size)
 
-    def forward(self, x, mask, position_ids):
+    def forward(self, x, mask, position_ids, key_mask=None):
         gc = self.gate_proj.config
+        pad = {} if key_mask is None else {"key_mask": key_mask}
         fused_norm = gc.get("mi355q_grouped_linear", False) and gc.get("mi355q_fused_norm", False)
         fres = self.down_proj.config.get("mi355q_fused_residual", False)      # the residual adds in o_proj's / down_proj's stores
         if fused_norm:      # the norms are applied by the quantiser of the projections they feed (grouped_linear(norm=...))
             n1, n2 = self.input_layernorm, self.post_attention_layernorm
-            x = (self.self_attn(x, mask, position_ids, norm=(n1.weight, n1.eps), residual=x) if fres
-                 else x + self.self_attn(x, mask, position_ids, norm=(n1.weight, n1.eps)))
+            x = (self.self_attn(x, mask, position_ids, norm=(n1.weight, n1.eps), residual=x, **pad) if fres
+                 else x + self.self_attn(x, mask, position_ids, norm=(n1.weight, n1.eps), **pad))
             if self.down_proj.config.get("mi355q_fused_activation", False):
                 # round 6: gate / up interleaved in ONE product whose epilogue writes down_proj's quantised operand (gated_mlp); None
                 # when the layers do not qualify: the grouped launch + the quantiser that reads silu(gate) * up, as before
@@ -416,7 +462,8 @@ class _LlamaLayer(nn.Module):
             if self.down_proj.config.get("mi355q_fused_activation", False):
                 return self.down_proj.forward_after(gate, "silu_mul", up, residual=x) if fres else x + self.down_proj.forward_after(gate, "silu_mul", up)
             return x + self.down_proj(F.silu(gate) * up)
-        x = self.self_attn(self.input_layernorm(x), mask, position_ids, residual=x) if fres else x + self.self_attn(self.input_layernorm(x), mask, position_ids)
+        x = (self.self_attn(self.input_layernorm(x), mask, position_ids, residual=x, **pad) if fres
+             else x + self.self_attn(self.input_layernorm(x), mask, position_ids, **pad))
         h = self.post_attention_layernorm(x)
         if self.gate_proj.config.get("mi355q_grouped_linear", False):
             gate, up = grouped_linear(h, (self.gate_proj, self.up_proj))
@@ -466,9 +513,11 @@ class TinyLlamaForCausalLM(nn.Module):
             out[k if k.startswith("lm_head") else "model." + k] = v.detach()
         return out
 
-    def forward(self, input_ids, labels=None, cache=None, counts=None):
-        """`cache` (a DecodeState), `counts`: see TinyOPTForCausalLM.forward"""
+    def forward(self, input_ids, labels=None, cache=None, counts=None, attention_mask=None):
+        """`cache` (a DecodeState), `counts`, `attention_mask`: see TinyOPTForCausalLM.forward.  The positions stay 0 .. T - 1 for every
+        row, padded or not (the reference's default position_ids, modeling_llama.py)."""
         if cache is not None:
+            _refuse_mask_with_cache(attention_mask)
             return _forward_cached(self, input_ids, labels, cache, counts)
         if counts is not None:
             raise ValueError("forward(counts=...) belongs to a cached call (cache=DecodeState)")
@@ -476,8 +525,14 @@ class TinyLlamaForCausalLM(nn.Module):
         position_ids = torch.arange(T, device=input_ids.device)[None].expand(B, T)
         x = self.embed_tokens(input_ids)
         mask = _causal_mask(T, T, self.cfg.sliding_window, x.dtype, x.device, self.cfg.attention_sinks)[None, None]
+        pad = {}
+        if attention_mask is not None:
+            key_mask = _check_attention_mask(attention_mask, input_ids)
+            neg = torch.finfo(x.dtype).min
+            mask = (mask + torch.where(key_mask != 0, 0.0, neg).to(x.dtype)[:, None, None, :]).clamp_(min=neg)
+            pad = {"key_mask": key_mask}
         for layer in self.layers:
-            x = layer(x, mask, position_ids)
+            x = layer(x, mask, position_ids, **pad)
         # (unquantised, modeling_llama.py:772,866: fp32-equivalent on the bf16 MFMA -- quantized_modules.linear.fp32_linear; "vendor" = F.linear)
         logits = fp32_linear(self.norm(x), self.lm_head, self.mi355q_lm_head)
         loss = None

@@ -1425,6 +1425,91 @@ def bfp_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, qk_params, 
     return out if tiled is None else TiledBf16(tiled, M, B * D)
 
 
+def _padded_check(q, k, v, widths, key_mask, causal, heads):
+    """the reason ops.bfp_attention_padded declines a call, None when it takes it.  Nothing here touches a device."""
+    if not all(isinstance(t, torch.Tensor) for t in (q, k, v, key_mask)):
+        return "q, k, v and key_mask must be tensors"
+    if q.ndim < 3 or k.ndim != q.ndim or v.shape != k.shape or q.shape[:-2] != k.shape[:-2] or q.shape[-1] != k.shape[-1]:
+        return f"q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}: q [..., T_q, D] and k, v [..., T_k, D] with equal leading dims expected"
+    if key_mask.ndim != 2 or key_mask.shape[1] != k.shape[-2]:
+        return f"key_mask {tuple(key_mask.shape)} is not [sequences, T_k = {k.shape[-2]}]"
+    if key_mask.dtype.is_floating_point or key_mask.dtype.is_complex:
+        return f"key_mask is {key_mask.dtype}: an integer or bool tensor expected, non-zero = a real key (an additive mask goes to bfp_attention)"
+    rows, nseq = q.shape[:-2].numel(), key_mask.shape[0]
+    if heads is None:
+        if q.ndim != 4:
+            return f"q {tuple(q.shape)} is not [sequences, heads, T_q, D]: flat leading dims need heads="
+        heads = q.shape[1]
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+        return f"heads = {heads!r} is not an integer >= 1"
+    if nseq < 1 or rows != nseq * heads:
+        return f"q has {rows} rows (sequences x heads), key_mask {nseq} sequences of {heads} heads"
+    if not (q.dtype == k.dtype == v.dtype == torch.float32):
+        return "fp32 q, k, v only"
+    if not (q.device == k.device == v.device == key_mask.device):
+        return "q, k, v and key_mask are on different devices"
+    if q.shape[-2] > k.shape[-2]:
+        return f"T_q = {q.shape[-2]} > T_k = {k.shape[-2]}"
+    if not (0 < rows <= 65535 and 0 < k.shape[-2] <= ATTENTION_MAX_KEYS and k.shape[-2] % 16 == 0 and q.shape[-2] > 0
+            and q.shape[-1] % 32 == 0 and 0 < q.shape[-1] <= ATTENTION_MAX_HEAD_DIM):
+        return (f"rows {rows} (<= 65535), T_k {k.shape[-2]} (a multiple of 16 up to {ATTENTION_MAX_KEYS}), head_dim {q.shape[-1]} "
+                f"(a multiple of 32 up to {ATTENTION_MAX_HEAD_DIM}): one of them is outside what the kernels take")
+    if not all(2 <= int(w) <= 9 for w in widths):
+        return f"widths {tuple(int(w) for w in widths)} outside 2 .. 9 (a quantised value must be exact in bf16)"
+    if not q.is_cuda:
+        return f"tensors are on '{q.device}': the kernels run on an MI355X only"
+    return None
+
+
+def bfp_attention_padded_supported(q, k, v, widths, key_mask, *, causal: bool = False, heads: int = None) -> bool:
+    """shapes / widths ops.bfp_attention_padded takes: bfp_attention_supported's, T_q <= T_k, and key_mask [sequences, T_k] of an integer
+    or bool dtype with sequences x heads = the leading dims of q (heads = q.shape[1] of a 4-d q unless given)"""
+    return _padded_check(q, k, v, widths, key_mask, causal, heads) is None
+
+
+def bfp_attention_padded(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, qk_params, pv_params, key_mask: torch.Tensor, *,
+                         causal: bool, scale_div: float = None, q_scale: float = None, heads: int = None) -> torch.Tensor:
+    """bfp_attention for a PADDED batch: key_mask [sequences, T_k] (integer or bool, non-zero = a real key) in place of an additive mask,
+
+        w(i, j) = max(s(i, j) + causal(i, j) + (key_mask[b, j] ? 0 : finfo.min), finfo.min)      out = bmm_1(Q(softmax(w)), Q(v))
+
+    -- modeling_opt.py:262-312 / modeling_llama.py:318-344 with HF's expanded [B, 1, T_q, T_k] mask.  q [sequences, heads, T_q, D] (or flat
+    [sequences x heads, T_q, D] with `heads`), k, v [..., T_k, D], T_q <= T_k.  Pad keys stay in every operand and quantiser block; only the
+    softmax masks them (T_k int32 a sequence; no [T, T] tensor exists).  A query with every visible key masked -- the pad queries of a
+    left-padded sequence -- gets 1 / T_k for EVERY key, as the reference does.  An all-ones mask gives bfp_attention's bits.
+    Raises ValueError naming what it does not take (bfp_attention_padded_supported); no rope / consumer / token-major output here."""
+    import ctypes
+    widths = (qk_params[0], qk_params[3], pv_params[0], pv_params[3])
+    why = _padded_check(q, k, v, widths, key_mask, causal, heads)
+    if why is not None:
+        raise ValueError(f"mi355q.bfp_attention_padded: {why}")
+    M, D = q.shape[-2:]
+    T = k.shape[-2]
+    H = int(heads) if heads is not None else q.shape[1]
+    q3, qsb, qsm = _as_heads_view(q)
+    k3, ksb, kst = _as_heads_view(k)
+    v3, vsb, vst = _as_heads_view(v)
+    B = q3.shape[0]
+    km = key_mask if key_mask.dtype == torch.int32 and key_mask.is_contiguous() and key_mask.data_ptr() % 16 == 0 else \
+        (key_mask != 0).to(torch.int32).contiguous()
+    out = torch.empty(*q.shape, dtype=torch.float32, device=q.device)
+    lib = _lib.load_library()
+    sp = _stream_ptr(q.device)
+    key = (q.device.index, sp, B, T, D)
+    ws = _ATTN_WS.get(key)
+    if ws is None:
+        ws = _ATTN_WS.put(key, torch.empty(lib.mi355q_bfp_attention_workspace_bytes(B, T, D), dtype=torch.uint8, device=q.device))
+    pa = (ctypes.c_int32 * 6)(*[_default_bias(p) if i % 3 == 2 else int(p) for i, p in enumerate(qk_params)])
+    pb = (ctypes.c_int32 * 6)(*[_default_bias(p) if i % 3 == 2 else int(p) for i, p in enumerate(pv_params)])
+    strides = (ctypes.c_int64 * 8)(qsb, qsm, ksb, kst, vsb, vst, M * D, D)
+    with _on_device(q.device):
+        rc = lib.mi355q_bfp_attention_padded(_ptr(q3), _ptr(k3), _ptr(v3), _ptr(km), H, int(bool(causal)), float(q_scale) if q_scale else 0.0,
+                                             float(scale_div) if scale_div else 0.0, _ptr(out), _ptr(ws), B, M, T, D, ctypes.addressof(pa),
+                                             ctypes.addressof(pb), ctypes.addressof(strides), sp)
+    _lib.check(rc, "mi355q_bfp_attention_padded")
+    return out
+
+
 # ---- incremental decoding: block_fp KV cache + split-key decode attention (csrc/mi355q_decode.hip) ----------------------------
 DECODE_MAX_QUERIES = 16          # rows of q one decode call takes (the 16 columns of the MFMA tiles)
 _DECODE_WS = _StreamCache(8)

@@ -169,7 +169,17 @@ def _make_softmax(style, arith="block_fp"):
     return f
 
 
-def attention_block_fp(q, k, v, config_qk, config_pv, mask=None, causal=False, scale_div=None, rope=None, consumer=None, q_scale=None):
+def _key_mask_dense(key_mask, q, k):
+    """the additive [B, 1.., T_q, T_k] fp32 mask a key mask [B, T_k] stands for (HF's expanded attention_mask without its causal half):
+    0 at a real key, finfo.min at a pad key, for every query"""
+    neg = torch.finfo(torch.float32).min
+    row = torch.where(key_mask != 0, 0.0, neg).to(device=q.device, dtype=torch.float32)
+    return row.reshape(key_mask.shape[0], *([1] * (q.ndim - 2)), k.shape[-2]).expand(key_mask.shape[0], *([1] * (q.ndim - 3)), q.shape[-2],
+                                                                                    k.shape[-2]).contiguous()
+
+
+def attention_block_fp(q, k, v, config_qk, config_pv, mask=None, causal=False, scale_div=None, rope=None, consumer=None, q_scale=None,
+                       key_mask=None):
     """The reference's quantised attention core as one call (modeling_opt.py:246-312, modeling_llama.py:309-344):
 
         w = bmm_0(q, k^T)  [w = w / scale_div]  w = max(w + mask, finfo.min)  p = softmax(w, -1)  out = bmm_1(p, v)
@@ -189,11 +199,46 @@ def attention_block_fp(q, k, v, config_qk, config_pv, mask=None, causal=False, s
     (one batch element, head_dim 64 / 128, no additive mask) the result is `ops.TiledBf16` -- that Linear's quantised activations
     [T_q, heads x hd], for `Linear.forward_tiled` -- instead of the fp32 tensor; the caller checks which it got.
     `q_scale`: the core runs on q * q_scale (OPT: `self.q_proj(hidden_states) * self.scaling`, modeling_opt.py:231) -- multiplied where
-    the HIP pass packs its Q fragments, by a torch kernel in front everywhere else: the same values."""
+    the HIP pass packs its Q fragments, by a torch kernel in front everywhere else: the same values.
+    `key_mask` [B, T_k], non-zero = a real key, for q [B, ..., T_q, hd]: a padded batch (HF's `attention_mask`).  It stands for the additive
+    mask [B, 1, T_q, T_k] that is 0 at real keys and finfo.min at pad keys -- pad positions stay in every operand and quantiser block, only
+    the softmax masks them, and a query with every visible key masked gets 1 / T_k for every key, as in the reference.  Where the HIP pass
+    takes it (ops.bfp_attention_padded) no [T, T] tensor exists; everywhere else that dense mask is built and today's route runs.  Not
+    together with `mask` (ValueError)."""
     from ... import ops
     if rope is not None:
         cos, sin, position_ids, rope_config = rope
         rope_fn = QUANTIZED_FUNC_MAP["rotary_positional_encoding"][rope_config["name"]]
+    if key_mask is not None:
+        if mask is not None:
+            raise ValueError("attention: key_mask together with mask (fold the key mask into the additive mask, or pass one of them)")
+        if key_mask.ndim != 2 or q.ndim < 3 or key_mask.shape != (q.shape[0], k.shape[-2]):
+            raise ValueError(f"attention: key_mask {tuple(key_mask.shape)} is not [B, T_k] = [{q.shape[0]}, {k.shape[-2]}] of q {tuple(q.shape)}")
+        padded_ok = (config_qk.get("name") == "block_fp" and config_pv.get("name") == "block_fp"
+                     and not config_qk.get("bypass", False) and not config_pv.get("bypass", False)
+                     and config_qk.get("mi355q_fused_matmul", True) and config_pv.get("mi355q_fused_matmul", True)
+                     and q.ndim == k.ndim == v.ndim and q.shape[:-2] == k.shape[:-2] == v.shape[:-2] and (not causal or k.shape[-2] >= q.shape[-2])
+                     and not (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)))
+        if padded_ok:
+            for c in (config_qk, config_pv):
+                for key in _KEYS["block_fp"]:
+                    c[f"data_in_{key}"], c[f"weight_{key}"]
+            nb, (tq, hd), tk = q.shape[:-2].numel(), q.shape[-2:], k.shape[-2]
+            blocks_ok = all(ops.resolve_blocking(list(shape), bs, True)[3:] == (1, 16) for shape, bs in (
+                ((nb, tq, hd), config_qk["data_in_block_size"]), ((nb, hd, tk), config_qk["weight_block_size"]),
+                ((nb, tq, tk), config_pv["data_in_block_size"]), ((nb, tk, hd), config_pv["weight_block_size"])))
+            widths = (config_qk["data_in_width"], config_qk["weight_width"], config_pv["data_in_width"], config_pv["weight_width"])
+            heads = nb // q.shape[0]
+            if blocks_ok and ops.bfp_attention_padded_supported(q, k, v, widths, key_mask, causal=causal, heads=heads):
+                par = lambda c: (c["data_in_width"], c["data_in_exponent_width"], c["data_in_exponent_bias"], c["weight_width"],
+                                 c["weight_exponent_width"], c["weight_exponent_bias"])
+                if rope is not None:                      # (the padded form has no rotary embedding on load: q and k are turned first)
+                    if q_scale:
+                        q, q_scale = q * q_scale, None
+                    q, k = rope_fn(q, k, cos, sin, position_ids, config=rope_config)
+                return ops.bfp_attention_padded(q, k, v, par(config_qk), par(config_pv), key_mask, causal=causal, scale_div=scale_div,
+                                                q_scale=q_scale or None, heads=heads)
+        mask, key_mask = _key_mask_dense(key_mask, q, k), None
     m2 = None if mask is None else _mask_2d(mask, q.shape[-2], k.shape[-2])
     both_fp = config_qk.get("name") == "block_fp" and config_pv.get("name") == "block_fp"
     fused_ok = (both_fp and not config_qk.get("bypass", False) and not config_pv.get("bypass", False)

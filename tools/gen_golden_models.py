@@ -292,7 +292,41 @@ def main_wide2():
     print(f"wide2 models: {len(meta)} cases, {sum(a.nbytes for a in arrays.values()) / 1e6:.2f} MB raw")
 
 
+def main_padded():
+    """tests/golden/opt_padded.npz: the reference's own OPT class on a LEFT-PADDED batch of 3 (attention_mask) -- the model of the
+    fixture "opt_w6a6_t48" (same seed: the weights are those of models.npz, which is checked), new token ids, real lengths 48 / 21 / 1.
+    Pins the fully masked row (the pad queries of a left-padded sequence) and the pad positions' embedding to the reference."""
+    torch.set_num_threads(4)
+    opt, optc, _, _ = load_reference_models()
+    arrays, meta = {}, {}
+    run_opt(opt, optc, "opt_w6a6_t48", {"default": bfp_default(6, 6)}, arrays, meta, hidden=128, ffn=256, heads=2, T=48, seed=80)
+    have = np.load(OUT / "models.npz")
+    for k, v in arrays.items():
+        if "/w/" in k:
+            assert np.array_equal(have[k], v), k
+    cfg = optc.OPTQuantizedConfig(vocab_size=128, hidden_size=128, num_hidden_layers=2, ffn_dim=256, max_position_embeddings=64,
+                                  num_attention_heads=2, dropout=0.0, word_embed_proj_dim=128,
+                                  quant_config=json.loads(json.dumps({"default": bfp_default(6, 6)})))
+    model = opt.OPTQuantizedForCausalLM(cfg).eval()
+    model.load_state_dict({k.split("/w/")[1]: torch.from_numpy(v) for k, v in arrays.items() if "/w/" in k})
+    g = torch.Generator().manual_seed(81)
+    T, lengths = 48, (48, 21, 1)
+    ids = torch.randint(3, 128, (3, T), generator=g)
+    mask = torch.zeros(3, T, dtype=torch.long)
+    for b, n in enumerate(lengths):
+        mask[b, T - n:] = 1
+    ids = torch.where(mask != 0, ids, torch.ones_like(ids))          # (pad token id 1)
+    with torch.no_grad():
+        logits = model(input_ids=ids, attention_mask=mask).logits
+    assert torch.isfinite(logits).all()
+    np.savez_compressed(OUT / "opt_padded.npz", input_ids=ids.numpy(), attention_mask=mask.numpy(), logits=logits.numpy(),
+                        model_tag=np.array("opt_w6a6_t48"))
+    print(f"opt_padded: logits {tuple(logits.shape)}, max |logit| {float(logits.abs().max()):.4f}")
+
+
 def main():
+    if "--padded" in sys.argv:
+        return main_padded()
     if "--wide2" in sys.argv:
         return main_wide2()
     if "--wide" in sys.argv:
