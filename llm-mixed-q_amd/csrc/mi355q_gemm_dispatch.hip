@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "mi355q_gemm_tile.h"
+#include "mi355q_gemm_v9_full.h"
 
 namespace mi355q {
 
@@ -24,6 +25,7 @@ namespace mi355q {
 //   MI355Q_V8_SPLITS=S       cap split-K at S slices (0 / 1: none, 8 K-steps a slice at least); set at all, as TILE_ROWS
 //   MI355Q_V9=0              keep the 256 x 256 tile on the v8 kernel
 //   MI355Q_V9_FIX=0          ... the launches with exception lists only
+//   MI355Q_V9_FULL=0         keep full-tile launches on the general 256 x 256 kernel (read ONCE, by the family-9 launcher: A/B runs)
 //   MI355Q_V9_DBG=n          GemmArgs::dbg of the int8 launches of the v8 / v9 kernels
 //   MI355Q_V8_CLOCK          (set) the v8 kernel that prints the clock it held over the K loop; no lists
 //   MI355Q_V8_STAMPS         (set) the v8 kernel that prints its phases' durations; with lists
@@ -143,4 +145,20 @@ extern "C" __attribute__((visibility("default"))) int mi355q_debug_gemm_plan(con
     const int32_t words[16] = {p.family, p.geom, p.bm, p.bn, p.ti, p.sched, p.fixmode, p.ns, p.occ, p.kg, p.splits, p.ticket_words_per_tile, (int32_t)p.grid, p.rc};
     for (int i = 0; i < 16; ++i) out[i] = words[i];
     return 0;
+}
+
+// diagnostic hook, not part of include/mi355q.h: whether a launch takes the full-tile unit of the 256 x 256 kernel (mi355q_gemm_v9_full.h),
+// without launching.  shape / e / workspace_ok as mi355q_debug_gemm_plan; flags = resid given, x_post, dbg, y 16-byte aligned,
+// the MI355Q_V9_FULL switch (1: on), ldy.  Returns 1 / 0, or a negative error.
+extern "C" __attribute__((visibility("default"))) int mi355q_debug_v9_full(const int64_t shape[8], const int32_t* e, int32_t workspace_ok,
+                                                                           const int64_t flags[6]) {
+    using namespace mi355q;
+    if (!shape || !flags) return MI355Q_E_BADARG;
+    int32_t plan[16];
+    const int rc = mi355q_debug_gemm_plan(shape, e, workspace_ok, plan);
+    if (rc) return rc;
+    if (plan[13]) return 0;                                     // (the plan refuses the launch)
+    const V9FullQuery q{plan[0], plan[10], (int)shape[3], shape[4] != 0 && shape[5] != 0, shape[7] != 0, shape[0], shape[1], flags[5],
+                        flags[0] != 0, flags[1] != 0, (int)flags[2], flags[3] != 0, flags[4] != 0};
+    return v9_full_tile_ok(q) ? 1 : 0;
 }

@@ -29,10 +29,12 @@
 #include <map>
 #include <hip/hip_ext.h>
 #include <mutex>
+#include <atomic>
 #include <type_traits>
 #include <utility>
 
 #include "mi355q_gemm_tile.h"
+#include "mi355q_gemm_v9_full.h"
 #ifdef V9_GATED_TU
 #include "mi355q_quant_dev.h"
 #endif
@@ -62,6 +64,14 @@
 // kernel's text (same register count, another allocation) -- so here they are not compiled.
 #ifdef V9_RESID_TU
 #define bfp_gemm_v9 bfp_gemm_v9r
+#endif
+// The FULL-TILE launch (mi355q_gemm_v9_full.h: one group, one slice of K, M and N multiples of 256, no residual, no x post-pass, no
+// debug bits) is a fifth unit, mi355q_gemm_v9f.hip = this file with V9_FULL_TU: the kernel takes plain arguments instead of the
+// argument block and builds a local GemmArgs whose unused fields are constants, so what the general body spends on groups, split-K,
+// ragged edges and debug bits folds away at compile time; the arithmetic, the ring schedule, the exception service and the stores
+// are this text.  It also requests K-step 0 in FRONT of the side area's loads (see V9_SIDE_WAIT).
+#ifdef V9_FULL_TU
+#define bfp_gemm_v9 bfp_gemm_v9f
 #endif
 
 namespace mi355q {
@@ -214,6 +224,45 @@ __device__ __forceinline__ void gated_post_tile(const GemmArgs& a, const unsigne
 }
 #endif
 
+// ---- the operand stream.  Piece p of a K-step: 16 rows of A (p < 16) or of B; this wave stages pieces wave + 8 q.
+//      One descriptor per operand, rooted at the tile's first piece row and ending with its last (rows past the
+//      operand read as zero); the lane's part of the address is fixed, the K-step rides in the scalar offset.
+//      row_bytes: one piece row (16 rows x K bytes).  The range check covers the lane's offset only, not the scalar one: a
+//      K-step past the end of the slice is requested through a descriptor of zero bytes -- no memory traffic, zeros land in
+//      the slot.  MIXED: the class-1 operands (tiled bf16: kp1 pieces of 16 rows x 32 values per piece row); the lane
+//      offsets of a class-1 piece differ only in the piece row's length: one scalar add per piece (dvo0 / dvo1).
+//      (The declarations as a macro: the full-tile unit states them in front of the side area's loads, every other unit
+//      behind them -- where moving the text itself changes the register allocation of the kernels that ship.)
+#ifdef V9_FULL_TU
+#define V9_TILE_ROWS constexpr int pa_rows = 16, pb_rows = 16;
+#else
+#define V9_TILE_ROWS const int pa_rows = min(16, ((Mi + 127) >> 7) * 8 - (m0 >> 4)), pb_rows = min(16, ((Ni + 127) >> 7) * 8 - (n0 >> 4));
+#endif
+#define V9_STREAM_DECLS                                                                                                 \
+    const long long row_bytes = (long long)kp * 1024;                                                                   \
+    V9_TILE_ROWS                                                                                                        \
+    const int8_t* xbase = a.xm + (long long)(m0 >> 4) * row_bytes + (long long)kstep0 * 1024;                           \
+    const int8_t* wbase = a.wm + (long long)(n0 >> 4) * row_bytes + (long long)kstep0 * 1024;                           \
+    const int x_nrec = (int)(pa_rows * row_bytes), w_nrec = (int)(pb_rows * row_bytes);                                 \
+    const long long row_bytes1 = (long long)kp1 * 1024;                                                                 \
+    const int8_t* xbase1 = MIXED ? a.xm1 + (long long)(m0 >> 4) * row_bytes1 : nullptr;                                 \
+    const int8_t* wbase1 = MIXED ? a.wm1 + (long long)(n0 >> 4) * row_bytes1 : nullptr;                                 \
+    const int x_nrec1 = (int)(pa_rows * row_bytes1), w_nrec1 = (int)(pb_rows * row_bytes1);                             \
+    int voff[4];                                                                                                        \
+    _Pragma("unroll") for (int q = 0; q < 4; ++q) voff[q] = (wave + 8 * (q & 1)) * (int)row_bytes + lane * 16;          \
+    const int dvo0 = MIXED ? wave * (int)(row_bytes1 - row_bytes) : 0, dvo1 = MIXED ? (wave + 8) * (int)(row_bytes1 - row_bytes) : 0;
+    // piece q (literal) of K-step `step` into ring slots at byte offsets sa (A) / sb (B)
+#define V9_PIECE(q, rxd, rwd, soff, sa, sb)                                                                             \
+    V9_BLDS16(MIXED ? voff[(q) & 3] + (c1_ ? (((q) & 1) ? dvo1 : dvo0) : 0) : voff[q], (q) < 2 ? rxd : rwd, soff,           \
+              ring_lds + ((q) < 2 ? (sa) : V9_B0 + (sb)) + (wave + 8 * ((q) & 1)) * 1024)
+#define V9_DESCS(step)                                                                                                  \
+    const bool more_ = (step) < nsteps;                                                                                 \
+    const bool c1_ = MIXED && (step) >= nsteps0;                                                                        \
+    const i32x4 rxd_ = v9_desc(c1_ ? xbase1 : xbase, more_ ? (c1_ ? x_nrec1 : x_nrec) : 0),                             \
+                rwd_ = v9_desc(c1_ ? wbase1 : wbase, more_ ? (c1_ ? w_nrec1 : w_nrec) : 0);                             \
+    const int soff_ = (c1_ ? (step) - nsteps0 : (step)) * 1024;
+#define V9_STAGE(step, sa, sb) { V9_DESCS(step) V9_PIECE(0, rxd_, rwd_, soff_, sa, sb); V9_PIECE(1, rxd_, rwd_, soff_, sa, sb); V9_PIECE(2, rxd_, rwd_, soff_, sa, sb); V9_PIECE(3, rxd_, rwd_, soff_, sa, sb); }
+
 // FIX_ 1: with the exception add-back formed by the tile itself behind its K loop.  STAMP: diagnostic build, phase times go
 // to a.stamps.
 // MIXED (round 6): the contraction in TWO column classes in one launch -- class 0 (a.K values: a.xm / a.wm, row-aligned int8 with
@@ -223,11 +272,29 @@ __device__ __forceinline__ void gated_post_tile(const GemmArgs& a, const unsigne
 // than the rest): the block columns that hold such a channel lie several exponents above their rows' window and their exponents
 // follow one element's magnitude -- no row window of the int8 container holds them (20 % of all blocks at K / 64 channels x 60),
 // so the whole layer used to run at the bf16 rate.  Here only those columns do: K1 / K of the MFMA work at half rate.
+#ifdef V9_FULL_TU
+// (what only the rare paths read -- the overflow fallback, the atomics last resort, the exception x exception terms, the stamps:
+//  passed by reference to the kernel argument segment, each field loaded where it is used and nowhere across the K loop)
+struct V9FullRare {
+    const uint8_t *xe, *we, *xf, *wf;
+    unsigned long long* stamps;
+    int x_bcap, w_bcap, row_mode, scale_bias;
+};
+template <int FIX_, bool BF16, bool STAMP, bool MIXED, bool BIAS>
+__global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const int8_t* __restrict__ xm_in, const int8_t* __restrict__ wm_in,
+                                                        const float* __restrict__ bias_in, float* __restrict__ y_in,
+                                                        const float* __restrict__ sx, const float* __restrict__ sw,
+                                                        const int* __restrict__ xlist, const int* __restrict__ wlist, const int M_in,
+                                                        const int N_in, const int K_in, const int ldy_in, const int x_off_in,
+                                                        const int w_off_in, const V9FullRare rare) {
+    static_assert(FIX_ == 1 && !BF16 && !MIXED, "the full-tile unit is the int8 kernel with its lists");
+#else
 template <int FIX_, bool BF16, bool STAMP, bool MIXED = false>
 __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, const float* __restrict__ sx,
                                                         const float* __restrict__ sw_in, const int* __restrict__ xlist,
                                                         const int* __restrict__ wlist_in, const uint8_t* __restrict__ xf,
                                                         const uint8_t* __restrict__ wf_in) {
+#endif
     constexpr int FIX = FIX_ != 0 ? 1 : 0;
     constexpr bool TPF = FIX_ == 1;                       // the tile's gathers ride in the K-steps past the end (round 4)
     static_assert(!BF16 || FIX_ == 0, "the bf16 arithmetic has no exception lists");
@@ -244,10 +311,19 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
     unsigned long long st_t[6] = {0, 0, 0, 0, 0, 0}, st_x[3] = {0, 0, 0}, st_y[2] = {0, 0};
     if (STAMP) st_t[0] = __builtin_amdgcn_s_memrealtime();
 
+#ifdef V9_FULL_TU
+    // (every field the launch does not use is a constant here: ngroup 0, splits 1, x_post 0, dbg 0, resid null)
+    GemmArgs a{};
+    a.xm = xm_in; a.wm = wm_in; a.bias = BIAS ? bias_in : nullptr; a.y = y_in;
+    a.M = M_in; a.N = N_in; a.K = K_in; a.ldy = ldy_in;
+    a.x_off = x_off_in; a.w_off = w_off_in;
+    a.splits = 1;
+#else
     GemmArgs a = a_in;
     const float* __restrict__ sw = sw_in;
     const int* __restrict__ wlist = wlist_in;
     const uint8_t* __restrict__ wf = wf_in;
+#endif
     const int ngroup = a.ngroup > 1 ? a.ngroup : 1;
     const int Mi = (int)a.M, Ni = (int)a.N;
     const int tiles_m = (Mi + 255) >> 8, tiles_n1 = (Ni + 255) >> 8, tiles_n = tiles_n1 * ngroup;
@@ -263,6 +339,7 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
     const int gsz = min(tiles_m - first_m, GM);
     const int tm = first_m + (tile_id % in_group) % gsz;
     int tn = (tile_id % in_group) / gsz;
+#ifndef V9_FULL_TU
     if (ngroup > 1) {
         const int which = tn / tiles_n1;                                  // (wave-uniform: scalar loads from the argument block)
         tn -= which * tiles_n1;
@@ -272,6 +349,7 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
         sw = V9_PICK(g_sw); wlist = V9_PICK(g_wlist); wf = V9_PICK(g_wf);
 #undef V9_PICK
     }
+#endif
     const int m0 = tm * 256, n0 = tn * 256;
     const int kp = (int)(a.K >> 6);                             // 1-KiB pieces per 16 rows
     const int kstep0 = S > 1 ? (int)((long long)kp * split / S) : 0;       // this workgroup's slice of the K-steps
@@ -299,6 +377,11 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
     // ---- in front of the operand stream (same queue, so landed by the first counted wait): the tile's scale / bias
     //      slices, its two exception buckets and the lists' overflow words
     const int ring_lds = (int)(size_t)(lptr_t)ring, side_lds = (int)(size_t)(lptr_t)side;     // the objects' own LDS addresses
+#ifdef V9_FULL_TU
+    // K-step 0 first: the side data is not needed before the bookkeeping, the first MFMA waits for this (see V9_SIDE_WAIT)
+    V9_STREAM_DECLS
+    V9_STAGE(0, 0, 0)
+#endif
     if (wave == 0 || wave == 1) {
         if (FIX && !(wave == 0 && a.x_post)) {
             const int* b = wave == 0 ? row_bucket(xlist, m0) : row_bucket(wlist, n0);
@@ -313,8 +396,13 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
         V9_GLDS16(sw + n0 + lane * 4, side_lds + V9_SWT);
     } else if (wave == 4) {
         // (bounds-checked by the descriptor: columns past N read as zero, no address past the array is touched)
+#ifdef V9_FULL_TU
+        if (BIAS) {
+            const i32x4 rb = v9_desc(a.bias + n0, 1024);
+#else
         if (a.bias) {
             const i32x4 rb = v9_desc(a.bias + n0, (Ni - n0) * 4);
+#endif
 #pragma unroll
             for (int q = 0; q < 4; ++q) V9_BLDS4(lane * 4 + q * 256, rb, 0, side_lds + V9_BIAS + q * 256);
         } else {
@@ -336,38 +424,12 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
     };
     if (FIX) clear_maps_and_vectors();
 
-    // ---- the operand stream.  Piece p of a K-step: 16 rows of A (p < 16) or of B; this wave stages pieces wave + 8 q.
-    //      One descriptor per operand, rooted at the tile's first piece row and ending with its last (rows past the
-    //      operand read as zero); the lane's part of the address is fixed, the K-step rides in the scalar offset.
-    const long long row_bytes = (long long)kp * 1024;           // one piece row (16 rows x K bytes)
-    const int pa_rows = min(16, ((Mi + 127) >> 7) * 8 - (m0 >> 4)), pb_rows = min(16, ((Ni + 127) >> 7) * 8 - (n0 >> 4));
-    const int8_t* xbase = a.xm + (long long)(m0 >> 4) * row_bytes + (long long)kstep0 * 1024;
-    const int8_t* wbase = a.wm + (long long)(n0 >> 4) * row_bytes + (long long)kstep0 * 1024;
-    // (the range check covers the lane's offset only, not the scalar one: a K-step past the end of the slice is requested
-    //  through a descriptor of zero bytes -- no memory traffic, zeros land in the slot)
-    const int x_nrec = (int)(pa_rows * row_bytes), w_nrec = (int)(pb_rows * row_bytes);
-    // MIXED: the class-1 operands (tiled bf16: kp1 pieces of 16 rows x 32 values per piece row)
-    const long long row_bytes1 = (long long)kp1 * 1024;
-    const int8_t* xbase1 = MIXED ? a.xm1 + (long long)(m0 >> 4) * row_bytes1 : nullptr;
-    const int8_t* wbase1 = MIXED ? a.wm1 + (long long)(n0 >> 4) * row_bytes1 : nullptr;
-    const int x_nrec1 = (int)(pa_rows * row_bytes1), w_nrec1 = (int)(pb_rows * row_bytes1);
-    int voff[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) voff[q] = (wave + 8 * (q & 1)) * (int)row_bytes + lane * 16;
-    // (the lane offsets of a class-1 piece differ only in the piece row's length: one scalar add per piece)
-    const int dvo0 = MIXED ? wave * (int)(row_bytes1 - row_bytes) : 0, dvo1 = MIXED ? (wave + 8) * (int)(row_bytes1 - row_bytes) : 0;
-    // piece q (literal) of K-step `step` into ring slots at byte offsets sa (A) / sb (B)
-#define V9_PIECE(q, rxd, rwd, soff, sa, sb)                                                                             \
-    V9_BLDS16(MIXED ? voff[(q) & 3] + (c1_ ? (((q) & 1) ? dvo1 : dvo0) : 0) : voff[q], (q) < 2 ? rxd : rwd, soff,           \
-              ring_lds + ((q) < 2 ? (sa) : V9_B0 + (sb)) + (wave + 8 * ((q) & 1)) * 1024)
-#define V9_DESCS(step)                                                                                                  \
-    const bool more_ = (step) < nsteps;                                                                                 \
-    const bool c1_ = MIXED && (step) >= nsteps0;                                                                        \
-    const i32x4 rxd_ = v9_desc(c1_ ? xbase1 : xbase, more_ ? (c1_ ? x_nrec1 : x_nrec) : 0),                             \
-                rwd_ = v9_desc(c1_ ? wbase1 : wbase, more_ ? (c1_ ? w_nrec1 : w_nrec) : 0);                             \
-    const int soff_ = (c1_ ? (step) - nsteps0 : (step)) * 1024;
-#define V9_STAGE(step, sa, sb) { V9_DESCS(step) V9_PIECE(0, rxd_, rwd_, soff_, sa, sb); V9_PIECE(1, rxd_, rwd_, soff_, sa, sb); V9_PIECE(2, rxd_, rwd_, soff_, sa, sb); V9_PIECE(3, rxd_, rwd_, soff_, sa, sb); }
+#ifndef V9_FULL_TU
+    V9_STREAM_DECLS
+#endif
+#ifndef V9_FULL_TU
     V9_STAGE(0, 0, 0)
+#endif
     V9_STAGE(1, V9_HALF, V9_HALF)
     V9_STAGE(2, 2 * V9_HALF, 2 * V9_HALF)
     if (STAMP) st_t[1] = __builtin_amdgcn_s_memrealtime();
@@ -388,7 +450,11 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
             const bool valid = i < nent, is_x = i < cx;
             int* e = v8_entry(xb, wb, cx, valid ? i : 0);
             const int r = e[0], base = is_x ? m0 : n0;
+#ifdef V9_FULL_TU
+            const bool live = valid && (is_x ? (r >= m0 && r < m0 + 256) : (r >= n0 && r < n0 + 256));     // (every tile is full)
+#else
             const bool live = valid && (is_x ? (r >= m0 && r < m0 + 256 && r < Mi) : (r >= n0 && r < n0 + 256 && r < Ni));
+#endif
             const int lo = is_x ? 0 : cx, hi = is_x ? cx : nent;
             // (slot = the list index of the row's entry with the SMALLEST BLOCK: a property of the data, not of the order in
             //  which rows reserved their list slots -- the sums below start from it and go on in ascending block order)
@@ -408,11 +474,23 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
             }
         }
     };
+    // (V9_SIDE_WAIT.  A wave's vector-memory queue at this point, oldest first -- loads return, and vmcnt counts down, in order:
+    //    every other unit:  [side area: 0-4 by wave] [K-step 0: 4] [K-step 1: 4] [K-step 2: 4]  -- at most 12 outstanding: the side
+    //                       data has landed; at most 8 (below): K-step 0 too;
+    //    full-tile unit:    [K-step 0: 4] [side area: 0-4 by wave] [K-step 1: 4] [K-step 2: 4]  -- the side data is behind K-step 0, so
+    //                       it has landed only when no more than the 8 pieces of K-steps 1 and 2 are outstanding: 8.  12 would let a
+    //                       wave with four side loads go on with all of them in flight.  The wait below for K-step 0 (8) then holds
+    //                       already, and from there on the queue is what it is in every other unit: the loop's counts stay.)
+#ifdef V9_FULL_TU
+#define V9_SIDE_WAIT 8
+#else
+#define V9_SIDE_WAIT 12
+#endif
     // TPF: the bookkeeping runs HERE, in the shadow of the first stages' flight: the buckets, scales and header words were
     // requested in front of the operand pieces, so twelve outstanding LDS-DMA instructions mean they have landed
     bool early_bk = false;
     if (TPF && !(a.dbg & 16)) {                                 // (dbg 16, A/B: bookkeeping behind the loop)
-        V9_WAITV(12);
+        V9_WAITV(V9_SIDE_WAIT);
         V9_LGKM(0);                                             // (this thread's share of the cleared maps has landed)
         __builtin_amdgcn_s_barrier();
         const int ecx = a.x_post ? 0 : __builtin_amdgcn_readfirstlane(min(xb[0], ROW_BCAP));
@@ -433,6 +511,14 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
         if (__builtin_amdgcn_readfirstlane(ovf[0] | ovf[64]) != 0) {
             V9_WAITV(0);
             __syncthreads();
+#ifdef V9_FULL_TU
+            // (what the shared fallback reads beside the plain arguments -- the blockwise operands, their exponents, the bucket
+            //  capacities: from the argument segment, in this branch only)
+            const uint8_t* const xf = rare.xf;
+            const uint8_t* const wf = rare.wf;
+            a.xe = rare.xe; a.we = rare.we; a.row_mode = rare.row_mode; a.x_bcap = rare.x_bcap; a.w_bcap = rare.w_bcap;
+            a.scale_bias = rare.scale_bias;
+#endif
             if constexpr (MIXED) {
                 // the mixed contraction's own fallback, tile by tile (no other workgroup touches this tile): first the class-1
                 // product of this 256 x 256 tile -- fragments straight from memory (the tiled pieces ARE fragments: lane = (row,
@@ -512,6 +598,9 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
                     __syncthreads();
                 }
             }
+            return;
+#elif defined(V9_FULL_TU)
+            v8_fallback(a, xf, wf, xlist, wlist, ring, (int)blockIdx.x, nwg);
             return;
 #else
             v8_fallback(a, xf, wf, xlist, wlist, ring, ngroup > 1 ? (tm * tiles_n1 + tn) * S + split : (int)blockIdx.x,
@@ -651,6 +740,10 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
         V9_PAIR(acc, nsteps - 2, 4, 5)
     }
     }
+#ifdef V9_FULL_TU
+    a.scale_bias = rare.scale_bias;   // (read behind the K loop only: the exception x exception terms, the atomics last resort)
+    if (STAMP) a.stamps = rare.stamps;
+#endif
     const int dead_a = a3;            // (the A half of the last K-step: nothing was requested into it, dead behind the loop)
     // ring slots (byte offsets) of the steps past the end: step nsteps + j went to a_j / b_j (the rotation above)
     const int ga_[3] = {a0, a1, a2}, gb_[3] = {b0, b1, b2};
@@ -840,7 +933,15 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
     const int* const cslot_r = rslot_r + 256;
     unsigned cmask = 0, jmask = 0;      // bit 4 j + r: some lane of the wave has a vector for that column; bit j: tile column j has one
     unsigned rmask = 0;                 // bit i: some row of fragment i has a vector (set by the one-pass epilogue from its preloads)
+    // (the full-tile unit: every row and column of the tile exists and the launcher has checked y's alignment)
+#ifdef V9_FULL_TU
+#define V9_ROW_IN(row) true
+#define V9_VEC4_IN(col) true
+#else
+#define V9_ROW_IN(row) row < a.M
+#define V9_VEC4_IN(col) vec_ok && col + 3 < Ni
     const bool vec_ok = ((reinterpret_cast<uintptr_t>(a.y) | (uintptr_t)(a.ldy * 4)) & 15) == 0;
+#endif
     // tiles of fragment i: pass 0 the ones no vector touches, pass 1 the others (with their vectors)
     auto store_rows = [&](int i, int pass) {
         const bool rowv = (rmask >> i) & 1;
@@ -881,7 +982,7 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
                             val[r] += c4[r] >= 0 ? V9_VEC(max(c4[r], 0))[rl] : 0.f;
                 }
             }
-            if (row < a.M) {
+            if (V9_ROW_IN(row)) {
                 const int col = n0 + cl;
                 if (a.resid) {                                   // (uniform) the caller's residual add, in the store
                     const float* rr = a.resid + row * a.ldr + col;
@@ -891,7 +992,7 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
                         for (int r = 0; r < 4; ++r)
                             if (col + r < Ni) val[r] += rr[r];
                 }
-                if (vec_ok && col + 3 < Ni) {
+                if (V9_VEC4_IN(col)) {
                     *reinterpret_cast<f32x4*>(yrow + j * 16) = val;
                 } else {
 #pragma unroll
@@ -1213,7 +1314,7 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
                             val[j][r] += c4[r] >= 0 ? V9_VEC(max(c4[r], 0))[rl] : 0.f;
                 }
             }
-            if (row < a.M) {
+            if (V9_ROW_IN(row)) {
 #ifdef V9_RESID_TU
                 if (a.resid) {                                   // (uniform) the caller's residual add, in the store (see V9_RESID_TU)
                     const float* rr = a.resid + row * a.ldr + n0 + wn * 64 + lq * 4;
@@ -1231,7 +1332,7 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int col = n0 + wn * 64 + j * 16 + lq * 4;
-                    if (vec_ok && col + 3 < Ni) {
+                    if (V9_VEC4_IN(col)) {
                         V9_STORE16(yrow + j * 16, val[j]);
                     } else {
 #pragma unroll
@@ -1275,7 +1376,7 @@ __global__ __launch_bounds__(V9_NT, 1) void bfp_gemm_v9(const GemmArgs a_in, con
     }
 }
 
-#if !defined(V9_MIXED_TU) && !defined(V9_GATED_TU) && !defined(V9_RESID_TU)
+#if !defined(V9_MIXED_TU) && !defined(V9_GATED_TU) && !defined(V9_RESID_TU) && !defined(V9_FULL_TU)
 static unsigned long long* g_v9_stamps = nullptr;       // diagnostic (tools/dbg/v9_stamps.py): where the stamps build writes
 #endif
 
@@ -1314,7 +1415,44 @@ int launch_bfp_gemm_v9_resid(const GemmArgs& a, const float* sx, const float* sw
     hipLaunchKernelGGL((bfp_gemm_v9<1, false, false>), grid, V9_NT, 0, st, a, sx, sw, xlist, wlist, xf, wf);
     return (int)hipGetLastError();
 }
+#elif defined(V9_FULL_TU)
+static std::atomic<long long> g_v9_full_launches{0};     // diagnostic (mi355q_debug_v9_full_count): launches that took this unit
+// the full-tile launch: the caller (launch_bfp_gemm_v9) has asked v9_full_tile_ok.  `stamps`: the registered stamps buffer or null.
+int launch_bfp_gemm_v9_full(const GemmArgs& a, const float* sx, const float* sw, const int* xlist, const int* wlist, hipStream_t st,
+                            const uint8_t* xf, const uint8_t* wf, unsigned long long* stamps) {
+    if (!xlist || !wlist || !xf || !wf || !sx || !sw) return MI355Q_E_BADARG;
+    if (a.M % 256 != 0 || a.N % 256 != 0 || a.K % 128 != 0 || a.K < 256 || a.splits > 1 || a.ngroup > 1 || a.x_post || a.resid || a.dbg)
+        return MI355Q_E_UNSUPPORTED;
+    const dim3 grid((unsigned)((a.M / 256) * (a.N / 256))), block(V9_NT);
+    const V9FullRare rare{a.xe, a.we, xf, wf, stamps, a.x_bcap, a.w_bcap, a.row_mode, a.scale_bias};
+    const int M = (int)a.M, N = (int)a.N, K = (int)a.K, ldy = (int)a.ldy;
+    // (benchmark timing: the events carry this dispatch's own start and end -- mi355q_internal.h; never with the stamps build)
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (!stamps && g_kernel_events.start) {
+        ev0 = g_kernel_events.start;
+        ev1 = g_kernel_events.stop;
+        g_kernel_events.start = nullptr;
+    }
+#define V9F_ARGS a.xm, a.wm, a.bias, a.y, sx, sw, xlist, wlist, M, N, K, ldy, a.x_off, a.w_off, rare
+#define V9F_LAUNCH(BIAS_, STAMP_)                                                                                                  \
+    if (ev0) hipExtLaunchKernelGGL((bfp_gemm_v9<1, false, STAMP_, false, BIAS_>), grid, block, 0, st, ev0, ev1, 0, V9F_ARGS);      \
+    else hipLaunchKernelGGL((bfp_gemm_v9<1, false, STAMP_, false, BIAS_>), grid, block, 0, st, V9F_ARGS)
+    if (stamps) {
+        if (a.bias) { V9F_LAUNCH(true, true); } else { V9F_LAUNCH(false, true); }
+    } else {
+        if (a.bias) { V9F_LAUNCH(true, false); } else { V9F_LAUNCH(false, false); }
+    }
+#undef V9F_LAUNCH
+#undef V9F_ARGS
+    g_v9_full_launches.fetch_add(1, std::memory_order_relaxed);
+    return (int)hipGetLastError();
+}
 #else
+// MI355Q_V9_FULL=0 (read once, at the first launch): every launch on the general kernel, for A/B runs against the full-tile unit
+static bool v9_full_enabled() {
+    static const bool on = [] { const char* e = getenv("MI355Q_V9_FULL"); return !e || atoi(e) != 0; }();
+    return on;
+}
 int launch_bfp_gemm_v9(const GemmArgs& a_in, const float* sx, const float* sw, const int* xlist, const int* wlist,
                        hipStream_t st, const uint8_t* xf, const uint8_t* wf, bool bf16) {
     if (a_in.resid && !bf16 && xlist && wlist) return launch_bfp_gemm_v9_resid(a_in, sx, sw, xlist, wlist, st, xf, wf);
@@ -1325,6 +1463,11 @@ int launch_bfp_gemm_v9(const GemmArgs& a_in, const float* sx, const float* sw, c
     if (want_stamps) a.stamps = g_v9_stamps;
     const bool fix = xlist && wlist;
     if (fix && (!xf || !wf)) return MI355Q_E_BADARG;
+    // the full-tile unit where nothing of the general body is needed (mi355q_gemm_v9_full.h); with a stamps buffer, its stamps build
+    const bool y_aligned = ((reinterpret_cast<uintptr_t>(a.y) | (uintptr_t)(a.ldy * 4)) & 15) == 0;
+    if (v9_full_tile_ok(V9FullQuery{9, a.splits, a.ngroup, fix, bf16, a.M, a.N, a.ldy, a.resid != nullptr, a.x_post != 0, a.dbg, y_aligned,
+                                    v9_full_enabled()}))
+        return launch_bfp_gemm_v9_full(a, sx, sw, xlist, wlist, st, xf, wf, want_stamps ? a.stamps : nullptr);
     const unsigned tiles = (unsigned)((a.M + 255) / 256 * ((a.N + 255) / 256));
     const unsigned grid = tiles * (a.ngroup > 1 ? a.ngroup : 1) * (a.splits > 1 ? a.splits : 1);
     if (bf16) hipLaunchKernelGGL((bfp_gemm_v9<0, true, false>), grid, V9_NT, 0, st, a, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
@@ -1342,7 +1485,11 @@ int launch_bfp_gemm_v9(const GemmArgs& a_in, const float* sx, const float* sw, c
 
 }  // namespace mi355q
 
-#if !defined(V9_MIXED_TU) && !defined(V9_GATED_TU) && !defined(V9_RESID_TU)
+#if !defined(V9_MIXED_TU) && !defined(V9_GATED_TU) && !defined(V9_RESID_TU) && !defined(V9_FULL_TU)
 // diagnostic hook, not part of include/mi355q.h: the buffer ([workgroups][2][8] 64-bit words) the MI355Q_V9_STAMPS build fills
 extern "C" __attribute__((visibility("default"))) void mi355q_debug_v9_stamps(void* buf) { mi355q::g_v9_stamps = static_cast<unsigned long long*>(buf); }
+#endif
+#ifdef V9_FULL_TU
+// diagnostic hook, not part of include/mi355q.h: how many launches of this process took the full-tile unit (tests tell the two kernels apart by it)
+extern "C" __attribute__((visibility("default"))) long long mi355q_debug_v9_full_count(void) { return mi355q::g_v9_full_launches.load(std::memory_order_relaxed); }
 #endif

@@ -1,5 +1,6 @@
 """In-kernel phase stamps of the 256 x 256 tile GEMM (MI355Q_V9_STAMPS=1 selects the stamps build): after 150 ms of
-un-stamped work (steady clocks) a few stamped launches; medians over the workgroups, wave 0 and wave 7."""
+un-stamped work (steady clocks; `python tools/dbg/v9_stamps.py SECONDS` for a longer soak) a few stamped launches; medians over
+the workgroups, wave 0 and wave 7.  The headline shape takes the full-tile unit's stamps build; MI355Q_V9_FULL=0 the general kernel's."""
 import os, sys, time, ctypes
 os.environ["MI355Q_V9_STAMPS"] = "1"
 sys.path.insert(0, 'llm-mixed-q_amd'); sys.path.insert(0, '.')
@@ -14,7 +15,7 @@ y = torch.empty(4096, 4096, device=dev)
 lib = ctypes.CDLL(os.path.join(os.path.dirname(_lib.__file__), "libmi355q.so"))
 stamps = torch.zeros(256 * 2 * 8, dtype=torch.int64, device=dev)
 xa = ops.block_fp_quantize_aligned_rows(x, 6, 8, 127)
-t_end = time.time() + 0.15
+t_end = time.time() + (float(sys.argv[1]) if len(sys.argv) > 1 else 0.15)
 while time.time() < t_end:
     for _ in range(10): ops.bfp_gemm_aligned(xa, wa, bq, out=y)
     torch.cuda.synchronize()
