@@ -856,6 +856,27 @@ int mi355q_bm_attention_decode(const float* q, const void* kq, const void* vq, i
                                int64_t C, int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides,
                                int32_t splits, void* stream);
 
+/* mi355q_bm_attention: the quantised attention core of a block_minifloat layer as ONE pass -- mi355q_bfp_attention_strided for a layer
+ * whose bmm_0 / bmm_1 (matmul_0 / matmul_1) are block_minifloat [1,16], without mask, rotary embedding and consumer.  Replaces
+ * modeling_opt.py:246-312, modeling_llama.py:309-344 and modeling_bert.py:366-436 (both products through matmul.py:199-249, the scale,
+ * the causal mask, the softmax) for such a layer: neither the scores nor the probabilities [B, M, T] exist in memory.
+ *   q fp32 [B, M, D], k / v fp32 [B, T, D] (k NOT transposed), out fp32 [B, M, D], all by `strides` = int64[8] {q batch, q row, k batch,
+ *   k row, v batch, v row, out batch, out row} in elements, innermost stride 1 (NULL: contiguous; a token-major output is out strides).
+ *   qk_params / pv_params: int32[6] each, (width, exponent_width, exponent_bias_width) of data_in, then of weight, with the accepted
+ *   ranges of mi355q_bm_kv_append.  causal != 0: query i sees keys 0 .. i + T - M.  q_scale != 0: q * q_scale in front of the Q quantiser
+ *   (OPT).  scale_div != 0: scores / scale_div (Llama).  workspace: mi355q_bm_attention_workspace_bytes(B, T, D) bytes, 16-byte aligned;
+ *   a pack launch leaves K^T and V there as the bytes a block_minifloat cache of T keys holds after the same keys were appended.
+ * The arithmetic is mi355q_bm_attention_decode's: the softmax statistics are final before any probability is quantised; a probability
+ * <= 1e-8 passes through UNQUANTISED, as in the reference (minifloat.py: |x| <= 1e-8 is kept), and the pass-through probabilities'
+ * products are accumulated apart from the quantised ones' and added once at the end.
+ * MI355Q_E_UNSUPPORTED: T % 16 != 0, D not 32 / 64 / 96 / 128, causal with M > T, a format outside exponent_width 1 .. 8, mantissa bits
+ * 1 .. 7, exponent_bias_width 1 .. 8.  MI355Q_E_BADARG: a NULL pointer, a negative size, T == 0, B > 65535.  MI355Q_E_ALIGN: a pointer
+ * that is not 16-byte aligned, a stride that is no multiple of 4.  B == 0 or M == 0: 0, nothing is launched.  Streaming form only. */
+size_t mi355q_bm_attention_workspace_bytes(int64_t B, int64_t T, int64_t D);
+int mi355q_bm_attention(const float* q, const float* k, const float* v, float* out, void* workspace, int64_t B, int64_t M, int64_t T,
+                        int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides, int32_t causal,
+                        float scale_div, float q_scale, void* stream);
+
 /* Sliding window: decode and extend with every query bound to its last `window` = W >= 1 keys, its own included -- a query at absolute
  * position p (decode: L_b - M + i; extend: L_b - m_b + i) sees keys max(0, p - W + 1) .. p.  That is the `past_key_value` call with an
  * additive mask that is finfo.min below the window as well as above the horizon: the cache is unchanged, K^T's and P's 16-key blocks

@@ -19,6 +19,7 @@
 #include "mi355q_kv_call.h"
 #include "mi355q_sink.h"
 #include "mi355q_kv_copy.h"
+#include "mi355q_attention_bm.h"
 #include "mi355q_align_row.h"
 
 using namespace mi355q;
@@ -1195,6 +1196,35 @@ int mi355q_bm_attention_decode(const float* q, const void* kq, const void* vq, i
                                int32_t splits, void* stream) {
     return decode(KvCall(KV_EXPORTS[KVX_BM_DECODE]).cache(kq, vq, nullptr, B, C, D).lens(lengths, nullptr, max_length)
                       .query(q, out, workspace, M, G, causal, 0, splits).quant(qk_params, pv_params, strides), q, out, workspace, q_scale, scale_div, stream);
+}
+
+// the one-pass attention core of a block_minifloat layer (mi355q_attention_bm.h): pack launch + streaming launch, no cache involved
+size_t mi355q_bm_attention_workspace_bytes(int64_t B, int64_t T, int64_t D) {
+    if (B <= 0 || T <= 0 || D <= 0) return 0;
+    return bm_attention_workspace_bytes(B, T, D);
+}
+
+int mi355q_bm_attention(const float* q, const float* k, const float* v, float* out, void* workspace, int64_t B, int64_t M, int64_t T,
+                        int64_t D, const int32_t* qk_params, const int32_t* pv_params, const int64_t* strides, int32_t causal,
+                        float scale_div, float q_scale, void* stream) {
+    if (B < 0 || M < 0 || T < 0 || D < 0) return MI355Q_E_BADARG;
+    if (B == 0 || M == 0) return 0;
+    if (!q || !k || !v || !out || !workspace || !qk_params || !pv_params || T == 0 || B > 65535) return MI355Q_E_BADARG;
+    if (T % 16 != 0 || (D != 32 && D != 64 && D != 96 && D != 128) || (causal && M > T)) return MI355Q_E_UNSUPPORTED;
+    QuantArgs a[4] = {};                                    // Q, K^T, P, V
+    int rc;
+    if ((rc = bm_quant_pair(qk_params, pv_params, 0, a[0], a[2])) != 0 || (rc = bm_quant_pair(qk_params, pv_params, 3, a[1], a[3])) != 0) return rc;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(out) |
+         reinterpret_cast<uintptr_t>(workspace)) % 16)
+        return MI355Q_E_ALIGN;
+    long long st8[8];
+    if (strides)
+        for (int i = 0; i < 8; ++i) {
+            if (strides[i] % 4) return MI355Q_E_ALIGN;            // (16-byte loads / stores of every row)
+            st8[i] = strides[i];
+        }
+    return launch_bm_attention(a[0], a[1], a[2], a[3], q, k, v, out, workspace, B, M, T, D, causal ? T - M : -1, q_scale, scale_div,
+                               strides ? st8 : nullptr, static_cast<hipStream_t>(stream));
 }
 
 // sliding window: a query sees its last `window` keys; always the ragged form, paged or (block_table == NULL) contiguous

@@ -186,6 +186,21 @@ __device__ __forceinline__ float at_bm_quant(float x, int bias, int mbits, const
     }
     return q;
 }
+// kv_store_block of mi355q_decode.hip under block_minifloat: one block of 16 values x with maximum bmax, value e the low halfword of a
+// lane's slot, 8 halfwords apart.  An all-zero block (bmax = 0) takes bias 0 and stores zeros: the reference gives it the smallest
+// non-zero block maximum of the whole tensor, which no zero can show (|x| <= 1e-8 passes through under any bias).
+__device__ __forceinline__ void kvbm_store_block(uint16_t* __restrict__ dst, const float (&x)[16], float bmax, const QuantArgs& a) {
+    const int mbits = (int)__builtin_log2f(a.shift);
+    const int bias = at_bm_bias_mem(bmax, a);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        // (an input -0.0 becomes +0.0 in the reference's mask arithmetic; a NEGATIVE value whose mantissa rounds to 0 stays -0.0 there --
+        //  sign * 2^e * 0 -- unlike block_fp's, so no "+ 0" on the quantised value)
+        const float qe = at_bm_quant(x[e], bias, mbits, a);
+        const float q = x[e] == 0.f ? 0.f : qe;
+        dst[e * 8] = (uint16_t)(pack_bf16(q, 0.f) & 0xFFFFu);
+    }
+}
 // at_quant_q_frag under block_minifloat: the same lanes, loads and block maximum (lanes l, l ^ 16 of a chunk), the block's bias from
 // at_bm_bias_mem, the elements through at_bm_quant
 template <int DC>

@@ -129,6 +129,8 @@ SIGNATURES = {
     "mi355q_bm_kv_append": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "mi355q_bm_attention_decode": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, C.c_float, C.c_float, _vp, _vp, _i64, _i64, _i64,
                                              _i64, _i64, _vp, _vp, _vp, _i32, _vp]),
+    "mi355q_bm_attention_workspace_bytes": (C.c_size_t, [_i64, _i64, _i64]),
+    "mi355q_bm_attention": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i32, C.c_float, C.c_float, _vp]),
     "mi355q_stream_capture_id": (C.c_uint64, [_vp]),
     "mi355q_rope_apply": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "mi355q_bfp_gemm_aligned": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),

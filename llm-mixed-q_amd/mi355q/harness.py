@@ -32,6 +32,18 @@ def _attention_consumer(c1: dict, proj, hs, B: int):
     return proj.consumer_quantiser() if ok is not None and ok() else None
 
 
+def _one_pass_attention(c0: dict, c1: dict) -> str:
+    """which one-pass attention function config["mi355q_fused_attention"] of the second product switches on: "block_fp" (the second
+    product is block_fp: attention_block_fp with its consumer / rotary / token-major shortcuts), "block_minifloat" (BOTH products are
+    block_minifloat: attention_block_minifloat, plain fp32 output and none of the shortcuts), or None (knob off or absent, any other
+    format)"""
+    if not c1.get("mi355q_fused_attention", False):
+        return None
+    if c1["name"] == "block_fp":
+        return "block_fp"
+    return "block_minifloat" if c0.get("name") == c1["name"] == "block_minifloat" else None
+
+
 def _project_attention_output(o, proj, out, B, T, width, residual):
     """out_proj / o_proj behind the attention function: on its tiled operand (ops.TiledBf16) where the pass wrote one"""
     if isinstance(o, ops.TiledBf16):
@@ -85,7 +97,8 @@ class _Attention(nn.Module):
         nh = self.nh if hs is None else self.q_proj.local.out_features // self.hd
         shape = lambda t: t.view(B, T, nh, self.hd).transpose(1, 2).contiguous().view(B * nh, T, self.hd)
         c1 = self.qc["bmm_1"]
-        if c1["name"] == "block_fp" and c1.get("mi355q_fused_attention", False):
+        one_pass = _one_pass_attention(self.qc["bmm_0"], c1)
+        if one_pass is not None:
             # both products, the mask and the softmax in one pass per 16 queries (the harness' mask is the causal one); the
             # kernel reads the [heads, T, hd] views of the projections in place: no `_shape(...).contiguous()` copies
             heads = lambda t: t.view(B, T, nh, self.hd).transpose(1, 2)
@@ -96,7 +109,8 @@ class _Attention(nn.Module):
             # (q * scaling, modeling_opt.py:231: formed where the attention pass packs its Q fragments -- q_scale)
             pad = {} if key_mask is None else {"key_mask": key_mask}
             o = get_quantized_func("attention", c1)(heads(qp), heads(kp), heads(vp), self.qc["bmm_0"], c1, causal=True,
-                                                    q_scale=self.scaling, consumer=_attention_consumer(c1, self.out_proj, hs, B), **pad)
+                                                    q_scale=self.scaling, **pad,
+                                                    consumer=_attention_consumer(c1, self.out_proj, hs, B) if one_pass == "block_fp" else None)
             return _project_attention_output(o, self.out_proj, out, B, T, nh * self.hd, residual)
         q = shape(self.q_proj(x) * self.scaling)
         k, v = shape(self.k_proj(x)), shape(self.v_proj(x))
@@ -137,7 +151,7 @@ class _DecoderLayer(nn.Module):
         c1 = self.self_attn.qc["bmm_1"]
         pad = {} if key_mask is None else {"key_mask": key_mask}
         fused_norm = (self.fc1.config.get("mi355q_fused_norm", False) and c1.get("mi355q_grouped_linear", False)
-                      and c1.get("mi355q_fused_attention", False) and c1["name"] == "block_fp")
+                      and _one_pass_attention(self.self_attn.qc["bmm_0"], c1) is not None)
         ln = lambda m: (m.weight, m.bias, m.eps)
         fres = self.fc2.config.get("mi355q_fused_residual", False)      # the residual adds in out_proj's / fc2's stores
         if fused_norm:      # the LayerNorms are applied by the quantiser of the projections they feed (grouped_linear(norm=...))
@@ -393,8 +407,9 @@ class _LlamaAttention(nn.Module):
         c1 = self.qc["matmul_1"]
         # (sliding window: the fused causal paths take no additive mask, so a windowed model with T > W takes the mask route below)
         windowed = self.window is not None and T > self.window
-        fused = c1["name"] == "block_fp" and c1.get("mi355q_fused_attention", False) and not windowed
-        if fused and c1.get("mi355q_fused_rotary", False):
+        one_pass = None if windowed else _one_pass_attention(self.qc["matmul_0"], c1)
+        fused = one_pass is not None
+        if one_pass == "block_fp" and c1.get("mi355q_fused_rotary", False):
             # (the rotary embedding applied where the attention pass loads q and k: attention_block_fp(rope=...))
             o = get_quantized_func("attention", c1)(q, k, v, self.qc["matmul_0"], c1, causal=True, scale_div=math.sqrt(self.hd),
                                                     rope=(self.cos[:, :, :T], self.sin[:, :, :T], position_ids, rc),
@@ -403,8 +418,8 @@ class _LlamaAttention(nn.Module):
         q, k = get_quantized_func("rotary_positional_encoding", rc)(q, k, self.cos[:, :, :T], self.sin[:, :, :T],
                                                                    position_ids, config=rc)
         if fused:
-            o = get_quantized_func("attention", c1)(q, k, v, self.qc["matmul_0"], c1, causal=True, scale_div=math.sqrt(self.hd),
-                                                    consumer=_attention_consumer(c1, self.o_proj, hs, B), **pad)
+            o = get_quantized_func("attention", c1)(q, k, v, self.qc["matmul_0"], c1, causal=True, scale_div=math.sqrt(self.hd), **pad,
+                                                    consumer=_attention_consumer(c1, self.o_proj, hs, B) if one_pass == "block_fp" else None)
             return _project_attention_output(o, self.o_proj, out, B, T, nh * self.hd, residual)
         w = get_quantized_func("matmul", self.qc["matmul_0"])(q, k.transpose(2, 3), config=self.qc["matmul_0"])
         if c1["name"] in ("block_fp", "block_minifloat") and c1.get("mi355q_fused_softmax", False) and not windowed and key_mask is None:
@@ -549,7 +564,8 @@ class DecodeState:
     mode "block": EACH layer gets the cache of its own format -- ops.KVCache where both products are block_fp (the calls of mode
         "block_fp", unchanged), ops.MinifloatKVCache where both are block_minifloat; any other format, a bypassed product or two
         formats in one layer: ValueError here, naming the layer.  A block_minifloat layer's prompt runs, behind its append, the
-        registry steps of the layer's full forward (the products, the mask, the softmax).  What the block_minifloat cache has no kernel
+        registry steps of the layer's full forward (the products, the mask, the softmax) -- or, with config["mi355q_fused_attention"]
+        of its second product, the registry's one-pass function (attention_block_minifloat).  What the block_minifloat cache has no kernel
         for is refused by name: extend=True, a sliding-window model, pages; a mixed call and more than 16 new tokens behind a non-empty
         cache keep raising NotImplementedError.
     mode "fp32": the reference's literal route for ANY arithmetic (modeling_llama.py:301-344): torch.cat of fp32 K / V per layer, the
@@ -793,7 +809,8 @@ class DecodeState:
         # the sequence alone runs); prefill is not the hot path here
         o = q.new_zeros(B, nh, n, hd)
         for b, c in enumerate(call["counts"]):
-            if c and isinstance(cache, ops.MinifloatKVCache):   # (no one-pass attention function: the layer's full-forward steps)
+            if c and isinstance(cache, ops.MinifloatKVCache) and not c1.get("mi355q_fused_attention", False):
+                # (config["mi355q_fused_attention"] off: the layer's full-forward steps; on: attention_block_minifloat below)
                 o[b, :, :c] = self._reference_steps(q[b:b + 1, :, :c], k[b:b + 1, :, :c], v[b:b + 1, :, :c], c0, c1, scale_div, style)[0]
             elif c:
                 o[b, :, :c] = get_quantized_func("attention", c1)(q[b:b + 1, :, :c], k[b:b + 1, :, :c], v[b:b + 1, :, :c], c0, c1, causal=True,
@@ -820,8 +837,9 @@ class DecodeState:
                 if self.sinks:
                     gq["sinks"] = self.sinks
                 wide = wide or (self.length == 0 and n > self.window)      # (a prompt longer than the window: the windowed extend kernel)
-            if self.length == 0 and isinstance(cache, ops.MinifloatKVCache):
-                # the prompt of a block_minifloat layer: no one-pass attention function, the steps of the layer's full forward
+            if self.length == 0 and isinstance(cache, ops.MinifloatKVCache) and not c1.get("mi355q_fused_attention", False):
+                # the prompt of a block_minifloat layer without config["mi355q_fused_attention"]: the steps of the layer's full forward
+                # (with it: attention_block_minifloat below, as a block_fp layer's prompt takes attention_block_fp)
                 return self._reference_steps(q, k, v, c0, c1, scale_div, style)
             if self.length == 0 and not wide:
                 # the prompt's own queries against the prompt: the existing attention function (M = n)

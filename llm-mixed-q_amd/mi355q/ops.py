@@ -1510,6 +1510,85 @@ def bfp_attention_padded(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, qk_p
     return out
 
 
+# ---- the one-pass attention core of a block_minifloat layer (csrc/mi355q_attention_bm.hip) --------------------------------------
+_BM_ATTN_WS = _StreamCache(8)
+BM_ATTENTION_HEAD_DIMS = (32, 64, 96, 128)
+
+
+def _bm_attention_check(q, k, v, qk_params, pv_params, causal):
+    """the reason ops.bm_attention declines a call, None when it takes it.  Nothing here touches a device."""
+    if not all(isinstance(t, torch.Tensor) for t in (q, k, v)):
+        return "q, k and v must be tensors"
+    if q.ndim < 3 or k.ndim != q.ndim or v.shape != k.shape or q.shape[:-2] != k.shape[:-2] or q.shape[-1] != k.shape[-1]:
+        return f"q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}: q [..., T_q, D] and k, v [..., T_k, D] with equal leading dims expected"
+    if not (q.dtype == k.dtype == v.dtype == torch.float32):
+        return "fp32 q, k, v only"
+    if not (q.device == k.device == v.device):
+        return "q, k and v are on different devices"
+    rows, (M, D), T = q.shape[:-2].numel(), q.shape[-2:], k.shape[-2]
+    if causal and M > T:
+        return f"causal with T_q = {M} > T_k = {T}"
+    if not 0 < rows <= 65535:
+        return f"{rows} rows (batch x heads) outside 1 .. 65535"
+    if M < 1:
+        return "no queries"
+    if not (0 < T <= ATTENTION_MAX_KEYS and T % 16 == 0):
+        return f"T_k = {T} is not a multiple of 16 up to {ATTENTION_MAX_KEYS}"
+    if D not in BM_ATTENTION_HEAD_DIMS:
+        return f"head_dim {D} is not one of {BM_ATTENTION_HEAD_DIMS}"
+    for what, params in (("qk_params", qk_params), ("pv_params", pv_params)):
+        try:
+            _minifloat_params(params, what)
+        except (ValueError, TypeError) as e:
+            return str(e)
+    if not q.is_cuda:
+        return f"tensors are on '{q.device}': the kernels run on an MI355X only"
+    return None
+
+
+def bm_attention_supported(q, k, v, qk_params, pv_params, *, causal: bool = False) -> bool:
+    """shapes and formats ops.bm_attention takes: q [..., M, D], k / v [..., T, D] fp32 with equal leading dims, T % 16 == 0, D in
+    32 / 64 / 96 / 128, M <= T under a causal mask, and the formats ops.MinifloatKVCache accepts"""
+    return _bm_attention_check(q, k, v, qk_params, pv_params, causal) is None
+
+
+def bm_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, qk_params, pv_params, *, causal: bool = False, scale_div: float = None,
+                 q_scale: float = None) -> torch.Tensor:
+    """bfp_attention for two block_minifloat [1,16] products (matmul.py:199-249): out[b] = Qc(softmax(Qa(q[b] [* q_scale]) @ Qb(k[b]^T)
+    [/ scale_div] + causal)) @ Qd(v[b]), q [..., M, D], k and v [..., T, D] fp32 (k untransposed; strided head views are read in place);
+    neither scores nor probabilities are written.  qk_params / pv_params: (width, exponent_width, exponent_bias_width) of data_in, then of
+    weight, as ops.MinifloatKVCache takes them.  The arithmetic is that of bfp_attention_decode on a MinifloatKVCache holding the same
+    keys (a probability <= 1e-8 passes through unquantised).  Returns a contiguous fp32 tensor of q's shape.  Streaming kernel only; no
+    additive mask, key mask, rotary embedding on load or consumer operand.  Raises ValueError naming what it does not take
+    (bm_attention_supported)."""
+    import ctypes
+    why = _bm_attention_check(q, k, v, qk_params, pv_params, causal)
+    if why is not None:
+        raise ValueError(f"mi355q.bm_attention: {why}")
+    M, D = q.shape[-2:]
+    T = k.shape[-2]
+    q3, qsb, qsm = _as_heads_view(q)
+    k3, ksb, kst = _as_heads_view(k)
+    v3, vsb, vst = _as_heads_view(v)
+    B = q3.shape[0]
+    out = torch.empty(*q.shape, dtype=torch.float32, device=q.device)
+    lib = _lib.load_library()
+    sp = _stream_ptr(q.device)
+    key = (q.device.index, sp, B, T, D)
+    ws = _BM_ATTN_WS.get(key)
+    if ws is None:
+        ws = _BM_ATTN_WS.put(key, torch.empty(lib.mi355q_bm_attention_workspace_bytes(B, T, D), dtype=torch.uint8, device=q.device))
+    pa = (ctypes.c_int32 * 6)(*_minifloat_params(qk_params, "qk_params"))
+    pb = (ctypes.c_int32 * 6)(*_minifloat_params(pv_params, "pv_params"))
+    strides = (ctypes.c_int64 * 8)(qsb, qsm, ksb, kst, vsb, vst, M * D, D)
+    with _on_device(q.device):
+        rc = lib.mi355q_bm_attention(_ptr(q3), _ptr(k3), _ptr(v3), _ptr(out), _ptr(ws), B, M, T, D, ctypes.addressof(pa), ctypes.addressof(pb),
+                                     ctypes.addressof(strides), int(bool(causal)), float(scale_div) if scale_div else 0.0,
+                                     float(q_scale) if q_scale else 0.0, sp)
+    _lib.check(rc, "mi355q_bm_attention")
+    return out
+
+
 # ---- incremental decoding: block_fp KV cache + split-key decode attention (csrc/mi355q_decode.hip) ----------------------------
 DECODE_MAX_QUERIES = 16          # rows of q one decode call takes (the 16 columns of the MFMA tiles)
 _DECODE_WS = _StreamCache(8)

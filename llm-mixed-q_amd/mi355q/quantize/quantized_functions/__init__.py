@@ -178,6 +178,32 @@ def _key_mask_dense(key_mask, q, k):
                                                                                     k.shape[-2]).contiguous()
 
 
+def _attention_steps(q, k, v, config_qk, config_pv, mask, causal, scale_div, rope, q_scale):
+    """the attention core step by step through the registry's own functions -- q * q_scale, the rotary function, the first product, the
+    scale, the causal and the additive mask, the softmax, the second product: what attention_block_fp and attention_block_minifloat run
+    wherever their one-pass kernels do not apply"""
+    if q_scale:
+        q = q * q_scale
+    if rope is not None:
+        cos, sin, position_ids, rope_config = rope
+        q, k = QUANTIZED_FUNC_MAP["rotary_positional_encoding"][rope_config["name"]](q, k, cos, sin, position_ids, config=rope_config)
+    style = "bmm" if q.ndim == 3 else "matmul"
+    w = QUANTIZED_FUNC_MAP[style][config_qk["name"]](q, k.transpose(-1, -2), config=config_qk)
+    if scale_div:
+        w = w / scale_div
+    if config_pv["name"] == "block_fp":
+        return QUANTIZED_FUNC_MAP["softmax_" + style]["block_fp"](w, v, config_pv, mask=mask, causal=causal)
+    if causal:
+        tq, tk = w.shape[-2], w.shape[-1]
+        w = w + torch.full((tq, tk), torch.finfo(w.dtype).min, device=w.device).triu(1 + tk - tq)
+    if mask is not None:
+        w = w + mask
+    if causal or mask is not None:
+        w = torch.max(w, w.new_full((), torch.finfo(w.dtype).min))
+    p = torch.nn.functional.softmax(w, dim=-1, dtype=torch.float32).to(q.dtype)
+    return QUANTIZED_FUNC_MAP[style][config_pv["name"]](p, v, config=config_pv)
+
+
 def attention_block_fp(q, k, v, config_qk, config_pv, mask=None, causal=False, scale_div=None, rope=None, consumer=None, q_scale=None,
                        key_mask=None):
     """The reference's quantised attention core as one call (modeling_opt.py:246-312, modeling_llama.py:309-344):
@@ -275,25 +301,46 @@ def attention_block_fp(q, k, v, config_qk, config_pv, mask=None, causal=False, s
                                      token_major=bool(config_pv.get("mi355q_token_major_output", False)), rope=rope_in,
                                      consumer=consumer if consumer is not None and ops.bfp_attention_consumer_supported(q, m2) else None,
                                      q_scale=qs)
-    if q_scale:
-        q = q * q_scale
-    if rope is not None:
-        q, k = rope_fn(q, k, cos, sin, position_ids, config=rope_config)
-    style = "bmm" if q.ndim == 3 else "matmul"
-    w = QUANTIZED_FUNC_MAP[style][config_qk["name"]](q, k.transpose(-1, -2), config=config_qk)
-    if scale_div:
-        w = w / scale_div
-    if config_pv["name"] == "block_fp":
-        return QUANTIZED_FUNC_MAP["softmax_" + style]["block_fp"](w, v, config_pv, mask=mask, causal=causal)
-    if causal:
-        tq, tk = w.shape[-2], w.shape[-1]
-        w = w + torch.full((tq, tk), torch.finfo(w.dtype).min, device=w.device).triu(1 + tk - tq)
-    if mask is not None:
-        w = w + mask
-    if causal or mask is not None:
-        w = torch.max(w, w.new_full((), torch.finfo(w.dtype).min))
-    p = torch.nn.functional.softmax(w, dim=-1, dtype=torch.float32).to(q.dtype)
-    return QUANTIZED_FUNC_MAP[style][config_pv["name"]](p, v, config=config_pv)
+    return _attention_steps(q, k, v, config_qk, config_pv, mask, causal, scale_div, rope, q_scale)
+
+
+def attention_block_minifloat(q, k, v, config_qk, config_pv, mask=None, causal=False, scale_div=None, rope=None, consumer=None, q_scale=None,
+                              key_mask=None):
+    """attention_block_fp for a layer whose two products are block_minifloat (registry key "attention", name "block_minifloat"): the same
+    signature, the same result as the steps.  The one-pass kernel (ops.bm_attention: neither scores nor probabilities are written) takes
+    the call when both configs are block_minifloat, neither is bypassed, `mi355q_fused_matmul` is not off, all four blockings are
+    [1, 16], autograd is not recording, there is no `mask` and no `key_mask`, and ops.bm_attention_supported holds; every other call runs
+    the steps attention_block_fp's tail runs (a `key_mask` as the dense mask it stands for).  `rope`: the registry's rotary function
+    runs first (no rotary embedding on load here).  `consumer`: ignored -- the result is always the fp32 tensor, and the caller checks
+    what it got.  No token-major output."""
+    from ... import ops
+    if key_mask is not None:
+        if mask is not None:
+            raise ValueError("attention: key_mask together with mask (fold the key mask into the additive mask, or pass one of them)")
+        if key_mask.ndim != 2 or q.ndim < 3 or key_mask.shape != (q.shape[0], k.shape[-2]):
+            raise ValueError(f"attention: key_mask {tuple(key_mask.shape)} is not [B, T_k] = [{q.shape[0]}, {k.shape[-2]}] of q {tuple(q.shape)}")
+        mask, key_mask = _key_mask_dense(key_mask, q, k), None
+    fused_ok = (mask is None and config_qk.get("name") == "block_minifloat" and config_pv.get("name") == "block_minifloat"
+                and not config_qk.get("bypass", False) and not config_pv.get("bypass", False)
+                and config_qk.get("mi355q_fused_matmul", True) and config_pv.get("mi355q_fused_matmul", True)
+                and q.ndim == k.ndim == v.ndim and q.ndim >= 3 and q.shape[:-2] == k.shape[:-2] == v.shape[:-2]
+                and not (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)))
+    if fused_ok:
+        for c in (config_qk, config_pv):
+            for key in _KEYS["block_minifloat"]:
+                c[f"data_in_{key}"], c[f"weight_{key}"]
+        nb, (tq, hd), tk = q.shape[:-2].numel(), q.shape[-2:], k.shape[-2]
+        blocks_ok = all(ops.resolve_blocking(list(shape), bs, True)[3:] == (1, 16) for shape, bs in (
+            ((nb, tq, hd), config_qk["data_in_block_size"]), ((nb, hd, tk), config_qk["weight_block_size"]),
+            ((nb, tq, tk), config_pv["data_in_block_size"]), ((nb, tk, hd), config_pv["weight_block_size"])))
+        par = lambda c: (c["data_in_width"], c["data_in_exponent_width"], c["data_in_exponent_bias_width"], c["weight_width"],
+                         c["weight_exponent_width"], c["weight_exponent_bias_width"])
+        if blocks_ok and ops.bm_attention_supported(q, k, v, par(config_qk), par(config_pv), causal=causal):
+            if rope is not None:
+                cos, sin, position_ids, rope_config = rope
+                q, k = QUANTIZED_FUNC_MAP["rotary_positional_encoding"][rope_config["name"]](q, k, cos, sin, position_ids, config=rope_config)
+            return ops.bm_attention(q, k, v, par(config_qk), par(config_pv), causal=causal, scale_div=scale_div, q_scale=q_scale or None)
+    return _attention_steps(q, k, v, config_qk, config_pv, mask, causal, scale_div, rope, q_scale)
 
 
 def decode_cache_params(config_qk, config_pv, head_dim):
@@ -501,7 +548,7 @@ QUANTIZED_FUNC_MAP = {
     },
     "softmax_matmul": {"block_fp": softmax_matmul_block_fp, "block_minifloat": softmax_matmul_block_minifloat},
     "softmax_bmm": {"block_fp": softmax_bmm_block_fp, "block_minifloat": softmax_bmm_block_minifloat},
-    "attention": {"block_fp": attention_block_fp},
+    "attention": {"block_fp": attention_block_fp, "block_minifloat": attention_block_minifloat},
     "rotary_positional_encoding": {
         "block_fp": apply_rotary_pos_emb_block_fp, "block_log": apply_rotary_pos_emb_block_log,
         "block_minifloat": apply_rotary_pos_emb_block_minifloat, "integer": apply_rotary_pos_emb_integer,
